@@ -8,16 +8,23 @@ resident in HBM when the timed region starts.  N > 1: one process per GPU, indep
 (no collective in the data path; weak scaling), barrier + max over ranks around the timed region.
 
 The headline `value` is measured with flash_attn = false: the reference-order path whose results are bit-identical to the reference
-engine (the parity tests' bar).  The other path (flash_attn = true: F16 MFMA encoder, tested to |d logit| <= 1e-3 max|logit|) is
-timed in the same run and reported beside it as `flash_attn_path`, never as `value`.
+engine (the parity tests' bar).  With --full, the other path (flash_attn = true: F16 MFMA encoder, tested to |d logit| <= 1e-3
+max|logit|) is timed in the same run and reported beside it as `flash_attn_path`, never as `value`.
 
-Extra objects on the JSON line:
+A plain run sets up, warms up, times --steps steps and prints the JSON line (metric, value, unit, higher_is_better, dtype, ms_per_step,
+...).  --dump-outputs DIR then also writes what the last timed step returned to its caller, per chunk c (the id that seeds its audio),
+as float64 arrays: DIR/chunk<c>_segments.npy [n_segments, 5] = t0, t1, n_tokens, no_speech_prob, text length in bytes;
+DIR/chunk<c>_tokens.npy [n_tokens, 11] = segment, id, tid, p, plog, pt, ptsum, t0, t1, t_dtw, vlen (whisper_token_data);
+DIR/chunk<c>_text.npy = the segments' text bytes, concatenated.  Model and audio are seeded: equal arguments, equal inputs.
+
+Extra objects on the JSON line, measured only with --full:
   roofline     - the decode step (dominant by time): HBM-bound; achieved = algorithmic bytes per decode
                  step (weights + cross K/V + self K/V) / device time per step measured with
                  HIP events on the state's stream (whisper_amd_decode_step_probe).
   encoder      - encoder ms per 30 s chunk + fraction of the dense F16 MFMA peak (second half of the metric).
   cpu_baseline - the reference engine itself (oracle/_ref, kind "reference") timed on this box's host
                  cores on the same chunk, same parameters (bounded: one chunk, token count capped).
+  also: value_incl_h2d, concurrent_chunks, beam5_step, whisper_bench, host timings, config3 (N > 1), configs 4 and 5.
 """
 import argparse
 import ctypes as C
@@ -75,6 +82,23 @@ class Hip:
         self.check(self.lib.hipDeviceSynchronize(), "hipDeviceSynchronize")
 
 
+def dump_outputs(out_dir, states, chunk_ids):
+    """What the last full() returned to its caller, per chunk (module docstring: --dump-outputs)."""
+    os.makedirs(out_dir, exist_ok=True)
+    for cid, st in zip(chunk_ids, states):
+        segs, toks, text = [], [], b""
+        for i in range(st.full_n_segments()):
+            n, b = st.full_n_tokens(i), st.full_get_segment_bytes(i) or b""
+            segs.append([st.full_get_segment_t0(i), st.full_get_segment_t1(i), n, st.full_get_segment_no_speech_prob(i), len(b)])
+            text += b
+            for j in range(n):
+                t = st.full_get_token_data(i, j)
+                toks.append([i, t.id, t.tid, t.p, t.plog, t.pt, t.ptsum, t.t0, t.t1, t.t_dtw, t.vlen])
+        np.save(os.path.join(out_dir, "chunk%d_segments.npy" % cid), np.asarray(segs, dtype=np.float64).reshape(-1, 5))
+        np.save(os.path.join(out_dir, "chunk%d_tokens.npy" % cid), np.asarray(toks, dtype=np.float64).reshape(-1, 11))
+        np.save(os.path.join(out_dir, "chunk%d_text.npy" % cid), np.frombuffer(text, dtype=np.uint8).astype(np.float64))
+
+
 class StubEngine:
     """Stands in for the HIP library in the CPU rehearsal of the N > 1 control flow (tests/test_bench_dist.py, --stub): the model image is
     only check-summed, a step sleeps a few ms per chunk and "decodes" 7 tokens per chunk.  Everything around it - rank / chunk partition,
@@ -105,7 +129,12 @@ def main():
     ap.add_argument("--json-out", default=None, help="also write the JSON line to this file (profiler runs mix their log into stdout)")
     ap.add_argument("--dist-backend", default="nccl", help="nccl (= RCCL, default) or gloo (rehearsal of the N>1 path on a 1-GPU box / on CPU)")
     ap.add_argument("--stub", action="store_true", help="CPU rehearsal of the N > 1 control flow: no HIP library, a stub step (tests/test_bench_dist.py)")
+    ap.add_argument("--full", action="store_true", help="also measure everything beside the headline: the other flash_attn path, roofline and encoder "
+                    "figures, concurrent chunks, config 3 (N > 1), the CPU reference, configs 4 and 5 (the --no-* options pick among them)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="write what the last timed step computed as DIR/*.npy (float64; see the module docstring)")
     args = ap.parse_args()
+    if args.stub and args.dump_outputs:
+        ap.error("--dump-outputs needs the real engine (not --stub)")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -226,6 +255,8 @@ def main():
     barrier()
     dt = reduce_max(time.perf_counter() - t0)
     ntok_all = reduce_sum(ntok)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, states, my_ids)
 
     audio_s = 30.0 * n_chunks * world * args.steps
     rtf = audio_s / dt
@@ -242,7 +273,7 @@ def main():
 
     # ---- BASELINE config 3's shape on every N: 8 chunks per GPU (64 over 8 GPUs), each rank's chunks through its lock-step batcher;
     #      same protocol (barrier, MAX over ranks); reported beside the headline, which stays one chunk per GPU unless --chunks-per-gpu says so
-    if (world > 1 or args.stub) and n_chunks != 8:
+    if args.full and (world > 1 or args.stub) and n_chunks != 8:
         c3_ids = list(chunk_dp.shard_chunks(world * 8, rank, world))
         if args.stub:
             def c3_step():
@@ -279,7 +310,7 @@ def main():
             dist.destroy_process_group()
         return
 
-    if rank == 0 and world == 1:
+    if rank == 0 and world == 1 and args.full:
         # ---- the same step with the PCM handed over in HOST memory (what whisper-rs does): + 1.92 MB H2D per chunk
         t1 = time.perf_counter()
         for _ in range(args.steps):
@@ -303,7 +334,7 @@ def main():
                           "bit-identical to the reference engine (tests/test_parity_gpu.py)"}
             ost.free(); octx.free()
 
-    if rank == 0:
+    if rank == 0 and args.full:
         # ---- stage timings of the last step (per-state counters) + roofline probes
         tm = (C.c_int64 * 12)()
         lib.whisper_amd_get_timings_us.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
@@ -462,6 +493,7 @@ def main():
                 except Exception as ex:  # extension only; never fail the headline
                     out[name] = {"error": "%s: %s" % (type(ex).__name__, ex)}
                 out[name]["wall_s"] = round(time.perf_counter() - t1, 1)
+    if rank == 0:
         print(json.dumps(out), flush=True)
         if args.json_out:
             with open(args.json_out, "w") as f:

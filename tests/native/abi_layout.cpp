@@ -1,6 +1,6 @@
 // abi_layout.cpp - prints sizeof / offsetof of every field of the structs that cross the whisper C ABI by value.
-// Compiled twice by tests/test_abi.py: once against the reference header (-DABI_HEADER='"whisper.h"' with the reference's include
-// paths, where /root/reference is present) and once against include/whisper_amd.h; the two outputs must be identical, and both must
+// Compiled against the reference header by oracle/Makefile (oracle/_ref/abi_layout_ref, where the reference sources are present) and
+// against include/whisper_amd.h by tests/test_abi.py; the two outputs must be identical, and both must
 // equal the committed listing tests/golden/abi_layout.txt (what the reference header gave when the fixture was made).
 // ref: sys/whisper.cpp/include/whisper.h:106-151, 192-199, 485-588; callers src/whisper_params.rs:50, src/whisper_state.rs:289-321.
 #include ABI_HEADER

@@ -12,7 +12,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def _run(n):
     port = 29600 + (os.getpid() % 1500)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(n), "--master-addr", "127.0.0.1", "--master-port", str(port),
-           os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--steps", "2", "--warmup", "1", "--dist-backend", "gloo", "--stub"]
+           os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--steps", "2", "--warmup", "1", "--dist-backend", "gloo", "--stub", "--full"]
     r = subprocess.run(cmd, capture_output=True, timeout=300, cwd=ROOT)
     assert r.returncode == 0, r.stderr.decode(errors="replace")[-1500:]
     lines = [l for l in r.stdout.decode().splitlines() if l.startswith("{")]
@@ -34,7 +34,21 @@ def test_two_ranks_gloo_stub():
 
 
 def test_single_rank_stub():
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--stub", "--steps", "1", "--warmup", "0"], capture_output=True, timeout=120, cwd=ROOT)
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--stub", "--steps", "1", "--warmup", "0", "--full"], capture_output=True, timeout=120, cwd=ROOT)
     assert out.returncode == 0, out.stderr.decode(errors="replace")[-800:]
     j = json.loads([l for l in out.stdout.decode().splitlines() if l.startswith("{")][0])
     assert j["n_gpus"] == 1 and j["config3"]["chunks"] == 8
+
+
+def test_plain_run_times_only_the_headline():
+    """Without --full the run is the headline alone: --steps timed steps, ms_per_step on the line, no config-3 leg."""
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--stub", "--steps", "3", "--warmup", "1"], capture_output=True, timeout=120, cwd=ROOT)
+    assert out.returncode == 0, out.stderr.decode(errors="replace")[-800:]
+    lines = [l for l in out.stdout.decode().splitlines() if l.startswith("{")]
+    assert len(lines) == 1, lines
+    j = json.loads(lines[0])
+    assert j["steps"] == 3 and j["warmup"] == 1 and "config3" not in j
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in j, k
+    assert j["ms_per_step"] >= 2.0                  # the stub sleeps 2 ms per chunk and step
+    assert abs(j["value"] * j["ms_per_step"] * 1e-3 - 30.0) < 0.5
