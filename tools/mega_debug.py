@@ -8,6 +8,7 @@ import wsynth, whisper_rs as W
 
 name = sys.argv[1] if len(sys.argv) > 1 else "s128"
 runs = int(sys.argv[2]) if len(sys.argv) > 2 else 6
+os.environ["WHISPER_AMD_MEGA_DBG"] = "1"      # (the cross-attention role publishes the query it computes - edge QC - only with the debug buffer)
 lib = W.load_library(); W.set_log_callback(lib, lambda l, t: sys.stderr.write(t) if l >= 3 else None)
 ctx = W.WhisperContext.new_with_params(wsynth.model_path(name), W.WhisperContextParameters(lib), lib=lib)
 os.environ["WHISPER_AMD_NO_MEGA"] = "1"; ref = ctx.create_state()

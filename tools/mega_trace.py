@@ -18,7 +18,10 @@ g = np.zeros(L * 8 * 2 * d, dtype=np.uint64); lg = np.zeros(nv, dtype=np.float32
 for it in range(3):
     rc = lib.whisper_amd_mega_debug(ctx.ptr, st.ptr, 1000, n_past, g.ctypes.data, lg.ctypes.data)
 tr = np.fromfile("gpurun_out/mega_dbg.bin", dtype=np.uint32)[L * H * 5120:].reshape(-1, 8)
-names = ["P1 ln+qkv", "P3 out", "P4 ln+cq", "P6 cout", "P7 ln+fc1", "P8 fc2", "S  self", "C  cross"]
+# F16 models at d = 768 run the cross query inside the cross-attention role (wa_mega.hip, mg_role_cross CQ): P4 is then only the GEMV
+# workgroups' gather of x, and the cross role's own LayerNorm stamps 8 slots per layer at slot 6144 (tr row 768 + layer)
+cq = L * 8 <= 768 and tr[768].any()
+names = ["P1 ln+qkv", "P3 out", "P4 x" if cq else "P4 ln+cq", "P6 cout", "P7 ln+fc1", "P8 fc2", "S  self", "C  ln+q+x" if cq else "C  cross"]
 t0 = int(tr[0, 2])            # layer 0 P1: LayerNorm of the embeddings done
 us = lambda t: (int(t) - t0) / 100.0
 print("rc", rc, " times in us since layer-0 LN ready; [input seen (polls)] [lds ready] [published]")
@@ -27,10 +30,18 @@ for l in range(L):
     for p in order:
         r = tr[l * 8 + p]
         extra = "  scores %.2f softmax %.2f pv %.2f gathered %.2f" % (us(r[4]), us(r[5]), us(r[6]), us(r[7])) if p >= 6 else ("  ln: sums %.2f squares %.2f" % (us(r[4]), us(r[5])) if p in (0, 2, 4) else ("  gathered+barrier %.2f dot %.2f" % (us(r[4]), us(r[5])) if p == 5 else ""))
+        if cq and p == 7:         # x seen by the cross role's LayerNorm, its sums / squares / output, the query in LDS; then attention
+            c = tr[768 + l]
+            print("L%02d %-10s in %8.2f (%4d polls)  ln: sums %.2f squares %.2f ready %.2f  query %8.2f  pub %8.2f%s" % (l, names[p], us(c[0]), c[1], us(c[4]), us(c[5]), us(c[2]), us(r[0]), us(r[3]), extra))
+            continue
+        if cq and p == 2:
+            print("L%02d %-10s in %8.2f (%4d polls)" % (l, names[p], us(r[0]), r[1]))
+            continue
         print("L%02d %-10s in %8.2f (%4d polls)  ready %8.2f  pub %8.2f%s" % (l, names[p], us(r[0]), r[1], us(r[2]) if r[2] else 0.0, us(r[3]), extra))
 r = tr[L * 8]
 print("final      in %8.2f (%4d polls)  ready %8.2f  done %8.2f" % (us(r[0]), r[1], us(r[2]), us(r[3])))
 print("final done %.2f us after layer-0 LayerNorm ready" % us(r[3]))
+print("per layer (layers 1..%d, P1 input seen to P1 input seen): %.2f us" % (L - 1, (us(tr[(L - 1) * 8][0]) - us(tr[8][0])) / (L - 2)) if L > 2 else "")
 print("entry %8.2f  token picked %8.2f  (kernel start to layer-0 LayerNorm ready: %.2f us)" % (us(r[6]), us(r[7]), -us(r[6])))
 
 # per-workgroup stamps of one layer's P3 -> P4 (MG_WGTRACE_LAYER): how far apart the workgroups are
@@ -44,7 +55,9 @@ def stat(name, col, rows=slice(None)):
     v = v[np.isfinite(v)]
     print("%-28s min %8.2f  median %8.2f  p90 %8.2f  max %8.2f  (argmax wg %d)" % (name, v.min(), np.median(v), np.percentile(v, 90), v.max(), int(np.argmax(v))))
 print("layer 4, all %d GEMV workgroups:" % nG)
-stat("P3 out-projection published", 3); stat("P4 input complete (sweep)", 0); stat("P4 sums", 4); stat("P4 squares", 5); stat("P4 LayerNorm ready", 2); stat("P4 cross query published", 6)
+stat("P3 out-projection published", 3); stat("P4 input complete (sweep)", 0)
+if not cq:
+    stat("P4 sums", 4); stat("P4 squares", 5); stat("P4 LayerNorm ready", 2); stat("P4 cross query published", 6)
 pub = np.array([us(x) for x in w[:, 3]]); inn = np.array([us(x) for x in w[:, 0]])
 print("last P3 publish -> first / median / last 'input complete': %.2f / %.2f / %.2f us" % (inn.min() - pub.max(), np.median(inn) - pub.max(), inn.max() - pub.max()))
 print("polls per workgroup: median %d max %d" % (np.median(w[:, 1]), w[:, 1].max()))

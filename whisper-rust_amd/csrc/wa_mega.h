@@ -89,3 +89,5 @@ WA_HD inline void mg_role_of(int n, int H, int b, int & role, int & idx) {
 // n_wg workgroups of 512 threads, every one of them resident at once (n_wg <= number of CUs; 1 workgroup per CU)
 bool   wa_launch_decode_mega(hipStream_t s, const wa_mega_args & a, int n_wg);      // a.quant selects the quantised-weights form of the kernel; false: the launch failed
 size_t wa_mega_lds_bytes();
+// (F16, d = 768: the form whose cross-attention role computes its own query - wa_mega.hip built with -DMG_CQ_TU; called by wa_launch_decode_mega)
+bool   wa_launch_decode_mega_cq(hipStream_t s, const wa_mega_args & a, int n_wg, size_t lds);

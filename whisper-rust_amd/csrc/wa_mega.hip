@@ -160,15 +160,16 @@ __device__ __forceinline__ unsigned mg_sweep(gu64 * g, F idx, mg_ctl & c, int la
 // prefetch - a poll behind it would wait for those loads first, vmcnt being in order).  Returns the wave's slot or -1.
 #define MG_WGTRACE_LAYER 4
 #define MG_NQ 6
-#define MG_EX_P1 (MG_DEFER ? 0x06u : 0x20u)      /* waves 1, 2 have just asked for the next QKV rows (without MG_DEFER: wave 5 for the next FC2 rows) */
+#define MG_EX_P1 (CQ ? 0x20u : MG_DEFER ? 0x06u : 0x20u)      /* waves 1, 2 have just asked for the next QKV rows (without MG_DEFER: wave 5 for the next FC2 rows; CQ: wave 5 ran FC2) */
 /* With MG_DEFER the fresh requests sit elsewhere: before P4 waves 1, 2 (FC1 rows, asked for after the P3 barrier); before P7 wave 4 (next
    cross-query rows, after the P6 barrier) - or wave 3 in the quantised whole-block form (its FC1 rows, after its P6 product); before the
    FC2 gather wave 3 (next out-projection rows, after P7's LayerNorm). */
 #define MG_EX_P4 (MG_DEFER ? 0x06u : 0x08u)      /* (without MG_DEFER wave 3: next out-projection rows) */
 #define MG_EX_P7 (BIGP ? 0x18u : MG_DEFER && !QB ? 0x10u : 0x08u)      /* wide form: waves 3 and 4 have both just asked for their FC1 rows */
-#define MG_EX_AO 0x06u      /* waves 1, 2: FC1 rows */
-#define MG_EX_AO2 0x10u     /* wave 4: next cross-query rows */
-#define MG_EX_HF (MG_DEFER ? 0x08u : 0x06u)      /* (without MG_DEFER waves 1, 2: next QKV rows) */
+#define MG_EX_AO (CQ ? 0xc0u : 0x06u)      /* waves 1, 2: FC1 rows (CQ: waves 6, 7 run the QKV product) */
+#define MG_EX_AO2 (CQ ? 0xc0u : 0x10u)     /* wave 4: next cross-query rows (CQ: waves 6, 7 have asked for the next QKV rows) */
+#define MG_EX_HF (CQ ? 0x06u : MG_DEFER ? 0x08u : 0x06u)      /* (without MG_DEFER waves 1, 2: next QKV rows; CQ: waves 1, 2 run FC1) */
+#define MG_EX_X1 0x06u      /* CQ, the residual row after self-attention: waves 1, 2 have just asked for their FC1 rows */
 #define MG_EX_HFQ 0x18u     /* quantised, whole-block FC1: waves 3, 4 have just asked for the next out-projection / cross-query rows */
 #define MG_EX_FINAL 0x20u   /* wave 5: first logits rows */
 __device__ __forceinline__ int mg_slot(int wave, unsigned ex) {
@@ -296,6 +297,16 @@ __device__ __forceinline__ void mg_gather_h2(mg_ctl & c, gu64 * edge, int i0, in
     if (tslot >= 0) { mg_trace(A, lane == 0, tslot, mg_now()); mg_trace(A, lane == 0, tslot + 1, sp); }
 #pragma unroll
     for (int k = 0; k < NPL; ++k) { const int i = i0 + lane + 64 * k; if (i < i1) dst32[i] = v[k]; }
+}
+
+// wave(s): copy the F32 granules [i0, i1) into LDS once they are all valid
+template <int NPL>
+__device__ __forceinline__ void mg_gather_f32(mg_ctl & c, gu64 * edge, int i0, int i1, int lane, float * dst, unsigned code, mg_kargs A = nullptr, int tslot = -1) {
+    unsigned v[NPL];
+    const unsigned sp = mg_sweep<NPL>(edge, [&](int k) { const int i = i0 + lane + 64 * k; return i < i1 ? i : -1; }, c, lane, v, code);
+    if (tslot >= 0) { mg_trace(A, lane == 0, tslot, mg_now()); mg_trace(A, lane == 0, tslot + 1, sp); }
+#pragma unroll
+    for (int k = 0; k < NPL; ++k) { const int i = i0 + lane + 64 * k; if (i < i1) dst[i] = __uint_as_float(v[k]); }
 }
 
 // wave(s): the F32 granules [i0, i1) (whole 32-element blocks) quantised to Q8_0 into the activation row in LDS once they are all valid
@@ -780,8 +791,12 @@ __device__ __forceinline__ void mg_final(mg_kargs A, mg_ctl & c, unsigned char *
 // role: GEMV workgroup.  wave 0 gathers (and normalises) the input of every phase; waves 1,2 own the QKV and FC1 rows,
 // wave 3 the two out-projections, wave 4 the cross query, wave 5 FC2; waves 6,7 help gather the 4d-wide FC2 input.
 // Every wave loads the weights of its NEXT task right after finishing the current one.
+// CQ form (F16, d = 768; k_decode_mega_cq): the cross-attention role computes its own query (mg_role_cross), P4 only gathers x into the residual row,
+// and every product wave owns ONE matrix: waves 6,7 QKV, 1,2 FC1, 3 the out-projection, 4 the cross out-projection, 5 FC2.  Each asks for
+// its next rows where no hand-off among GEMV workgroups follows - behind the P1 LayerNorm (FC2) or the P3 / P4 gathers (the rest), i.e.
+// ahead of an attention phase -, so that the gathers of P7, P8 and the next P1 poll on a CU with no weight loads in flight.
 // -------------------------------------------------------------------------------------------------
-template <int NP3, int NS, bool Q = false>
+template <int NP3, int NS, bool Q = false, bool CQ = false>        // CQ: see below (k_decode_mega_cq only)
 __device__ __forceinline__ void mg_role_gemv(mg_kargs A_, int idx_) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const mg_kargs A = mg_uniform(A_);
@@ -804,6 +819,7 @@ __device__ __forceinline__ void mg_role_gemv(mg_kargs A_, int idx_) {
     // 6, 7, which hold no logits rows until the last layer), and waves 3, 4 ask for the first half of their FC2 rows right after FC1 - an assist
     // that fetches on demand exposes an HBM round trip per group (P7 5.3 -> ~1.5 us, P8 5.9 -> ~4 us per layer on large-v3).
     constexpr bool BIGP = BIG && MG_DEFER;
+    static_assert(!CQ || (!Q && !BIG && MG_DEFER), "the CQ form is the F16 small-width schedule");
     // (fc1x / fc1cnt sit in the xin area at byte 7 MAX_D = 8960 .. 9092.  The whole-block form runs for d <= 768 only (QB = Q && !BIG): the widest thing
     //  ever written into xin there is the FC2 operand - quants [4d <= 3072] bytes at 0, block scales [4d / 32 <= 96] floats at 6 MAX_D = 7680 .. 8064 -, so
     //  no gather reaches byte 8960; the counter is never reset, only compared modulo 4.)
@@ -837,11 +853,12 @@ __device__ __forceinline__ void mg_role_gemv(mg_kargs A_, int idx_) {
     if (wave == 0) mg_pick(A, lane, pk);
     if (QB && wave == 0 && lane == 0) *fc1cnt = 0u;
     mg_task t; t.valid = false; t.row = 0; t.wrow = nullptr; t.bias = 0.f; t.scale = 1.f;
-    if (wave == 1 || wave == 2) t = mg_mk8<Q, NS>(pf, Ly[0].qkv_w, Ly[0].qkv_d, Ly[0].qkv_b, Ly[0].qkv_s, 3 * d, d, row_qkv, r_qkv, wave - 1, lane);
+    if (CQ && L > 0 && wave >= 6) t = mg_mk8<Q, NS>(pf, Ly[0].qkv_w, Ly[0].qkv_d, Ly[0].qkv_b, Ly[0].qkv_s, 3 * d, d, row_qkv, r_qkv, wave - 6, lane);
+    else if ((wave == 1 || wave == 2) && !CQ) t = mg_mk8<Q, NS>(pf, Ly[0].qkv_w, Ly[0].qkv_d, Ly[0].qkv_b, Ly[0].qkv_s, 3 * d, d, row_qkv, r_qkv, wave - 1, lane);
     else if (wave == 3)         t = mg_mk8<Q, NS>(pf, Ly[0].out_w, Ly[0].out_d, Ly[0].out_b, nullptr, d, d, row_d, r_d, 0, lane);
-    else if (wave == 4)         t = mg_mk8<Q, NS>(pf, Ly[0].cq_w, Ly[0].cq_d, Ly[0].cq_b, nullptr, d, d, row_d, r_d, 0, lane);
+    else if (wave == 4 && !CQ)  t = mg_mk8<Q, NS>(pf, Ly[0].cq_w, Ly[0].cq_d, Ly[0].cq_b, nullptr, d, d, row_d, r_d, 0, lane);
     else if (wave == 5)         t = mg_mk16<Q, 4 * NS>(pf, Ly[0].fc2_w, Ly[0].fc2_d, Ly[0].fc2_b, d, d4, row_d, r_d, 0, lane);
-    else if (wave >= 6 && !(BIGP && L > 0)) mg_prefetch_logits<NS, Q>(A, pf, have_pf, lane, wave);      // held until the final phase (wide form: they own FC1 rows, the logits rows come in the last layer)
+    else if (wave >= 6 && !((BIGP || CQ) && L > 0)) mg_prefetch_logits<NS, Q>(A, pf, have_pf, lane, wave);      // held until the final phase (wide form: they own FC1 rows, CQ: QKV rows; the logits rows come in the last layer)
     mg_barrier();                   // the picked token is in LDS for the three embedding waves
     mg_trace(A, wg == 0 && wave == 0 && lane == 0, (A->n_layer * 8) * 8 + 7, mg_now());
     if (wave >= 3 && wave <= 5) {   // GELU table -> LDS by LDS-DMA (no registers, nothing waits here); first needed by FC1 of layer 0
@@ -863,16 +880,16 @@ __device__ __forceinline__ void mg_role_gemv(mg_kargs A_, int idx_) {
         MG_FRESH();
         mg_ln3<NP3, Q>(A, c, l == 0 ? nullptr : mg_edge(A, l - 1, E_X3), gw, gb, mg_slot(wave, MG_EX_P1), lane, xf, xinB, lnred, 100u + l, wg == 0 && wave == 0 ? (l * 8 + 0) * 8 : -1, pk[0]);
         MG_FRESH();
-        mg_ln_params<NP3>(gw, gb, Y.ln2_w, Y.ln2_b, d, mg_slot(wave, MG_EX_P4), lane);
+        if (!CQ) mg_ln_params<NP3>(gw, gb, Y.ln2_w, Y.ln2_b, d, mg_slot(wave, MG_EX_P4), lane);
         if (MG_DEFER && l > 0 && wave == 5) t = mg_mk16<Q, 4 * NS>(pf, Y.fc2_w, Y.fc2_d, Y.fc2_b, d, d4, row_d, r_d, 0, lane);      // deferred from the previous layer's P8
         // (Wide models give a workgroup more row groups than the one per wave that is prefetched.  The waves idle in a phase then
         //  assist: they take the extra groups on demand - overwriting the rows they hold for a later phase - and fetch those again
         //  afterwards, long before that phase.  ggml-small and below: one group per wave, nothing changes.)
-        if (wave == 1 || wave == 2 || (BIG && (wave == 3 || wave == 4))) {
+        if (CQ ? wave >= 6 : wave == 1 || wave == 2 || (BIG && (wave == 3 || wave == 4))) {
             const bool own = !BIG || wave <= 2;
             bool assisted = false;
             gu64 * eq = mg_edge(A, l, E_QKV);
-            for (int grp = wave - 1; grp < g_qkv; grp += BIG ? 4 : 2) {
+            for (int grp = CQ ? wave - 6 : wave - 1; grp < g_qkv; grp += BIG ? 4 : 2) {
                 if (grp >= 2) { t = mg_mk8<Q, NS>(pf, Y.qkv_w, Y.qkv_d, Y.qkv_b, Y.qkv_s, 3 * d, d, row_qkv, r_qkv, grp, lane); assisted = true; }
                 MG_CHAOS_AT(1u);
                 float v = mg_do8<Q, NS>(pf, t, d >> 5, xinB, lane);
@@ -885,7 +902,7 @@ __device__ __forceinline__ void mg_role_gemv(mg_kargs A_, int idx_) {
                     *(GAS unsigned *) cell = pk;
                 }
             }
-            mg_trace(A, wg == 0 && wave == 1 && lane == 0, (l * 8 + 0) * 8 + 3, mg_now());
+            mg_trace(A, wg == 0 && wave == (CQ ? 6 : 1) && lane == 0, (l * 8 + 0) * 8 + 3, mg_now());
             if (own && !MG_DEFER) t = mg_mk8<Q, NS>(pf, Y.fc1_w, Y.fc1_d, Y.fc1_b, nullptr, d4, d, row_ff, r_ff, wave - 1, lane);
             else if (assisted) t = wave == 3 ? mg_mk8<Q, NS>(pf, Y.out_w, Y.out_d, Y.out_b, nullptr, d, d, row_d, r_d, 0, lane)
                                              : mg_mk8<Q, NS>(pf, Y.cq_w, Y.cq_d, Y.cq_b, nullptr, d, d, row_d, r_d, 0, lane);
@@ -918,16 +935,31 @@ __device__ __forceinline__ void mg_role_gemv(mg_kargs A_, int idx_) {
             if (own && !MG_DEFER) t = mg_mk8<Q, NS>(pf, Y.co_w, Y.co_d, Y.co_b, nullptr, d, d, row_d, r_d, 0, lane);
             else if (assisted) t = mg_mk16<Q, 4 * NS>(pf, Y.fc2_w, Y.fc2_d, Y.fc2_b, d, d4, row_d, r_d, 0, lane);
         }
-        // ---------------- P4: LayerNorm + cross query ----------------
+        // ---------------- P4: LayerNorm + cross query (CQ: x -> the residual row only) ----------------
         MG_FRESH();
         // (debug: at layer MG_WGTRACE_LAYER every workgroup stamps this phase - the spread over workgroups is what a hand-off waits for)
+        if constexpr (CQ) {
+            // The gather writes xf, as P4's LayerNorm did: this workgroup's own rows of x are complete only after its P3 product has read xf.
+            // Nothing downstream waits for this phase (P6 is a cross-attention away), so the weights of the next phases are asked for here.
+            const int qs = mg_slot(wave, MG_EX_X1), sg = mg_seg(d), i0 = qs * sg, i1 = min(d, i0 + sg);
+            if (qs >= 0) mg_gather_f32<NP3>(c, mg_edge(A, l, E_X1), i0, i1, lane, xf, 300u + l, A,
+                                            wave == 0 ? (wg == 0 ? (l * 8 + 2) * 8 : (A->dbg && l == MG_WGTRACE_LAYER ? 1024 + wg * 8 : -1)) : -1);
+            mg_barrier();
+            MG_FRESH();
+            if (wave == 4) t = mg_mk8<Q, NS>(pf, Y.co_w, Y.co_d, Y.co_b, nullptr, d, d, row_d, r_d, 0, lane);
+            else if (wave == 3 || wave >= 6) {
+                if (l + 1 >= L) mg_prefetch_logits<NS, Q>(A, pf, have_pf, lane, wave);
+                else if (wave == 3) t = mg_mk8<Q, NS>(pf, Ly[l + 1].out_w, Ly[l + 1].out_d, Ly[l + 1].out_b, nullptr, d, d, row_d, r_d, 0, lane);
+                else t = mg_mk8<Q, NS>(pf, Ly[l + 1].qkv_w, Ly[l + 1].qkv_d, Ly[l + 1].qkv_b, Ly[l + 1].qkv_s, 3 * d, d, row_qkv, r_qkv, wave - 6, lane);
+            }
+        } else
         mg_ln3<NP3, Q>(A, c, mg_edge(A, l, E_X1), gw, gb, mg_slot(wave, MG_EX_P4), lane, xf, xinB, lnred, 300u + l,
                        wave == 0 ? (wg == 0 ? (l * 8 + 2) * 8 : (A->dbg && l == MG_WGTRACE_LAYER ? 1024 + wg * 8 : -1)) : -1);
         MG_FRESH();
-        if (MG_DEFER && wave == 3) t = mg_mk8<Q, NS>(pf, Y.co_w, Y.co_d, Y.co_b, nullptr, d, d, row_d, r_d, 0, lane);
+        if (MG_DEFER && !CQ && wave == 3) t = mg_mk8<Q, NS>(pf, Y.co_w, Y.co_d, Y.co_b, nullptr, d, d, row_d, r_d, 0, lane);
         if (BIGP && wave >= 6 && wave - 2 < g_ff) t = mg_mk8<Q, NS>(pf, Y.fc1_w, Y.fc1_d, Y.fc1_b, nullptr, d4, d, row_ff, r_ff, wave - 2, lane);      // FC1 groups 4, 5 (the next gather is a cross-attention away)
         mg_ln_params<NP3>(gw, gb, Y.ln3_w, Y.ln3_b, d, mg_slot(wave, MG_EX_P7), lane);
-        if (wave == 4 || (BIG && wave == 3)) {        // wave 3 assists (it holds this layer's cross-attention output rows, next needed in P6)
+        if (!CQ && (wave == 4 || (BIG && wave == 3))) {        // wave 3 assists (it holds this layer's cross-attention output rows, next needed in P6)
             const bool own = !BIG || wave == 4;
             bool assisted = false;
             gu64 * eq = mg_edge(A, l, E_QC);
@@ -955,11 +987,11 @@ __device__ __forceinline__ void mg_role_gemv(mg_kargs A_, int idx_) {
         }
         mg_barrier();
         MG_FRESH();
-        if (MG_DEFER && !QB && !BIGP && wave == 4) {
+        if (MG_DEFER && !QB && !BIGP && !CQ && wave == 4) {
             if (l + 1 < L) t = mg_mk8<Q, NS>(pf, Ly[l + 1].cq_w, Ly[l + 1].cq_d, Ly[l + 1].cq_b, nullptr, d, d, row_d, r_d, 0, lane);
             else mg_prefetch_logits<NS, Q>(A, pf, have_pf, lane, wave);
         }
-        if (wave == 3 || (BIG && wave == 4)) {        // wave 4 assists (it holds the next layer's cross-query rows)
+        if (wave == (CQ ? 4 : 3) || (BIG && wave == 4)) {        // wave 4 assists (it holds the next layer's cross-query rows)
             const bool own = !BIG || wave == 3;
             bool assisted = false;
             gu64 * ex = mg_edge(A, l, E_X2);
@@ -973,6 +1005,7 @@ __device__ __forceinline__ void mg_role_gemv(mg_kargs A_, int idx_) {
             mg_trace(A, wg == 0 && own && lane == 0, (l * 8 + 3) * 8 + 3, mg_now());
             if (A->dbg && l == MG_WGTRACE_LAYER) mg_trace(A, own && lane == 0, 4096 + wg * 8 + 3, mg_now());
             if (QB) t = mg_mk8<Q, NS>(pf, Y.fc1_w, Y.fc1_d, Y.fc1_b, nullptr, d4, d, 32 * wg, 32, 2, lane);
+            else if (CQ) { if (l + 1 >= L) mg_prefetch_logits<NS, Q>(A, pf, have_pf, lane, wave); }      // (the next rows: after the next P4)
             else if (BIGP) {                 // FC1 group 2 (wave 3) / 3 (wave 4), used in P7
                 if (wave - 1 < g_ff) t = mg_mk8<Q, NS>(pf, Y.fc1_w, Y.fc1_d, Y.fc1_b, nullptr, d4, d, row_ff, r_ff, wave - 1, lane);
                 else big_next(wave);
@@ -990,7 +1023,7 @@ __device__ __forceinline__ void mg_role_gemv(mg_kargs A_, int idx_) {
         mg_ln3<NP3, Q>(A, c, mg_edge(A, l, E_X2), gw, gb, mg_slot(wave, MG_EX_P7), lane, xf, xinB, lnred, 500u + l,
                        wave == 0 ? (wg == 0 ? (l * 8 + 4) * 8 : (A->dbg && l == MG_WGTRACE_LAYER ? 4096 + wg * 8 : -1)) : -1);
         MG_FRESH();
-        if (MG_DEFER && !QB && !BIGP && wave == 3) {
+        if (MG_DEFER && !QB && !BIGP && !CQ && wave == 3) {
             if (l + 1 < L) t = mg_mk8<Q, NS>(pf, Ly[l + 1].out_w, Ly[l + 1].out_d, Ly[l + 1].out_b, nullptr, d, d, row_d, r_d, 0, lane);
             else mg_prefetch_logits<NS, Q>(A, pf, have_pf, lane, wave);
         }
@@ -1069,6 +1102,8 @@ __device__ __forceinline__ void mg_role_gemv(mg_kargs A_, int idx_) {
             if (own && !MG_DEFER) {
                 if (l + 1 < L) t = mg_mk8<Q, NS>(pf, Ly[l + 1].qkv_w, Ly[l + 1].qkv_d, Ly[l + 1].qkv_b, Ly[l + 1].qkv_s, 3 * d, d, row_qkv, r_qkv, wave - 1, lane);
                 else mg_prefetch_logits<NS, Q>(A, pf, have_pf, lane, wave);
+            } else if (CQ) {
+                if (l + 1 >= L) mg_prefetch_logits<NS, Q>(A, pf, have_pf, lane, wave);      // (the next FC1 rows: after the next P3)
             } else if (assisted) {
                 if (l + 1 >= L) mg_prefetch_logits<NS, Q>(A, pf, have_pf, lane, wave);
                 else t = wave == 3 ? mg_mk8<Q, NS>(pf, Ly[l + 1].out_w, Ly[l + 1].out_d, Ly[l + 1].out_b, nullptr, d, d, row_d, r_d, 0, lane)
@@ -1087,7 +1122,7 @@ __device__ __forceinline__ void mg_role_gemv(mg_kargs A_, int idx_) {
         mg_barrier();
         MG_FRESH();
         mg_trace(A, wg == 0 && wave == 5 && lane == 0, (l * 8 + 5) * 8 + 4, mg_now());
-        if (MG_DEFER && (wave == 1 || wave == 2)) {
+        if (MG_DEFER && !CQ && (wave == 1 || wave == 2)) {
             if (l + 1 < L) t = mg_mk8<Q, NS>(pf, Ly[l + 1].qkv_w, Ly[l + 1].qkv_d, Ly[l + 1].qkv_b, Ly[l + 1].qkv_s, 3 * d, d, row_qkv, r_qkv, wave - 1, lane);
             else mg_prefetch_logits<NS, Q>(A, pf, have_pf, lane, wave);
         }
@@ -1362,12 +1397,21 @@ __device__ __forceinline__ void mg_role_self(mg_kargs A_, int idx_) {
 #define MG_CGR_SUM 8
 #define MG_CGR_XCC 16                                   // (layer 0 area only) the four workgroups' XCC_IDs
 #define MG_CGR_PART 64                                  // + (w - 1) * 576: 512 chain sums + 8 leftover probabilities
+#define MG_CX_XF 32768                                  // (CQ) LDS of the role's own LayerNorm: residual row [d] f32 | normalised row [d] f16 | partial sums
+#define MG_CX_XIN (MG_CX_XF + WA_MEGA_MAX_D * 4)
+#define MG_CX_LNRED (MG_CX_XIN + WA_MEGA_MAX_D * 2)
+#define MG_CX_END (MG_CX_LNRED + 256)
+#define MG_CX_TRACE 6144                                // (debug) trace slots of the role's LayerNorm: 8 per layer
 
-template <bool Q = false>
+// CQ >= 0 (F16 models, d = 768: k_decode_mega_cq): the role computes its head's cross query itself - gathers x (edge E_X1), runs LN2 (mg_ln3: the same
+// certificates) and the head's 64 rows of W_q,cross (one row per 8 lanes: mg_dot8's chains and tree, + bias, rounded to F16), redundantly in
+// each quarter: the hand-off P4 -> C of the GEMV role's query is gone.  CQ = the rows' step count at compile time (0: run time).
+// CQ < 0: the query arrives from the GEMV role through E_QC.
+template <bool Q = false, int CQ = -1>
 __device__ __forceinline__ void mg_role_cross(mg_kargs A_, int idx_) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const mg_kargs A = mg_uniform(A_);
-    const int tid = threadIdx.x, lane = tid & 63;
+    int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int H = A->n_head;
     const int ci = __builtin_amdgcn_readfirstlane(idx_);
@@ -1389,7 +1433,7 @@ __device__ __forceinline__ void mg_role_cross(mg_kargs A_, int idx_) {
 
     const int T = A->T, tpad = A->cross_tpad, L = A->n_layer;
     const float kq_scale = A->kq_scale;
-    const int a = tid & 3, ks = tid >> 2;
+    int a = tid & 3, ks = tid >> 2;
     const int np = T & ~31, nsteps = np >> 5, nl = T - np, n8 = T & ~7, ng = n8 >> 3;
     if (wave == 0) mg_pick(A, lane, (int *) (smem + MG_PICK_OFF));
     // Do the head's four workgroups share an XCD (mg_role_of places them 8 apart, which is where the dispatcher has been observed to put
@@ -1405,7 +1449,16 @@ __device__ __forceinline__ void mg_role_cross(mg_kargs A_, int idx_) {
     }
     mg_barrier();
     const bool local = bc[2] != 0.0f;
+    const __attribute__((address_space(4))) wa_mega_layer * Ly = (const __attribute__((address_space(4))) wa_mega_layer *) A->layers;
+    float  * xf    = (float *) (smem + MG_CX_XF);
+    wa_f16 * xin   = (wa_f16 *) (smem + MG_CX_XIN);
+    double * lnred = (double *) (smem + MG_CX_LNRED);
+    const int d = A->d;
     for (int l = 0; l < L; ++l) {
+        if constexpr (CQ >= 0) {        // (as mq_fresh: with the query rows in registers, thread-derived addresses hoisted out of the loop were spilled)
+            unsigned z = threadIdx.x; asm volatile("" : "+v"(z));
+            tid = (int) z; lane = tid & 63; a = tid & 3; ks = tid >> 2;
+        }
         gu64 * X = (gu64 *) A->cross_gr + ((size_t) l * H + h) * MG_CGR;
         const gch kp = (gch) A->cross_k + (size_t) l * A->cross_layer_stride + (size_t) h * tpad * 64;
         const gch vp = (gch) A->cross_v + (size_t) l * A->cross_layer_stride + (size_t) h * tpad * 64;
@@ -1423,7 +1476,28 @@ __device__ __forceinline__ void mg_role_cross(mg_kargs A_, int idx_) {
             const int row = tid >> 3;
             if (row < nl) *(u32x4 *) (vleft + (size_t) tid * 8) = *(const GAS u32x4 *) (vp + (size_t) (np + row) * 64 + (tid & 7) * 8);
         }
-        if (wave == 0) {
+        if constexpr (CQ >= 0) {
+            // ---- the head's query: rows 64 h + 8 wave + lane / 8, loaded with the keys (the poll below finds them landed: x arrives
+            //      three phases later), LN2 of x (its gamma / beta likewise), then the product as the GEMV role's P4 ran it ----
+            unsigned pf[96];
+            float gw[2], gb[2];
+            const int row = 64 * h + 8 * wave + (lane >> 3);
+            const gch wrow = (gch) Ly[l].cq_w + (size_t) row * d + 4 * (lane & 7);
+            mg_pf8<CQ>(pf, wrow, true, d >> 5, 0);
+            const float bias = ((gcf) Ly[l].cq_b)[row];
+            mg_ln_params<2>(gw, gb, Ly[l].ln2_w, Ly[l].ln2_b, d, mg_slot(wave, 0u), lane);
+            mg_trace(A, ci == 0 && lane == 0 && wave == 0, (l * 8 + 7) * 8 + 2, mg_now());
+            mg_ln3<2>(A, c, mg_edge(A, l, E_X1), gw, gb, mg_slot(wave, 0u), lane, xf, xin, lnred, 2000u + l,
+                      ci == 0 && wave == 0 ? MG_CX_TRACE + l * 8 : -1);
+            MG_CHAOS_ID(2000 + ci, 30u, seq);
+            float v = mg_dot8<CQ>(pf, wrow, true, d >> 5, xin, lane & 7, true);
+            v = v + bias;
+            const unsigned hq = (unsigned) f2h(v);
+            if ((lane & 7) == 0) qs[8 * wave + (lane >> 3)] = (wa_f16) hq;
+            if (A->dbg && w == 0) mg_pub_h2(mg_edge(A, l, E_QC), seq, true, row, hq, lane);      // (debug tools compare the query edge)
+            mg_trace(A, ci == 0 && lane == 0 && wave == 0, (l * 8 + 7) * 8 + 0, mg_now());
+            if (A->dbg && l == MG_WGTRACE_LAYER && w == 0) mg_trace(A, tid == 0, 3200 + h, mg_now());
+        } else if (wave == 0) {
             unsigned v[1];
             mg_trace(A, ci == 0 && lane == 0, (l * 8 + 7) * 8 + 2, mg_now());
             const unsigned sp = mg_sweep<1>(mg_edge(A, l, E_QC), [&](int) { return lane < 32 ? h * 32 + lane : -1; }, c, lane, v, 2000u + l);
@@ -1559,6 +1633,7 @@ __device__ __forceinline__ void mg_role_cross(mg_kargs A_, int idx_) {
     mg_final<MG_NP3, 0, Q>(A, c, smem, pf, have_pf, gw, gb, lane, wave);
 }
 
+#ifndef MG_CQ_TU
 __global__ __launch_bounds__(MG_THREADS) void k_decode_mega(const wa_mega_args A) {
     int role, idx;                                       // H self-attention + 4 H cross-attention workgroups, the rest stream weights
     mg_role_of((int) gridDim.x, A.n_head, (int) blockIdx.x, role, idx);
@@ -1570,6 +1645,7 @@ __global__ __launch_bounds__(MG_THREADS) void k_decode_mega(const wa_mega_args A
     else if (role == 1) mg_role_self(Ap, idx);
     else                mg_role_cross(Ap, idx);
 }
+
 
 // the same step for a quantised model (Q5_0 / Q8_0 files): a kernel of its own, so that the F16 kernel's code and registers stay as tuned
 __global__ __launch_bounds__(MG_THREADS) void k_decode_mega_q(const wa_mega_args A) {
@@ -1586,7 +1662,7 @@ __global__ __launch_bounds__(MG_THREADS) void k_decode_mega_q(const wa_mega_args
 
 size_t wa_mega_lds_bytes() {
     const size_t s_self  = (size_t) WA_MEGA_MAX_KV * 64 * 2 * 2 + MG_ATT_SMEM(WA_MEGA_MAX_KV);
-    const size_t s_cross = 32768;       // 14.9 KB of the role's arrays, then 2 x 8 KB at 16 KB for mg_attn_finish's split form
+    const size_t s_cross = MG_CX_END;   // 14.9 KB of the role's arrays, then 2 x 8 KB at 16 KB for mg_attn_finish's split form, then its LayerNorm
     const size_t s_gemv  = MG_PICK_OFF;
     size_t m = s_self > s_cross ? s_self : s_cross;
     m = m > s_gemv ? m : s_gemv;
@@ -1604,7 +1680,33 @@ bool wa_launch_decode_mega(hipStream_t s, const wa_mega_args & a, int n_wg) {
             hipFuncSetAttribute((const void *) k_decode_mega_q, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds) != hipSuccess) return false;
         attr_set[dev & 63] = true;
     }
+    if (MG_DEFER && !a.quant && a.d == 768) return wa_launch_decode_mega_cq(s, a, n_wg, lds);
     if (a.quant) hipLaunchKernelGGL(k_decode_mega_q, dim3(n_wg), dim3(MG_THREADS), lds, s, a);
     else         hipLaunchKernelGGL(k_decode_mega, dim3(n_wg), dim3(MG_THREADS), lds, s, a);
     return hipGetLastError() == hipSuccess;
 }
+#else
+// F16 models of d = 768 (ggml-small): the cross-attention role computes its own query (the CQ forms of both roles).  A kernel of its own,
+// in a code object of its own (this file built with -DMG_CQ_TU): beside k_decode_mega it moved the other widths' code (tiny 0.142 -> 0.145,
+// base 0.203 -> 0.207 ms per token), and the d < 768 instantiation of the cross role spills (its rows' length is a run-time value).
+__global__ __launch_bounds__(MG_THREADS) void k_decode_mega_cq(const wa_mega_args A) {
+    int role, idx;
+    mg_role_of((int) gridDim.x, A.n_head, (int) blockIdx.x, role, idx);
+    const mg_kargs Ap = (mg_kargs) __builtin_amdgcn_kernarg_segment_ptr();
+    if (role == 0)      mg_role_gemv<2, 24, false, true>(Ap, idx);
+    else if (role == 1) mg_role_self(Ap, idx);
+    else                mg_role_cross<false, 24>(Ap, idx);
+}
+
+bool wa_launch_decode_mega_cq(hipStream_t s, const wa_mega_args & a, int n_wg, size_t lds) {
+    static bool attr_set[64] = {};
+    int dev = 0;
+    (void) hipGetDevice(&dev);
+    if (!attr_set[dev & 63]) {
+        if (hipFuncSetAttribute((const void *) k_decode_mega_cq, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds) != hipSuccess) return false;
+        attr_set[dev & 63] = true;
+    }
+    hipLaunchKernelGGL(k_decode_mega_cq, dim3(n_wg), dim3(MG_THREADS), lds, s, a);
+    return hipGetLastError() == hipSuccess;
+}
+#endif
