@@ -50,6 +50,8 @@ struct wa_epi {
 
 // C[M x N] = A[M x K] (f16, row stride lda) * W[N x K]^T (f16, row stride ldw); K % 32 == 0.
 // MFMA path (any M); rows/cols beyond M/N are neither read out of bounds (clamped) nor stored.
+// Modes: F16, ENC_QKV, GELU_F16, RESID, CONV2, F32, CROSS_KV, DEC_QKV.  GELU_F32 and ATTN_PV have no case in its switches: such a
+// call launches nothing and returns normally (those products run in wa_exact.hip / wa_quant.hip only).
 void wa_launch_gemm(hipStream_t stream, wa_epi_mode mode, const wa_f16 * A, int lda, const wa_f16 * W, int ldw,
                     int M, int N, int K, const wa_epi & e);
 
