@@ -591,7 +591,7 @@ struct wa_batch_groups {
     std::vector<wa_batcher *> bats;
     wa_batch_groups(whisper_context * c, const std::vector<whisper_state *> & m) : ctx(c), members(m) {
         static const bool off = getenv("WHISPER_AMD_NO_BATCHER") != nullptr;
-        int group = !members.empty() && members[0]->rows_enabled ? WA_MAX_DECODERS : 4;
+        int group = !members.empty() && members[0]->rows_form.enabled() ? WA_MAX_DECODERS : 4;
         if (const char * g = getenv("WHISPER_AMD_BATCH_GROUP")) group = std::max(2, std::min(WA_MAX_DECODERS, atoi(g)));
         for (size_t i0 = 0; i0 < members.size() && !off; i0 += group) {
             const size_t n = std::min((size_t) group, members.size() - i0);

@@ -81,6 +81,12 @@ void wa_kv_seq_cp(wa_kv_cache & c, int32_t src, int32_t dst, int32_t p0, int32_t
 // -------------------------------------------------------------------------------------------------
 // decoder pass
 // -------------------------------------------------------------------------------------------------
+// the audio context a state decodes against: the one it encoded, else the one its next encode takes (whisper.cpp:2000)
+static int audio_ctx(const whisper_state & st) { return st.enc_n_ctx > 0 ? st.enc_n_ctx : (st.exp_n_audio_ctx > 0 ? st.exp_n_audio_ctx : st.ctx->model.hp.n_audio_ctx); }
+// the one it encoded, else the model's: the key of the captured single-token graph and the debug / probe entries keep this form - they may run on
+// a state that was never encoded, where the two differ once a whisper_full call has set audio_ctx
+static int encoded_ctx(const whisper_state & st) { return st.enc_n_ctx > 0 ? st.enc_n_ctx : st.ctx->model.hp.n_audio_ctx; }
+
 // small-M products stream the weights once (GEMV, HBM-bound, reference summation order);
 // larger M (prompt): reference-order VALU GEMM, or the MFMA GEMM when flash_attn is on
 // LayerNorm followed by a projection: one fused launch for M <= 8, LayerNorm kernel + GEMM otherwise
@@ -112,7 +118,7 @@ static void decode_launch(whisper_context & ctx, whisper_state & st, int n_token
     auto & kv = st.kv_self;
     const int n_vocab = hp.n_vocab;
     const int d = hp.n_text_state, H = hp.n_text_head;
-    const int T = st.enc_n_ctx > 0 ? st.enc_n_ctx : (st.exp_n_audio_ctx > 0 ? st.exp_n_audio_ctx : hp.n_audio_ctx);
+    const int T = audio_ctx(st);
     hipStream_t s = st.stream;
 
     wa_launch_dec_embed(s, st.d_tok, st.d_pos, n_tokens, d, m.d_te, m.d_pe, st.d_dx);
@@ -178,7 +184,7 @@ static void decode_launch_quant(whisper_context & ctx, whisper_state & st, int n
     const auto & hp = m.hp;
     auto & kv = st.kv_self;
     const int n_vocab = hp.n_vocab, d = hp.n_text_state, H = hp.n_text_head;
-    const int T = st.enc_n_ctx > 0 ? st.enc_n_ctx : (st.exp_n_audio_ctx > 0 ? st.exp_n_audio_ctx : hp.n_audio_ctx);
+    const int T = audio_ctx(st);
     hipStream_t s = st.stream;
     auto qmul = [&](wa_epi_mode mode, const wa_lin & L, int M, const wa_epi & e) {      // operand already in d_q8 / d_q8d
         wa_launch_qgemm_exact(s, mode, st.d_q8, st.d_q8d, M, L.qs, L.qd, L.n_out, L.n_in, e);
@@ -238,8 +244,7 @@ static void decode_launch_quant(whisper_context & ctx, whisper_state & st, int n
 }
 
 // -------------------------------------------------------------------------------------------------
-// the single-token pass as ONE launch (wa_mega.hip).  Only one such launch may be in flight per device: its
-// workgroups wait for each other, so two of them interleaved by the dispatcher could each hold CUs the other needs.
+// the single-token pass as ONE launch (wa_mega.hip), one such launch in flight per device (wa_one_launch.h).
 // Returns 1 = done (logits in h_logits_pinned), 0 = not applicable / gave up (caller runs the launch sequence).
 // -------------------------------------------------------------------------------------------------
 // One slot per DEVICE (two devices never wait for each other).  Ownership rules: mega_step and the probes hold it for one launch +
@@ -247,41 +252,51 @@ static void decode_launch_quant(whisper_context & ctx, whisper_state & st, int n
 // st.spec_owner, so that wa_spec_end releases exactly what wa_spec_begin took - also on every failure path (a begin that fails after
 // taking the slot gives it back itself).  While a window owns the slot, other states' single-token steps on that device wait; steps
 // that do not need the slot (several tokens, masks, beams: the launch sequence) run concurrently on their own streams.
-static std::mutex & mega_slot(int device) { static std::mutex m[64]; return m[(unsigned) device & 63u]; }
+static wa_device_slot & device_slot(int device) { static wa_device_slot s[64]; return s[(unsigned) device & 63u]; }
 // (tests) every cross soft-max total of the several-rows kernel through its in-order path
 static int rows_force_inorder() { static const int v = getenv("WHISPER_AMD_ROWS_FORCE_INORDER") != nullptr ? 1 : 0; return v; }
 
-// a one-launch form gave up at a hand-off: pause it (the launch sequence serves meanwhile), try again later, give up for good after 8 time-outs
-static void one_launch_timeout(int & pause, int & timeouts, bool & enabled, const char * what, unsigned status) {
-    timeouts += 1;
-    if (timeouts > 8) { enabled = false; WA_WARN("%s: gave up at hand-off %u for the 9th time - using the launch sequence from now on\n", what, status); return; }
-    pause = 32 << std::min(timeouts, 6);
-    WA_WARN("%s: gave up at hand-off %u - the launch sequence serves the next %d decoder passes, then it is tried again\n", what, status, pause);
+// a one-launch form gave up at a hand-off: it pauses (the launch sequence serves meanwhile) and is tried again later, or it is off for good
+static void form_timed_out(wa_launch_form & form, const char * what, unsigned status) {
+    if (const int pause = form.timed_out()) WA_WARN("%s: gave up at hand-off %u - the launch sequence serves the next %d decoder passes, then it is tried again\n", what, status, pause);
+    else WA_WARN("%s: gave up at hand-off %u for the 9th time - using the launch sequence from now on\n", what, status);
+}
+// the number a state's next one-launch launch echoes beside its status word: the host takes the launch's results only with that number there
+static unsigned next_seq(whisper_state & st) { st.mega_seq += 1; if (st.mega_seq == 0) st.mega_seq = 1; return st.mega_seq; }
+
+// The model and state part of a one-launch step's arguments (wa_mega_args and wa_rows_args name these fields alike), everything else zeroed:
+// audio context T against `st`'s cross K / V, `kv_size` self-attention cells per layer.  false: the kernels cannot take this T.
+template <class A> static bool one_launch_args(const whisper_context & ctx, const whisper_state & st, A & a, int T, uint32_t kv_size) {
+    const auto & m = ctx.model; const auto & hp = m.hp;
+    if (T < 1 || (T >> 5) > 47 || T > st.cross_tpad) return false;
+    memset(&a, 0, sizeof(a));
+    a.layers = (const wa_mega_layer *) m.d_mega_layers;
+    a.n_layer = hp.n_text_layer; a.d = hp.n_text_state; a.n_head = hp.n_text_head; a.n_vocab = hp.n_vocab; a.eps = hp.eps; a.rn_d = 1.0 / (double) hp.n_text_state;
+    a.te = m.d_te; a.pe = m.d_pe; a.lnf_w = m.d_ln.w; a.lnf_b = m.d_ln.b; a.gelu = m.d_gelu; a.quant = m.wtype != 1 ? 1 : 0;
+    if (a.quant) { a.te = (const wa_f16 *) m.te_q.qs; a.te_d = m.te_q.qd; }
+    a.kv_layer_stride = (unsigned long long) kv_size * hp.n_text_state;
+    a.cross_layer_stride = (unsigned long long) hp.n_text_head * st.cross_tpad * 64; a.cross_tpad = st.cross_tpad; a.T = T;
+    a.kq_scale = pow(float(64), -0.25);       // whisper.cpp:2522
+    a.token_beg = ctx.vocab.token_beg; a.token_eot = ctx.vocab.token_eot;
+    return true;
+}
+// the run-ahead fields of launch k of a window (wa_mega_args, wa_rows_row: the same names).  token < 0: the launch picks its token from the
+// records launch k - 1 left.  Records and sampling state alternate by the parity of k.
+template <class R> static void set_ahead(R & r, int k, int token, unsigned * const * rec, int * const * ps, const unsigned * smask, const wa_spec_state & after) {
+    const int p = k & 1;
+    r.spec = token < 0 ? 1 : 0;
+    r.rec_in = rec[p ^ 1]; r.rec_out = rec[p]; r.ps_in = ps[p ^ 1]; r.ps_out = ps[p]; r.smask = smask;
+    r.s_last = after.last; r.s_penult = after.penult; r.s_seek_delta = after.seek_delta; r.s_has_ts = after.has_ts;
 }
 
 static bool mega_args(whisper_context & ctx, whisper_state & st, wa_mega_args & a, int token, int pos, int n_kv, int kv_head) {
-    const auto & m = ctx.model;
-    const auto & hp = m.hp;
-    const int T = st.enc_n_ctx > 0 ? st.enc_n_ctx : (st.exp_n_audio_ctx > 0 ? st.exp_n_audio_ctx : hp.n_audio_ctx);
-    if (!st.mega_enabled || st.mega_pause > 0 || n_kv > WA_MEGA_KV_ROOM || n_kv < 1 || kv_head < 0 || kv_head >= n_kv || T < 1 || (T >> 5) > 47 || T > st.cross_tpad) return false;
-    a.layers = (const wa_mega_layer *) m.d_mega_layers;
-    a.n_layer = hp.n_text_layer; a.d = hp.n_text_state; a.n_head = hp.n_text_head; a.n_vocab = hp.n_vocab; a.eps = hp.eps; a.rn_d = 1.0 / (double) hp.n_text_state;
-    a.te = m.d_te; a.pe = m.d_pe; a.lnf_w = m.d_ln.w; a.lnf_b = m.d_ln.b; a.gelu = m.d_gelu;
-    a.quant = m.wtype != 1 ? 1 : 0; a.te_d = nullptr;
-    if (a.quant) { a.te = (const wa_f16 *) m.te_q.qs; a.te_d = m.te_q.qd; }
-    a.kv_k = st.kv_self.k; a.kv_v = st.kv_self.v; a.kv_layer_stride = (unsigned long long) st.kv_self.size * hp.n_text_state;
-    a.cross_k = st.d_cross_k; a.cross_v = st.d_cross_v;
-    a.cross_layer_stride = (unsigned long long) hp.n_text_head * st.cross_tpad * 64; a.cross_tpad = st.cross_tpad; a.T = T;
-    a.granules = st.d_mega_gr; a.edge_stride = 4 * hp.n_text_state; a.cross_gr = st.d_mega_cgr;      // (4 d: the quantised form hands the MLP's hidden row over in F32)
-    a.logits = st.d_mega_out; a.status = st.d_mega_status; a.dbg = nullptr;
-    a.token = token; a.pos = pos; a.n_kv = n_kv; a.kv_head = kv_head;
-    a.spec = 0; a.rec_in = st.d_mega_rec[1]; a.rec_out = st.d_mega_rec[0]; a.n_rec = std::min(m.n_cu, 256);
-    a.ps_in = st.d_mega_ps[1]; a.ps_out = st.d_mega_ps[0]; a.smask = st.d_mega_smask;
-    a.token_beg = ctx.vocab.token_beg; a.token_eot = ctx.vocab.token_eot;
-    a.s_last = token; a.s_penult = -1; a.s_seek_delta = 0; a.s_has_ts = 0;
-    a.kq_scale = pow(float(64), -0.25);       // whisper.cpp:2522
-    st.mega_seq += 1; if (st.mega_seq == 0) st.mega_seq = 1;
-    a.seq = st.mega_seq;
+    if (n_kv > WA_MEGA_KV_ROOM || n_kv < 1 || kv_head < 0 || kv_head >= n_kv || !one_launch_args(ctx, st, a, audio_ctx(st), st.kv_self.size)) return false;
+    a.kv_k = st.kv_self.k; a.kv_v = st.kv_self.v; a.cross_k = st.d_cross_k; a.cross_v = st.d_cross_v;
+    a.granules = st.d_mega_gr; a.edge_stride = 4 * ctx.model.hp.n_text_state; a.cross_gr = st.d_mega_cgr;      // (4 d: the quantised form hands the MLP's hidden row over in F32)
+    a.logits = st.d_mega_out; a.status = st.d_mega_status;
+    a.token = token; a.pos = pos; a.n_kv = n_kv; a.kv_head = kv_head; a.n_rec = std::min(ctx.model.n_cu, 256);
+    set_ahead(a, 0, 0, st.d_mega_rec, st.d_mega_ps, st.d_mega_smask, { token, -1, 0, 0 });      // a plain step: launch 0, the state after `token`
+    a.seq = next_seq(st);
     return true;
 }
 
@@ -293,11 +308,11 @@ static int mega_step(whisper_context & ctx, whisper_state & st, int token, int p
     unsigned status = 0, echo = 0;
     {
         // (a member of a lock-step group never WAITS for the slot: its group may hold it for the others' run-ahead windows, and they wait for this member)
-        std::unique_lock<std::mutex> lk(mega_slot(ctx.device), std::defer_lock);
-        if (st.batcher) { if (!lk.try_lock()) return 0; } else lk.lock();
-        if (!wa_launch_decode_mega(s, a, std::min(ctx.model.n_cu, 256))) { st.mega_enabled = false; return 0; }
+        wa_slot_guard slot(device_slot(ctx.device), st.batcher == nullptr);
+        if (!slot.held()) return 0;
+        if (!wa_launch_decode_mega(s, a, std::min(ctx.model.n_cu, 256))) { st.mega_form.disable(); return 0; }
         (void) hipMemcpyAsync(st.h_logits_pinned, st.d_mega_out, ((size_t) n_vocab + 3) * sizeof(float), hipMemcpyDeviceToHost, s);
-        if (!WA_HIP_OK(hipStreamSynchronize(s))) { st.mega_enabled = false; return 0; }
+        if (!WA_HIP_OK(hipStreamSynchronize(s))) { st.mega_form.disable(); return 0; }
         status = ((const unsigned *) st.h_logits_pinned)[n_vocab];
         echo = ((const unsigned *) st.h_logits_pinned)[n_vocab + 2];
     }
@@ -305,7 +320,7 @@ static int mega_step(whisper_context & ctx, whisper_state & st, int token, int p
     (void) hipMemsetAsync(st.d_mega_status, 0, sizeof(unsigned), s);
     if (status == WA_MEGA_REDO) return 0;       // an uncertifiable soft-max sum (~1e-9 per soft-max): this token goes through the launch sequence
     // a hand-off timed out (workgroups not co-resident?), or the launch never ran (no echo of its number): the logits are not this step's
-    one_launch_timeout(st.mega_pause, st.mega_timeouts, st.mega_enabled, "one-launch decode step", status);
+    form_timed_out(st.mega_form, "one-launch decode step", status);
     return 0;
 }
 
@@ -315,57 +330,56 @@ static int mega_step(whisper_context & ctx, whisper_state & st, int token, int p
 // Returns 1 = done (logits rows in bst.h_logits_pinned), 0 = not applicable / gave up for this pass (caller runs the launch sequence).
 // The slot is taken with try_lock by default: a step that finds another one-launch pass on the device just takes the launch sequence.
 // -------------------------------------------------------------------------------------------------
-static int rows_step(whisper_context & ctx, whisper_state & bst, int B, const wa_rows_row * rows, int n_out, const int32_t * out_row, int T, int cross_tpad,
-                     uint32_t kv_size, bool wait_slot) {
-    const auto & m = ctx.model;
-    const auto & hp = m.hp;
-    if (bst.rows_pause > 0) { bst.rows_pause -= 1; return 0; }
-    if (B < 1 || B > WA_ROWS_MAX || n_out < 1 || n_out > B || !bst.rows_enabled || T < 1 || (T >> 5) > 47 || T > cross_tpad) return 0;
+// A several-rows launch of rows[0..B), every row's logits wanted: the model and state part on `own`'s granules (`kv_size` cells per layer), and
+// own's next launch number.  false: the form cannot serve this shape.
+static bool rows_args(whisper_context & ctx, whisper_state & own, wa_rows_args & a, int B, const wa_rows_row * rows, int T, uint32_t kv_size) {
+    const auto & hp = ctx.model.hp;
+    if (B < 1 || B > WA_ROWS_MAX || !one_launch_args(ctx, own, a, T, kv_size)) return false;
     for (int i = 0; i < B; ++i)
-        if (rows[i].n_kv < 1 || rows[i].n_kv > WA_ROWS_MAXKV || rows[i].kv_head < 0 || rows[i].kv_head >= rows[i].n_kv) return 0;
-    const int n_wg = std::min(m.n_cu, 256);
-    wa_rows_args a;
-    memset(&a, 0, sizeof(a)); a.force_inorder = rows_force_inorder();
-    const int quant = m.wtype != 1 ? 1 : 0;
-    if (wa_rows_lds_bytes(hp.n_text_state, B, n_wg, quant, &a.slot_bytes) == 0) return 0;
-    if (!wa_rows_prepare(ctx, bst)) return 0;
-    a.layers = (const wa_mega_layer *) m.d_mega_layers;
-    a.n_layer = hp.n_text_layer; a.d = hp.n_text_state; a.n_head = hp.n_text_head; a.n_vocab = hp.n_vocab; a.eps = hp.eps; a.rn_d = 1.0 / (double) hp.n_text_state;
-    a.te = m.d_te; a.pe = m.d_pe; a.lnf_w = m.d_ln.w; a.lnf_b = m.d_ln.b; a.gelu = m.d_gelu; a.te_d = nullptr; a.quant = quant;
-    if (quant) { a.te = (const wa_f16 *) m.te_q.qs; a.te_d = m.te_q.qd; }
-    a.kv_layer_stride = (unsigned long long) kv_size * hp.n_text_state;
-    a.cross_layer_stride = (unsigned long long) hp.n_text_head * cross_tpad * 64; a.cross_tpad = cross_tpad; a.T = T;
-    a.granules = bst.d_rows_gr; a.row_gr = 2 * hp.n_text_state; a.cross_gr = bst.d_rows_cgr;
-    a.logits = bst.d_logits; a.status = bst.d_rows_status; a.row_status = bst.d_rows_status + 4; a.dbg = nullptr;
-    a.kq_scale = pow(float(64), -0.25);
-    a.B = B;
-    for (int i = 0; i < B; ++i) a.rows[i] = rows[i];
-    a.n_out = n_out;
-    for (int i = 0; i < n_out; ++i) a.out_row[i] = out_row ? out_row[i] : i;
-    bst.mega_seq += 1; if (bst.mega_seq == 0) bst.mega_seq = 1;
-    a.seq = bst.mega_seq;
-    hipStream_t s = bst.stream;
-    unsigned * h_status = (unsigned *) (bst.h_logits_pinned + (size_t) WA_MAX_DECODERS * hp.n_vocab);      // (the staging buffer has 64 spare words)
-    std::unique_lock<std::mutex> lk(mega_slot(ctx.device), std::defer_lock);
-    if (wait_slot) lk.lock(); else if (!lk.try_lock()) return 0;
-    // the logits rows go straight into the pinned staging rows (whole-line stores, wa_rows.hip: mb_logits_out); WHISPER_AMD_ROWS_HOST_OUT=0: device rows + a copy
-    static const bool host_out_env = getenv("WHISPER_AMD_ROWS_HOST_OUT") == nullptr || atoi(getenv("WHISPER_AMD_ROWS_HOST_OUT")) != 0;
+        if (rows[i].n_kv < 1 || rows[i].n_kv > WA_ROWS_MAXKV || rows[i].kv_head < 0 || rows[i].kv_head >= rows[i].n_kv) return false;
+    if (wa_rows_lds_bytes(hp.n_text_state, B, std::min(ctx.model.n_cu, 256), a.quant, &a.slot_bytes) == 0 || !wa_rows_prepare(ctx, own)) return false;
+    a.force_inorder = rows_force_inorder();
+    a.granules = own.d_rows_gr; a.row_gr = 2 * hp.n_text_state; a.cross_gr = own.d_rows_cgr;
+    a.B = a.n_out = B;
+    for (int i = 0; i < B; ++i) { a.rows[i] = rows[i]; a.out_row[i] = i; }
+    a.seq = next_seq(own);
+    return true;
+}
+// the device address of pinned host rows that a several-rows launch stores its logits rows to (whole-line stores, wa_rows.hip: mb_logits_out);
+// null with the switch below set to 0: the rows go through device memory and a copy
+static float * rows_host_out(float * h_rows) {
+    static const bool on = [] { const char * e = getenv("WHISPER_AMD_ROWS_HOST_OUT"); return e == nullptr || atoi(e) != 0; }();
     float * h_dev = nullptr;
-    const bool host_out = host_out_env && hipHostGetDevicePointer((void **) &h_dev, bst.h_logits_pinned, 0) == hipSuccess && h_dev;
-    if (host_out) a.logits = h_dev;
-    (void) hipMemsetAsync(bst.d_rows_status + 4, 0, WA_ROWS_MAX * sizeof(unsigned), s);
-    if (!wa_launch_decode_rows(s, a, n_wg)) { bst.rows_enabled = false; return 0; }
-    if (!host_out) (void) hipMemcpyAsync(bst.h_logits_pinned, bst.d_logits, (size_t) n_out * hp.n_vocab * sizeof(float), hipMemcpyDeviceToHost, s);
-    (void) hipMemcpyAsync(h_status, bst.d_rows_status, 12 * sizeof(unsigned), hipMemcpyDeviceToHost, s);
-    if (!WA_HIP_OK(hipStreamSynchronize(s))) { bst.rows_enabled = false; return 0; }
-    lk.unlock();
+    return on && hipHostGetDevicePointer((void **) &h_dev, h_rows, 0) == hipSuccess ? h_dev : nullptr;
+}
+
+static int rows_step(whisper_context & ctx, whisper_state & bst, int B, const wa_rows_row * rows, int n_out, const int32_t * out_row, bool wait_slot) {
+    const int n_vocab = ctx.model.hp.n_vocab;
+    wa_rows_args a;
+    if (!bst.rows_form.take_pass() || n_out < 1 || n_out > B || !rows_args(ctx, bst, a, B, rows, audio_ctx(bst), bst.kv_self.size)) return 0;
+    a.logits = bst.d_logits; a.status = bst.d_rows_status; a.row_status = bst.d_rows_status + 4;
+    a.n_out = n_out;
+    if (out_row) for (int i = 0; i < n_out; ++i) a.out_row[i] = out_row[i];
+    hipStream_t s = bst.stream;
+    unsigned * h_status = (unsigned *) (bst.h_logits_pinned + (size_t) WA_MAX_DECODERS * n_vocab);      // (the staging buffer has 64 spare words)
+    {
+        wa_slot_guard slot(device_slot(ctx.device), wait_slot);
+        if (!slot.held()) return 0;
+        float * h_dev = rows_host_out(bst.h_logits_pinned);      // the logits rows straight into the pinned staging rows, or device rows + a copy
+        if (h_dev) a.logits = h_dev;
+        (void) hipMemsetAsync(bst.d_rows_status + 4, 0, WA_ROWS_MAX * sizeof(unsigned), s);
+        if (!wa_launch_decode_rows(s, a, std::min(ctx.model.n_cu, 256))) { bst.rows_form.disable(); return 0; }
+        if (!h_dev) (void) hipMemcpyAsync(bst.h_logits_pinned, bst.d_logits, (size_t) n_out * n_vocab * sizeof(float), hipMemcpyDeviceToHost, s);
+        (void) hipMemcpyAsync(h_status, bst.d_rows_status, 12 * sizeof(unsigned), hipMemcpyDeviceToHost, s);
+        if (!WA_HIP_OK(hipStreamSynchronize(s))) { bst.rows_form.disable(); return 0; }
+    }
     unsigned status = h_status[0]; const unsigned echo = h_status[1];
     for (int i = 0; i < B && status == 0; ++i) if (h_status[4 + i] != 0) status = WA_MEGA_REDO;      // (one caller for all rows here: any row to be redone sends the pass back)
     if (status == 0 && echo == a.seq) { bst.n_rows_steps += 1; return 1; }
     bst.n_rows_fallback += 1;
     (void) hipMemsetAsync(bst.d_rows_status, 0, sizeof(unsigned), s);
     if (status == WA_MEGA_REDO) return 0;          // an uncertifiable soft-max sum (~1e-9 per soft-max): this pass goes through the launch sequence
-    one_launch_timeout(bst.rows_pause, bst.rows_timeouts, bst.rows_enabled, "several-rows one-launch step", status);
+    form_timed_out(bst.rows_form, "several-rows one-launch step", status);
     return 0;
 }
 
@@ -386,7 +400,7 @@ static void bspec_end(wa_batcher & b, whisper_state & st);
 
 bool wa_spec_begin(whisper_context & ctx, whisper_state & st, const std::vector<uint32_t> & bits) {
     if (st.batcher) return bspec_begin(*st.batcher, st, bits);        // a member of a lock-step group: its window runs on the group's passes
-    if (!st.mega_enabled || st.mega_pause > 0 || bits.size() > (size_t) ctx.model.hp.n_vocab / 32 + 2) return false;
+    if (!wa_window_form(st).usable() || bits.size() > (size_t) ctx.model.hp.n_vocab / 32 + 2) return false;
     if (!WA_HIP_OK(hipSetDevice(ctx.device))) return false;
     if (!st.copy_stream) {      // first use on this state
         for (int b = 0; b < 2; ++b) {
@@ -405,7 +419,7 @@ bool wa_spec_begin(whisper_context & ctx, whisper_state & st, const std::vector<
     const std::vector<uint32_t> & up = sab.empty() ? bits : sab;
     (void) hipMemcpyAsync(st.d_mega_smask, up.data(), up.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st.stream);
     if (!WA_HIP_OK(hipStreamSynchronize(st.stream))) return false;
-    mega_slot(ctx.device).lock();       // last: nothing below can fail, so a false return never leaves the slot taken
+    device_slot(ctx.device).acquire();       // last: nothing below can fail, so a false return never leaves the slot taken
     st.spec_owner = true;
     return true;
 }
@@ -416,59 +430,37 @@ void wa_spec_end(whisper_context & ctx, whisper_state & st) {
     if (st.copy_stream) (void) hipStreamSynchronize(st.copy_stream);
     (void) hipMemsetAsync(st.d_mega_smask, 0, ((size_t) st.ctx->model.hp.n_vocab / 32 + 2) * sizeof(uint32_t), st.stream);   // plain steps use no mask
     (void) hipStreamSynchronize(st.stream);
-    if (st.spec_owner) { st.spec_owner = false; mega_slot(ctx.device).unlock(); }      // idempotent: only the owner gives the slot back
+    if (st.spec_owner) { st.spec_owner = false; device_slot(ctx.device).release(); }      // idempotent: only the owner gives the slot back
 }
 
 // the window's launch for a state whose single-token step is the several-rows kernel with one row (single_via_rows): same records, sampling state and
 // suppression bits as the k_decode_mega form; behind the logits: [n_vocab] status, [+1] the launch's sequence number, [+2] the token decoded, [+4] the row's status
 static bool spec_launch_rows(whisper_context & ctx, whisper_state & st, int k, int pos, int token, const wa_spec_state & after) {
-    const auto & m = ctx.model; const auto & hp = m.hp;
-    const int T = st.enc_n_ctx > 0 ? st.enc_n_ctx : (st.exp_n_audio_ctx > 0 ? st.exp_n_audio_ctx : hp.n_audio_ctx);
-    const int n_wg = std::min(m.n_cu, 256), quant = m.wtype != 1 ? 1 : 0, n_kv = pos + 1;
-    if (!st.rows_enabled || st.rows_pause > 0 || n_kv > WA_ROWS_MAXKV || T < 1 || (T >> 5) > 47 || T > st.cross_tpad) return false;
+    const int n_vocab = ctx.model.hp.n_vocab, b = k & 1;
+    wa_rows_row r = { st.kv_self.k, st.kv_self.v, st.d_cross_k, st.d_cross_v, nullptr, pos + 1, pos, token < 0 ? 0 : token, pos };       // greedy steady state: cell == position
+    set_ahead(r, k, token, st.d_mega_rec, st.d_mega_ps, st.d_mega_smask, after);
     wa_rows_args a;
-    memset(&a, 0, sizeof(a)); a.force_inorder = rows_force_inorder();
-    if (wa_rows_lds_bytes(hp.n_text_state, 1, n_wg, quant, &a.slot_bytes) == 0 || !wa_rows_prepare(ctx, st)) return false;
-    const int b = k & 1;
-    a.layers = (const wa_mega_layer *) m.d_mega_layers;
-    a.n_layer = hp.n_text_layer; a.d = hp.n_text_state; a.n_head = hp.n_text_head; a.n_vocab = hp.n_vocab; a.eps = hp.eps; a.rn_d = 1.0 / (double) hp.n_text_state;
-    a.te = m.d_te; a.pe = m.d_pe; a.lnf_w = m.d_ln.w; a.lnf_b = m.d_ln.b; a.gelu = m.d_gelu; a.quant = quant;
-    if (quant) { a.te = (const wa_f16 *) m.te_q.qs; a.te_d = m.te_q.qd; }
-    a.kv_layer_stride = (unsigned long long) st.kv_self.size * hp.n_text_state;
-    a.cross_layer_stride = (unsigned long long) hp.n_text_head * st.cross_tpad * 64; a.cross_tpad = st.cross_tpad; a.T = T;
-    a.granules = st.d_rows_gr; a.row_gr = 2 * hp.n_text_state; a.cross_gr = st.d_rows_cgr;
+    if (!rows_args(ctx, st, a, 1, &r, audio_ctx(st), st.kv_self.size)) return false;
     a.logits = b ? st.d_mega_out2 : st.d_mega_out;
-    a.status = (unsigned *) (a.logits + hp.n_vocab); a.tok_out = (int *) (a.logits + hp.n_vocab + 2); a.row_status = (unsigned *) (a.logits + hp.n_vocab + 4);
-    a.kq_scale = pow(float(64), -0.25); a.B = 1; a.n_out = 1; a.out_row[0] = 0;
-    a.token_beg = ctx.vocab.token_beg; a.token_eot = ctx.vocab.token_eot;
-    wa_rows_row & r = a.rows[0];
-    r.kv_k = st.kv_self.k; r.kv_v = st.kv_self.v; r.cross_k = st.d_cross_k; r.cross_v = st.d_cross_v; r.mask = nullptr;
-    r.n_kv = n_kv; r.kv_head = pos; r.token = token < 0 ? 0 : token; r.pos = pos;       // greedy steady state: cell == position
-    r.spec = token < 0 ? 1 : 0;
-    r.rec_in = st.d_mega_rec[b ^ 1]; r.rec_out = st.d_mega_rec[b]; r.ps_in = (const int *) st.d_mega_ps[b ^ 1]; r.ps_out = (int *) st.d_mega_ps[b]; r.smask = st.d_mega_smask;
-    r.s_last = after.last; r.s_penult = after.penult; r.s_seek_delta = after.seek_delta; r.s_has_ts = after.has_ts;
-    st.mega_seq += 1; if (st.mega_seq == 0) st.mega_seq = 1;
-    a.seq = st.mega_seq;
+    a.status = (unsigned *) (a.logits + n_vocab); a.tok_out = (int *) (a.logits + n_vocab + 2); a.row_status = (unsigned *) (a.logits + n_vocab + 4);
     (void) hipMemsetAsync(a.row_status, 0, sizeof(unsigned), st.stream);
-    if (!wa_launch_decode_rows(st.stream, a, n_wg)) { st.rows_enabled = false; st.single_via_rows = false; return false; }
+    if (!wa_launch_decode_rows(st.stream, a, std::min(ctx.model.n_cu, 256))) { st.rows_form.disable(); st.single_via_rows = false; return false; }
     st.spec_seq[b] = a.seq;
     // (on the launch's own stream: beside the next launch of THIS kernel a copy on another stream gets no CU until that launch has finished - wa_batcher)
-    (void) hipMemcpyAsync(st.h_spec[b], a.logits, ((size_t) hp.n_vocab + 8) * sizeof(float), hipMemcpyDeviceToHost, st.stream);
+    (void) hipMemcpyAsync(st.h_spec[b], a.logits, ((size_t) n_vocab + 8) * sizeof(float), hipMemcpyDeviceToHost, st.stream);
     return WA_HIP_OK(hipEventRecord(st.ev_c[b], st.stream));
 }
 
 bool wa_spec_launch(whisper_context & ctx, whisper_state & st, int k, int pos, int token, const wa_spec_state & after) {
     if (st.batcher) return bspec_launch(*st.batcher, st, k, pos, token, after);
+    if (!wa_window_form(st).usable()) return false;
     if (st.single_via_rows) return spec_launch_rows(ctx, st, k, pos, token, after);
     wa_mega_args a;
     if (!mega_args(ctx, st, a, token < 0 ? 0 : token, pos, pos + 1, pos)) return false;       // greedy steady state: cell == position
     const int b = k & 1;
     a.logits = b ? st.d_mega_out2 : st.d_mega_out;
     a.status = (unsigned *) (a.logits + ctx.model.hp.n_vocab);
-    a.spec = token < 0 ? 1 : 0;
-    a.rec_in = st.d_mega_rec[b ^ 1]; a.rec_out = st.d_mega_rec[b];
-    a.ps_in = st.d_mega_ps[b ^ 1];   a.ps_out = st.d_mega_ps[b];
-    a.s_last = after.last; a.s_penult = after.penult; a.s_seek_delta = after.seek_delta; a.s_has_ts = after.has_ts;
+    set_ahead(a, k, token, st.d_mega_rec, st.d_mega_ps, st.d_mega_smask, after);
     if (!wa_launch_decode_mega(st.stream, a, a.n_rec)) return false;
     st.spec_seq[b] = a.seq;
     (void) hipEventRecord(st.ev_k[b], st.stream);
@@ -485,7 +477,8 @@ int wa_spec_wait(whisper_context & ctx, whisper_state & st, int k, int * token_u
         return rc;
     }
     const int b = k & 1, n_vocab = ctx.model.hp.n_vocab;
-    if (!WA_HIP_OK(hipEventSynchronize(st.ev_c[b]))) { st.mega_enabled = false; return -1; }
+    wa_launch_form & form = wa_window_form(st);
+    if (!WA_HIP_OK(hipEventSynchronize(st.ev_c[b]))) { form.disable(); return -1; }
     unsigned status = ((const unsigned *) st.h_spec[b])[n_vocab];
     const int i_echo = st.single_via_rows ? 1 : 2, i_tok = st.single_via_rows ? 2 : 1;          // (spec_launch_rows: the words behind the logits)
     if (status == 0 && ((const unsigned *) st.h_spec[b])[n_vocab + i_echo] != st.spec_seq[b]) status = 9999u;      // the launch never ran: not this step's logits
@@ -498,7 +491,7 @@ int wa_spec_wait(whisper_context & ctx, whisper_state & st, int k, int * token_u
         (void) hipMemsetAsync(st.d_mega_out2 + n_vocab, 0, sizeof(unsigned), st.stream);
         (void) hipStreamSynchronize(st.stream);
         if (status == WA_MEGA_REDO) return 1;
-        one_launch_timeout(st.mega_pause, st.mega_timeouts, st.mega_enabled, "one-launch decode step", status);
+        form_timed_out(form, "one-launch decode step", status);
         return -1;
     }
     st.logits.resize(n_vocab);
@@ -651,7 +644,7 @@ static void batcher_release_device(wa_batcher & b) {       // (b.m held) give th
     if (!b.slot_held) return;
     for (const auto & sl : b.slots) if (sl.st && (sl.ahead || !sl.q.empty())) return;
     b.slot_held = false;
-    mega_slot(b.ctx->device).unlock();
+    device_slot(b.ctx->device).release();
 }
 
 // The requests of a group as ONE launch (wa_rows.hip), asynchronously: launch, copy the rows out behind it, record an event - no host wait here.
@@ -659,61 +652,39 @@ static void batcher_release_device(wa_batcher & b) {       // (b.m held) give th
 static bool batcher_launch_async(wa_batcher & b, wa_bslot ** run, int B, int T, uint32_t kv_size) {
     whisper_context & ctx = *b.ctx;
     whisper_state & bs = *b.bst;
-    const auto & m = ctx.model; const auto & hp = m.hp;
-    if (!bs.rows_enabled || bs.rows_pause > 0 || !batcher_async_prepare(b) || T < 1 || (T >> 5) > 47 || T > bs.cross_tpad) return false;
-    const int n_wg = std::min(m.n_cu, 256), quant = m.wtype != 1 ? 1 : 0;
-    wa_rows_args a;
-    memset(&a, 0, sizeof(a)); a.force_inorder = rows_force_inorder();
-    if (wa_rows_lds_bytes(hp.n_text_state, B, n_wg, quant, &a.slot_bytes) == 0 || !wa_rows_prepare(ctx, bs)) return false;
-    for (int i = 0; i < B; ++i) { const wa_breq & r = *batcher_next(*run[i]); if (r.n_kv < 1 || r.n_kv > WA_ROWS_MAXKV || r.kv_head < 0 || r.kv_head >= r.n_kv) return false; }
-    const int par = (int) (b.n_launched & 1);
-    a.layers = (const wa_mega_layer *) m.d_mega_layers;
-    a.n_layer = hp.n_text_layer; a.d = hp.n_text_state; a.n_head = hp.n_text_head; a.n_vocab = hp.n_vocab; a.eps = hp.eps; a.rn_d = 1.0 / (double) hp.n_text_state;
-    a.te = m.d_te; a.pe = m.d_pe; a.lnf_w = m.d_ln.w; a.lnf_b = m.d_ln.b; a.gelu = m.d_gelu; a.quant = quant;
-    if (quant) { a.te = (const wa_f16 *) m.te_q.qs; a.te_d = m.te_q.qd; }
-    a.kv_layer_stride = (unsigned long long) kv_size * hp.n_text_state;
-    a.cross_layer_stride = (unsigned long long) hp.n_text_head * bs.cross_tpad * 64; a.cross_tpad = bs.cross_tpad; a.T = T;
-    a.granules = bs.d_rows_gr; a.row_gr = 2 * hp.n_text_state; a.cross_gr = bs.d_rows_cgr;
-    // the logits rows go straight into the pinned host rows (whole 256-byte stores, wa_rows.hip: mb_logits_out): kernel + 15 us instead of kernel - 30 us + a
-    // 63 us copy per pass (WHISPER_AMD_ROWS_HOST_OUT=0: through device memory and a copy)
-    static const bool host_out_env = getenv("WHISPER_AMD_ROWS_HOST_OUT") == nullptr || atoi(getenv("WHISPER_AMD_ROWS_HOST_OUT")) != 0;
-    float * h_dev = nullptr;
-    const bool host_out = host_out_env && hipHostGetDevicePointer((void **) &h_dev, b.h_out[par], 0) == hipSuccess && h_dev;
-    a.logits = host_out ? h_dev : b.d_out[par]; a.status = b.d_stat[par]; a.tok_out = (int *) (b.d_stat[par] + 4); a.row_status = b.d_stat[par] + 12;
-    a.kq_scale = pow(float(64), -0.25); a.B = B; a.n_out = B;
-    a.token_beg = ctx.vocab.token_beg; a.token_eot = ctx.vocab.token_eot;
+    const int n_vocab = ctx.model.hp.n_vocab;
+    if (!batcher_async_prepare(b)) return false;
+    wa_rows_row rows[WA_ROWS_MAX];
     for (int i = 0; i < B; ++i) {
-        wa_bslot & sl = *run[i];
-        wa_breq & r = *batcher_next(sl);
-        whisper_state & ms = *sl.st;
-        wa_rows_row & rr = a.rows[i];
-        rr.kv_k = ms.kv_self.k; rr.kv_v = ms.kv_self.v; rr.cross_k = ms.d_cross_k; rr.cross_v = ms.d_cross_v; rr.mask = nullptr;
-        rr.n_kv = r.n_kv; rr.kv_head = r.kv_head; rr.token = r.token < 0 ? 0 : r.token; rr.pos = r.pos;
-        a.out_row[i] = i;
-        if (r.ahead) {
-            b.n_ahead += 1; if (r.token < 0) b.n_picks += 1;
-            const int p = r.k & 1;
-            rr.spec = r.token < 0 ? 1 : 0;
-            rr.rec_in = sl.d_rec[p ^ 1]; rr.rec_out = sl.d_rec[p]; rr.ps_in = sl.d_ps[p ^ 1]; rr.ps_out = sl.d_ps[p]; rr.smask = sl.d_smask;
-            rr.s_last = r.after.last; rr.s_penult = r.after.penult; rr.s_seek_delta = r.after.seek_delta; rr.s_has_ts = r.after.has_ts;
-        }
+        const wa_bslot & sl = *run[i];
+        const wa_breq & r = *batcher_next(*run[i]);
+        rows[i] = { sl.st->kv_self.k, sl.st->kv_self.v, sl.st->d_cross_k, sl.st->d_cross_v, nullptr, r.n_kv, r.kv_head, r.token < 0 ? 0 : r.token, r.pos };
+        if (r.ahead) set_ahead(rows[i], r.k, r.token, sl.d_rec, sl.d_ps, sl.d_smask, r.after);
     }
-    bs.mega_seq += 1; if (bs.mega_seq == 0) bs.mega_seq = 1;
-    a.seq = bs.mega_seq;
-    if (!b.slot_held) { mega_slot(ctx.device).lock(); b.slot_held = true; }
+    wa_rows_args a;
+    if (!rows_args(ctx, bs, a, B, rows, T, kv_size)) return false;
+    const int par = (int) (b.n_launched & 1);
+    // the logits rows go straight into the pinned host rows (whole 256-byte stores): kernel + 15 us instead of kernel - 30 us + a 63 us copy per pass
+    float * h_dev = rows_host_out(b.h_out[par]);
+    a.logits = h_dev ? h_dev : b.d_out[par]; a.status = b.d_stat[par]; a.tok_out = (int *) (b.d_stat[par] + 4); a.row_status = b.d_stat[par] + 12;
+    if (!b.slot_held) { device_slot(ctx.device).acquire(); b.slot_held = true; }
     hipStream_t s = bs.stream;
     (void) hipMemsetAsync(b.d_stat[par] + 12, 0, WA_ROWS_MAX * sizeof(unsigned), s);
-    if (!wa_launch_decode_rows(s, a, n_wg)) { bs.rows_enabled = false; batcher_release_device(b); return false; }
+    if (!wa_launch_decode_rows(s, a, std::min(ctx.model.n_cu, 256))) { bs.rows_form.disable(); batcher_release_device(b); return false; }
     // The rows go out on the SAME stream, in front of the next pass.  (On a stream of their own they were a copy kernel running beside the next
     // pass's persistent workgroups, which starved it: 1.66 MB took 0.95 ms - the members got pass k's logits when pass k + 1 ended, and every
     // second pass started 0.4 ms late; passes alternating between two streams, so that a copy could overlap the next kernel, gave the same starved copy
     // kernel.  On the pass's stream the copy is a DMA of 63 us; by default there is none: host_out above.)
-    if (!host_out) (void) hipMemcpyAsync(b.h_out[par], b.d_out[par], (size_t) B * hp.n_vocab * sizeof(float), hipMemcpyDeviceToHost, s);
+    if (!h_dev) (void) hipMemcpyAsync(b.h_out[par], b.d_out[par], (size_t) B * n_vocab * sizeof(float), hipMemcpyDeviceToHost, s);
     (void) hipMemcpyAsync(b.h_stat[par], b.d_stat[par], 128, hipMemcpyDeviceToHost, s);
     (void) hipEventRecord(b.ev_c[par], s);
     wa_bpass & ps = b.passes[b.n_launched & 3];
     ps = wa_bpass(); ps.seq = a.seq; ps.B = B; ps.parity = par; ps.launched = true;
-    for (int i = 0; i < B; ++i) { wa_breq & r = *batcher_next(*run[i]); r.pass = b.n_launched; r.row = i; r.result = 1; }
+    for (int i = 0; i < B; ++i) {
+        wa_breq & r = *batcher_next(*run[i]);
+        if (r.ahead) { b.n_ahead += 1; if (r.token < 0) b.n_picks += 1; }
+        r.pass = b.n_launched; r.row = i; r.result = 1;
+    }
     b.n_launched += 1; b.n_steps += 1; b.n_rows += B; b.n_one_launch += 1;
     return true;
 }
@@ -776,21 +747,21 @@ static void batcher_try_launch(wa_batcher & b) {
     for (auto & sl : b.slots) if (sl.st && batcher_next(sl)) run[n++] = &sl;
     if (n == 0 || n < b.n_members) return;
     whisper_context & ctx = *b.ctx;
-    const auto & hp = ctx.model.hp;
-    // members must agree on what the kernels take as launch-uniform: cells per layer and the audio context
+    // the group's one-launch form counts every pass the group forms, whoever serves it: the form, the launch sequence or the members alone
+    const bool one_launch = b.bst->rows_form.take_pass();
+    // members must agree on what the kernels take as launch-uniform: cells per layer and the audio context (a member has encoded before it decodes)
     const whisper_state & s0 = *run[0]->st;
-    const int T = s0.enc_n_ctx > 0 ? s0.enc_n_ctx : hp.n_audio_ctx;
+    const int T = audio_ctx(s0);
     wa_bslot * ok_run[WA_MAX_DECODERS]; int B = 0;
     for (int i = 0; i < n; ++i) {
         const whisper_state & s = *run[i]->st;
-        const int Ts = s.enc_n_ctx > 0 ? s.enc_n_ctx : hp.n_audio_ctx;
-        if (s.kv_self.size == s0.kv_self.size && Ts == T && s.cross_tpad == b.bst->cross_tpad) ok_run[B++] = run[i];
+        if (s.kv_self.size == s0.kv_self.size && audio_ctx(s) == T && s.cross_tpad == b.bst->cross_tpad) ok_run[B++] = run[i];
         else batcher_next(*run[i])->result = -1;           // decoded by its own thread the ordinary way
     }
     // (tests: a pass whose launch failed must not hand out the stale contents of the staging buffer - every member then decodes alone)
     static const bool test_fail = getenv("WHISPER_AMD_TEST_FAIL_BATCH_LAUNCH") != nullptr;
     if (test_fail || !WA_HIP_OK(hipSetDevice(ctx.device))) { for (int i = 0; i < B; ++i) batcher_next(*ok_run[i])->result = -1; b.cv.notify_all(); return; }
-    if (B > 0 && !batcher_launch_async(b, ok_run, B, T, s0.kv_self.size)) {
+    if (B > 0 && !(one_launch && batcher_launch_async(b, ok_run, B, T, s0.kv_self.size))) {
         bool any_ahead = false;
         for (int i = 0; i < B; ++i) any_ahead = any_ahead || batcher_next(*ok_run[i])->ahead;
         if (any_ahead) { for (int i = 0; i < B; ++i) for (auto & r : ok_run[i]->q) if (r.pass == -1 && r.result == 0) r.result = -1; }      // (no one-launch form: every member on its own from here)
@@ -837,7 +808,7 @@ static int batcher_collect(wa_batcher & b, wa_bslot & sl, int * token_used) {
             if (trace_f) { const int * tk = (const int *) (b.h_stat[par] + 4); fprintf(stderr, "[batcher] pass %ld failed: status %u echo %u seq %u B %d tokens %d %d %d %d %d %d %d %d  logits[0][0..3] %g %g %g %g\n", r.pass, ps.status, b.h_stat[par][1], ps.seq, ps.B,
                                     tk[0], tk[1], tk[2], tk[3], tk[4], tk[5], tk[6], tk[7], b.h_out[par][0], b.h_out[par][1], b.h_out[par][2], b.h_out[par][3]); }
             (void) hipMemsetAsync(b.d_stat[par], 0, sizeof(unsigned), bs.stream);
-            if (ps.status != WA_MEGA_REDO) one_launch_timeout(bs.rows_pause, bs.rows_timeouts, bs.rows_enabled, "several-rows one-launch step (lock-step group)", ps.status);
+            if (ps.status != WA_MEGA_REDO) form_timed_out(bs.rows_form, "several-rows one-launch step (lock-step group)", ps.status);
         } else b.bst->n_rows_steps += 1;
     }
     const bool ok = ps.ok && b.h_stat[par][12 + r.row] == 0;
@@ -883,10 +854,10 @@ void wa_batcher_leave(wa_batcher * b) {
 static bool bspec_begin(wa_batcher & b, whisper_state & st, const std::vector<uint32_t> & bits) {
     whisper_context & ctx = *b.ctx;
     static const bool trace_b = getenv("WHISPER_AMD_BATCH_TRACE") != nullptr;
-    if (trace_b) fprintf(stderr, "[batcher] run-ahead window asked for: members %d rows_enabled %d pause %d\n", b.n_members, (int) b.bst->rows_enabled, b.bst->rows_pause);
+    if (trace_b) fprintf(stderr, "[batcher] run-ahead window asked for: members %d rows form usable %d\n", b.n_members, (int) b.bst->rows_form.usable());
     const size_t n_mask = (size_t) ctx.model.hp.n_vocab / 32 + 2;
     std::unique_lock<std::mutex> lk(b.m);
-    if (b.n_members < 2 || !b.bst->rows_enabled || b.bst->rows_pause > 0 || bits.size() > n_mask) return false;
+    if (b.n_members < 2 || !b.bst->rows_form.usable() || bits.size() > n_mask) return false;
     static const bool off = getenv("WHISPER_AMD_NO_RUN_AHEAD") != nullptr;
     if (off || !batcher_async_prepare(b)) return false;
     wa_bslot * sl = batcher_slot(b, st, true);
@@ -992,21 +963,18 @@ bool wa_decode(whisper_context & ctx, whisper_state & st, const wa_batch & batch
     if (steady && st.batcher && !solo) done = from_batcher = batcher_step(*st.batcher, st, h_tok[0], h_pos[0], n_kv, kv_head) == 1;
     if (!done && steady && st.single_via_rows && device_free) {        // a wide quantised model: the several-rows kernel with ONE row (wa_internal.h: single_via_rows)
         const wa_rows_row r1 = { kv.k, kv.v, st.d_cross_k, st.d_cross_v, nullptr, n_kv, kv_head, h_tok[0], h_pos[0] };
-        const int T1 = st.enc_n_ctx > 0 ? st.enc_n_ctx : (st.exp_n_audio_ctx > 0 ? st.exp_n_audio_ctx : hp.n_audio_ctx);
-        done = rows_step(ctx, st, 1, &r1, 1, nullptr, T1, st.cross_tpad, kv.size, st.batcher == nullptr) == 1;
+        done = rows_step(ctx, st, 1, &r1, 1, nullptr, st.batcher == nullptr) == 1;
     }
-    if (done) { }
-    else if (!done && steady && st.mega_enabled && st.mega_pause > 0) st.mega_pause -= 1;      // (paused after a time-out: this pass takes the launch sequence)
-    else if (!done && steady && st.mega_enabled && device_free) done = mega_step(ctx, st, h_tok[0], h_pos[0], n_kv, kv_head) == 1;
-    if (!done && !steady && n_tokens <= WA_ROWS_MAX && n_rows >= 1 && !save_aheads && st.rows_enabled && n_kv <= WA_ROWS_MAXKV && device_free) {
+    // (take_pass: a form paused after a time-out counts this pass down, which the launch sequence serves)
+    if (!done && steady && st.mega_form.take_pass() && device_free) done = mega_step(ctx, st, h_tok[0], h_pos[0], n_kv, kv_head) == 1;
+    if (!done && !steady && n_tokens <= WA_ROWS_MAX && n_rows >= 1 && !save_aheads && st.rows_form.enabled() && n_kv <= WA_ROWS_MAXKV && device_free) {
         // one token per live decoder (beam search, best_of, the bench's small batches): all rows in ONE launch (wa_rows.hip)
         if (need_mask) (void) hipMemcpyAsync(st.d_mask, h_mask, (size_t) n_tokens * n_kv, hipMemcpyHostToDevice, s);
         wa_rows_row rr[WA_MAX_DECODERS];
         for (int i = 0; i < n_tokens; ++i)
             rr[i] = { kv.k, kv.v, st.d_cross_k, st.d_cross_v, need_mask ? st.d_mask + (size_t) i * n_kv : nullptr, n_kv, kv_head + i, h_tok[i], h_pos[i] };
-        const int T = st.enc_n_ctx > 0 ? st.enc_n_ctx : (st.exp_n_audio_ctx > 0 ? st.exp_n_audio_ctx : hp.n_audio_ctx);
         static const bool wait_slot = getenv("WHISPER_AMD_ROWS_WAIT") != nullptr;
-        done = rows_step(ctx, st, n_tokens, rr, n_rows, h_rows, T, st.cross_tpad, kv.size, wait_slot) == 1;
+        done = rows_step(ctx, st, n_tokens, rr, n_rows, h_rows, wait_slot) == 1;
     }
     if (!done) {
     (void) hipMemcpyAsync(st.d_tok,  h_tok,  n_tokens * sizeof(int32_t), hipMemcpyHostToDevice, s);
@@ -1016,7 +984,7 @@ bool wa_decode(whisper_context & ctx, whisper_state & st, const wa_batch & batch
 
     const int32_t row0 = 0;
     if (st.graphs_enabled && steady) {
-        const int T = st.enc_n_ctx > 0 ? st.enc_n_ctx : hp.n_audio_ctx;
+        const int T = encoded_ctx(st);
         if (st.dec_graph && (st.dec_graph_T != T || st.dec_graph_kv_size != kv.size || st.dec_graph_kv_k != kv.k)) {
             (void) hipGraphExecDestroy(st.dec_graph); st.dec_graph = nullptr;
         }
@@ -1081,25 +1049,23 @@ extern "C" int whisper_amd_decode_step_probe(struct whisper_context * ctx, struc
     (void) hipMemcpyAsync(st->d_rows, h + 2, sizeof(int32_t), hipMemcpyHostToDevice, s);
     hipEvent_t e0, e1;
     if (!WA_HIP_OK(hipEventCreate(&e0)) || !WA_HIP_OK(hipEventCreate(&e1))) return -1;
-    if (st->mega_enabled) {     // the one-launch step: n_iters launches back to back, each with its own sequence number
-        wa_mega_args a;
-        if (mega_args(*ctx, *st, a, h[0], n_past, n_past + 1, n_past)) {
-            std::lock_guard<std::mutex> lk(mega_slot(ctx->device));
-            const int n_wg = std::min(ctx->model.n_cu, 256);
-            (void) wa_launch_decode_mega(s, a, n_wg);      // warm-up
-            (void) hipEventRecord(e0, s);
-            for (int i = 0; i < n_iters; ++i) { mega_args(*ctx, *st, a, h[0], n_past, n_past + 1, n_past); (void) wa_launch_decode_mega(s, a, n_wg); }
-            (void) hipEventRecord(e1, s);
-            if (!WA_HIP_OK(hipEventSynchronize(e1))) return -1;
-            float ms = 0.f;
-            (void) hipEventElapsedTime(&ms, e0, e1);
-            (void) hipEventDestroy(e0); (void) hipEventDestroy(e1);
-            unsigned status = 0;
-            (void) hipMemcpy(&status, st->d_mega_status, sizeof(status), hipMemcpyDeviceToHost);
-            if (status != 0) { (void) hipMemset(st->d_mega_status, 0, sizeof(unsigned)); st->mega_enabled = false; return -2; }
-            *ms_per_step = ms / n_iters;
-            return 0;
-        }
+    wa_mega_args a;
+    if (st->mega_form.usable() && mega_args(*ctx, *st, a, h[0], n_past, n_past + 1, n_past)) {     // the one-launch step: n_iters launches back to back, each with its own sequence number
+        wa_slot_guard slot(device_slot(ctx->device), true);
+        const int n_wg = std::min(ctx->model.n_cu, 256);
+        (void) wa_launch_decode_mega(s, a, n_wg);      // warm-up
+        (void) hipEventRecord(e0, s);
+        for (int i = 0; i < n_iters; ++i) { a.seq = next_seq(*st); (void) wa_launch_decode_mega(s, a, n_wg); }
+        (void) hipEventRecord(e1, s);
+        if (!WA_HIP_OK(hipEventSynchronize(e1))) return -1;
+        float ms = 0.f;
+        (void) hipEventElapsedTime(&ms, e0, e1);
+        (void) hipEventDestroy(e0); (void) hipEventDestroy(e1);
+        unsigned status = 0;
+        (void) hipMemcpy(&status, st->d_mega_status, sizeof(status), hipMemcpyDeviceToHost);
+        if (status != 0) { (void) hipMemset(st->d_mega_status, 0, sizeof(unsigned)); st->mega_form.disable(); return -2; }
+        *ms_per_step = ms / n_iters;
+        return 0;
     }
     h[3] = n_past + 1; h[4] = n_past;
     (void) hipMemcpyAsync(st->d_dyn, h + 3, 2 * sizeof(int32_t), hipMemcpyHostToDevice, s);
@@ -1141,14 +1107,14 @@ extern "C" void whisper_amd_mega_role_of(int n_wg, int n_head, int wg, int * rol
 extern "C" int whisper_amd_mega_debug(struct whisper_context * ctx, struct whisper_state * st, int token, int n_past, unsigned long long * granules_out,
                                       float * logits_out) {
     static float * d_dbg = nullptr;
-    if (!ctx || !st || !st->mega_enabled) return -1;
+    if (!ctx || !st || !st->mega_form.enabled()) return -1;
     if (!WA_HIP_OK(hipSetDevice(ctx->device))) return -1;
     wa_mega_args a;
-    if (!mega_args(*ctx, *st, a, token, n_past, n_past + 1, n_past)) return -2;
+    if (!st->mega_form.usable() || !mega_args(*ctx, *st, a, token, n_past, n_past + 1, n_past)) return -2;
     const auto & hp = ctx->model.hp;
     const size_t n_dbg = (size_t) hp.n_text_layer * hp.n_text_head * 5120 + 8192;
     if (getenv("WHISPER_AMD_MEGA_DBG")) { if (!d_dbg) (void) hipMalloc((void **) &d_dbg, n_dbg * 4); a.dbg = d_dbg; }
-    std::lock_guard<std::mutex> lk(mega_slot(ctx->device));
+    wa_slot_guard slot(device_slot(ctx->device), true);
     int n_wg = std::min(ctx->model.n_cu, 256);
     if (const char * e = getenv("WHISPER_AMD_MEGA_WG")) n_wg = std::max(2 * hp.n_text_head + 1, std::min(n_wg, atoi(e)));
     (void) wa_launch_decode_mega(st->stream, a, n_wg);
@@ -1169,32 +1135,20 @@ extern "C" int whisper_amd_mega_debug(struct whisper_context * ctx, struct whisp
 extern "C" void whisper_amd_rows_stats(struct whisper_state * st, long out[2]) {
     out[0] = st ? st->n_rows_steps : 0; out[1] = st ? st->n_rows_fallback : 0;
 }
-extern "C" int whisper_amd_rows_enabled(struct whisper_state * st) { return st && st->rows_enabled ? 1 : 0; }
+extern "C" int whisper_amd_rows_enabled(struct whisper_state * st) { return st && st->rows_form.enabled() ? 1 : 0; }
 
 static bool rows_probe_args(whisper_context & ctx, whisper_state & own, whisper_state ** sts, int B, const int * tokens, int n_past, wa_rows_args & a) {
-    const auto & m = ctx.model; const auto & hp = m.hp;
-    const int T = own.enc_n_ctx > 0 ? own.enc_n_ctx : hp.n_audio_ctx;
-    memset(&a, 0, sizeof(a)); a.force_inorder = rows_force_inorder();
-    if (B < 1 || B > WA_ROWS_MAX || !own.rows_enabled || n_past < 0 || n_past + 1 > (int) own.kv_self.size || n_past + 1 > WA_ROWS_MAXKV || (T >> 5) > 47) return false;
-    const int quant = m.wtype != 1 ? 1 : 0;
-    if (wa_rows_lds_bytes(hp.n_text_state, B, std::min(m.n_cu, 256), quant, &a.slot_bytes) == 0 || !wa_rows_prepare(ctx, own)) return false;
-    a.layers = (const wa_mega_layer *) m.d_mega_layers;
-    a.n_layer = hp.n_text_layer; a.d = hp.n_text_state; a.n_head = hp.n_text_head; a.n_vocab = hp.n_vocab; a.eps = hp.eps; a.rn_d = 1.0 / (double) hp.n_text_state;
-    a.te = m.d_te; a.pe = m.d_pe; a.lnf_w = m.d_ln.w; a.lnf_b = m.d_ln.b; a.gelu = m.d_gelu; a.quant = quant;
-    if (quant) { a.te = (const wa_f16 *) m.te_q.qs; a.te_d = m.te_q.qd; }
-    a.kv_layer_stride = (unsigned long long) own.kv_self.size * hp.n_text_state;
-    a.cross_layer_stride = (unsigned long long) hp.n_text_head * own.cross_tpad * 64; a.cross_tpad = own.cross_tpad; a.T = T;
-    a.granules = own.d_rows_gr; a.row_gr = 2 * hp.n_text_state; a.cross_gr = own.d_rows_cgr;
-    a.logits = own.d_logits; a.status = own.d_rows_status; a.row_status = own.d_rows_status + 4; a.kq_scale = pow(float(64), -0.25); a.B = B;
-    a.n_out = B; for (int i = 0; i < B; ++i) a.out_row[i] = i;
+    if (B < 1 || B > WA_ROWS_MAX || n_past + 1 > (int) own.kv_self.size) return false;
+    wa_rows_row rows[WA_ROWS_MAX];
     for (int i = 0; i < B; ++i) {
         whisper_state & ms = sts && sts[i] ? *sts[i] : own;
         if (ms.kv_self.size != own.kv_self.size || ms.cross_tpad != own.cross_tpad) return false;
-        a.rows[i] = { ms.kv_self.k, ms.kv_self.v, ms.d_cross_k, ms.d_cross_v, nullptr, n_past + 1, n_past, tokens ? tokens[i] : 100, n_past };
+        rows[i] = { ms.kv_self.k, ms.kv_self.v, ms.d_cross_k, ms.d_cross_v, nullptr, n_past + 1, n_past, tokens ? tokens[i] : 100, n_past };
     }
+    if (!rows_args(ctx, own, a, B, rows, encoded_ctx(own), own.kv_self.size)) return false;
+    a.logits = own.d_logits; a.status = own.d_rows_status; a.row_status = own.d_rows_status + 4;
     return true;
 }
-static void rows_next_seq(whisper_state & st, wa_rows_args & a) { st.mega_seq += 1; if (st.mega_seq == 0) st.mega_seq = 1; a.seq = st.mega_seq; }
 
 // B rows = the SAME (token, position n_past) of this state (cell n_past; identical rows write it identically): every row's granules must then
 // equal the one-row step's (whisper_amd_mega_debug) and every logits row the launch sequence's.  granules_out [layer][8][B][2 d], logits_out [B][n_vocab].
@@ -1205,7 +1159,6 @@ extern "C" int whisper_amd_rows_debug(struct whisper_context * ctx, struct whisp
     int toks[WA_ROWS_MAX]; for (int i = 0; i < WA_ROWS_MAX; ++i) toks[i] = token;
     wa_rows_args a;
     if (!rows_probe_args(*ctx, *st, nullptr, B, toks, n_past, a)) return -2;
-    rows_next_seq(*st, a);
     static float * d_dbg = nullptr;
     if (const char * e = getenv("WHISPER_AMD_ROWS_TRACE")) {       // stamps of workgroup `e` (tools/rows_trace.py)
         if (!d_dbg) (void) hipMalloc((void **) &d_dbg, 16384 * 4);
@@ -1214,9 +1167,9 @@ extern "C" int whisper_amd_rows_debug(struct whisper_context * ctx, struct whisp
         (void) hipMemcpy((int *) d_dbg + 4095, &twg, 4, hipMemcpyHostToDevice);
         a.dbg = d_dbg;
     }
-    std::lock_guard<std::mutex> lk(mega_slot(ctx->device));
+    wa_slot_guard slot(device_slot(ctx->device), true);
     if (!wa_launch_decode_rows(st->stream, a, std::min(ctx->model.n_cu, 256))) return -4;
-    if (a.dbg) { rows_next_seq(*st, a); (void) wa_launch_decode_rows(st->stream, a, std::min(ctx->model.n_cu, 256)); }      // (the stamps of a warm run)
+    if (a.dbg) { a.seq = next_seq(*st); (void) wa_launch_decode_rows(st->stream, a, std::min(ctx->model.n_cu, 256)); }      // (the stamps of a warm run)
     if (!WA_HIP_OK(hipStreamSynchronize(st->stream))) return -3;
     if (a.dbg) { std::vector<unsigned> h(16384); (void) hipMemcpy(h.data(), d_dbg, 16384 * 4, hipMemcpyDeviceToHost); FILE * f = fopen("gpurun_out/rows_trace.bin", "wb"); if (f) { fwrite(h.data(), 4, 16384, f); fclose(f); } else WA_WARN("%s: cannot write gpurun_out/rows_trace.bin\n", __func__); }
     const auto & hp = ctx->model.hp;
@@ -1241,11 +1194,10 @@ extern "C" int whisper_amd_rows_step_probe(struct whisper_context * ctx, struct 
     hipStream_t s = own.stream;
     hipEvent_t e0, e1;
     if (!WA_HIP_OK(hipEventCreate(&e0)) || !WA_HIP_OK(hipEventCreate(&e1))) return -1;
-    std::lock_guard<std::mutex> lk(mega_slot(ctx->device));
-    rows_next_seq(own, a);
+    wa_slot_guard slot(device_slot(ctx->device), true);
     if (!wa_launch_decode_rows(s, a, n_wg)) return -4;       // warm-up
     (void) hipEventRecord(e0, s);
-    for (int i = 0; i < n_iters; ++i) { rows_next_seq(own, a); (void) wa_launch_decode_rows(s, a, n_wg); }
+    for (int i = 0; i < n_iters; ++i) { a.seq = next_seq(own); (void) wa_launch_decode_rows(s, a, n_wg); }
     (void) hipEventRecord(e1, s);
     if (!WA_HIP_OK(hipEventSynchronize(e1))) return -3;
     float ms = 0.f;
@@ -1259,7 +1211,7 @@ extern "C" int whisper_amd_rows_step_probe(struct whisper_context * ctx, struct 
     return 0;
 }
 
-extern "C" int whisper_amd_mega_enabled(struct whisper_state * st) { return st && st->mega_enabled ? 1 : 0; }
+extern "C" int whisper_amd_mega_enabled(struct whisper_state * st) { return st && st->mega_form.enabled() ? 1 : 0; }
 
 // The same step through the launch sequence, stage by stage, with every stage's output copied out in the granule
 // layout of whisper_amd_mega_debug (values only: F32 bits, or two F16 per word) - to localise a difference.
@@ -1270,7 +1222,7 @@ extern "C" int whisper_amd_seq_debug(struct whisper_context * ctxp, struct whisp
     if (!WA_HIP_OK(hipSetDevice(ctx.device))) return -1;
     const auto & m = ctx.model; const auto & hp = m.hp;
     const int d = hp.n_text_state, H = hp.n_text_head, n_kv = n_past + 1, kv_head = n_past;
-    const int T = st.enc_n_ctx > 0 ? st.enc_n_ctx : hp.n_audio_ctx;
+    const int T = encoded_ctx(st);
     hipStream_t s = st.stream;
     auto & kv = st.kv_self;
     const int32_t h3[3] = { token, n_past, 0 };

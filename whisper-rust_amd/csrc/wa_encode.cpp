@@ -47,7 +47,7 @@ bool wa_kv_self_realloc(whisper_context & ctx, whisper_state & st, int n_cells) 
 
 // Buffers of the several-rows one-launch decode step (wa_rows.hip), on first use: only states that decode several rows pay for them.
 bool wa_rows_prepare(whisper_context & ctx, whisper_state & st) {
-    if (!st.rows_enabled) return false;
+    if (!st.rows_form.enabled()) return false;
     if (st.d_rows_gr) return true;
     const auto & hp = ctx.model.hp;
     const int dt = hp.n_text_state, Ht = hp.n_text_head;
@@ -55,7 +55,7 @@ bool wa_rows_prepare(whisper_context & ctx, whisper_state & st) {
     if (!dev_alloc(st.d_rows_gr, (size_t) hp.n_text_layer * WA_MEGA_EDGES * WA_ROWS_MAX * row_gr) ||
         !dev_alloc(st.d_rows_cgr, (size_t) hp.n_text_layer * WA_ROWS_MAX * Ht * WA_ROWS_CGR) || !dev_alloc(st.d_rows_status, 32)) {
         dev_free(st.d_rows_gr); dev_free(st.d_rows_cgr); dev_free(st.d_rows_status);
-        st.rows_enabled = false;
+        st.rows_form.disable();
         return false;
     }
     return true;
@@ -105,9 +105,9 @@ bool wa_state_alloc(whisper_context & ctx, whisper_state & st) {
     {   // one-launch decode step: needs one workgroup per CU with all of them resident, d_head 64, d <= 1280
         const char * g = getenv("WHISPER_AMD_NO_MEGA");
         const int dt = hp.n_text_state, Ht = hp.n_text_head;
-        st.mega_enabled = !(g && g[0] == '1') && ctx.model.d_mega_layers && ctx.model.n_loaded > 0 && dt == Ht * 64 && dt % 128 == 0 &&
-                          dt <= WA_MEGA_MAX_D && hp.n_audio_ctx <= 1500 && ctx.model.n_cu >= 5 * Ht + 16 && tpad <= WA_MEGA_MAX_T;
-        if (st.mega_enabled) {
+        st.mega_form = wa_launch_form(!(g && g[0] == '1') && ctx.model.d_mega_layers && ctx.model.n_loaded > 0 && dt == Ht * 64 && dt % 128 == 0 &&
+                                      dt <= WA_MEGA_MAX_D && hp.n_audio_ctx <= 1500 && ctx.model.n_cu >= 5 * Ht + 16 && tpad <= WA_MEGA_MAX_T);
+        if (st.mega_form.enabled()) {
             // logits of the step and, right behind them, the status word: one device-to-host copy per token
             if (!dev_alloc(st.d_mega_cgr, (size_t) hp.n_text_layer * Ht * WA_MEGA_CGR)) return false;
             if (!dev_alloc(st.d_mega_gr, (size_t) hp.n_text_layer * WA_MEGA_EDGES * 4 * dt) || !dev_alloc(st.d_mega_out, (size_t) hp.n_vocab + 64)) return false;
@@ -118,9 +118,9 @@ bool wa_state_alloc(whisper_context & ctx, whisper_state & st) {
             {   // the several-rows form shares the one-launch step's preconditions (its buffers come with the first such pass: wa_rows_prepare)
                 const char * r = getenv("WHISPER_AMD_NO_ROWS");
                 int slot = 0;
-                st.rows_enabled = !(r && r[0] == '1') && wa_rows_lds_bytes(dt, 2, std::min(ctx.model.n_cu, 256), ctx.model.wtype != 1 ? 1 : 0, &slot) != 0;
+                st.rows_form = wa_launch_form(!(r && r[0] == '1') && wa_rows_lds_bytes(dt, 2, std::min(ctx.model.n_cu, 256), ctx.model.wtype != 1 ? 1 : 0, &slot) != 0);
                 const char * sr = getenv("WHISPER_AMD_SINGLE_ROWS");
-                st.single_via_rows = st.rows_enabled && wa_rows_lds_bytes(dt, 1, std::min(ctx.model.n_cu, 256), ctx.model.wtype != 1 ? 1 : 0, &slot) != 0 &&
+                st.single_via_rows = st.rows_form.enabled() && wa_rows_lds_bytes(dt, 1, std::min(ctx.model.n_cu, 256), ctx.model.wtype != 1 ? 1 : 0, &slot) != 0 &&
                                      (sr ? sr[0] == '1' : (ctx.model.wtype != 1 && dt > 768));
             }
             // (the copy stream, events and pinned buffers of the host overlap are created on first use, wa_spec_begin: a state that

@@ -9,6 +9,7 @@
 #pragma once
 
 #include "../../include/whisper_amd.h"
+#include "wa_one_launch.h"
 
 #include <hip/hip_runtime.h>
 
@@ -263,10 +264,7 @@ struct whisper_state {
     float * d_mega_out = nullptr;         // [n_vocab] logits + status word
     unsigned * d_mega_status = nullptr;   // = d_mega_out + n_vocab
     unsigned mega_seq = 0;
-    bool mega_enabled = false;
-    // a hand-off time-out (e.g. a co-tenant kernel held CUs: the step's workgroups were not all resident) pauses the one-launch forms for
-    // `*_pause` decoder passes, which take the launch sequence, and then tries again (doubling the pause each time; after 8 time-outs: off)
-    int mega_pause = 0, mega_timeouts = 0, rows_pause = 0, rows_timeouts = 0;
+    wa_launch_form mega_form;                      // on / paused / off (wa_one_launch.h)
     unsigned spec_seq[2] = { 0, 0 };               // launch numbers of the two launches in flight (their echo is checked on arrival)
     // host overlap (wa_decode.cpp wa_spec_*): the device predicts the next token and decodes it while the host still
     // applies the reference's sampling rules to the previous logits; two output / record / state buffers alternate
@@ -280,7 +278,7 @@ struct whisper_state {
     // area [layer][8][head][2048], {status, sequence echo}; allocated on first use (wa_rows_prepare)
     unsigned long long * d_rows_gr = nullptr, * d_rows_cgr = nullptr;
     unsigned * d_rows_status = nullptr;
-    bool rows_enabled = false;
+    wa_launch_form rows_form;                      // on / paused / off (wa_one_launch.h)
     long n_rows_steps = 0, n_rows_fallback = 0;      // passes served by the one-launch form / sent to the launch sequence after a status
     struct wa_batcher * batcher = nullptr;   // set while this state is a member of a whisper_amd_full_batch call (wa_decode.cpp)
     bool solo_step = false;                  // the next plain step of a lock-step member is decoded by the member alone (its row of a pass asked to be redone by the launch sequence)
@@ -321,6 +319,8 @@ struct whisper_state {
     std::vector<float> aheads_cross_QKs_data;
     int aheads_n = 0;
 };
+// the form a state's single-token run-ahead window (wa_spec_*) runs on, is gated on and is charged with its time-outs
+inline wa_launch_form & wa_window_form(whisper_state & st) { return st.single_via_rows ? st.rows_form : st.mega_form; }
 
 // ---------------------------------------------------------------------------------------------
 // internal entry points
