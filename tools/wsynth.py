@@ -206,7 +206,8 @@ def model_path(shape_name: str, seed: int = 0, cache_dir: str | None = None) -> 
 
 
 def quant_model_path(shape_name: str, qtype: str, seed: int = 0, cache_dir: str | None = None) -> str:
-    """Path of the cached Q5_0 / Q8_0 version of a synthetic model, produced on first use by the REFERENCE's own quantizer
+    """Path of the cached quantised version of a synthetic model (qtype: any name the tool knows - "q5_0", "q8_0", "q5_1", "q4_1",
+    "q4_0", ...), produced on first use by the REFERENCE's own quantizer
     (examples/quantize, compiled by oracle/Makefile into oracle/_ref/quantize-ref; test infrastructure only)."""
     import subprocess
     src = model_path(shape_name, seed, cache_dir)

@@ -138,7 +138,7 @@ static void decode_launch(whisper_context & ctx, whisper_state & st, int n_token
             ln_linear(s, ctx.exact, WA_EPI_DEC_QKV, st.d_dx, d, L.attn_ln, hp.eps, st.d_dxn, L.qkv, n_tokens, nullptr, e);
         }
         wa_launch_attn_exact(s, st.d_dq, d, kv.k + il * kv_layer, 64, d, kv.v + il * kv_layer, 64, d, H, n_tokens, n_kv, mask, 1.0f,
-                             st.d_att_partial, st.d_att_pleft, st.d_dao, d, nullptr, dyn, nullptr, nullptr, nullptr, rowp, 0, (long long) (il * kv_layer));
+                             st.d_att_partial, st.d_att_pleft, st.d_dao, d, nullptr, dyn, nullptr, wa_q8_rows(), rowp, 0, (long long) (il * kv_layer));
         {
             wa_epi e; e.bias = L.out.b; e.out = st.d_dx; e.ldo = d; e.resid = st.d_dx; e.ldr = d;
             linear(s, ctx.exact, WA_EPI_RESID, st.d_dao, d, L.out, n_tokens, e);
@@ -153,7 +153,7 @@ static void decode_launch(whisper_context & ctx, whisper_state & st, int n_token
             qk_out = st.d_aheads_qk + (size_t) st.aheads_slot[il] * n_tokens * H * T;
         wa_launch_attn_exact(s, st.d_dq, d, st.d_cross_k + il * cross_layer, (size_t) st.cross_tpad * 64, 64, st.d_cross_v + il * cross_layer,
                              (size_t) st.cross_tpad * 64, 64, H, n_tokens, T, nullptr, KQscale, st.d_att_partial, st.d_att_pleft, st.d_dao, d, qk_out,
-                             nullptr, nullptr, nullptr, nullptr, rowp, 1, (long long) (il * cross_layer));
+                             nullptr, nullptr, wa_q8_rows(), rowp, 1, (long long) (il * cross_layer));
         {
             wa_epi e; e.bias = L.cross_out.b; e.out = st.d_dx; e.ldo = d; e.resid = st.d_dx; e.ldr = d;
             linear(s, ctx.exact, WA_EPI_RESID, st.d_dao, d, L.cross_out, n_tokens, e);
@@ -176,8 +176,9 @@ static void decode_launch(whisper_context & ctx, whisper_state & st, int n_token
     }
 }
 
-// The same pass for a quantised model (Q5_0 / Q8_0 weights, wa_quant.hip): every product quantises its F32 operand row to Q8_0
-// first (fused into the LayerNorm launch where the operand is a LayerNorm output), so attention and GELU hand over F32.
+// The same pass for a quantised model (Q5_0 / Q8_0 / Q4_1 / Q5_1 weights, wa_quant.hip): every product quantises its F32 operand row to
+// Q8_0 first (fused into the LayerNorm launch where the operand is a LayerNorm output), so attention and GELU hand over F32.  Weights
+// with a block minimum (L.qm set) take Q8_1 rows: the same quants and scales plus the block sums in d_q8s (null for the other formats).
 static void decode_launch_quant(whisper_context & ctx, whisper_state & st, int n_tokens, int n_kv, int kv_head, const int8_t * mask, int n_rows,
                                 const int32_t * h_rows, bool save_aheads, const int * dyn = nullptr) {
     const auto & m  = ctx.model;
@@ -187,21 +188,23 @@ static void decode_launch_quant(whisper_context & ctx, whisper_state & st, int n
     const int T = audio_ctx(st);
     hipStream_t s = st.stream;
     auto qmul = [&](wa_epi_mode mode, const wa_lin & L, int M, const wa_epi & e) {      // operand already in d_q8 / d_q8d
-        wa_launch_qgemm_exact(s, mode, st.d_q8, st.d_q8d, M, L.qs, L.qd, L.n_out, L.n_in, e);
+        wa_launch_qgemm_exact(s, mode, st.d_q8, st.d_q8d, M, L.qs, L.qd, L.n_out, L.n_in, e, st.d_q8s, L.qm);
     };
     auto qlin = [&](wa_epi_mode mode, const float * A, int lda, const wa_lin & L, int M, const wa_epi & e) {
-        wa_launch_quantize_q8_0(s, A, lda, M, L.n_in, st.d_q8, st.d_q8d);
+        wa_launch_quantize_q8_0(s, A, lda, M, L.n_in, st.d_q8, st.d_q8d, st.d_q8s);
         qmul(mode, L, M, e);
     };
     auto ln_q = [&](const float * x, int rows, const wa_ln & ln) {
-        if (rows == 1 && d <= 2048) wa_launch_ln_q8_row(s, x, d, ln.w, ln.b, hp.eps, st.d_q8, st.d_q8d);
-        else wa_launch_layernorm_exact(s, x, d, rows, d, ln.w, ln.b, hp.eps, nullptr, 0, nullptr, 0, st.d_q8, st.d_q8d);
+        if (rows == 1 && d <= 2048) wa_launch_ln_q8_row(s, x, d, ln.w, ln.b, hp.eps, st.d_q8, st.d_q8d, st.d_q8s);
+        else wa_launch_layernorm_exact(s, x, d, rows, d, ln.w, ln.b, hp.eps, nullptr, 0, nullptr, 0, st.d_q8, st.d_q8d, st.d_q8s);
     };
-    wa_launch_dec_embed_q(s, st.d_tok, st.d_pos, n_tokens, d, m.te_q.qs, m.te_q.qd, m.d_pe, st.d_dx);
+    wa_launch_dec_embed_q(s, st.d_tok, st.d_pos, n_tokens, d, m.te_q.qs, m.te_q.qd, m.d_pe, st.d_dx, m.te_q.qm);
     const float KQscale = pow(float(64), -0.25);
     const size_t kv_layer = (size_t) kv.size * d, cross_layer = (size_t) H * st.cross_tpad * 64;
     // second operand buffer (upper half of d_q8 / d_q8d) for the one product whose output is quantised by its own launch
     int8_t * q8b = st.d_q8 + (size_t) st.q8_rows * 2 * d; float * q8bd = st.d_q8d + (size_t) st.q8_rows * 2 * d / 32;
+    const wa_q8_rows q8r{ st.d_q8, st.d_q8d, st.d_q8s };      // where attention hands its rows over
+    float * q8bs = st.d_q8s ? st.d_q8s + (size_t) st.q8_rows * 2 * d / 32 : nullptr;
     for (int il = 0; il < hp.n_text_layer; ++il) {
         const auto & L = m.dec[il];
         ln_q(st.d_dx, n_tokens, L.attn_ln);
@@ -212,7 +215,7 @@ static void decode_launch_quant(whisper_context & ctx, whisper_state & st, int n
             qmul(WA_EPI_DEC_QKV, L.qkv, n_tokens, e);
         }
         wa_launch_attn_exact(s, st.d_dq, d, kv.k + il * kv_layer, 64, d, kv.v + il * kv_layer, 64, d, H, n_tokens, n_kv, mask, 1.0f,
-                             st.d_att_partial, st.d_att_pleft, st.d_dao, d, nullptr, dyn, nullptr, st.d_q8, st.d_q8d);
+                             st.d_att_partial, st.d_att_pleft, st.d_dao, d, nullptr, dyn, nullptr, q8r);
         { wa_epi e; e.bias = L.out.b; e.out = st.d_dx; e.ldo = d; e.resid = st.d_dx; e.ldr = d; qmul(WA_EPI_RESID, L.out, n_tokens, e); }
         ln_q(st.d_dx, n_tokens, L.cross_ln);
         { wa_epi e; e.bias = L.cross_q.b; e.out = st.d_dq; e.ldo = d; qmul(WA_EPI_F16, L.cross_q, n_tokens, e); }
@@ -221,13 +224,13 @@ static void decode_launch_quant(whisper_context & ctx, whisper_state & st, int n
             qk_out = st.d_aheads_qk + (size_t) st.aheads_slot[il] * n_tokens * H * T;
         wa_launch_attn_exact(s, st.d_dq, d, st.d_cross_k + il * cross_layer, (size_t) st.cross_tpad * 64, 64, st.d_cross_v + il * cross_layer,
                              (size_t) st.cross_tpad * 64, 64, H, n_tokens, T, nullptr, KQscale, st.d_att_partial, st.d_att_pleft, st.d_dao, d, qk_out,
-                             nullptr, nullptr, st.d_q8, st.d_q8d);
+                             nullptr, nullptr, q8r);
         { wa_epi e; e.bias = L.cross_out.b; e.out = st.d_dx; e.ldo = d; e.resid = st.d_dx; e.ldr = d; qmul(WA_EPI_RESID, L.cross_out, n_tokens, e); }
         ln_q(st.d_dx, n_tokens, L.mlp_ln);
         wa_epi e2; e2.bias = L.fc2.b; e2.out = st.d_dx; e2.ldo = d; e2.resid = st.d_dx; e2.ldr = d;
         if (n_tokens == 1) {
-            wa_launch_qgemv_gelu_q8(s, st.d_q8, st.d_q8d, L.fc1.qs, L.fc1.qd, 4 * d, d, L.fc1.b, m.d_gelu, q8b, q8bd);
-            wa_launch_qgemm_exact(s, WA_EPI_RESID, q8b, q8bd, 1, L.fc2.qs, L.fc2.qd, d, 4 * d, e2);
+            wa_launch_qgemv_gelu_q8(s, st.d_q8, st.d_q8d, L.fc1.qs, L.fc1.qd, 4 * d, d, L.fc1.b, m.d_gelu, q8b, q8bd, st.d_q8s, L.fc1.qm, q8bs);
+            wa_launch_qgemm_exact(s, WA_EPI_RESID, q8b, q8bd, 1, L.fc2.qs, L.fc2.qd, d, 4 * d, e2, q8bs, L.fc2.qm);
         } else {
             { wa_epi e; e.bias = L.fc1.b; e.gelu = m.d_gelu; e.out = st.d_q32b; e.ldo = 4 * d; qmul(WA_EPI_GELU_F32, L.fc1, n_tokens, e); }
             qlin(WA_EPI_RESID, st.d_q32b, 4 * d, L.fc2, n_tokens, e2);
@@ -237,7 +240,7 @@ static void decode_launch_quant(whisper_context & ctx, whisper_state & st, int n
         const int nb = d >> 5;
         for (int i = 0; i < n_rows; ++i)
             wa_launch_layernorm_exact(s, st.d_dx + (size_t) h_rows[i] * d, d, 1, d, m.d_ln.w, m.d_ln.b, hp.eps, nullptr, 0, nullptr, 0,
-                                      st.d_q8 + (size_t) i * d, st.d_q8d + (size_t) i * nb);
+                                      st.d_q8 + (size_t) i * d, st.d_q8d + (size_t) i * nb, st.d_q8s ? st.d_q8s + (size_t) i * nb : nullptr);
         wa_epi e; e.out = st.d_logits; e.ldo = n_vocab;
         qmul(WA_EPI_F32, m.te_q, n_rows, e);
     }

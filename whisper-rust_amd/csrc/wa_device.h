@@ -100,7 +100,10 @@ __device__ __forceinline__ float wa_gelu(float x, const wa_f16 * __restrict__ ta
 // quantize_row_q8_0 (ggml-cpu/arch/x86/quants.c, AVX2: d = max|x| / 127, q = rint(x * (127 / max|x|)), d kept as F16) of one 32-element
 // block whose element `el` = lane & 31 is held by each lane of a half-wave; output in the kernel layout of wa_quant.hip
 // (qs [row][el / 4][block][el % 4], qd [row][block]).  All 32 lanes of the half-wave must be active.
-__device__ __forceinline__ void wa_q8_store(float y, int row, int blk, int el, int nb, int8_t * __restrict__ qs, float * __restrict__ qd) {
+// qsum set (the same for the whole wave): the row is the Q8_1 operand of a Q4_1 / Q5_1 product (quantize_row_q8_1, same file), which
+// carries qsum [row][block] = f16(d * (float) sum of the block's quants) besides - d the F32 quotient BEFORE it is rounded to F16.
+__device__ __forceinline__ void wa_q8_store(float y, int row, int blk, int el, int nb, int8_t * __restrict__ qs, float * __restrict__ qd,
+                                            float * __restrict__ qsum = nullptr) {
     float a = fabsf(y);
     a = fmaxf(a, dpp_f32<0x128>(a));        // row_ror:8, 4, 2, 1: the maximum over a 16-lane row, in every lane of it (one VALU op each;
     a = fmaxf(a, dpp_f32<0x124>(a));        //  five ds_bpermute exchanges here were half of a single-row LayerNorm launch)
@@ -109,8 +112,18 @@ __device__ __forceinline__ void wa_q8_store(float y, int row, int blk, int el, i
     a = fmaxf(a, __shfl_xor(a, 16, 32));    // the block's two rows
     const float d = a / 127.f;
     const float id = a != 0.0f ? 127.f / a : 0.0f;
-    qs[(((size_t) row * 8 + (el >> 2)) * nb + blk) * 4 + (el & 3)] = (int8_t) (int) rintf(y * id);      // to nearest, ties to even
+    const int q = (int) rintf(y * id);                            // to nearest, ties to even
+    qs[(((size_t) row * 8 + (el >> 2)) * nb + blk) * 4 + (el & 3)] = (int8_t) q;
     if (el == 0) qd[(size_t) row * nb + blk] = h2f(f2h(d));       // the dot product reads the scale back from its F16 field
+    if (qsum) {                                                   // exact integer sum over the half-wave, as the maximum above
+        int t = q;
+        t += __builtin_amdgcn_update_dpp(0, t, 0x128, 0xf, 0xf, true);
+        t += __builtin_amdgcn_update_dpp(0, t, 0x124, 0xf, 0xf, true);
+        t += __builtin_amdgcn_update_dpp(0, t, 0x122, 0xf, 0xf, true);
+        t += __builtin_amdgcn_update_dpp(0, t, 0x121, 0xf, 0xf, true);
+        t += __shfl_xor(t, 16, 32);
+        if (el == 0) qsum[(size_t) row * nb + blk] = h2f(f2h(d * (float) t));
+    }
 }
 
 // =================================================================================================

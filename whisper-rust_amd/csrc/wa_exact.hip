@@ -420,7 +420,8 @@ __device__ __forceinline__ void wa_ln_stats(const float * __restrict__ xr, int d
 template <int LN_NPL>
 __global__ __launch_bounds__(256) void k_layernorm_exact(const float * __restrict__ x, int ldx, int rows, int d, const float * __restrict__ w,
                                                          const float * __restrict__ b, float eps, wa_f16 * __restrict__ out16, int ld16,
-                                                         float * __restrict__ out32, int ld32, int8_t * __restrict__ qs, float * __restrict__ qd) {
+                                                         float * __restrict__ out32, int ld32, int8_t * __restrict__ qs, float * __restrict__ qd,
+                                                         float * __restrict__ qsum) {
     __shared__ __attribute__((aligned(16))) float lrows[4][64 * LN_NPL];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int row = blockIdx.x * 4 + wave;
@@ -440,14 +441,14 @@ __global__ __launch_bounds__(256) void k_layernorm_exact(const float * __restric
             y = y + gb[k];
             if (out16) out16[(size_t) row * ld16 + i] = f2h(y);
             if (out32) out32[(size_t) row * ld32 + i] = y;
-            if (qs) wa_q8_store(y, row, i >> 5, i & 31, d >> 5, qs, qd);      // d % 32 == 0: a half-wave holds one block
+            if (qs) wa_q8_store(y, row, i >> 5, i & 31, d >> 5, qs, qd, qsum);      // d % 32 == 0: a half-wave holds one block
         }
     }
 }
 void wa_launch_layernorm_exact(hipStream_t stream, const float * x, int ldx, int rows, int d, const float * w, const float * b, float eps,
-                               wa_f16 * out16, int ld16, float * out32, int ld32, int8_t * qs, float * qd) {
+                               wa_f16 * out16, int ld16, float * out32, int ld32, int8_t * qs, float * qd, float * qsum) {
     // elements per lane sized to the row (d <= 1280): 6 for d <= 384, 12 for <= 768, 16 for <= 1024
-#define WA_LN_CASE(NPL) hipLaunchKernelGGL((k_layernorm_exact<NPL>), dim3((rows + 3) / 4), dim3(256), 0, stream, x, ldx, rows, d, w, b, eps, out16, ld16, out32, ld32, qs, qd)
+#define WA_LN_CASE(NPL) hipLaunchKernelGGL((k_layernorm_exact<NPL>), dim3((rows + 3) / 4), dim3(256), 0, stream, x, ldx, rows, d, w, b, eps, out16, ld16, out32, ld32, qs, qd, qsum)
     if (d <= 384) WA_LN_CASE(6); else if (d <= 768) WA_LN_CASE(12); else if (d <= 1024) WA_LN_CASE(16); else WA_LN_CASE(20);
 #undef WA_LN_CASE
 }
@@ -473,7 +474,8 @@ typedef _Float16 half4v __attribute__((ext_vector_type(4)));
 // All 256 threads share the row, so each touches K/256 elements: the prologue is issue-bound, not bandwidth-bound.
 __device__ __forceinline__ void wa_block_layernorm(const float * __restrict__ xr, int K, const wa_ln_in & ln, wa_f16 * __restrict__ dst,
                                                    double * __restrict__ red /*[16] shared*/, float * __restrict__ lrow /*[K] shared*/, int tid,
-                                                   int8_t * __restrict__ qs = nullptr, float * __restrict__ qd = nullptr /* when set: the row as Q8_0 (wa_q8_store, K % 32 == 0) */) {
+                                                   int8_t * __restrict__ qs = nullptr, float * __restrict__ qd = nullptr /* when set: the row as Q8_0 (wa_q8_store, K % 32 == 0) */,
+                                                   float * __restrict__ qsum = nullptr /* with qs: the Q8_1 block sums too */) {
     const int lane = tid & 63, wave = tid >> 6;
     float xv[GEMV_LN_NPL], gw[GEMV_LN_NPL], gb[GEMV_LN_NPL];
 #pragma unroll
@@ -526,7 +528,7 @@ __device__ __forceinline__ void wa_block_layernorm(const float * __restrict__ xr
             y = y * gw[k];
             y = y + gb[k];
             if (dst) dst[i] = f2h(y);
-            if (qs) wa_q8_store(y, 0, i >> 5, i & 31, K >> 5, qs, qd);
+            if (qs) wa_q8_store(y, 0, i >> 5, i & 31, K >> 5, qs, qd, qsum);
         }
     }
     __syncthreads();       // `red` is reused by the next row
@@ -534,14 +536,15 @@ __device__ __forceinline__ void wa_block_layernorm(const float * __restrict__ xr
 
 // one F32 row -> LayerNorm -> Q8_0, by a whole block (the decode step of a quantised model: one wave per row, k_layernorm_exact, leaves
 // a single wave with 20 elements per lane; here every thread has at most 8)
-__global__ __launch_bounds__(GEMV_THREADS) void k_ln_q8_row(const float * __restrict__ x, int K, wa_ln_in ln, int8_t * __restrict__ qs, float * __restrict__ qd) {
+__global__ __launch_bounds__(GEMV_THREADS) void k_ln_q8_row(const float * __restrict__ x, int K, wa_ln_in ln, int8_t * __restrict__ qs, float * __restrict__ qd,
+                                                            float * __restrict__ qsum) {
     __shared__ double red[16];
     __shared__ __attribute__((aligned(16))) float lrow[GEMV_THREADS * GEMV_LN_NPL];
-    wa_block_layernorm(x, K, ln, nullptr, red, lrow, threadIdx.x, qs, qd);
+    wa_block_layernorm(x, K, ln, nullptr, red, lrow, threadIdx.x, qs, qd, qsum);
 }
-void wa_launch_ln_q8_row(hipStream_t stream, const float * x, int K, const float * w, const float * b, float eps, int8_t * qs, float * qd) {
+void wa_launch_ln_q8_row(hipStream_t stream, const float * x, int K, const float * w, const float * b, float eps, int8_t * qs, float * qd, float * qsum) {
     wa_ln_in ln; ln.x = x; ln.ldx = K; ln.w = w; ln.b = b; ln.eps = eps;
-    hipLaunchKernelGGL(k_ln_q8_row, dim3(1), dim3(GEMV_THREADS), 0, stream, x, K, ln, qs, qd);
+    hipLaunchKernelGGL(k_ln_q8_row, dim3(1), dim3(GEMV_THREADS), 0, stream, x, K, ln, qs, qd, qsum);
 }
 
 template <int MT, int EPI>
@@ -754,7 +757,8 @@ __global__ __launch_bounds__(ATT_THREADS) void k_attn_exact(const wa_f16 * __res
                                                             int n_kv_arg, const int8_t * __restrict__ mask, float scale, float * __restrict__ partial,
                                                             wa_f16 * __restrict__ p_left, wa_f16 * __restrict__ out, int ldo, float * __restrict__ qk_out,
                                                             const int * __restrict__ dyn, float * __restrict__ out32, int8_t * __restrict__ q8,
-                                                            float * __restrict__ q8d, const wa_rowptr * __restrict__ rowp, int rowp_cross, long long rowp_off) {
+                                                            float * __restrict__ q8d, const wa_rowptr * __restrict__ rowp, int rowp_cross, long long rowp_off,
+                                                            float * __restrict__ q8s) {
     constexpr int NW = ATT_THREADS / 64;
     if (rowp) {        // query row j belongs to its own state: that state's cells (self) or encoder K / V (cross)
         const wa_rowptr r = rowp[blockIdx.y];
@@ -909,7 +913,7 @@ __global__ __launch_bounds__(ATT_THREADS) void k_attn_exact(const wa_f16 * __res
             }
 #pragma unroll
             for (int c = 0; c < 32; ++c) if (c < nl) sumf += (double) prod[c];
-            if (q8) wa_q8_store((float) sumf, j, 2 * h + (tid >> 5), tid & 31, ldo >> 5, q8, q8d);       // F32 hand-over, quantised (wa_quant.hip)
+            if (q8) wa_q8_store((float) sumf, j, 2 * h + (tid >> 5), tid & 31, ldo >> 5, q8, q8d, q8s);       // F32 hand-over, quantised (wa_quant.hip)
             else if (out32) out32[(size_t) j * ldo + h * 64 + tid] = (float) sumf;
             else out[(size_t) j * ldo + h * 64 + tid] = f2h((float) sumf);
         }
@@ -1082,7 +1086,7 @@ __global__ __launch_bounds__(ATT_THREADS) void k_attn_exact_mq(const wa_f16 * __
                                                                int k_row_stride, const wa_f16 * __restrict__ vbase, size_t v_head_stride, int v_row_stride,
                                                                int n_tokens, int n_kv, int kvp, const int8_t * __restrict__ mask, float scale,
                                                                wa_f16 * __restrict__ out, int ldo, float * __restrict__ qk_out,
-                                                               float * __restrict__ out32, int8_t * __restrict__ q8, float * __restrict__ q8d) {
+                                                               float * __restrict__ out32, int8_t * __restrict__ q8, float * __restrict__ q8d, float * __restrict__ q8s) {
     constexpr int NW = ATT_THREADS / 64;
     extern __shared__ __attribute__((aligned(16))) unsigned char mq_smem[];
     float  * sc   = (float *) mq_smem;                                  // [NQ][kvp]
@@ -1266,7 +1270,7 @@ __global__ __launch_bounds__(ATT_THREADS) void k_attn_exact_mq(const wa_f16 * __
         }
 #pragma unroll
         for (int c = 0; c < 32; ++c) if (c < nl) sumf += (double) prod[c];
-        if (q8) wa_q8_store((float) sumf, j, 2 * h + (lane >> 5), lane & 31, ldo >> 5, q8, q8d);
+        if (q8) wa_q8_store((float) sumf, j, 2 * h + (lane >> 5), lane & 31, ldo >> 5, q8, q8d, q8s);
         else if (out32) out32[(size_t) j * ldo + h * 64 + lane] = (float) sumf;
         else out[(size_t) j * ldo + h * 64 + lane] = f2h((float) sumf);
     }
@@ -1276,7 +1280,7 @@ __global__ __launch_bounds__(64) void k_attn_combine(const float * __restrict__ 
                                                      const wa_f16 * vbase, size_t v_head_stride, int v_row_stride, int n_kv_arg,
                                                      wa_f16 * __restrict__ out, int ldo, const int * __restrict__ dyn, float * __restrict__ out32,
                                                      int8_t * __restrict__ q8, float * __restrict__ q8d, const wa_rowptr * __restrict__ rowp, int rowp_cross,
-                                                     long long rowp_off) {
+                                                     long long rowp_off, float * __restrict__ q8s) {
     const int j = blockIdx.x, h = blockIdx.y, n_head = gridDim.y, dh = threadIdx.x;
     if (rowp) { const wa_rowptr r = rowp[j]; vbase = (rowp_cross ? r.cross_v : r.kv_v) + rowp_off; if (!rowp_cross) n_kv_arg = r.n_kv; }
     const int n_kv = dyn ? dyn[0] : n_kv_arg;
@@ -1295,7 +1299,7 @@ __global__ __launch_bounds__(64) void k_attn_combine(const float * __restrict__ 
     }
 #pragma unroll
     for (int c = 0; c < 32; ++c) if (c < nl) sumf += (double) prod[c];
-    if (q8) wa_q8_store((float) sumf, j, 2 * h + (dh >> 5), dh & 31, ldo >> 5, q8, q8d);
+    if (q8) wa_q8_store((float) sumf, j, 2 * h + (dh >> 5), dh & 31, ldo >> 5, q8, q8d, q8s);
     else if (out32) out32[(size_t) j * ldo + h * 64 + dh] = (float) sumf;
     else out[(size_t) j * ldo + h * 64 + dh] = f2h((float) sumf);
 }
@@ -1303,7 +1307,8 @@ __global__ __launch_bounds__(64) void k_attn_combine(const float * __restrict__ 
 void wa_launch_attn_exact(hipStream_t s, const wa_f16 * q, int ldq, const wa_f16 * kbase, size_t k_head_stride, int k_row_stride,
                           const wa_f16 * vbase, size_t v_head_stride, int v_row_stride, int n_head, int n_tokens, int n_kv, const int8_t * mask,
                           float scale, float * partial, wa_f16 * p_left, wa_f16 * out, int ldo, float * qk_out, const int * dyn, float * out32,
-                          int8_t * q8, float * q8d, const wa_rowptr * rowp, int rowp_cross, long long rowp_off) {
+                          wa_q8_rows q8r, const wa_rowptr * rowp, int rowp_cross, long long rowp_off) {
+    int8_t * q8 = q8r.qs; float * q8d = q8r.qd; float * q8s = q8r.qsum;
     // few (token, head) pairs and a long key range (decode cross-attention): spread the 32 partial-sum chains over 4 blocks
     // per pair and finish in k_attn_combine; otherwise one block per pair finishes in LDS (encoder, prompt, self-attention)
     const bool split = (long) n_tokens * n_head < 512 && n_kv > 512;
@@ -1315,16 +1320,16 @@ void wa_launch_attn_exact(hipStream_t s, const wa_f16 * q, int ldq, const wa_f16
         static bool attr_done = false;
         if (!attr_done) { (void) hipFuncSetAttribute((const void *) k_attn_exact_mq<NQ>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 4096); attr_done = true; }
         hipLaunchKernelGGL((k_attn_exact_mq<NQ>), dim3(n_head, (n_tokens + NQ - 1) / NQ), dim3(ATT_THREADS), lds, s, q, ldq, kbase, k_head_stride, k_row_stride,
-                           vbase, v_head_stride, v_row_stride, n_tokens, n_kv, kvp, mask, scale, out, ldo, qk_out, out32, q8, q8d);
+                           vbase, v_head_stride, v_row_stride, n_tokens, n_kv, kvp, mask, scale, out, ldo, qk_out, out32, q8, q8d, q8s);
         return;
     }
     if (!split) {
         hipLaunchKernelGGL((k_attn_exact<1>), dim3(n_head, n_tokens), dim3(ATT_THREADS), 0, s, q, ldq, kbase, k_head_stride, k_row_stride, vbase,
-                           v_head_stride, v_row_stride, n_kv, mask, scale, partial, p_left, out, ldo, qk_out, dyn, out32, q8, q8d, rowp, rowp_cross, rowp_off);
+                           v_head_stride, v_row_stride, n_kv, mask, scale, partial, p_left, out, ldo, qk_out, dyn, out32, q8, q8d, rowp, rowp_cross, rowp_off, q8s);
     } else {
         hipLaunchKernelGGL((k_attn_exact<4>), dim3(n_head * 4, n_tokens), dim3(ATT_THREADS), 0, s, q, ldq, kbase, k_head_stride, k_row_stride, vbase,
-                           v_head_stride, v_row_stride, n_kv, mask, scale, partial, p_left, out, ldo, qk_out, dyn, out32, q8, q8d, rowp, rowp_cross, rowp_off);
+                           v_head_stride, v_row_stride, n_kv, mask, scale, partial, p_left, out, ldo, qk_out, dyn, out32, q8, q8d, rowp, rowp_cross, rowp_off, q8s);
         hipLaunchKernelGGL(k_attn_combine, dim3(n_tokens, n_head), dim3(64), 0, s, partial, p_left, vbase, v_head_stride, v_row_stride, n_kv,
-                           out, ldo, dyn, out32, q8, q8d, rowp, rowp_cross, rowp_off);
+                           out, ldo, dyn, out32, q8, q8d, rowp, rowp_cross, rowp_off, q8s);
     }
 }

@@ -64,12 +64,14 @@ typedef uint16_t wa_f16;  // raw IEEE half bits on the host side
 
 struct wa_ln  { const float * w = nullptr; const float * b = nullptr; };
 // A linear layer.  F16 weights: w [n_out][n_in].  Quantised weights (ggml block formats, ggml-common.h:187-214; wtype = ggml type
-// 6 Q5_0 / 8 Q8_0): qs = the quants as signed bytes [n_out][8][n_in/32][4] (element 4l + e of block b at [row][l][b][e]; Q5_0's
-// 5-bit values expanded at load), qd [n_out][n_in/32] the block scales widened from F16 to F32 (exact).
+// 6 Q5_0 / 8 Q8_0 / 3 Q4_1 / 7 Q5_1): qs = the quants as signed bytes [n_out][8][n_in/32][4] (element 4l + e of block b at [row][l][b][e];
+// the 4- and 5-bit values expanded at load), qd [n_out][n_in/32] the block scales widened from F16 to F32 (exact); Q4_1 / Q5_1 only
+// (wa_quant1.h): qm [n_out][n_in/32] the block minimums likewise, and the quants are the unsigned values 0..15 / 0..31.
 struct wa_lin {
     const wa_f16 * w = nullptr; const float * b = nullptr; const float * s = nullptr; int n_out = 0, n_in = 0;
-    int wtype = 1; const int8_t * qs = nullptr; const float * qd = nullptr;
+    int wtype = 1; const int8_t * qs = nullptr; const float * qd = nullptr; const float * qm = nullptr;
 };
+inline bool wa_wtype_has_min(int wtype) { return wtype == 3 || wtype == 7; }     // Q4_1, Q5_1: multiplied with Q8_1 activation rows
 
 struct wa_enc_layer {
     wa_ln  attn_ln, mlp_ln;
@@ -91,7 +93,7 @@ struct wa_model {
     int n_mel_filt = 0, n_fft_filt = 0;
     std::vector<float> filters;     // host copy [n_mel][n_fft]
     int n_loaded = 0;               // 0 => header/vocab-only test model (ref: whisper.cpp:1959-1960)
-    int wtype = 1;                  // ggml type of the 2-D weight matrices: 1 F16, 6 Q5_0, 8 Q8_0 (whisper.cpp:1567-1573)
+    int wtype = 1;                  // ggml type of the 2-D weight matrices: 1 F16, 6 Q5_0, 8 Q8_0, 3 Q4_1, 7 Q5_1 (whisper.cpp:1567-1573)
 
     // ---- device (all inside `arena`) ----
     void * arena = nullptr; size_t arena_size = 0;
@@ -251,6 +253,7 @@ struct whisper_state {
     int8_t * d_q8   = nullptr;      // [tpad][4d]  Q8_0 operand rows (q8_rows = tpad)
     int      q8_rows = 0;
     float  * d_q8d  = nullptr;      // [tpad][4d / 32]
+    float  * d_q8s  = nullptr;      // [tpad][4d / 32]  Q4_1 / Q5_1 models only: the Q8_1 block sums of those rows (wa_quant1.h), else null
 
     // hipGraph of the single-token decoder pass (launch-bound inner loop); parameters that change per token live in d_dyn
     int32_t * d_dyn = nullptr;            // {n_kv, kv_head}

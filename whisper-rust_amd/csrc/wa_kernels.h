@@ -31,6 +31,10 @@ enum wa_epi_mode {
 // self K/V cells and its encoder K/V (layer 0; the kernels add the layer offset, equal for all rows), and its cell range.
 struct wa_rowptr { wa_f16 * kv_k; wa_f16 * kv_v; const wa_f16 * cross_k; const wa_f16 * cross_v; int n_kv; int kv_head; };
 
+// Where a kernel that hands over F32 rows writes them quantised instead (the operand of the next quantised product, wa_quant.hip): quants in the
+// kernel layout, block scales, and - for the Q8_1 rows of a Q4_1 / Q5_1 product only, else null - the block sums.  qs null: not quantised.
+struct wa_q8_rows { int8_t * qs = nullptr; float * qd = nullptr; float * qsum = nullptr; };
+
 struct wa_epi {
     const float * bias  = nullptr;
     const float * scale = nullptr;
@@ -86,7 +90,8 @@ void wa_launch_ln_gemv_exact(hipStream_t stream, wa_epi_mode mode, const float *
                              const float * ln_b, float eps, const wa_f16 * W, int ldw, int M, int N, int K, const wa_epi & e);
 void wa_launch_im2col3(hipStream_t stream, const wa_f16 * src, int src_ld, int row0, int stride, int IC, int OL, wa_f16 * dst, int dst_ld);
 void wa_launch_layernorm_exact(hipStream_t stream, const float * x, int ldx, int rows, int d, const float * w, const float * b, float eps,
-                               wa_f16 * out16, int ld16, float * out32, int ld32, int8_t * qs = nullptr, float * qd = nullptr);
+                               wa_f16 * out16, int ld16, float * out32, int ld32, int8_t * qs = nullptr, float * qd = nullptr,
+                               float * qsum = nullptr /* with qs: the Q8_1 block sums [rows][d / 32] (operand of a Q4_1 / Q5_1 product) */);
 // q [n_tokens][ldq] f16; K row c of head h at kbase + h*k_head_stride + c*k_row_stride (64 halfs), V likewise.
 // partial: f32 [n_tokens][n_head][32][64], p_left: f16 [n_tokens][n_head][32] (used when n_tokens*n_head < 512).
 // Reference-order self-attention of the encoder on the matrix cores (T queries = T keys of every head, no mask), bit-identical to
@@ -100,21 +105,23 @@ void wa_launch_attn_exact(hipStream_t stream, const wa_f16 * q, int ldq, const w
                           const wa_f16 * vbase, size_t v_head_stride, int v_row_stride, int n_head, int n_tokens, int n_kv, const int8_t * mask,
                           float scale, float * partial, wa_f16 * p_left, wa_f16 * out, int ldo, float * qk_out, const int * dyn_n_kv = nullptr,
                           float * out32 = nullptr /* when set: the result in F32 [n_tokens][ldo] instead of F16 (quantised models) */,
-                          int8_t * q8 = nullptr, float * q8d = nullptr /* when set: the F32 result as Q8_0 rows in the layout of wa_launch_quantize_q8_0 */,
+                          wa_q8_rows q8 = wa_q8_rows() /* qs set: the F32 result as Q8_0 / Q8_1 rows in the layout of wa_launch_quantize_q8_0 */,
                           const wa_rowptr * rowp = nullptr, int rowp_cross = 0, long long rowp_off = 0
                           /* rowp: query row j reads ITS state's K / V (self cells [0, rowp[j].n_kv), or the encoder's when rowp_cross) at + rowp_off */);
 
-// ---- quantised weights (wa_quant.hip): ggml's Q5_0 / Q8_0 x Q8_0 products in the reference's AVX2 order ----
-// quantize_row_q8_0 (arch/x86/quants.c): x f32 [rows][ldx] -> qs int8 [rows][8][K/32][4] (kernel layout), qd f32 [rows][K/32] (block scale, rounded through F16)
-void wa_launch_quantize_q8_0(hipStream_t stream, const float * x, int ldx, int rows, int K, int8_t * qs, float * qd);
-// C[M][N] = xq . Wq^T, ggml_vec_dot_q5_0_q8_0 / q8_0_q8_0 order; wq int8 [N][8][K/32][4], wd f32 [N][K/32] (wa_internal.h: wa_lin); any M
+// ---- quantised weights (wa_quant.hip): ggml's Q5_0 / Q8_0 x Q8_0 and Q4_1 / Q5_1 x Q8_1 products in the reference's AVX2 order ----
+// The formats with a block minimum (Q4_1, Q5_1; wa_quant1.h) take two more arrays: wm f32 [N][K/32], the weights' minimums, and xs / qsum
+// f32 [rows][K/32], the Q8_1 block sums of the activation rows.  Both null: the Q5_0 / Q8_0 product.  Both set: the Q4_1 / Q5_1 one.
+// quantize_row_q8_0 / q8_1 (arch/x86/quants.c): x f32 [rows][ldx] -> qs int8 [rows][8][K/32][4] (kernel layout), qd f32 [rows][K/32] (block scale, rounded through F16)
+void wa_launch_quantize_q8_0(hipStream_t stream, const float * x, int ldx, int rows, int K, int8_t * qs, float * qd, float * qsum = nullptr);
+// C[M][N] = xq . Wq^T, ggml_vec_dot_q5_0_q8_0 / q8_0_q8_0 / q4_1_q8_1 / q5_1_q8_1 order; wq int8 [N][8][K/32][4], wd f32 [N][K/32] (wa_internal.h: wa_lin); any M
 void wa_launch_qgemm_exact(hipStream_t stream, wa_epi_mode mode, const int8_t * xq, const float * xd, int M, const int8_t * wq, const float * wd, int N, int K,
-                           const wa_epi & e);
+                           const wa_epi & e, const float * xs = nullptr, const float * wm = nullptr);
 // one row (K <= 2048, K % 32 == 0): LayerNorm in reference order, quantised to Q8_0 row 0 of (qs, qd), by one 256-thread block
-void wa_launch_ln_q8_row(hipStream_t stream, const float * x, int K, const float * w, const float * b, float eps, int8_t * qs, float * qd);
+void wa_launch_ln_q8_row(hipStream_t stream, const float * x, int K, const float * w, const float * b, float eps, int8_t * qs, float * qd, float * qsum = nullptr);
 // M == 1: GELU(x Wq^T + bias) quantised to Q8_0 straight away (the operand of the second MLP product); N % 32 == 0
 void wa_launch_qgemv_gelu_q8(hipStream_t stream, const int8_t * xq, const float * xd, const int8_t * wq, const float * wd, int N, int K, const float * bias,
-                             const wa_f16 * gelu, int8_t * oq, float * oqd);
-// token embedding rows of a quantised matrix (dequantize_row_q5_0 / q8_0) + positional embedding
+                             const wa_f16 * gelu, int8_t * oq, float * oqd, const float * xs = nullptr, const float * wm = nullptr, float * oqs = nullptr);
+// token embedding rows of a quantised matrix (dequantize_row_q5_0 / q8_0: q * d; q4_1 / q5_1 with wm: q * d, then + m) + positional embedding
 void wa_launch_dec_embed_q(hipStream_t stream, const int32_t * tok, const int32_t * pos, int n_tokens, int d, const int8_t * wq, const float * wd,
-                           const float * pe, float * x);
+                           const float * pe, float * x, const float * wm = nullptr);

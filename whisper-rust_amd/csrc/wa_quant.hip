@@ -9,6 +9,14 @@
 // token), the three DPP exchanges reproduce hsum_float_8.  Up to 8 activation rows share one pass over the weights.
 // The weights are stored for this access pattern at load (wa_loader.cpp: signed bytes, [row][lane][block][4]).
 // Bit-identical to the reference engine on the Q5_0 / Q8_0 goldens (tests/test_parity_gpu.py).
+//
+// Q4_1 / Q5_1 (template flag Q1; the arithmetic is stated in host code in wa_quant1.h): the quants are the unsigned 4- / 5-bit values
+// (0..31 fits a signed byte, so the same v_dot4_i32_i8), the weight is q * d + m, and the reference multiplies with a Q8_1 row, whose
+// blocks carry s = f16(d * sum q) besides d (quantize_row_q8_1).  Beside the lane chain above runs a SCALAR chain over the blocks,
+//     summs = summs + (f32(m_w) * f32(s_x))        a multiplication, then an addition - not an fma
+// and the output is hsum_float_8(acc) + summs (ggml_vec_dot_q4_1_q8_1 / q5_1_q8_1).  In the one-row product every lane of a row's group
+// runs that chain redundantly (one v_mul + one v_add per block); with 8 activation rows lane l of the group runs the chain of activation
+// row l and hands it to lane 0 over DPP.  The minimums wm [row][block] and the sums xs [row][block] are read like the scales.
 #include "wa_device.h"
 
 // -------------------------------------------------------------------------------------------------
@@ -16,18 +24,18 @@
 // ([row][l = 0..7][block][4], wa_internal.h: wa_lin): lane l of a dot product reads four blocks with one 16-byte load.
 // -------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_quantize_q8_0(const float * __restrict__ x, int ldx, int rows, int K, int8_t * __restrict__ qs,
-                                                       float * __restrict__ qd) {
+                                                       float * __restrict__ qd, float * __restrict__ qsum) {
     const int nb = K >> 5;
     const long g = (long) blockIdx.x * blockDim.x + threadIdx.x;
     const long gb = g >> 5;
     const int l = (int) (g & 31);
     if (gb >= (long) rows * nb) return;
     const int row = (int) (gb / nb), b = (int) (gb - (long) row * nb);
-    wa_q8_store(x[(size_t) row * ldx + b * 32 + l], row, b, l, nb, qs, qd);
+    wa_q8_store(x[(size_t) row * ldx + b * 32 + l], row, b, l, nb, qs, qd, qsum);
 }
-void wa_launch_quantize_q8_0(hipStream_t stream, const float * x, int ldx, int rows, int K, int8_t * qs, float * qd) {
+void wa_launch_quantize_q8_0(hipStream_t stream, const float * x, int ldx, int rows, int K, int8_t * qs, float * qd, float * qsum) {
     const long n = (long) rows * K;
-    hipLaunchKernelGGL(k_quantize_q8_0, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, stream, x, ldx, rows, K, qs, qd);
+    hipLaunchKernelGGL(k_quantize_q8_0, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, stream, x, ldx, rows, K, qs, qd, qsum);
 }
 
 typedef int   wq_i4 __attribute__((ext_vector_type(4)));
@@ -42,17 +50,29 @@ __device__ __forceinline__ float wq_hsum8(float v) {
 #define WQ_BLOCK(acc, w, dw, x, dx) acc = fmaf((dw) * (dx), (float) __builtin_amdgcn_sdot4((w), (x), 0, false), acc)
 #define WQ_STEP4(acc, W, DW, X, DX) do { WQ_BLOCK(acc, (W).x, (DW).x, (X).x, (DX).x); WQ_BLOCK(acc, (W).y, (DW).y, (X).y, (DX).y); \
                                          WQ_BLOCK(acc, (W).z, (DW).z, (X).z, (DX).z); WQ_BLOCK(acc, (W).w, (DW).w, (X).w, (DX).w); } while (0)
+// the minimum chain of Q4_1 / Q5_1, four blocks in order: two roundings per block (the file is built with -ffp-contract=off)
+#define WQ_MIN(sm, m, sx) do { const float wq_p = (m) * (sx); sm = sm + wq_p; } while (0)
+#define WQ_MIN4(sm, M, SX) do { WQ_MIN(sm, (M).x, (SX).x); WQ_MIN(sm, (M).y, (SX).y); WQ_MIN(sm, (M).z, (SX).z); WQ_MIN(sm, (M).w, (SX).w); } while (0)
+// lane 0 of an 8-lane group reads lane m's value (m = 0..7, a constant once the caller's loop is unrolled): row_shl:m
+__device__ __forceinline__ float wq_from_lane(float v, int m) {
+    switch (m) {
+        case 1: return dpp_f32<0x101>(v); case 2: return dpp_f32<0x102>(v); case 3: return dpp_f32<0x103>(v); case 4: return dpp_f32<0x104>(v);
+        case 5: return dpp_f32<0x105>(v); case 6: return dpp_f32<0x106>(v); case 7: return dpp_f32<0x107>(v); default: return v;
+    }
+}
 
 // -------------------------------------------------------------------------------------------------
 // C[M][N] = xq Wq^T, M > 1; grid = (ceil(N / 32), ceil(M / 8)); 256 threads = 32 output rows x 8 lanes; the 8 activation rows in LDS
 // -------------------------------------------------------------------------------------------------
-template <int EPI>
+template <int EPI, bool Q1>
 __global__ __launch_bounds__(256) void k_qgemm_exact(const int8_t * __restrict__ xq, const float * __restrict__ xd, int M, const int8_t * __restrict__ wq,
-                                                     const float * __restrict__ wd, int N, int K, wa_epi e) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];       // xs int8 [8][K] (kernel layout) | xds f32 [8][K/32]
+                                                     const float * __restrict__ wd, int N, int K, wa_epi e, const float * __restrict__ xsum,
+                                                     const float * __restrict__ wm) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];       // xs int8 [8][K] (kernel layout) | xds f32 [8][K/32] | Q1: xss f32 [8][K/32]
     const int nb = K >> 5;
     int8_t * xs = (int8_t *) smem;
     float * xds = (float *) (smem + (size_t) 8 * K);
+    float * xss = xds + 8 * nb;
     const int tid = threadIdx.x, l = tid & 7;
     const int m0 = blockIdx.y * 8, mt = min(8, M - m0);
     for (int c = tid; c < 8 * (K >> 4); c += 256) {
@@ -61,11 +81,16 @@ __global__ __launch_bounds__(256) void k_qgemm_exact(const int8_t * __restrict__
         if (m < mt) v = *(const uint4 *) (xq + (size_t) (m0 + m) * K + cc * 16);
         *(uint4 *) (xs + (size_t) m * K + cc * 16) = v;
     }
-    for (int c = tid; c < 8 * nb; c += 256) { const int m = c / nb, b = c - m * nb; xds[c] = m < mt ? xd[(size_t) (m0 + m) * nb + b] : 0.0f; }
+    for (int c = tid; c < 8 * nb; c += 256) {
+        const int m = c / nb, b = c - m * nb;
+        xds[c] = m < mt ? xd[(size_t) (m0 + m) * nb + b] : 0.0f;
+        if (Q1) xss[c] = m < mt ? xsum[(size_t) (m0 + m) * nb + b] : 0.0f;
+    }
     __syncthreads();
     const int n = blockIdx.x * 32 + (tid >> 3);
     const int nn = n < N ? n : N - 1;
     float acc[8];
+    float summs = 0.0f;       // Q1: THIS lane runs the minimum chain of activation row m = l
 #pragma unroll
     for (int m = 0; m < 8; ++m) acc[m] = 0.0f;
     wa_epi_pre pre[8];
@@ -74,29 +99,36 @@ __global__ __launch_bounds__(256) void k_qgemm_exact(const int8_t * __restrict__
     const int * wl = (const int *) wq + ((size_t) nn * 8 + l) * nb;            // this lane's quads, block after block
     const float * dl = wd + (size_t) nn * nb;
     const int * xl = (const int *) xs + (size_t) l * nb;
+    const float * ml = Q1 ? wm + (size_t) nn * nb : dl;
+    const float * sxl = xss + l * nb;
     if ((nb & 3) == 0) {
-        wq_i4 wn = *(const wq_i4 *) wl; wq_f4 dn = *(const wq_f4 *) dl;
+        wq_i4 wn = *(const wq_i4 *) wl; wq_f4 dn = *(const wq_f4 *) dl; wq_f4 mn = dn;
+        if (Q1) mn = *(const wq_f4 *) ml;
         for (int b = 0; b < nb; b += 4) {
-            const wq_i4 w = wn; const wq_f4 dw = dn;
+            const wq_i4 w = wn; const wq_f4 dw = dn; const wq_f4 mw = mn;
             const int bn = min(b + 4, nb - 4);
             wn = *(const wq_i4 *) (wl + bn); dn = *(const wq_f4 *) (dl + bn);
+            if (Q1) mn = *(const wq_f4 *) (ml + bn);
 #pragma unroll
             for (int m = 0; m < 8; ++m) {
                 const wq_i4 x = *(const wq_i4 *) (xl + (size_t) m * (K >> 2) + b);
                 const wq_f4 dx = *(const wq_f4 *) (xds + m * nb + b);
                 WQ_STEP4(acc[m], w, dw, x, dx);
             }
+            if (Q1) { const wq_f4 sx = *(const wq_f4 *) (sxl + b); WQ_MIN4(summs, mw, sx); }
         }
     } else {
         for (int b = 0; b < nb; ++b) {
             const int w = wl[b]; const float dw = dl[b];
 #pragma unroll
             for (int m = 0; m < 8; ++m) WQ_BLOCK(acc[m], w, dw, xl[(size_t) m * (K >> 2) + b], xds[m * nb + b]);
+            if (Q1) WQ_MIN(summs, ml[b], sxl[b]);
         }
     }
 #pragma unroll
     for (int m = 0; m < 8; ++m) {
-        const float v = wq_hsum8(acc[m]);
+        float v = wq_hsum8(acc[m]);
+        if (Q1) v = v + wq_from_lane(summs, m);
         if (l == 0 && n < N && m < mt) epi_apply<EPI>(e, m0 + m, n, v, pre[m]);
     }
 }
@@ -106,96 +138,113 @@ __global__ __launch_bounds__(256) void k_qgemm_exact(const int8_t * __restrict__
 // read from L2 with the same 16-byte pattern as the weights; 16 blocks (4 loads of each kind) in flight ahead of the arithmetic
 // -------------------------------------------------------------------------------------------------
 // one output row per 8 lanes: the row's dot product with the activation row (valid in lane l == 0 of the group)
+template <bool Q1>
 __device__ __forceinline__ float wq_row_dot(const int8_t * __restrict__ xq, const float * __restrict__ xd, const int8_t * __restrict__ wq,
-                                            const float * __restrict__ wd, int nn, int nb, int l) {
+                                            const float * __restrict__ wd, int nn, int nb, int l, const float * __restrict__ xsum,
+                                            const float * __restrict__ wm) {
     const int * wl = (const int *) wq + ((size_t) nn * 8 + l) * nb;
     const float * dl = wd + (size_t) nn * nb;
     const int * xl = (const int *) xq + (size_t) l * nb;
-    float acc = 0.0f;
+    const float * ml = Q1 ? wm + (size_t) nn * nb : dl;
+    const float * sl = Q1 ? xsum : xd;
+    float acc = 0.0f, summs = 0.0f;
     if ((nb & 3) == 0) {
-        wq_i4 wn[4], xn[4]; wq_f4 dn[4], en[4];
+        wq_i4 wn[4], xn[4]; wq_f4 dn[4], en[4], mn[4], sn[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const int bj = min(4 * j, nb - 4);
             wn[j] = *(const wq_i4 *) (wl + bj); dn[j] = *(const wq_f4 *) (dl + bj); xn[j] = *(const wq_i4 *) (xl + bj); en[j] = *(const wq_f4 *) (xd + bj);
+            if (Q1) { mn[j] = *(const wq_f4 *) (ml + bj); sn[j] = *(const wq_f4 *) (sl + bj); }
         }
         for (int b = 0; b < nb; b += 16) {
-            wq_i4 w[4], x[4]; wq_f4 dw[4], dx[4];
+            wq_i4 w[4], x[4]; wq_f4 dw[4], dx[4], mw[4], sx[4];
 #pragma unroll
-            for (int j = 0; j < 4; ++j) { w[j] = wn[j]; x[j] = xn[j]; dw[j] = dn[j]; dx[j] = en[j]; }
+            for (int j = 0; j < 4; ++j) { w[j] = wn[j]; x[j] = xn[j]; dw[j] = dn[j]; dx[j] = en[j]; if (Q1) { mw[j] = mn[j]; sx[j] = sn[j]; } }
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const int bj = min(b + 16 + 4 * j, nb - 4);
                 wn[j] = *(const wq_i4 *) (wl + bj); dn[j] = *(const wq_f4 *) (dl + bj); xn[j] = *(const wq_i4 *) (xl + bj); en[j] = *(const wq_f4 *) (xd + bj);
+                if (Q1) { mn[j] = *(const wq_f4 *) (ml + bj); sn[j] = *(const wq_f4 *) (sl + bj); }
             }
 #pragma unroll
-            for (int j = 0; j < 4; ++j) if (b + 4 * j < nb) WQ_STEP4(acc, w[j], dw[j], x[j], dx[j]);
+            for (int j = 0; j < 4; ++j) if (b + 4 * j < nb) { WQ_STEP4(acc, w[j], dw[j], x[j], dx[j]); if (Q1) WQ_MIN4(summs, mw[j], sx[j]); }
         }
     } else {
-        for (int b = 0; b < nb; ++b) WQ_BLOCK(acc, wl[b], dl[b], xl[b], xd[b]);
+        for (int b = 0; b < nb; ++b) { WQ_BLOCK(acc, wl[b], dl[b], xl[b], xd[b]); if (Q1) WQ_MIN(summs, ml[b], sl[b]); }
     }
-    return wq_hsum8(acc);
+    const float v = wq_hsum8(acc);
+    return Q1 ? v + summs : v;
 }
 
-template <int EPI>
+template <int EPI, bool Q1>
 __global__ __launch_bounds__(64) void k_qgemv_exact(const int8_t * __restrict__ xq, const float * __restrict__ xd, const int8_t * __restrict__ wq,
-                                                    const float * __restrict__ wd, int N, int K, wa_epi e) {
+                                                    const float * __restrict__ wd, int N, int K, wa_epi e, const float * __restrict__ xsum,
+                                                    const float * __restrict__ wm) {
     const int tid = threadIdx.x, l = tid & 7;
     const int n = blockIdx.x * 8 + (tid >> 3);
     const int nn = n < N ? n : N - 1;
     wa_epi_pre pre;
     if (l == 0) pre = epi_preload<EPI>(e, 0, nn);
-    const float v = wq_row_dot(xq, xd, wq, wd, nn, K >> 5, l);
+    const float v = wq_row_dot<Q1>(xq, xd, wq, wd, nn, K >> 5, l, xsum, wm);
     if (l == 0 && n < N) epi_apply<EPI>(e, 0, n, v, pre);
 }
 
 // the first MLP product of the decode step: 4 waves = 32 output rows = one Q8_0 block of the GELU output (N % 32 == 0)
+template <bool Q1>
 __global__ __launch_bounds__(256) void k_qgemv_gelu_q8(const int8_t * __restrict__ xq, const float * __restrict__ xd, const int8_t * __restrict__ wq,
                                                        const float * __restrict__ wd, int N, int K, const float * __restrict__ bias,
-                                                       const wa_f16 * __restrict__ gelu, int8_t * __restrict__ oq, float * __restrict__ oqd) {
+                                                       const wa_f16 * __restrict__ gelu, int8_t * __restrict__ oq, float * __restrict__ oqd,
+                                                       const float * __restrict__ xsum, const float * __restrict__ wm, float * __restrict__ oqs) {
     __shared__ float g[32];
     const int tid = threadIdx.x, l = tid & 7;
     const int n = blockIdx.x * 32 + (tid >> 3);
     const float bn = l == 0 ? bias[n] : 0.0f;
-    const float v = wq_row_dot(xq, xd, wq, wd, n, K >> 5, l);
+    const float v = wq_row_dot<Q1>(xq, xd, wq, wd, n, K >> 5, l, xsum, wm);
     if (l == 0) g[tid >> 3] = wa_gelu(v + bn, gelu);
     __syncthreads();
-    if (tid < 32) wa_q8_store(g[tid], 0, blockIdx.x, tid, N >> 5, oq, oqd);
+    if (tid < 32) wa_q8_store(g[tid], 0, blockIdx.x, tid, N >> 5, oq, oqd, Q1 ? oqs : nullptr);
 }
 void wa_launch_qgemv_gelu_q8(hipStream_t s, const int8_t * xq, const float * xd, const int8_t * wq, const float * wd, int N, int K, const float * bias,
-                             const wa_f16 * gelu, int8_t * oq, float * oqd) {
-    hipLaunchKernelGGL(k_qgemv_gelu_q8, dim3(N / 32), dim3(256), 0, s, xq, xd, wq, wd, N, K, bias, gelu, oq, oqd);
+                             const wa_f16 * gelu, int8_t * oq, float * oqd, const float * xs, const float * wm, float * oqs) {
+    if (wm) hipLaunchKernelGGL(k_qgemv_gelu_q8<true>, dim3(N / 32), dim3(256), 0, s, xq, xd, wq, wd, N, K, bias, gelu, oq, oqd, xs, wm, oqs);
+    else    hipLaunchKernelGGL(k_qgemv_gelu_q8<false>, dim3(N / 32), dim3(256), 0, s, xq, xd, wq, wd, N, K, bias, gelu, oq, oqd, xs, wm, oqs);
 }
 
 void wa_launch_qgemm_exact(hipStream_t s, wa_epi_mode mode, const int8_t * xq, const float * xd, int M, const int8_t * wq, const float * wd, int N, int K,
-                           const wa_epi & e) {
+                           const wa_epi & e, const float * xs, const float * wm) {
     const dim3 grid((N + 31) / 32, (M + 7) / 8);
-    const size_t lds = (size_t) 8 * K + (size_t) 8 * (K >> 5) * sizeof(float);
-#define WA_CASE(E) case E: { \
-        if (M == 1) { hipLaunchKernelGGL((k_qgemv_exact<E>), dim3((N + 7) / 8), dim3(64), 0, s, xq, xd, wq, wd, N, K, e); break; } \
-        if (lds > 48 * 1024) (void) hipFuncSetAttribute((const void *) k_qgemm_exact<E>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds); \
-        hipLaunchKernelGGL((k_qgemm_exact<E>), grid, dim3(256), lds, s, xq, xd, M, wq, wd, N, K, e); } break;
+    const size_t lds = (size_t) 8 * K + (size_t) (wm ? 16 : 8) * (K >> 5) * sizeof(float);
+#define WA_CASE_Q(E, Q1) { \
+        if (M == 1) { hipLaunchKernelGGL((k_qgemv_exact<E, Q1>), dim3((N + 7) / 8), dim3(64), 0, s, xq, xd, wq, wd, N, K, e, xs, wm); break; } \
+        if (lds > 48 * 1024) (void) hipFuncSetAttribute((const void *) k_qgemm_exact<E, Q1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds); \
+        hipLaunchKernelGGL((k_qgemm_exact<E, Q1>), grid, dim3(256), lds, s, xq, xd, M, wq, wd, N, K, e, xs, wm); }
+#define WA_CASE(E) case E: if (wm) WA_CASE_Q(E, true) else WA_CASE_Q(E, false) break;
     switch (mode) {
         WA_CASE(WA_EPI_F16) WA_CASE(WA_EPI_ENC_QKV) WA_CASE(WA_EPI_GELU_F32) WA_CASE(WA_EPI_RESID) WA_CASE(WA_EPI_F32) WA_CASE(WA_EPI_CROSS_KV) WA_CASE(WA_EPI_DEC_QKV)
         default: break;
     }
 #undef WA_CASE
+#undef WA_CASE_Q
 }
 
 // -------------------------------------------------------------------------------------------------
-// ggml_get_rows on the quantised token embedding (dequantize_row_q5_0 / q8_0, ggml-quants.c: q * d) + positional embedding
+// ggml_get_rows on the quantised token embedding (dequantize_row_q5_0 / q8_0, ggml-quants.c: q * d; dequantize_row_q4_1 / q5_1 with
+// wm set: q * d, then + m - two roundings) + positional embedding
 // -------------------------------------------------------------------------------------------------
 __global__ void k_dec_embed_q(const int32_t * __restrict__ tok, const int32_t * __restrict__ pos, int n_tokens, int d,
-                              const int8_t * __restrict__ wq, const float * __restrict__ wd, const float * __restrict__ pe, float * __restrict__ x) {
+                              const int8_t * __restrict__ wq, const float * __restrict__ wd, const float * __restrict__ pe, float * __restrict__ x,
+                              const float * __restrict__ wm) {
     const int j = blockIdx.x;
     const int t = tok[j], p = pos[j], nb = d >> 5;
     for (int i = threadIdx.x; i < d; i += blockDim.x) {
         const int b = i >> 5, el = i & 31;
         const int q = (int) wq[(((size_t) t * 8 + (el >> 2)) * nb + b) * 4 + (el & 3)];
-        x[(size_t) j * d + i] = (float) q * wd[(size_t) t * nb + b] + pe[(size_t) p * d + i];
+        float v = (float) q * wd[(size_t) t * nb + b];
+        if (wm) v = v + wm[(size_t) t * nb + b];
+        x[(size_t) j * d + i] = v + pe[(size_t) p * d + i];
     }
 }
 void wa_launch_dec_embed_q(hipStream_t stream, const int32_t * tok, const int32_t * pos, int n_tokens, int d, const int8_t * wq, const float * wd,
-                           const float * pe, float * x) {
-    hipLaunchKernelGGL(k_dec_embed_q, dim3(n_tokens), dim3(256), 0, stream, tok, pos, n_tokens, d, wq, wd, pe, x);
+                           const float * pe, float * x, const float * wm) {
+    hipLaunchKernelGGL(k_dec_embed_q, dim3(n_tokens), dim3(256), 0, stream, tok, pos, n_tokens, d, wq, wd, pe, x, wm);
 }
