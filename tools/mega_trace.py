@@ -29,7 +29,7 @@ order = [0, 6, 1, 2, 7, 3, 4, 5]
 for l in range(L):
     for p in order:
         r = tr[l * 8 + p]
-        extra = "  scores %.2f softmax %.2f pv %.2f gathered %.2f" % (us(r[4]), us(r[5]), us(r[6]), us(r[7])) if p >= 6 else ("  ln: sums %.2f squares %.2f" % (us(r[4]), us(r[5])) if p in (0, 2, 4) else ("  gathered+barrier %.2f dot %.2f" % (us(r[4]), us(r[5])) if p == 5 else ""))
+        extra = ("  scores %.2f softmax %.2f pv %.2f %s %.2f" % (us(r[4]), us(r[5]), us(r[6]), "products" if cq and p == 7 else "gathered", us(r[7]))) if p >= 6 else ("  ln: sums %.2f squares %.2f" % (us(r[4]), us(r[5])) if p in (0, 2, 4) else ("  gathered+barrier %.2f dot %.2f" % (us(r[4]), us(r[5])) if p == 5 else ""))
         if cq and p == 7:         # x seen by the cross role's LayerNorm, its sums / squares / output, the query in LDS; then attention
             c = tr[768 + l]
             print("L%02d %-10s in %8.2f (%4d polls)  ln: sums %.2f squares %.2f ready %.2f  query %8.2f  pub %8.2f%s" % (l, names[p], us(c[0]), c[1], us(c[4]), us(c[5]), us(c[2]), us(r[0]), us(r[3]), extra))
@@ -76,7 +76,13 @@ hp = np.array([us(x) for x in flat[3100:3100 + H]]); hi = np.array([us(x) for x 
 print("cross-attention per head: query seen %s" % " ".join("%.2f" % x for x in hi))
 print("cross-attention per head: published  %s" % " ".join("%.2f" % x for x in hp))
 f = flat[3010:3017]
-print("cross-attention (layer 4, head 0, workgroup 0): query in LDS %.2f | scores + wave max done %.2f | barrier %.2f | maxima exchanged %.2f | exp + sums done %.2f | total exchanged %.2f | p16 written + barrier %.2f" % tuple(us(x) for x in f))
+if cq:      # the one-exchange form (mg_role_cross X1): score granules at [layer][head][cell], one gather, the soft-max whole in every quarter
+    print("cross-attention (layer 4, head 0, workgroup 0): query in LDS %.2f | scores published %.2f | scores gathered + wave max %.2f | barrier %.2f | exp + sums done %.2f | total certified, p16 written %.2f | barrier %.2f" % tuple(us(x) for x in f))
+    c4 = tr[4 * 8 + 7]
+    print("cross-attention (layer 4, head 0, workgroup 0): P V + leftover products %.2f | barrier %.2f | tree (16 outputs) %.2f | leftovers added %.2f | published %.2f" % (us(c4[6]), us(c4[7]), us(flat[3001]), us(flat[3002]), us(c4[3])))
+    print("cross-attention (layer 4, head 0, workgroup 0): query in LDS -> published %.2f us" % (us(c4[3]) - us(f[0])))
+else:
+    print("cross-attention (layer 4, head 0, workgroup 0): query in LDS %.2f | scores + wave max done %.2f | barrier %.2f | maxima exchanged %.2f | exp + sums done %.2f | total exchanged %.2f | p16 written + barrier %.2f" % tuple(us(x) for x in f))
 f = flat[3020:3024].astype(np.int64)
 cyc = (int(f[2]) - int(f[0])) & 0xffffffff; wall = (int(f[3]) - int(f[1])) & 0xffffffff
 print("shader clock during the launch: %d cycles in %.2f us = %.0f MHz" % (cyc, wall / 100.0, cyc / (wall / 100.0)))

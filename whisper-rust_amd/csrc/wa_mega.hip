@@ -1252,6 +1252,32 @@ __device__ __forceinline__ void mg_attn_finish(const float * part, const wa_f16 
     }
 }
 
+// The same finish for a workgroup that owns 16 of the head's outputs (the one-exchange cross-attention role: part [32][16], the leftover
+// products dbl [32][16] already converted to F64 - one per thread, -0.0 beyond nl - before the caller's barrier): lanes 0..15 of wave 0 run
+// the tree and the 32 ordered F64 additions (vec.cpp:221-223) and publish outputs o0 .. o0 + 15 as 8 packed granules.  All reads at
+// constant offsets, all in flight together.
+__device__ __forceinline__ void mg_attn_finish16(const float * part, const double * dbl, gu64 * edge, int o0, unsigned seq, int tid,
+                                                 mg_kargs A = nullptr, int tslot = -1) {
+    if (tid < 16) {
+        if (tslot >= 0) mg_trace(A, tid == 0, tslot, mg_now());
+        float s32[32];
+        double dv[32];
+#pragma unroll
+        for (int r = 0; r < 32; ++r) s32[r] = part[r * 16 + tid];
+#pragma unroll
+        for (int cc = 0; cc < 32; ++cc) dv[cc] = dbl[cc * 16 + tid];
+        __builtin_amdgcn_sched_barrier(0);       // all 64 reads in flight together
+        double sumf = (double) wa_tree32(s32);
+        if (tslot >= 0) mg_trace(A, tid == 0, tslot + 1, mg_now() + (sumf == 1e300 ? 1u : 0u));
+#pragma unroll
+        for (int cc = 0; cc < 32; ++cc) sumf += dv[cc];
+        if (tslot >= 0) mg_trace(A, tid == 0, tslot + 2, mg_now() + (sumf == 1e300 ? 1u : 0u));
+        const unsigned hv = (unsigned) f2h((float) sumf);
+        const unsigned hi = dpp_u32<0x101>(hv);          // row_shl:1: lane i reads lane i+1
+        if ((tid & 1) == 0) gr_store(edge + ((o0 + tid) >> 1), seq, (hv & 0xffffu) | (hi << 16));
+    }
+}
+
 // -------------------------------------------------------------------------------------------------
 // role: self-attention of head h (whisper.cpp:2636-2651), every layer.  The K/V cells of earlier tokens are copied
 // into LDS while the GEMV workgroups are busy with the previous phases; the new cell arrives with the query.
@@ -1390,6 +1416,8 @@ __device__ __forceinline__ void mg_role_self(mg_kargs A_, int idx_) {
 //       final tree, the F64 leftovers and publishes the head's output.
 // The F64 sum is order-independent when certified (k_attn_exact); an uncertified sum (~1e-9 per soft-max) raises
 // status WA_MEGA_REDO and the host recomputes the token with the launch sequence.
+// k_decode_mega_cq (F16, d = 768) runs the role's ONE-EXCHANGE form instead (X1, described at the template below): only the scores
+// are exchanged, every quarter runs the whole soft-max, and P V is split by output dimension - no workgroup 0 that finishes the head.
 // -------------------------------------------------------------------------------------------------
 #define MG_CSTEPS 48                                    // steps of a chain incl. the leftover step: T <= 1535
 #define MG_CGR 2048                                     // granules per (layer, head) of the cross exchange area
@@ -1397,6 +1425,9 @@ __device__ __forceinline__ void mg_role_self(mg_kargs A_, int idx_) {
 #define MG_CGR_SUM 8
 #define MG_CGR_XCC 16                                   // (layer 0 area only) the four workgroups' XCC_IDs
 #define MG_CGR_PART 64                                  // + (w - 1) * 576: 512 chain sums + 8 leftover probabilities
+// one-exchange form (X1): score granule of cell c at index c < WA_MEGA_MAX_T; the XCC_IDs (layer 0 area) behind them
+#define MG_CGR_XCC1 WA_MEGA_MAX_T
+#define MG_CP_LD 56                                     // (X1) halfs between the chains' probability rows in LDS: 16-byte aligned, 28 words apart
 #define MG_CX_XF 32768                                  // (CQ) LDS of the role's own LayerNorm: residual row [d] f32 | normalised row [d] f16 | partial sums
 #define MG_CX_XIN (MG_CX_XF + WA_MEGA_MAX_D * 4)
 #define MG_CX_LNRED (MG_CX_XIN + WA_MEGA_MAX_D * 2)
@@ -1407,8 +1438,21 @@ __device__ __forceinline__ void mg_role_self(mg_kargs A_, int idx_) {
 // certificates) and the head's 64 rows of W_q,cross (one row per 8 lanes: mg_dot8's chains and tree, + bias, rounded to F16), redundantly in
 // each quarter: the hand-off P4 -> C of the GEMV role's query is gone.  CQ = the rows' step count at compile time (0: run time).
 // CQ < 0: the query arrives from the GEMV role through E_QC.
-template <bool Q = false, int CQ = -1>
+//
+// X1 (k_decode_mega_cq only): the ONE-EXCHANGE form.  The three exchanges above are store-to-load round trips that compute nothing
+// (0.64 + 1.00 + 1.28 us per layer); they exist because scores, soft-max and P V chains are all split by cells.  Here only the scores are:
+//   * K stays split by cells (mg_score unchanged); a quarter publishes each score as a granule at index = cell the moment it is computed
+//     and all eight waves gather the other quarters' (<= 1128 granules), keeping the running maximum: every quarter holds all T scores;
+//   * every quarter runs the WHOLE soft-max identically: same maximum, same wa_expf / wa_expf_libm split at n8, ops.cpp's 8-lane group
+//     tree, the F64 total over the same addends (certificate below), the same WA_MEGA_REDO decision, all F16 probabilities in its own LDS;
+//   * P V is split by OUTPUT: quarter w owns d_head indices [16 w, 16 w + 16) of all 32 chains - thread = (chain tid / 16, index tid % 16),
+//     V[32 s + r][16 w + j], the same <= 47 fmaf steps per chain in the same order - runs wa_tree32 and the ordered F64 leftovers for its
+//     16 outputs and publishes its 8 granules of E_AO2 itself: no gathering workgroup.
+// Which cells exist follows from T alone (cell c exists iff c < T; its owner is (c / 8) mod 4): a quarter without cells (T < 8 w + 1 <= 32)
+// publishes no score and nobody polls one of its indices, but it still computes and publishes its 16 outputs.
+template <bool Q = false, int CQ = -1, bool X1 = false>
 __device__ __forceinline__ void mg_role_cross(mg_kargs A_, int idx_) {
+    static_assert(!X1 || (CQ >= 0 && !Q), "the one-exchange form is the F16 d = 768 kernel's");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const mg_kargs A = mg_uniform(A_);
     int tid = threadIdx.x, lane = tid & 63;
@@ -1430,6 +1474,24 @@ __device__ __forceinline__ void mg_role_cross(mg_kargs A_, int idx_) {
     double * redd  = (double *) (smem + 8192 + 4096 + 1536 + 768 + 64 + 128);
     float  * red   = (float *) (smem + 8192 + 4096 + 1536 + 768 + 64 + 128 + 64);
     float  * bc    = red + 8;
+    double * dbl   = nullptr;
+    if constexpr (X1) {
+        // LDS: sc [MAX_T] f32 | p16 [32][MG_CP_LD] f16 by chain | part [32][16] f32 | dbl [32][16] f64 | vleft [32][16] f16 | pleft [32] f16 | qs [64] f16 | redd [8] | red [8] | bc [4]
+        constexpr int o_sc = 0, o_p16 = o_sc + WA_MEGA_MAX_T * 4, o_part = o_p16 + 32 * MG_CP_LD * 2, o_dbl = o_part + 32 * 16 * 4, o_vleft = o_dbl + 32 * 16 * 8,
+                      o_pleft = o_vleft + 32 * 16 * 2, o_qs = o_pleft + 32 * 2, o_redd = o_qs + 64 * 2, o_red = o_redd + 8 * 8, o_bc = o_red + 8 * 4, o_end = o_bc + 4 * 4;
+        static_assert(o_end <= MG_CX_XF && o_p16 % 16 == 0 && o_dbl % 8 == 0 && o_vleft % 16 == 0 && o_redd % 8 == 0 && MG_CP_LD % 8 == 0 && MG_CP_LD >= MG_CSTEPS,
+                      "LDS of the one-exchange form: below the role's LayerNorm area, 16-byte rows where 16 bytes are read");
+        sc    = (float *) (smem + o_sc);
+        p16   = (wa_f16 *) (smem + o_p16);
+        part  = (float *) (smem + o_part);
+        dbl   = (double *) (smem + o_dbl);
+        vleft = (wa_f16 *) (smem + o_vleft);
+        pleft = (wa_f16 *) (smem + o_pleft);
+        qs    = (wa_f16 *) (smem + o_qs);
+        redd  = (double *) (smem + o_redd);
+        red   = (float *) (smem + o_red);
+        bc    = (float *) (smem + o_bc);
+    }
 
     const int T = A->T, tpad = A->cross_tpad, L = A->n_layer;
     const float kq_scale = A->kq_scale;
@@ -1440,7 +1502,7 @@ __device__ __forceinline__ void mg_role_cross(mg_kargs A_, int idx_) {
     // them - not a promise)?  Each publishes its XCC_ID, all read the four; only then do the exchanges among them use L2-resident stores.
     if (wave == 0) {
         const unsigned xcc = (unsigned) __builtin_amdgcn_s_getreg(20 | (3 << 11)) & 0xfu;        // HW_REG_XCC_ID[3:0]
-        gu64 * X0 = (gu64 *) A->cross_gr + (size_t) h * MG_CGR + MG_CGR_XCC;
+        gu64 * X0 = (gu64 *) A->cross_gr + (size_t) h * MG_CGR + (X1 ? MG_CGR_XCC1 : MG_CGR_XCC);
         if (lane == 0) gr_store(X0 + w, seq, xcc);
         unsigned v[1];
         mg_sweep<1>(X0, [&](int) { return lane < 4 ? lane : -1; }, c, lane, v, 2900u);
@@ -1470,11 +1532,20 @@ __device__ __forceinline__ void mg_role_cross(mg_kargs A_, int idx_) {
             const int o = p * 128 + ks, cc = 32 * (o >> 3) + 8 * w + (o & 7);
             if (cc < T) { ka[p] = *(const GAS u32x4 *) (kp + (size_t) cc * 64 + 8 * a); kb[p] = *(const GAS u32x4 *) (kp + (size_t) cc * 64 + 32 + 8 * a); }
         }
+        if constexpr (X1) {      // chain tid / 16, own output tid % 16: V[32 s + r][16 w + j]; the leftover rows' own 32 bytes
+#pragma unroll
+            for (int s = 0; s < MG_CSTEPS; ++s) if (s < nsteps) vv[s] = *(const GAS unsigned short *) (vp + (size_t) (32 * s + (tid >> 4)) * 64 + 16 * w + (tid & 15));
+            if (wave == 0) {
+                const int row = tid >> 1;
+                if (row < nl) *(u32x4 *) (vleft + (size_t) tid * 8) = *(const GAS u32x4 *) (vp + (size_t) (np + row) * 64 + 16 * w + (tid & 1) * 8);
+            }
+        } else {
 #pragma unroll
         for (int s = 0; s < MG_CSTEPS; ++s) if (s < nsteps) vv[s] = *(const GAS unsigned short *) (vp + (size_t) (32 * s + 8 * w + wave) * 64 + lane);
         if (w == 0 && tid < 256) {
             const int row = tid >> 3;
             if (row < nl) *(u32x4 *) (vleft + (size_t) tid * 8) = *(const GAS u32x4 *) (vp + (size_t) (np + row) * 64 + (tid & 7) * 8);
+        }
         }
         if constexpr (CQ >= 0) {
             // ---- the head's query: rows 64 h + 8 wave + lane / 8, loaded with the keys (the poll below finds them landed: x arrives
@@ -1507,6 +1578,116 @@ __device__ __forceinline__ void mg_role_cross(mg_kargs A_, int idx_) {
         }
         mg_barrier();
 #define MG_CX(k) do { if (A->dbg && l == MG_WGTRACE_LAYER) mg_trace(A, ci == 0 && tid == 0, 3010 + (k), mg_now()); } while (0)
+        if constexpr (X1) {
+        MG_CX(0);
+        MG_CHAOS_ID(2000 + ci, 31u, seq);
+        // ---- scores of the own cells, each published (index = cell) as soon as it exists ----
+        float lmax = -INFINITY;
+        {
+            float qa[8], qb[8];
+#pragma unroll
+            for (int i = 0; i < 8; ++i) { qa[i] = h2f(qs[8 * a + i]); qb[i] = h2f(qs[32 + 8 * a + i]); }
+#pragma unroll
+            for (int p = 0; p < 3; ++p) {
+                const int o = p * 128 + ks, cc = 32 * (o >> 3) + 8 * w + (o & 7);
+                const float r = mg_score(ka[p], kb[p], qa, qb, kq_scale);
+                if (cc < T) {
+                    if (a == 0) { gr_store_l(X + cc, seq, __float_as_uint(r), local); sc[cc] = r; }
+                    lmax = fmaxf(lmax, r);
+                }
+            }
+        }
+        MG_CX(1);
+        MG_CHAOS_ID(2000 + ci, 33u, seq);
+        // ---- THE exchange: all eight waves gather the other quarters' scores (cells tid + 512 k), the running maximum with them ----
+        {
+            unsigned v[3];
+            const auto other = [&](int k) { const int cg = tid + 512 * k; return cg < T && ((cg >> 3) & 3) != w ? cg : -1; };
+            mg_sweep<3>(X, other, c, lane, v, 2400u + l);
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                const int cg = other(k);
+                if (cg >= 0) { const float r = __uint_as_float(v[k]); sc[cg] = r; lmax = fmaxf(lmax, r); }
+            }
+        }
+        lmax = wave_max(lmax);
+        if (lane == 0) red[wave] = lmax;
+        MG_CX(2);
+        mg_barrier();
+        MG_CX(3);
+        mg_trace(A, ci == 0 && tid == 0, (l * 8 + 7) * 8 + 4, mg_now());
+        MG_CHAOS_ID(2000 + ci, 34u, seq);
+        // ---- the whole soft-max, in every quarter alike: thread = cells tid + 512 k (a group of 8 cells = 8 consecutive lanes: ops.cpp's tree) ----
+        float mx = red[0];
+#pragma unroll
+        for (int k = 1; k < MG_NW; ++k) mx = fmaxf(mx, red[k]);
+        float e[3];
+        {
+            double ps = 0.0;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                const int cg = tid + 512 * k, g = cg >> 3;
+                const float sv = sc[cg];
+                e[k] = cg < n8 ? wa_expf(sv - mx) : (cg < T ? wa_expf_libm(sv - mx) : 0.0f);
+                float t = e[k] + dpp_f32<0x104>(e[k]);        // lanes r = 0..3 of the group: e[r] + e[r+4]
+                t = t + dpp_f32<0x102>(t);                    // r = 0: (e0+e4)+(e2+e6)   r = 1: (e1+e5)+(e3+e7)
+                t = t + dpp_f32<0x101>(t);                    // r = 0: the group sum, ops.cpp's tree
+                ps += g < ng ? ((tid & 7) == 0 ? (double) t : 0.0) : (double) e[k];      // (the n % 8 tail cells one by one; cells >= T add 0)
+            }
+            ps = wave_sum_d(ps);
+            if (lane == 0) redd[wave] = ps;
+        }
+        MG_CX(4);
+        mg_barrier();
+        mg_trace(A, ci == 0 && tid == 0, (l * 8 + 7) * 8 + 5, mg_now());
+        {
+            const double tot = ((redd[0] + redd[1]) + (redd[2] + redd[3])) + ((redd[4] + redd[5]) + (redd[6] + redd[7]));
+            // (the reference adds the ng + (n % 8) addends one after the other in F64: error <= (ng + 7) u S; this sum is a tree over the SAME
+            //  addends - <= 3 per thread in series (depth 2), wave_sum_d (6), the eight waves (3): depth 11 <= 16, error <= 16 u S; together
+            //  (ng + 8 + 16) u S as in the three-exchange form.  Every thread of every quarter forms the same total from the same values in
+            //  the same order, so all four take the same decision.)
+            const double delta = (double) (ng + 8 + 16) * 0x1p-53 * tot * 1.000001;
+            const float ilo = (float) (1.0 / (tot + delta)), ihi = (float) (1.0 / (tot - delta));
+            if (ilo != ihi && tid == 0 && !c.dead) __hip_atomic_store(c.status, (unsigned) WA_MEGA_REDO, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                const int cg = tid + 512 * k;
+                if (cg < T) {
+                    const wa_f16 ph = f2h(e[k] * ilo);
+                    if (cg < np) p16[(cg & 31) * MG_CP_LD + (cg >> 5)] = ph;       // by chain: a P V thread reads its chain's 48 probabilities as 6 x 16 bytes
+                    else pleft[cg - np] = ph;
+                }
+            }
+        }
+        MG_CX(5);
+        mg_barrier();
+        MG_CX(6);
+        MG_CHAOS_ID(2000 + ci, 32u, seq);
+        // ---- P V: thread = (chain r = tid / 16, own output j = tid % 16); then the leftover cell r's product for output j (vec.cpp:221-223) ----
+        {
+            const int r = tid >> 4;
+            float acc = 0.0f;
+            half8 pw[MG_CSTEPS / 8];
+#pragma unroll
+            for (int k = 0; k < MG_CSTEPS / 8; ++k) pw[k] = *(const half8 *) (p16 + r * MG_CP_LD + 8 * k);      // (16 lanes share an address: a broadcast)
+#pragma unroll
+            for (int s = 0; s < MG_CSTEPS; ++s) if (s < nsteps) acc = fmaf(h2f(vv[s]), (float) pw[s >> 3][s & 7], acc);
+            part[tid] = acc;
+            // as mg_attn_finish: ONE v_fma_mix_f32 with a -0.0 addend is the multiplication's float; rows >= nl hold stale LDS and become -0.0
+            float nzero = -0.0f;
+            asm volatile("" : "+v"(nzero));
+            int nlo = nl;
+            asm volatile("" : "+s"(nlo));
+            const float pr = fmaf(h2f(vleft[tid]), h2f(pleft[r]), nzero);
+            dbl[tid] = (double) (r < nlo ? pr : -0.0f);
+        }
+        mg_trace(A, ci == 0 && tid == 0, (l * 8 + 7) * 8 + 6, mg_now());
+        mg_barrier();
+        mg_trace(A, ci == 0 && tid == 0, (l * 8 + 7) * 8 + 7, mg_now());
+        mg_attn_finish16(part, dbl, mg_edge(A, l, E_AO2), 64 * h + 16 * w, seq, tid, A, A->dbg && ci == 0 && l == MG_WGTRACE_LAYER ? 3000 : -1);
+        mg_trace(A, ci == 0 && tid == 0, (l * 8 + 7) * 8 + 3, mg_now());
+        if (A->dbg && l == MG_WGTRACE_LAYER && w == 0) mg_trace(A, tid == 0, 3100 + h, mg_now());
+        } else {
         MG_CX(0);
         MG_CHAOS_ID(2000 + ci, 31u, seq);
         // ---- scores of the own cells (local index o = 8 s + r  <->  cell 32 s + 8 w + r) ----
@@ -1623,6 +1804,7 @@ __device__ __forceinline__ void mg_role_cross(mg_kargs A_, int idx_) {
             mg_trace(A, ci == 0 && tid == 0, (l * 8 + 7) * 8 + 3, mg_now());
             if (A->dbg && l == MG_WGTRACE_LAYER) mg_trace(A, tid == 0, 3100 + h, mg_now());
         }
+        }
         mg_barrier();
     }
     unsigned pf[96];
@@ -1695,7 +1877,7 @@ __global__ __launch_bounds__(MG_THREADS) void k_decode_mega_cq(const wa_mega_arg
     const mg_kargs Ap = (mg_kargs) __builtin_amdgcn_kernarg_segment_ptr();
     if (role == 0)      mg_role_gemv<2, 24, false, true>(Ap, idx);
     else if (role == 1) mg_role_self(Ap, idx);
-    else                mg_role_cross<false, 24>(Ap, idx);
+    else                mg_role_cross<false, 24, true>(Ap, idx);
 }
 
 bool wa_launch_decode_mega_cq(hipStream_t s, const wa_mega_args & a, int n_wg, size_t lds) {
