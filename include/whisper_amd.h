@@ -135,8 +135,8 @@ typedef struct whisper_model_loader {
     void   (*close)(void * ctx);
 } whisper_model_loader;
 
-/* ref: include/whisper.h:162-190 (grammar types are part of whisper_full_params' layout; grammar
- * sampling itself is out of scope, SURVEY.md §2 row 17: n_grammar_rules > 0 is ignored with a warning) */
+/* ref: include/whisper.h:162-190 (grammar-constrained sampling: whisper_full_params::grammar_rules is an array of
+ * n_grammar_rules pointers, one END-terminated element array per rule; a malformed grammar makes whisper_full return -20) */
 enum whisper_gretype {
     WHISPER_GRETYPE_END            = 0,
     WHISPER_GRETYPE_ALT            = 1,

@@ -21,6 +21,7 @@ SHAPES = {
     # tiny synthetic shapes for fast CPU-oracle tests (not real Whisper sizes)
     "s64":    dict(d=64,   heads=1,  enc=2,  dec=3,  n_mels=80,  n_vocab=51865),
     "s128":   dict(d=128,  heads=2,  enc=3,  dec=4,  n_mels=80,  n_vocab=51865),
+    "s128u":  dict(d=128,  heads=2,  enc=3,  dec=4,  n_mels=80,  n_vocab=51865, vocab="utf8"),   # s128 with multi-byte token texts (synth_vocab)
     "s192":   dict(d=192,  heads=3,  enc=2,  dec=2 + 1, n_mels=80, n_vocab=51865),   # d not a multiple of 128: tile guards
     "w1280":  dict(d=1280, heads=20, enc=1,  dec=3,  n_mels=128, n_vocab=51866),      # large-v3's width with few layers: the wide-model paths
     "m1024":  dict(d=1024, heads=16, enc=1,  dec=3,  n_mels=80,  n_vocab=51865),      # medium's width and head count with few layers (config 4's products)
@@ -81,7 +82,30 @@ def mel_filterbank(n_mels: int = 80, n_fft: int = 400, sr: int = 16000) -> np.nd
 # --------------------------------------------------------------------------------------------------
 # vocabulary: 50257 unique byte strings; id 220 == " " (as in GPT-2), id 50256 == "" (multilingual)
 # --------------------------------------------------------------------------------------------------
-def synth_vocab() -> list[bytes]:
+UTF8_BLOCK = 1000      # first id of the block that the "utf8" variant replaces
+
+
+def utf8_block() -> list[bytes]:
+    """Token texts of the "utf8" vocabulary variant: whole 2-, 3- and 4-byte characters, pairs of them, every proper prefix of the
+    longer ones, a continuation byte in front of a whole character, and lone lead and continuation bytes - what a byte-level BPE
+    vocabulary holds, and what reaches the grammar sampler's partial-sequence rules."""
+    two = [chr(c).encode() for c in range(0xC0, 0xC0 + 96)] + [chr(c).encode() for c in range(0x400, 0x400 + 64)]
+    three = [chr(c).encode() for c in range(0x800, 0x800 + 16)] + [chr(c).encode() for c in range(0x4E00, 0x4E00 + 96)] + [chr(c).encode() for c in range(0xFFF0, 0xFFFE)]
+    four = [chr(c).encode() for c in range(0x10000, 0x10000 + 16)] + [chr(c).encode() for c in range(0x1F600, 0x1F600 + 64)] + [chr(c).encode() for c in range(0x10FFF0, 0x110000)]
+    out = two + three + four
+    out += [a + b for a, b in zip(two[::4], three[::3])] + [a + b for a, b in zip(four[::5], two[1::7])]
+    for w in three + four:
+        out += [w[:k] for k in range(1, len(w))]
+    out += [w[-1:] + v for w, v in zip(three[::6], two[2::9])]                      # finishes a pending sequence, then a whole character
+    out += [bytes([b]) for b in range(0x80, 0x100)]                                  # lone continuation and lead bytes (0xC0, 0xC1, 0xF5.. never start a character)
+    seen, uniq = set(), []
+    for w in out:
+        if w not in seen:
+            seen.add(w); uniq.append(w)
+    return uniq
+
+
+def synth_vocab(variant: str | None = None) -> list[bytes]:
     words = []
     for i in range(N_BASE_VOCAB):
         if i == 220:
@@ -99,7 +123,12 @@ def synth_vocab() -> list[bytes]:
         if i % 3 == 0:
             s = " " + s
         words.append(s.encode())
-    assert len(set(words)) == len(words)
+    if variant == "utf8":
+        block = utf8_block()
+        words[UTF8_BLOCK:UTF8_BLOCK + len(block)] = block
+    else:
+        assert variant is None, variant
+    assert len(set(words)) == len(words) == N_BASE_VOCAB
     return words
 
 
@@ -177,7 +206,7 @@ def write_model(path: str, shape_name: str = "s64", seed: int = 0, with_tensors:
         filt = mel_filterbank(shape["n_mels"])
         f.write(struct.pack("<2i", shape["n_mels"], N_FFT_BINS))
         f.write(filt.tobytes())
-        vocab = synth_vocab()
+        vocab = synth_vocab(shape.get("vocab"))
         f.write(struct.pack("<i", len(vocab)))
         for w in vocab:
             f.write(struct.pack("<I", len(w)))

@@ -346,6 +346,8 @@ struct runner {
     std::vector<int> suppress_ids;      // tokens killed by suppress_regex / suppress_nst, resolved once per call
     int blank_id = -1;
     std::unique_ptr<wa_pool> pool;      // created with the first multi-decoder step
+    wa_grammar_rules grammar;           // params.grammar_rules, validated and copied once per call; empty(): no grammar, nothing below changes
+    std::shared_ptr<const wa_grammar_vocab> grammar_vocab;
     // (WHISPER_AMD_SAMPLE_TRACE) where decoder 0's host time goes: logit rules + log-soft-max, probabilities, top-k draws, beam bookkeeping, state machine
     int64_t tr_rules = 0, tr_probs = 0, tr_topk = 0, tr_beam = 0, tr_state = 0, tr_steps = 0;
     const bool tr_on = getenv("WHISPER_AMD_SAMPLE_TRACE") != nullptr;
@@ -446,6 +448,12 @@ struct runner {
             }
             const float max_text = max_f32(logprobs, vocab.token_beg);
             if (ts_logprob > max_text) for (int i = 0; i < vocab.token_beg; ++i) { logits[i] = -INFINITY; logprobs[i] = -INFINITY; }
+            else if (!grammar.empty() && !dec.grammar.stacks.empty()) {
+                // text tokens that no stack of this decoder's grammar accepts lose grammar_penalty (a subtraction, EOT never); the log-probs
+                // are formed again over all logits (whisper.cpp:6335-6357).  The greedy arg-max reads these log-probs, so !full_probs stands.
+                for (int32_t id : wa_grammar_rejects(grammar, *grammar_vocab, dec.grammar, dec.grammar_cache)) logits[id] -= p.grammar_penalty;
+                compute_logprobs(logits, n, logprobs);
+            }
         }
         const int64_t tr1 = tr_on ? wa_time_us() : 0;
         if (full_probs) compute_probs(logits, n, logprobs, dec.probs.data());
@@ -577,7 +585,19 @@ int runner::run(const float * samples, int n_samples) {
             st->energy = signal_energy(pcm, n_samples, 32);
         }
     }
-    if (p.n_grammar_rules > 0) WA_WARN("%s: grammar sampling is not implemented by this backend; rules ignored\n", __func__);
+    if (p.n_grammar_rules > 0 && p.grammar_rules != nullptr) {      // (either one alone: no grammar, whisper.cpp:6335 / 7064)
+        if (const char * why = wa_grammar_build(grammar, p.grammar_rules, p.n_grammar_rules, p.i_start_rule)) {
+            WA_ERROR("%s: grammar refused: %s\n", __func__, why);
+            return WA_ERR_GRAMMAR;
+        }
+        std::lock_guard<std::mutex> lk(ctx->grammar_vocab_m);
+        if (!ctx->grammar_vocab) {
+            auto v = std::make_shared<wa_grammar_vocab>();
+            wa_grammar_vocab_build(*v, vocab.id_to_token, vocab.token_eot);
+            ctx->grammar_vocab = v;
+        }
+        grammar_vocab = ctx->grammar_vocab;
+    }
 
     const int seek_start = p.offset_ms / 10;
     const int seek_end = p.duration_ms == 0 ? st->mel_n_len_org : seek_start + p.duration_ms / 10;
@@ -672,6 +692,7 @@ int runner::run(const float * samples, int n_samples) {
                 dec.sequence.score = -INFINITY;
                 dec.seek_delta = 100 * WHISPER_CHUNK_SIZE;
                 dec.failed = dec.completed = dec.has_ts = false;
+                wa_grammar_init(grammar, dec.grammar);              // whisper.cpp:7064 (no grammar: no stacks)
             }
 
             {   // prompt = [prev + last n_take past tokens] + sot/lang/task (whisper.cpp:7073-7085)
@@ -725,7 +746,7 @@ int runner::run(const float * samples, int n_samples) {
                 const int P = (int) prompt.size();
                 const auto & kvc = st->kv_self;
                 const bool seq_cells = wa_kv_cell_max(kvc) == P && P < (int) kvc.size && kvc.cells[P].pos < 0;
-                if (!(e && e[0] == '1') && p.strategy == WHISPER_SAMPLING_GREEDY && n_dec == 1 && t_cur < 1e-6f && !p.logits_filter_callback &&
+                if (!(e && e[0] == '1') && p.strategy == WHISPER_SAMPLING_GREEDY && n_dec == 1 && t_cur < 1e-6f && !p.logits_filter_callback && grammar.empty() &&
                     (wa_window_form(*st).usable() || st->batcher) && ctx->model.n_loaded > 0 && seq_cells)      // (a lock-step member: the window runs on its group's passes)
                     ov.on = wa_spec_begin(*ctx, *st, suppress_bits());
             }
@@ -771,6 +792,11 @@ int runner::run(const float * samples, int n_samples) {
                     };
                     uint32_t cur_c = 0;
                     std::vector<wa_sequence> next(n_dec);        // built from the decoders' sequences as they stand; swapped in once all are chosen
+                    // a candidate carries its source decoder's grammar state as it was when the candidate was drawn (whisper.cpp:7201, 7272): like the
+                    // sequences, copied from the decoders as they stand - several may adopt from one source - and swapped in once all are chosen;
+                    // a decoder that goes on from its own candidate keeps its state
+                    std::vector<wa_grammar_state> grammar_next(grammar.empty() ? 0 : n_dec);
+                    std::vector<char> grammar_adopted(n_dec, 0);
                     for (int j = 0; j < n_dec; ++j) {
                         auto & dec = st->decoders[j];
                         if (dec.completed || dec.failed) continue;
@@ -779,6 +805,7 @@ int runner::run(const float * samples, int n_samples) {
                         while (beam_candidates.size() > cur_c && same_candidate(beam_candidates[cur_c], cur) && i > 0) ++cur_c;
                         dec.seek_delta = cur.seek_delta;
                         dec.has_ts = cur.has_ts;
+                        if (!grammar.empty() && cur.decoder_idx != j) { grammar_next[j] = st->decoders[cur.decoder_idx].grammar; grammar_adopted[j] = 1; }
                         next[j] = st->decoders[cur.decoder_idx].sequence;
                         next[j].tokens.push_back(cur.tok);
                         next[j].sum_logprobs_all = cur.sum_logprobs_all;
@@ -788,6 +815,7 @@ int runner::run(const float * samples, int n_samples) {
                         auto & dec = st->decoders[j];
                         if (dec.completed || dec.failed) continue;
                         std::swap(dec.sequence, next[j]);
+                        if (grammar_adopted[j]) std::swap(dec.grammar, grammar_next[j]);
                     }
                     for (int j = 0; j < n_dec; ++j) {
                         auto & dec = st->decoders[j];
@@ -812,6 +840,7 @@ int runner::run(const float * samples, int n_samples) {
                         result_len = i + 1;
                         dec.has_ts = true;
                     }
+                    if (!grammar.empty()) wa_grammar_accept(grammar, dec.grammar, vocab.id_to_token[token.id].c_str());     // whisper.cpp:7329
                     if (token.id == vocab.token_eot || (p.max_tokens > 0 && i >= p.max_tokens) ||
                         (dec.has_ts && seek + dec.seek_delta + delta_min >= seek_end)) {
                         if (result_len == 0 && !p.no_timestamps) {
@@ -1002,5 +1031,9 @@ int runner::run(const float * samples, int n_samples) {
 
 int wa_full(whisper_context * ctx, whisper_state * st, whisper_full_params params, const float * samples, int n_samples) {
     runner r(ctx, st, params);
+    struct grammar_release {        // the decoders' grammar look-ups are valid for this call's rule table only: nothing of them stays with the state
+        whisper_state * s;
+        ~grammar_release() { for (auto & dec : s->decoders) { dec.grammar_cache.release(); dec.grammar = wa_grammar_state(); } }
+    } release { st };
     return r.run(samples, n_samples);
 }

@@ -10,12 +10,15 @@
 
 #include "../../include/whisper_amd.h"
 #include "wa_one_launch.h"
+#include "wa_grammar.h"
 
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 #include <cstdio>
 #include <map>
+#include <memory>
+#include <mutex>
 #include <random>
 #include <set>
 #include <string>
@@ -129,6 +132,8 @@ struct whisper_context {
     whisper_state * state = nullptr;      // default state (only for the non-_no_state constructors)
     std::string path_model;
     std::vector<void *> batcher_cache;    // idle lock-step batchers (wa_decode.cpp), kept between whisper_amd_full_batch / whisper_full_parallel calls
+    std::shared_ptr<const wa_grammar_vocab> grammar_vocab;     // the vocabulary's code points, decoded by the first call that brings a grammar (wa_full.cpp)
+    std::mutex grammar_vocab_m;
     long batch_steps = 0, batch_rows = 0, batch_one_launch = 0; // the last whisper_amd_full_batch call: lock-step passes, the token rows they served, passes that were one launch
 };
 
@@ -190,6 +195,8 @@ struct wa_decoder {
     std::vector<float> probs, logits, logprobs;
     std::vector<std::pair<double, int>> logits_id;
     mutable std::mt19937 rng;
+    wa_grammar_state grammar;             // whisper_full_params::grammar_rules: rebuilt for every temperature pass; travels with a beam candidate
+    wa_grammar_cache grammar_cache;       // this decoder's own look-ups for the current call (wa_grammar.h); stays when the state is replaced
 };
 
 struct whisper_state {

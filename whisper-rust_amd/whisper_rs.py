@@ -94,6 +94,13 @@ LOGITS_FILTER_CB = C.CFUNCTYPE(None, C.c_void_p, C.c_void_p, C.POINTER(whisper_t
 LOG_CB = C.CFUNCTYPE(None, C.c_int, C.c_char_p, C.c_void_p)
 
 
+GRETYPE_END, GRETYPE_ALT, GRETYPE_RULE_REF, GRETYPE_CHAR, GRETYPE_CHAR_NOT, GRETYPE_CHAR_RNG_UPPER, GRETYPE_CHAR_ALT = range(7)   # whisper.h:162-185
+
+
+class whisper_grammar_element(C.Structure):
+    _fields_ = [("type", C.c_int), ("value", C.c_uint32)]
+
+
 class _greedy(C.Structure):
     _fields_ = [("best_of", C.c_int)]
 
@@ -275,6 +282,20 @@ class FullParams:
             self._keep[name] = arr
             self.c.prompt_tokens = arr
             self.c.prompt_n_tokens = len(value)
+        elif name == "grammar":
+            # `value` = (rules, i_start_rule); rules[r] = the (type, value) elements of rule r, the closing END added here (None: a null
+            # pointer in the array, for tests of the refusal).  whisper.h wants an
+            # array of n_grammar_rules POINTERS, one END-terminated element array per rule; whisper-rs 0.14.3's own set_grammar hands over
+            # one flat element array instead (src/whisper_params.rs:743-762), which no engine can read - this mirror follows the header.
+            rules, i_start = value
+            arrs = [None if r is None else
+                    (whisper_grammar_element * (len(r) + 1))(*([whisper_grammar_element(t, v) for t, v in r] + [whisper_grammar_element(GRETYPE_END, 0)]))
+                    for r in rules]
+            ptrs = (C.c_void_p * max(1, len(arrs)))(*[None if a is None else C.addressof(a) for a in arrs])
+            self._keep[name] = (arrs, ptrs)
+            self.c.grammar_rules = C.cast(ptrs, C.c_void_p) if arrs else None
+            self.c.n_grammar_rules = len(arrs)
+            self.c.i_start_rule = i_start
         elif name.endswith("_callback"):
             ftype = dict(new_segment_callback=NEW_SEGMENT_CB, progress_callback=PROGRESS_CB,
                          encoder_begin_callback=ENCODER_BEGIN_CB, abort_callback=ABORT_CB,
