@@ -69,7 +69,7 @@ WHISPER_API void ggml_backend_load_all(void);
 struct whisper_context;      /* read-only model: weights resident in HBM, vocab, filters          */
 struct whisper_state;        /* per-stream mutable state: mel, activations, KV caches, results    */
 struct whisper_full_params;
-struct whisper_vad_context;  /* VAD is out of scope: constructors return NULL */
+struct whisper_vad_context;  /* Silero VAD: front end on the device, LSTM recurrence on the host ("VAD") */
 struct whisper_vad_segments;
 
 typedef int32_t whisper_pos;
@@ -403,8 +403,13 @@ WHISPER_API float   whisper_full_get_segment_no_speech_prob           (struct wh
 WHISPER_API float   whisper_full_get_segment_no_speech_prob_from_state(struct whisper_state * state, int i_segment);
 
 /* ------------------------------------------------------------------------------------------------
- * VAD + bench helpers: exported for link completeness only ("stubs returning
- * unsupported are acceptable").             ref: include/whisper.h:677-725
+ * VAD (ref: include/whisper.h:677-725): probabilities, segments and whisper_full's `vad = true` are
+ * bit-identical to the reference's CPU VAD.  One model shape is supported (the Silero 16 kHz model the
+ * reference's graph hard-codes); anything else is refused at load time with a message naming it.
+ * whisper_vad_context_params.use_gpu is not looked at (its default is false and there is no CPU path):
+ * the context always runs on `gpu_device`; a context that whisper_full creates from `vad_model_path`
+ * runs on the whisper context's device.  `n_threads` is accepted and unused.
+ * The bench helpers below remain link-completeness stubs.
  * ---------------------------------------------------------------------------------------------- */
 WHISPER_API struct whisper_vad_params         whisper_vad_default_params(void);
 WHISPER_API struct whisper_vad_context_params whisper_vad_default_context_params(void);
@@ -444,6 +449,14 @@ WHISPER_API void whisper_amd_abi_sizes(size_t out[6]);
 WHISPER_API int64_t whisper_amd_get_mel      (struct whisper_state * state, float * dst, int64_t cap, int * n_len, int * n_mel);
 WHISPER_API int64_t whisper_amd_get_embd_enc (struct whisper_state * state, float * dst, int64_t cap);
 WHISPER_API int64_t whisper_amd_get_embd_conv(struct whisper_state * state, float * dst, int64_t cap);
+
+/* VAD front end alone (k_vad_front): the [n_chunks][512] F32 LSTM gate inputs W_ih x + b_ih of every 512-sample window of
+ * `samples` (the last one zero-filled), gate order i, f, g, o.  Copies up to `cap` elements, returns the full count, -1 on failure.
+ * whisper_amd_vad_tile: windows per workgroup of that kernel (tests put chunk counts on either side of it).
+ * whisper_amd_vad_timings: out = { whisper_vad_detect_speech wall time, of it waiting for the device, of it host recurrence } in us. */
+WHISPER_API int64_t whisper_amd_vad_front  (struct whisper_vad_context * vctx, const float * samples, int n_samples, float * dst, int64_t cap);
+WHISPER_API int     whisper_amd_vad_tile   (void);
+WHISPER_API void    whisper_amd_vad_timings(struct whisper_vad_context * vctx, int64_t out_us[3]);
 
 /* Per-state stage timers in microseconds + call counts (the reference keeps them per state but
  * only prints ctx->state's, whisper.cpp:868-881,4274-4296):

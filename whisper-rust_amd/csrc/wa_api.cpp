@@ -320,7 +320,7 @@ struct whisper_state * whisper_init_state(struct whisper_context * ctx) {
     return st;
 }
 
-void whisper_free_state(struct whisper_state * st) { if (st) { wa_state_release(*st); delete st; } }
+void whisper_free_state(struct whisper_state * st) { if (st) { whisper_vad_free(st->vad_context); wa_state_release(*st); delete st; } }
 void whisper_free(struct whisper_context * ctx) {
     if (!ctx) return;
     wa_batcher_free_all(*ctx);
@@ -575,9 +575,22 @@ int whisper_full_with_state(struct whisper_context * ctx, struct whisper_state *
     catch (const std::exception & e) { WA_ERROR("%s: exception: %s\n", __func__, e.what()); return -1; }
     catch (...) { WA_ERROR("%s: unknown exception\n", __func__); return -1; }
 }
+// vad = true: the speech-only audio of whisper_full / whisper_full_parallel, computed on ctx->state (whose table the getters then use)
+static int vad_prepare(whisper_context * ctx, const whisper_full_params & params, const float * samples, int n_samples, std::vector<float> & vad_samples) {
+    try {
+        if (wa_vad_for_full(ctx, ctx->state, params, samples, n_samples, vad_samples)) return 0;
+        WA_ERROR("%s: failed to compute VAD\n", __func__);
+    } catch (const std::exception & e) { WA_ERROR("%s: exception: %s\n", __func__, e.what()); }
+    return -1;
+}
 int whisper_full(struct whisper_context * ctx, struct whisper_full_params params, const float * samples, int n_samples) {
     if (!ctx || !ctx->state) return -1;
-    if (params.vad) { WA_ERROR("%s: VAD is not supported by this backend\n", __func__); return -1; }
+    std::vector<float> vad_samples;
+    if (params.vad) {            // ref: whisper.cpp:7719-7732
+        if (vad_prepare(ctx, params, samples, n_samples, vad_samples) < 0) return -1;
+        if (vad_samples.empty()) { ctx->state->result_all.clear(); return 0; }
+        samples = vad_samples.data(); n_samples = (int) vad_samples.size();
+    }
     return whisper_full_with_state(ctx, ctx->state, params, samples, n_samples);
 }
 // Lock-step decode groups for chunks transcribed together on one device (whisper_amd_full_batch, whisper_full_parallel): groups of
@@ -613,7 +626,12 @@ int whisper_full_parallel(struct whisper_context * ctx, struct whisper_full_para
     // the transcription may be degraded near the cuts.
     if (!ctx || !ctx->state) return -1;
     if (n_processors <= 1) return whisper_full(ctx, params, samples, n_samples);
-    if (params.vad) { WA_ERROR("%s: VAD is not supported by this backend\n", __func__); return -1; }
+    std::vector<float> vad_samples;
+    if (params.vad) {            // ref: whisper.cpp:7747-7759 (no speech: 0, and unlike whisper_full the earlier results stay)
+        if (vad_prepare(ctx, params, samples, n_samples, vad_samples) < 0) return -1;
+        if (vad_samples.empty()) return 0;
+        samples = vad_samples.data(); n_samples = (int) vad_samples.size();
+    }
     const int offset_samples = (WHISPER_SAMPLE_RATE * params.offset_ms) / 1000;
     const int n_per = (n_samples - offset_samples) / n_processors;
     std::vector<whisper_state *> states;
@@ -667,16 +685,25 @@ int whisper_full_parallel(struct whisper_context * ctx, struct whisper_full_para
 }
 
 // -------------------------------------------------------------------------------------------------
-// result getters (ref: whisper.cpp:7866-8033); VAD time remapping does not apply (no VAD here)
+// result getters (ref: whisper.cpp:7866-8033); segment times map back through the state's VAD table when it has one (7924-7960)
 // -------------------------------------------------------------------------------------------------
 int whisper_full_n_segments_from_state(struct whisper_state * st) { return (int) st->result_all.size(); }
 int whisper_full_n_segments(struct whisper_context * ctx) { return (int) ctx->state->result_all.size(); }
 int whisper_full_lang_id_from_state(struct whisper_state * st) { return st->lang_id; }
 int whisper_full_lang_id(struct whisper_context * ctx) { return ctx->state->lang_id; }
-int64_t whisper_full_get_segment_t0_from_state(struct whisper_state * st, int i) { return st->result_all[i].t0; }
-int64_t whisper_full_get_segment_t0(struct whisper_context * ctx, int i) { return ctx->state->result_all[i].t0; }
-int64_t whisper_full_get_segment_t1_from_state(struct whisper_state * st, int i) { return st->result_all[i].t1; }
-int64_t whisper_full_get_segment_t1(struct whisper_context * ctx, int i) { return ctx->state->result_all[i].t1; }
+int64_t whisper_full_get_segment_t0_from_state(struct whisper_state * st, int i) {
+    if (!st->has_vad_segments || st->vad_mapping_table.empty()) return st->result_all[i].t0;
+    return wa_vad_map_time(st->result_all[i].t0, st->vad_mapping_table);
+}
+int64_t whisper_full_get_segment_t1_from_state(struct whisper_state * st, int i) {
+    if (!st->has_vad_segments || st->vad_mapping_table.empty()) return st->result_all[i].t1;
+    const int64_t orig_t0 = whisper_full_get_segment_t0_from_state(st, i);
+    int64_t orig_t1 = wa_vad_map_time(st->result_all[i].t1, st->vad_mapping_table);
+    if (orig_t1 - orig_t0 < 10) orig_t1 = orig_t0 + 10;          // minimum duration, as the reference
+    return orig_t1;
+}
+int64_t whisper_full_get_segment_t0(struct whisper_context * ctx, int i) { return whisper_full_get_segment_t0_from_state(ctx->state, i); }
+int64_t whisper_full_get_segment_t1(struct whisper_context * ctx, int i) { return whisper_full_get_segment_t1_from_state(ctx->state, i); }
 bool whisper_full_get_segment_speaker_turn_next_from_state(struct whisper_state * st, int i) { return st->result_all[i].speaker_turn_next; }
 bool whisper_full_get_segment_speaker_turn_next(struct whisper_context * ctx, int i) { return ctx->state->result_all[i].speaker_turn_next; }
 const char * whisper_full_get_segment_text_from_state(struct whisper_state * st, int i) { return st->result_all[i].text.c_str(); }
@@ -697,22 +724,8 @@ float whisper_full_get_segment_no_speech_prob_from_state(struct whisper_state * 
 float whisper_full_get_segment_no_speech_prob(struct whisper_context * ctx, int i) { return ctx->state->result_all[i].no_speech_prob; }
 
 // -------------------------------------------------------------------------------------------------
-// VAD / bench: link-completeness stubs (out of scope)
+// bench: link-completeness stubs (out of scope); the VAD API is in wa_vad.cpp
 // -------------------------------------------------------------------------------------------------
-struct whisper_vad_context_params whisper_vad_default_context_params(void) { whisper_vad_context_params r; r.n_threads = 4; r.use_gpu = false; r.gpu_device = 0; return r; }
-struct whisper_vad_context * whisper_vad_init_from_file_with_params(const char *, struct whisper_vad_context_params) { WA_ERROR("VAD is not supported by this backend\n"); return nullptr; }
-struct whisper_vad_context * whisper_vad_init_with_params(struct whisper_model_loader *, struct whisper_vad_context_params) { WA_ERROR("VAD is not supported by this backend\n"); return nullptr; }
-bool    whisper_vad_detect_speech(struct whisper_vad_context *, const float *, int) { return false; }
-int     whisper_vad_n_probs(struct whisper_vad_context *) { return 0; }
-float * whisper_vad_probs  (struct whisper_vad_context *) { return nullptr; }
-struct whisper_vad_segments * whisper_vad_segments_from_probs(struct whisper_vad_context *, struct whisper_vad_params) { return nullptr; }
-struct whisper_vad_segments * whisper_vad_segments_from_samples(struct whisper_vad_context *, struct whisper_vad_params, const float *, int) { return nullptr; }
-int   whisper_vad_segments_n_segments(struct whisper_vad_segments *) { return 0; }
-float whisper_vad_segments_get_segment_t0(struct whisper_vad_segments *, int) { return 0.0f; }
-float whisper_vad_segments_get_segment_t1(struct whisper_vad_segments *, int) { return 0.0f; }
-void  whisper_vad_free_segments(struct whisper_vad_segments *) {}
-void  whisper_vad_free(struct whisper_vad_context *) {}
-
 int          whisper_bench_memcpy(int) { return 0; }
 const char * whisper_bench_memcpy_str(int) { return "whisper_bench_memcpy: not applicable to the HIP backend (use bench.py)\n"; }
 int          whisper_bench_ggml_mul_mat(int) { return 0; }

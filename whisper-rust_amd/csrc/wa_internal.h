@@ -11,6 +11,7 @@
 #include "../../include/whisper_amd.h"
 #include "wa_one_launch.h"
 #include "wa_grammar.h"
+#include "wa_vad.h"
 
 #include <hip/hip_runtime.h>
 
@@ -313,6 +314,12 @@ struct whisper_state {
 
     std::vector<float> logits;            // [n_tokens][n_vocab] host copy (only flagged rows valid)
     std::vector<wa_segment> result_all;
+
+    // VAD (ref: whisper.cpp:950-963): created on the first whisper_full(vad = true) on this state, freed with it.  The table maps segment
+    // times of the speech-only audio back; only the next VAD call on this state replaces it (a later vad = false call still maps)
+    struct whisper_vad_context * vad_context = nullptr;
+    bool has_vad_segments = false;
+    std::vector<wa_vad_map_point> vad_mapping_table;
     std::vector<whisper_token> prompt_past;
     int   lang_id = 0;
     float no_speech_prob = 0.0f;
@@ -343,6 +350,10 @@ bool wa_mel_set    (whisper_context & ctx, whisper_state & st, const float * dat
 bool wa_encode     (whisper_context & ctx, whisper_state & st, int mel_offset, ggml_abort_callback cb, void * cb_data);
 bool wa_decode     (whisper_context & ctx, whisper_state & st, const wa_batch & batch, bool save_aheads,
                     ggml_abort_callback cb, void * cb_data);                         // wa_decode.cpp
+// VAD (wa_vad.cpp)
+whisper_vad_context * wa_vad_create_from_file(const char * path, int n_threads, int device);
+bool wa_vad_for_full(whisper_context * ctx, whisper_state * st, const whisper_full_params & params, const float * samples, int n_samples,
+                     std::vector<float> & filtered);           // false: failure; `filtered` empty: no speech
 // host-overlapped greedy decoding on the one-launch step (wa_decode.cpp); launch k decodes position pos0 + k
 struct wa_spec_state { int last, penult, seek_delta, has_ts; };
 bool wa_spec_begin (whisper_context & ctx, whisper_state & st, const std::vector<uint32_t> & suppress_bits);

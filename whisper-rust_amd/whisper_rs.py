@@ -85,6 +85,19 @@ class whisper_vad_params(C.Structure):
     ]
 
 
+class whisper_vad_context_params(C.Structure):
+    _fields_ = [("n_threads", C.c_int), ("use_gpu", C.c_bool), ("gpu_device", C.c_int)]
+
+
+LOADER_READ = C.CFUNCTYPE(C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t)
+LOADER_EOF = C.CFUNCTYPE(C.c_bool, C.c_void_p)
+LOADER_CLOSE = C.CFUNCTYPE(None, C.c_void_p)
+
+
+class whisper_model_loader(C.Structure):
+    _fields_ = [("context", C.c_void_p), ("read", LOADER_READ), ("eof", LOADER_EOF), ("close", LOADER_CLOSE)]
+
+
 NEW_SEGMENT_CB = C.CFUNCTYPE(None, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p)
 PROGRESS_CB = C.CFUNCTYPE(None, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p)
 ENCODER_BEGIN_CB = C.CFUNCTYPE(C.c_bool, C.c_void_p, C.c_void_p, C.c_void_p)
@@ -213,6 +226,34 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     proto("whisper_print_timings", None, P)
     proto("whisper_reset_timings", None, P)
     proto("whisper_log_set", None, LOG_CB, P)
+    # whisper_full / whisper_full_parallel on the context's own state, and the context-level getters
+    proto("whisper_init_from_file_with_params", P, C.c_char_p, whisper_context_params)
+    proto("whisper_full", I, P, whisper_full_params, C.POINTER(F), I)
+    proto("whisper_full_parallel", I, P, whisper_full_params, C.POINTER(F), I, I)
+    proto("whisper_full_n_segments", I, P)
+    proto("whisper_full_get_segment_t0", C.c_int64, P, I)
+    proto("whisper_full_get_segment_t1", C.c_int64, P, I)
+    proto("whisper_full_get_segment_text", C.c_char_p, P, I)
+    proto("whisper_full_n_tokens", I, P, I)
+    proto("whisper_full_get_token_data", whisper_token_data, P, I, I)
+    # voice activity detection (whisper.h: whisper_vad_*)
+    proto("whisper_vad_default_context_params", whisper_vad_context_params)
+    proto("whisper_vad_default_params", whisper_vad_params)
+    proto("whisper_vad_init_from_file_with_params", P, C.c_char_p, whisper_vad_context_params)
+    proto("whisper_vad_init_with_params", P, C.POINTER(whisper_model_loader), whisper_vad_context_params)
+    proto("whisper_vad_detect_speech", C.c_bool, P, C.POINTER(F), I)
+    proto("whisper_vad_n_probs", I, P)
+    proto("whisper_vad_probs", C.POINTER(F), P)
+    proto("whisper_vad_segments_from_probs", P, P, whisper_vad_params)
+    proto("whisper_vad_segments_from_samples", P, P, whisper_vad_params, C.POINTER(F), I)
+    proto("whisper_vad_segments_n_segments", I, P)
+    proto("whisper_vad_segments_get_segment_t0", F, P, I)
+    proto("whisper_vad_segments_get_segment_t1", F, P, I)
+    proto("whisper_vad_free_segments", None, P)
+    proto("whisper_vad_free", None, P)
+    if hasattr(lib, "whisper_amd_vad_front"):
+        proto("whisper_amd_vad_front", C.c_int64, P, C.POINTER(F), I, C.POINTER(F), C.c_int64)
+        proto("whisper_amd_vad_tile", I)
     if hasattr(lib, "whisper_amd_full_batch"):
         proto("whisper_amd_full_batch", I, P, C.POINTER(C.c_void_p), I, whisper_full_params, C.POINTER(C.c_void_p), C.POINTER(C.c_int))
     if hasattr(lib, "whisper_amd_rows_stats"):
@@ -273,7 +314,7 @@ class FullParams:
             self.c.greedy.best_of = value
         elif name == "beam_size":
             self.c.beam_search.beam_size = value
-        elif name in ("language", "initial_prompt", "suppress_regex"):
+        elif name in ("language", "initial_prompt", "suppress_regex", "vad_model_path"):
             b = None if value is None else value.encode()
             self._keep[name] = b  # whisper-rs leaks the CString; we keep a reference
             setattr(self.c, name, b)
@@ -513,4 +554,151 @@ class WhisperState:
     def free(self):
         if self.ptr:
             self.lib.whisper_free_state(self.ptr)
+            self.ptr = None
+
+
+# ---------------------------------------------------------------------------------------------------
+# voice activity detection (whisper.h: whisper_vad_*) and whisper_full on the context's own state
+# ---------------------------------------------------------------------------------------------------
+def vad_params(lib: C.CDLL, threshold=None, min_speech_duration_ms=None, min_silence_duration_ms=None, max_speech_duration_s=None,
+               speech_pad_ms=None, samples_overlap=None) -> whisper_vad_params:
+    """`whisper_vad_default_params()` with the given fields replaced."""
+    p = lib.whisper_vad_default_params()
+    for k, v in dict(threshold=threshold, min_speech_duration_ms=min_speech_duration_ms, min_silence_duration_ms=min_silence_duration_ms,
+                     max_speech_duration_s=max_speech_duration_s, speech_pad_ms=speech_pad_ms, samples_overlap=samples_overlap).items():
+        if v is not None:
+            setattr(p, k, v)
+    return p
+
+
+def _f32(pcm) -> np.ndarray:
+    return np.ascontiguousarray(pcm, dtype=np.float32)
+
+
+class WhisperVadContext:
+    """whisper_vad_context: `detect_speech` leaves one probability per 512 samples, `segments_*` turn them into (t0, t1) centiseconds."""
+
+    def __init__(self, lib: C.CDLL, ptr: int):
+        self.lib, self.ptr = lib, ptr
+
+    @staticmethod
+    def _params(lib, n_threads, gpu_device):
+        p = lib.whisper_vad_default_context_params()
+        if n_threads is not None:
+            p.n_threads = n_threads
+        p.gpu_device = gpu_device
+        return p
+
+    @classmethod
+    def new(cls, path: str, lib: Optional[C.CDLL] = None, n_threads: Optional[int] = None, gpu_device: int = 0) -> "WhisperVadContext":
+        lib = lib or load_library()
+        ptr = lib.whisper_vad_init_from_file_with_params(path.encode(), cls._params(lib, n_threads, gpu_device))
+        if not ptr:
+            raise WhisperError("InitError")
+        return cls(lib, ptr)
+
+    @classmethod
+    def new_from_loader(cls, data: bytes, lib: Optional[C.CDLL] = None, n_threads: Optional[int] = None, gpu_device: int = 0) -> "WhisperVadContext":
+        """Through `whisper_vad_init_with_params` with a whisper_model_loader that serves `data`."""
+        lib = lib or load_library()
+        pos = [0]
+
+        def rd(_ctx, out, n):
+            k = min(n, len(data) - pos[0])
+            if k > 0:
+                C.memmove(out, data[pos[0]:pos[0] + k], k)
+            hit_end = k < n
+            pos[0] += k
+            if hit_end:
+                pos[0] = len(data) + 1            # like a stream: eof is set by a read that runs past the end
+            return k
+
+        loader = whisper_model_loader(None, LOADER_READ(rd), LOADER_EOF(lambda _c: pos[0] > len(data)), LOADER_CLOSE(lambda _c: None))
+        ptr = lib.whisper_vad_init_with_params(C.byref(loader), cls._params(lib, n_threads, gpu_device))
+        if not ptr:
+            raise WhisperError("InitError")
+        return cls(lib, ptr)
+
+    def detect_speech(self, pcm) -> np.ndarray:
+        pcm = _f32(pcm)
+        if not self.lib.whisper_vad_detect_speech(self.ptr, pcm.ctypes.data_as(C.POINTER(C.c_float)), len(pcm)):
+            raise WhisperError("GenericError")
+        return self.probs()
+
+    def probs(self) -> np.ndarray:
+        n = self.lib.whisper_vad_n_probs(self.ptr)
+        if n == 0:
+            return np.zeros(0, dtype=np.float32)
+        return np.ctypeslib.as_array(self.lib.whisper_vad_probs(self.ptr), shape=(n,)).copy()
+
+    def _take(self, seg) -> list[tuple]:
+        if not seg:
+            raise WhisperError("GenericError")
+        out = [(self.lib.whisper_vad_segments_get_segment_t0(seg, i), self.lib.whisper_vad_segments_get_segment_t1(seg, i))
+               for i in range(self.lib.whisper_vad_segments_n_segments(seg))]
+        self.lib.whisper_vad_free_segments(seg)
+        return out
+
+    def segments_from_probs(self, params: whisper_vad_params) -> list[tuple]:
+        return self._take(self.lib.whisper_vad_segments_from_probs(self.ptr, params))
+
+    def segments_from_samples(self, params: whisper_vad_params, pcm) -> list[tuple]:
+        pcm = _f32(pcm)
+        return self._take(self.lib.whisper_vad_segments_from_samples(self.ptr, params, pcm.ctypes.data_as(C.POINTER(C.c_float)), len(pcm)))
+
+    def front(self, pcm) -> np.ndarray:
+        """Extension (whisper_amd_vad_front): the device front end's [n_chunks][512] LSTM gate inputs."""
+        pcm = _f32(pcm)
+        n = self.lib.whisper_amd_vad_front(self.ptr, pcm.ctypes.data_as(C.POINTER(C.c_float)), len(pcm), None, 0)
+        if n < 0:
+            raise WhisperError("GenericError", int(n))
+        out = np.empty(n, dtype=np.float32)
+        if self.lib.whisper_amd_vad_front(self.ptr, pcm.ctypes.data_as(C.POINTER(C.c_float)), len(pcm), out.ctypes.data_as(C.POINTER(C.c_float)), n) != n:
+            raise WhisperError("GenericError")
+        return out.reshape(-1, 512)
+
+    def free(self):
+        if self.ptr:
+            self.lib.whisper_vad_free(self.ptr)
+            self.ptr = None
+
+
+class WhisperFullContext:
+    """A context WITH its own state (`whisper_init_from_file_with_params`): `whisper_full`, `whisper_full_parallel` and the
+    context-level getters - the entry points that honour `vad = true`."""
+
+    def __init__(self, lib: C.CDLL, ptr: int):
+        self.lib, self.ptr = lib, ptr
+
+    @classmethod
+    def new_with_params(cls, path: str, params: Optional[WhisperContextParameters] = None, lib: Optional[C.CDLL] = None) -> "WhisperFullContext":
+        lib = lib or load_library()
+        params = params or WhisperContextParameters(lib)
+        ptr = lib.whisper_init_from_file_with_params(path.encode(), params.c)
+        if not ptr:
+            raise WhisperError("InitError")
+        ctx = cls(lib, ptr)
+        ctx._params = params
+        return ctx
+
+    def full(self, params: FullParams, pcm) -> int:
+        pcm = _f32(pcm)
+        return self.lib.whisper_full(self.ptr, params.c, pcm.ctypes.data_as(C.POINTER(C.c_float)), len(pcm))
+
+    def full_parallel(self, params: FullParams, pcm, n_processors: int) -> int:
+        pcm = _f32(pcm)
+        return self.lib.whisper_full_parallel(self.ptr, params.c, pcm.ctypes.data_as(C.POINTER(C.c_float)), len(pcm), n_processors)
+
+    def segments(self) -> list[dict]:
+        out = []
+        for i in range(self.lib.whisper_full_n_segments(self.ptr)):
+            toks = [self.lib.whisper_full_get_token_data(self.ptr, i, j) for j in range(self.lib.whisper_full_n_tokens(self.ptr, i))]
+            out.append(dict(t0=self.lib.whisper_full_get_segment_t0(self.ptr, i), t1=self.lib.whisper_full_get_segment_t1(self.ptr, i),
+                            text=self.lib.whisper_full_get_segment_text(self.ptr, i), ids=[t.id for t in toks],
+                            tok_t0=[t.t0 for t in toks], tok_t1=[t.t1 for t in toks]))
+        return out
+
+    def free(self):
+        if self.ptr:
+            self.lib.whisper_free(self.ptr)
             self.ptr = None
