@@ -77,10 +77,8 @@ static float v_expf(float x) {
 }
 
 // soft_max over one row: y = softmax(x*scale + mask) (ops.cpp:4792-4818, vec.cpp:257-308)
-static void softmax_row(int n, const float * x, float scale, const float * mask, float * y, std::vector<float> & wp) {
-    wp.resize(n);
-    for (int i = 0; i < n; ++i) wp[i] = x[i] * scale;
-    if (mask) for (int i = 0; i < n; ++i) wp[i] += 1.0f * mask[i];
+// softmax_exp: from the scaled and masked scores wp, the exponentials (into y), their F64 sum in the reference's order and its inverse
+static float softmax_exp(int n, const float * wp, float * y, double * sum_out) {
     float mx = -INFINITY;
     for (int i = 0; i < n; ++i) mx = wp[i] > mx ? wp[i] : mx;
     double sum = 0.0;
@@ -93,7 +91,14 @@ static void softmax_row(int n, const float * x, float scale, const float * mask,
         sum += (double) (b0 + b1);
     }
     for (; i < n; ++i) { const float v = expf(wp[i] - mx); sum += (double) v; y[i] = v; }
-    const float inv = (float) (1.0 / sum);
+    if (sum_out) *sum_out = sum;
+    return (float) (1.0 / sum);
+}
+static void softmax_row(int n, const float * x, float scale, const float * mask, float * y, std::vector<float> & wp) {
+    wp.resize(n);
+    for (int i = 0; i < n; ++i) wp[i] = x[i] * scale;
+    if (mask) for (int i = 0; i < n; ++i) wp[i] += 1.0f * mask[i];
+    const float inv = softmax_exp(n, wp.data(), y, nullptr);
     for (int k = 0; k < n; ++k) y[k] = y[k] * inv;
 }
 
@@ -150,6 +155,16 @@ static void mul_mat(const f16 * W, int n_out, int k, const float * X, int rows, 
 }
 
 extern "C" {
+
+// The two row operations whose F64 sums the GPU kernels certify, for tools/adversarial_rows.py and tests/test_exact_sums_math.py.
+// wo_softmax_row: the soft-max row above on scores that are already scaled (no mask), handing out what the generator steers: the
+// exponentials `e` [n], their F64 sum in the reference's order and the inverse; `y` [n] = e * inv.
+void wo_softmax_row(int n, const float * x, float * e, double * sum_out, float * inv_out, float * y) {
+    const float inv = softmax_exp(n, x, e, sum_out);
+    for (int k = 0; k < n; ++k) y[k] = e[k] * inv;
+    *inv_out = inv;
+}
+void wo_layernorm_row(int d, const float * x, const float * w, const float * b, float eps, float * y) { layernorm_row(d, x, w, b, eps, y); }
 
 void * wo_load(const char * path) {
     FILE * f = fopen(path, "rb");

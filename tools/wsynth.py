@@ -194,8 +194,10 @@ def _tensor_list(shape: dict, rng: np.random.Generator):
         yield p + "mlp.2.bias", vec(d)
 
 
-def write_model(path: str, shape_name: str = "s64", seed: int = 0, with_tensors: bool = True) -> str:
-    """Write a synthetic legacy-ggml Whisper model (ftype=1: F16 matrices, F32 vectors)."""
+def write_model(path: str, shape_name: str = "s64", seed: int = 0, with_tensors: bool = True, overrides: dict | None = None) -> str:
+    """Write a synthetic legacy-ggml Whisper model (ftype=1: F16 matrices, F32 vectors).
+    overrides: tensor name -> function(array) -> array of the same shape and type, applied to the seeded tensor before it is written
+    (every other tensor keeps the bits the seed gives it)."""
     shape = SHAPES[shape_name]
     rng = np.random.default_rng(seed)
     tmp = path + ".tmp%d" % os.getpid()
@@ -213,6 +215,10 @@ def write_model(path: str, shape_name: str = "s64", seed: int = 0, with_tensors:
             f.write(w)
         if with_tensors:
             for name, arr in _tensor_list(shape, rng):
+                if overrides and name in overrides:
+                    new = np.asarray(overrides[name](arr.copy()))
+                    assert new.shape == arr.shape and new.dtype == arr.dtype, name
+                    arr = new
                 ttype = 1 if arr.dtype == np.float16 else 0
                 nb = name.encode()
                 f.write(struct.pack("<3i", arr.ndim, len(nb), ttype))
@@ -224,22 +230,25 @@ def write_model(path: str, shape_name: str = "s64", seed: int = 0, with_tensors:
     return path
 
 
-def model_path(shape_name: str, seed: int = 0, cache_dir: str | None = None) -> str:
-    """Path of a cached synthetic model, written on first use (models are too big to commit)."""
+def model_path(shape_name: str, seed: int = 0, cache_dir: str | None = None, overrides: dict | None = None, tag: str | None = None) -> str:
+    """Path of a cached synthetic model, written on first use (models are too big to commit).
+    overrides + tag: a variant with some tensors replaced (write_model), cached under a name of its own, synth-<shape>-seed<seed>-<tag>.bin."""
+    assert (overrides is None) == (tag is None), "a variant needs both its overrides and a tag for its file name"
     cache_dir = cache_dir or os.environ.get("WHISPER_AMD_CACHE", "/tmp/whisper_amd_cache")
     os.makedirs(cache_dir, exist_ok=True)
-    p = os.path.join(cache_dir, f"synth-{shape_name}-seed{seed}.bin")
+    p = os.path.join(cache_dir, f"synth-{shape_name}-seed{seed}.bin" if tag is None else f"synth-{shape_name}-seed{seed}-{tag}.bin")
     if not os.path.exists(p):
-        write_model(p, shape_name, seed)
+        write_model(p, shape_name, seed, overrides=overrides)
     return p
 
 
-def quant_model_path(shape_name: str, qtype: str, seed: int = 0, cache_dir: str | None = None) -> str:
+def quant_model_path(shape_name: str, qtype: str, seed: int = 0, cache_dir: str | None = None, overrides: dict | None = None,
+                     tag: str | None = None) -> str:
     """Path of the cached quantised version of a synthetic model (qtype: any name the tool knows - "q5_0", "q8_0", "q5_1", "q4_1",
     "q4_0", ...), produced on first use by the REFERENCE's own quantizer
     (examples/quantize, compiled by oracle/Makefile into oracle/_ref/quantize-ref; test infrastructure only)."""
     import subprocess
-    src = model_path(shape_name, seed, cache_dir)
+    src = model_path(shape_name, seed, cache_dir, overrides, tag)
     dst = src[:-4] + "-" + qtype + ".bin"
     if not os.path.exists(dst):
         tool = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle", "_ref", "quantize-ref")
