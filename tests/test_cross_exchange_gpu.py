@@ -67,7 +67,7 @@ def test_one_exchange_cross_attention_equals_launch_sequence(wrs, amd_lib, actx,
 
 @pytest.mark.parametrize("actx", [50, 1500])
 def test_one_exchange_cross_attention_under_stalls(wrs, actx, monkeypatch):
-    """The same on the build whose waves stall at random in front of the gather, the soft-max and the P V product (-DMG_CHAOS)."""
+    """The same on the build whose waves stall at random in front of the gather, the soft-max and the P V product (-DWA_CHAOS)."""
     assert os.path.exists(CHAOS_LIB), "libwhisper_chaos.so missing: make -C whisper-rust_amd libwhisper_chaos.so (__graft_entry__.build() does)"
     lib = wrs.load_library(CHAOS_LIB)
     wrs.set_log_callback(lib, lambda lvl, txt: sys.stderr.write(txt) if lvl >= 3 else None)

@@ -375,7 +375,7 @@ def test_one_launch_decode_step_equals_launch_sequence(wrs, amd_lib, name, n_tok
 @pytest.mark.parametrize("name,n_tok", [("small", 16), ("m1024", 12), ("w1280", 8), ("small:q5_0", 16), ("w1280:q5_0", 8), ("s128:q8_0", 12)])
 def test_one_launch_step_under_stalls(wrs, name, n_tok, monkeypatch):
     """The same comparison on the test build whose product waves stall at random for ~25 us (libwhisper_chaos.so: wa_mega.hip with
-    -DMG_CHAOS): the rest of the workgroup and of the grid then runs far ahead of the stalled wave, so anything in LDS that relied on
+    -DWA_CHAOS): the rest of the workgroup and of the grid then runs far ahead of the stalled wave, so anything in LDS that relied on
     how long a product or a hand-off takes shows up as different logits.  (The kernel as it was before the LayerNorm outputs got an
     LDS area of their own fails this on every token.)"""
     path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "whisper-rust_amd", "libwhisper_chaos.so")
@@ -406,7 +406,7 @@ def test_one_launch_step_under_stalls(wrs, name, n_tok, monkeypatch):
 
 @pytest.mark.parametrize("name", ["small", "m1024", "s128:q5_0"])
 def test_several_rows_step_under_stalls(wrs, name, monkeypatch):
-    """The several-rows one-launch step (wa_rows.hip) on the stalled test build (-DMB_CHAOS: waves and whole workgroups sleep ~25 us at random in
+    """The several-rows one-launch step (wa_rows.hip) on the stalled test build (-DWA_CHAOS: waves and whole workgroups sleep ~25 us at random in
     front of products, attention units and gathers): batches of 2 / 5 / 8 tokens - causal masks, cells written by the launch itself - give the
     logits of the launch sequence, and every pass is served by the one-launch form."""
     path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "whisper-rust_amd", "libwhisper_chaos.so")

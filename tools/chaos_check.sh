@@ -1,6 +1,6 @@
 #!/bin/bash
 # On the GPU box: the one-launch decode step with random ~25 us stalls in front of its products (libwhisper_chaos.so = wa_mega.hip built with
-# -DMG_CHAOS, `make -C whisper-rust_amd libwhisper_chaos.so`) against the launch sequence, bit for bit, on several shapes.  The kernel of
+# -DWA_CHAOS, `make -C whisper-rust_amd libwhisper_chaos.so`) against the launch sequence, bit for bit, on several shapes.  The kernel of
 # commit f39fc2a (LayerNorm outputs and gathered inputs in one LDS area) fails this on every token; the test suite runs the same check
 # (tests/test_parity_gpu.py::test_one_launch_step_under_stalls).
 ROOT=$(cd "$(dirname "$0")/.." && pwd)

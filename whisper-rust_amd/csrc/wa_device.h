@@ -1,6 +1,6 @@
-// wa_device.h - device-side helpers shared by wa_kernels.hip (MFMA "flash" path) and wa_exact.hip
-// (reference-order path): F16 conversion, wave reductions, ggml's expf polynomial, the GELU table
-// lookup and the GEMM epilogues.
+// wa_device.h - device-side helpers of every kernel file (wa_kernels.hip, wa_exact.hip, wa_quant.hip, wa_vad.hip; wa_mega.hip / wa_rows.hip
+// through wa_one_launch_dev.h): F16 conversion, the LDS-only barrier, wave reductions and DPP moves, ggml's expf polynomial, the GELU table
+// lookup, the Q8_0 store, the GEMM epilogues, and the certificates of order-independent F64 sums (LayerNorm, soft-max).
 #pragma once
 #include "wa_kernels.h"
 
@@ -237,7 +237,7 @@ __device__ __forceinline__ float wa_expf_libm(float x) {
 }
 
 // -------------------------------------------------------------------------------------------------
-// certified F64 sums (LayerNorm / soft-max denominators), shared by wa_exact.hip and wa_mega.hip
+// certified F64 sums (LayerNorm / soft-max denominators), shared by wa_exact.hip, wa_mega.hip and wa_rows.hip
 // -------------------------------------------------------------------------------------------------
 // The reference sums a row in index order in F64 (ops.cpp:3225-3237).  A wave sums it in another order; the two
 // F64 results can differ by at most delta = 2 n u sum|x| (u = 2^-53).  Rounding to F32 after the division is
@@ -260,6 +260,16 @@ __device__ __forceinline__ bool wa_sum_certain(double S, double A, int n, float 
 // F32 are monotonic in m) -, and everything downstream is a function of those t.  Only a row with an element within ~2^-12 of its
 // mean still needs the in-order sum.
 __device__ __forceinline__ bool wa_mean_indifferent(float x, float lo, float hi) { return (x - lo) == (x - hi); }
+
+// The soft-max denominator of the one-launch decode steps: `tot` = their F64 sum of a row's ng group sums (ops.cpp's 8-lane tree) and
+// n % 8 tail cells.  The reference adds those ng + (n % 8) addends one after the other in F64: error <= (ng + 7) u S; the kernels' sum
+// is a tree of depth <= 16 over the SAME addends: error <= 16 u S; together (ng + 8 + 16) u S - not twice the reference's bound, which
+// sent twice as many soft-maxes back to the launch sequence.  ilo / ihi = 1 / total at the interval's ends, rounded to F32 (monotonic):
+// when they are the same float it is the reference's value whatever its order was; else (ilo != ihi) the caller falls back.
+__device__ __forceinline__ void wa_softmax_bounds(double tot, int ng, float & ilo, float & ihi) {
+    const double delta = (double) (ng + 8 + 16) * 0x1p-53 * tot * 1.000001;
+    ilo = (float) (1.0 / (tot + delta)); ihi = (float) (1.0 / (tot - delta));
+}
 
 // In-order F64 sum of an LDS-resident row by one lane (the certificate's fallback): b128 reads pipeline, the 8-cycle
 // dependent F64 adds are all that is left (~3 us for 768 elements; the same loop over global memory took ~60 us).

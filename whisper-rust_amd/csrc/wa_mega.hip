@@ -12,141 +12,58 @@
 //     (MI355X guide, Guideline 16 form R2).  Every poll is bounded and reports a time-out through `status`.
 // All arithmetic is the reference order of wa_exact.hip (ggml_vec_dot_f16 chains and tree, ops.cpp soft_max, certified
 // F64 LayerNorm sums): the logits are bit-identical to the launch-sequence path and to whisper.cpp CPU.
-#include "wa_device.h"
+#include "wa_one_launch_dev.h"
 #include "wa_mega.h"
 
-typedef unsigned long long u64;
-#define GAS __attribute__((address_space(1)))
-typedef GAS u64 gu64;
-typedef GAS unsigned gu32;
-typedef const GAS wa_f16 * gch;      // every global access is spelled global: a pointer read from the argument block or from
-typedef const GAS float * gcf;       // the layer table is generic to the compiler, and a flat access also waits on the LDS counter
-typedef _Float16 half4v __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));   // (HIP's u32x4 class cannot be read through an address-space pointer)
-
 // The roles are inlined into the kernel (as separate functions they saved 112 callee-saved VGPRs per thread on entry: 58 MB of scratch
-// per launch).  They read the launch arguments from the kernel-argument segment (scalar loads: every field stays wave-uniform); the
-// kernel hands them its address and mg_uniform makes it provably uniform again.
+// per launch) and read the launch arguments through mo_uniform.
 typedef const __attribute__((address_space(4))) wa_mega_args * mg_kargs;
-__device__ __forceinline__ mg_kargs mg_uniform(mg_kargs p) {
-    const unsigned long long v = (unsigned long long) p;
-    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned) v), hi = __builtin_amdgcn_readfirstlane((unsigned) (v >> 32));
-    return (mg_kargs) (((unsigned long long) hi << 32) | lo);
-}
 
 #define MG_THREADS 512
 #define MG_NW (MG_THREADS / 64)
 #define MG_NP3 4                  // LayerNorm elements per lane of one of the six gather waves: d <= 1536
-#define MG_SPIN_LIMIT 20000u      // polls (~0.5 us each, ~10 ms) before a hand-off is declared dead: the host then pauses the one-launch step and tries again later
-#ifndef MG_DEFER
-#define MG_DEFER 1                // request a wave's next weights after the CU's next gather instead of right away (BIG assist re-fetches stay in place)
-#endif
 
-enum { E_QKV = 0, E_AO, E_X1, E_QC, E_AO2, E_X2, E_HF, E_X3 };
-
-struct mg_ctl { gu32 * status; unsigned seq; bool dead; };
-
-__device__ __forceinline__ void gr_store(gu64 * g, unsigned seq, unsigned v) {
-    __hip_atomic_store(g, ((u64) seq << 32) | (u64) v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ u64 gr_load(gu64 * g) { return __hip_atomic_load(g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-// A granule whose readers all sit on the WRITER'S XCD (`local`, established at run time: mg_role_cross): a plain store keeps the line
-// in that XCD's L2, where the readers' L1-bypassing polls find it - an sc1 store drops it from L2 and every reader goes out to the
-// fabric (MI355X_MICROARCH.md, inter-workgroup visibility).  Never for a granule that another XCD reads: its L2 would stay stale.
-__device__ __forceinline__ void gr_store_l(gu64 * g, unsigned seq, unsigned v, bool local) {
-    if (local) __hip_atomic_store(g, ((u64) seq << 32) | (u64) v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    else       __hip_atomic_store(g, ((u64) seq << 32) | (u64) v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-template <int CTRL>
-__device__ __forceinline__ unsigned dpp_u32(unsigned v) { return (unsigned) __builtin_amdgcn_update_dpp(0, (int) v, CTRL, 0xf, 0xf, true); }
 // The lane index behind an opaque move: addresses and masks derived from it are recomputed where they are used instead of being hoisted
 // out of the layer loop - where they sat in scratch and came back behind an s_waitcnt vmcnt(0), i.e. behind the wave's weight prefetch.
 __device__ __forceinline__ int mq_fresh(int) {
     unsigned z = 0; asm volatile("" : "+v"(z));         // an opaque zero: the two mbcnt below cannot be merged with an earlier pair (nor kept, nor spilled)
     return (int) __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, z));
 }
-// quantize_row_q8_0 (arch/x86/quants.c) of whole 32-element blocks held one value per lane (as wa_q8_store), the quads packed over DPP:
-// one LDS word per four lanes at q32 (the lane's quad row and block), the scale rounded through F16 at dsc.  All lanes take part.
+// mq_quant32 of whole 32-element blocks held one value per lane, into the activation row in LDS: one word per four lanes at q32 (the lane's
+// quad row and block), the scale at dsc.  All lanes take part.
 __device__ __forceinline__ void mq_put(float y, bool act, unsigned * q32, float * dsc, int lane) {
-    float a = fabsf(y);
-    a = fmaxf(a, dpp_f32<0x128>(a)); a = fmaxf(a, dpp_f32<0x124>(a)); a = fmaxf(a, dpp_f32<0x122>(a)); a = fmaxf(a, dpp_f32<0x121>(a));
-    a = fmaxf(a, __shfl_xor(a, 16, 32));
-    const float dq = a / 127.f, id = a != 0.0f ? 127.f / a : 0.0f;
-    const unsigned q = (unsigned) (int) rintf(y * id) & 0xffu;
-    const unsigned w = q | (dpp_u32<0x101>(q) << 8) | (dpp_u32<0x102>(q) << 16) | (dpp_u32<0x103>(q) << 24);      // row_shl:1..3
+    float dq;
+    const unsigned w = mq_quant32(y, dq);
     if (act && (lane & 3) == 0) *q32 = w;
-    if (act && (lane & 31) == 0) *dsc = h2f(f2h(dq));
+    if (act && (lane & 31) == 0) *dsc = dq;
 }
 
 __device__ __forceinline__ gu64 * mg_edge(mg_kargs A, int layer, int e) {
     return (gu64 *) A->granules + ((size_t) layer * WA_MEGA_EDGES + e) * A->edge_stride;
 }
 
-// Workgroup barrier that orders LDS only.  __syncthreads() also drains the vector-memory counter (s_waitcnt vmcnt(0)), i.e. it
-// would make every wave wait here for the weights it has just started to prefetch - the opposite of what the prefetch is for.
-__device__ __forceinline__ void mg_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
 // (quantised models) LDS of the quantised activation row inside the xin area: quants [4d] bytes, then the block scales
 __device__ __forceinline__ int8_t * mq_xq(wa_f16 * xin) { return (int8_t *) xin; }
 __device__ __forceinline__ float  * mq_xd(wa_f16 * xin) { return (float *) ((unsigned char *) xin + 6 * WA_MEGA_MAX_D); }
-// words between the quad rows u = 0..7 of the activation row: nb | 8 puts the eight 16-byte reads of a product step on disjoint banks
-// (u * nb alone: nb = 96 folds them onto two)
-__device__ __forceinline__ int mq_ld(int nb) { return nb | 8; }
 
 // optional timeline (tools/mega_debug.py): 100 MHz wall-clock ticks of one workgroup per role, behind the cross-attention dumps
 __device__ __forceinline__ void mg_trace(mg_kargs A, bool who, int slot, unsigned v) {
     if (A->dbg && who) ((GAS unsigned *) A->dbg)[(size_t) A->n_layer * A->n_head * 5120 + slot] = v;
 }
 __device__ __forceinline__ unsigned mg_now() { return (unsigned) wall_clock64(); }
-// MG_CHAOS (a test build, tools/chaos_check.sh): some product waves of some workgroups stall for ~25 us right before their product, so that
-// the rest of the workgroup - and the rest of the grid - runs far ahead of them.  Results must not change: nothing in LDS may rely on how long
-// a product or a hand-off takes.
-#ifdef MG_CHAOS
-__device__ __forceinline__ void mg_chaos(unsigned wg, unsigned wave, unsigned l, unsigned phase, unsigned seq) {
-    unsigned h = (wg * 2654435761u) ^ (wave * 40503u) ^ (l * 2246822519u) ^ (phase * 3266489917u) ^ (seq * 668265263u);
-    h ^= h >> 15; h *= 2246822519u; h ^= h >> 13;
-    if ((h & 7u) == 0u) for (int i = 0; i < 8; ++i) __builtin_amdgcn_s_sleep(127);
-}
-#define MG_CHAOS_AT(phase) mg_chaos((unsigned) wg, (unsigned) wave, (unsigned) l, (phase), seq)
-#define MG_CHAOS_ID(id, phase, sq) mg_chaos((unsigned) (id), (unsigned) wave, (unsigned) l, (phase), (sq))       /* attention roles: id = 1000 + head / 2000 + workgroup */
+// (test build, WA_CHAOS) some product waves of some workgroups stall right before their product
+#ifdef WA_CHAOS
+#define MG_CHAOS_AT(phase) mo_chaos((unsigned) wg, (unsigned) wave, (unsigned) l, (phase), seq)
+#define MG_CHAOS_ID(id, phase, sq) mo_chaos((unsigned) (id), (unsigned) wave, (unsigned) l, (phase), (sq))       /* attention roles: id = 1000 + head / 2000 + workgroup */
 #else
 #define MG_CHAOS_AT(phase) do { } while (0)
 #define MG_CHAOS_ID(id, phase, sq) do { } while (0)
 #endif
 // (test build) a workgroup may also START late: whole workgroups stall at the head of their role
 __device__ __forceinline__ void mg_chaos_start(unsigned seq) {
-#ifdef MG_CHAOS
-    mg_chaos(blockIdx.x, 0u, 99u, 41u, seq);
+#ifdef WA_CHAOS
+    mo_chaos(blockIdx.x, 0u, 99u, 41u, seq);
 #endif
-}
-
-// One wave polls the granules idx(0..NPL-1) (idx < 0: none) until every tag equals this launch's sequence number.
-// (Measured: a second, staggered poll in flight per wave makes every hand-off LONGER - 0.377 -> 0.401 ms per token -, longer pauses between
-// polls too (s_sleep 6: 0.384, 14: 0.402), none at all changes nothing; a pause before the first poll of the gathers that follow an attention phase cuts their polls by 2-3 x and changes
-// nothing either: the hand-off time is the store-to-load path itself, not contention by the polls.)
-template <int NPL, typename F>
-__device__ __forceinline__ unsigned mg_sweep(gu64 * g, F idx, mg_ctl & c, int lane, unsigned (&v)[NPL], unsigned code) {
-    for (unsigned spins = 0;; ++spins) {
-        bool ok = true;
-#pragma unroll
-        for (int k = 0; k < NPL; ++k) {
-            const int i = idx(k);
-            if (i >= 0) { const u64 x = gr_load(g + i); v[k] = (unsigned) x; ok &= (unsigned) (x >> 32) == c.seq; }
-        }
-        if (__all(ok) || c.dead) return spins;
-        if ((spins & 127u) == 127u) {
-            const unsigned st = __builtin_amdgcn_readfirstlane(__hip_atomic_load(c.status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-            if (st != 0u) { c.dead = true; return spins; }
-            if (spins >= MG_SPIN_LIMIT) {
-                if (lane == 0) __hip_atomic_store(c.status, code, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                c.dead = true;
-                return spins;
-            }
-        }
-        __builtin_amdgcn_s_sleep(1);
-    }
 }
 
 // -------------------------------------------------------------------------------------------------
@@ -160,15 +77,15 @@ __device__ __forceinline__ unsigned mg_sweep(gu64 * g, F idx, mg_ctl & c, int la
 // prefetch - a poll behind it would wait for those loads first, vmcnt being in order).  Returns the wave's slot or -1.
 #define MG_WGTRACE_LAYER 4
 #define MG_NQ 6
-#define MG_EX_P1 (CQ ? 0x20u : MG_DEFER ? 0x06u : 0x20u)      /* waves 1, 2 have just asked for the next QKV rows (without MG_DEFER: wave 5 for the next FC2 rows; CQ: wave 5 ran FC2) */
-/* With MG_DEFER the fresh requests sit elsewhere: before P4 waves 1, 2 (FC1 rows, asked for after the P3 barrier); before P7 wave 4 (next
+#define MG_EX_P1 (CQ ? 0x20u : 0x06u)      /* waves 1, 2 have just asked for the next QKV rows (CQ: wave 5 ran FC2) */
+/* The fresh requests in front of the other gathers: before P4 waves 1, 2 (FC1 rows, asked for after the P3 barrier); before P7 wave 4 (next
    cross-query rows, after the P6 barrier) - or wave 3 in the quantised whole-block form (its FC1 rows, after its P6 product); before the
    FC2 gather wave 3 (next out-projection rows, after P7's LayerNorm). */
-#define MG_EX_P4 (MG_DEFER ? 0x06u : 0x08u)      /* (without MG_DEFER wave 3: next out-projection rows) */
-#define MG_EX_P7 (BIGP ? 0x18u : MG_DEFER && !QB ? 0x10u : 0x08u)      /* wide form: waves 3 and 4 have both just asked for their FC1 rows */
+#define MG_EX_P4 0x06u      /* waves 1, 2: FC1 rows */
+#define MG_EX_P7 (BIG ? 0x18u : !QB ? 0x10u : 0x08u)      /* wide form: waves 3 and 4 have both just asked for their FC1 rows */
 #define MG_EX_AO (CQ ? 0xc0u : 0x06u)      /* waves 1, 2: FC1 rows (CQ: waves 6, 7 run the QKV product) */
 #define MG_EX_AO2 (CQ ? 0xc0u : 0x10u)     /* wave 4: next cross-query rows (CQ: waves 6, 7 have asked for the next QKV rows) */
-#define MG_EX_HF (CQ ? 0x06u : MG_DEFER ? 0x08u : 0x06u)      /* (without MG_DEFER waves 1, 2: next QKV rows; CQ: waves 1, 2 run FC1) */
+#define MG_EX_HF (CQ ? 0x06u : 0x08u)      /* wave 3: next out-projection rows (CQ: waves 1, 2 run FC1) */
 #define MG_EX_X1 0x06u      /* CQ, the residual row after self-attention: waves 1, 2 have just asked for their FC1 rows */
 #define MG_EX_HFQ 0x18u     /* quantised, whole-block FC1: waves 3, 4 have just asked for the next out-projection / cross-query rows */
 #define MG_EX_FINAL 0x20u   /* wave 5: first logits rows */
@@ -192,14 +109,14 @@ __device__ __forceinline__ void mg_ln_params(float (&gw)[NP3], float (&gb)[NP3],
 // gw / gb: gamma and beta of THIS LayerNorm, loaded one phase ahead (a load issued here would sit, with its pointer fetch, in
 // front of the polling loads: measured 5 us per LayerNorm phase)
 template <int NP3, bool Q = false>        // Q: the normalised row leaves as Q8_0 (quantize_row_q8_0: the next product's operand), not as F16
-__device__ __forceinline__ void mg_ln3(mg_kargs A, mg_ctl & c, gu64 * edge /* null: embeddings */, const float (&gw)[NP3], const float (&gb)[NP3], int q,
+__device__ __forceinline__ void mg_ln3(mg_kargs A, mo_ctl & c, gu64 * edge /* null: embeddings */, const float (&gw)[NP3], const float (&gb)[NP3], int q,
                                        int lane, float * xf, wa_f16 * xin, double * lnred, unsigned code, int tslot = -1, int token = 0) {
     const int d = A->d, seg = mg_ln_seg(d), i0 = q * seg, i1 = min(d, i0 + seg);
     float xv[NP3];
     if (q >= 0) {
         if (edge) {
             unsigned v[NP3];
-            const unsigned sp = mg_sweep<NP3>(edge, [&](int k) { const int i = i0 + lane + 64 * k; return i < i1 ? i : -1; }, c, lane, v, code);
+            const unsigned sp = mo_sweep<MO_POLL_OWN, NP3>(edge, [&](int k) { const int i = i0 + lane + 64 * k; return i < i1 ? i : -1; }, c, lane, v, code);
             if (tslot >= 0) { mg_trace(A, lane == 0, tslot, mg_now()); mg_trace(A, lane == 0, tslot + 1, sp); }
 #pragma unroll
             for (int k = 0; k < NP3; ++k) xv[k] = (i0 + lane + 64 * k < i1) ? __uint_as_float(v[k]) : 0.0f;
@@ -225,7 +142,7 @@ __device__ __forceinline__ void mg_ln3(mg_kargs A, mg_ctl & c, gu64 * edge /* nu
         s = wave_sum_d(s); a = wave_sum_d(a);
         if (lane == 0) { lnred[q] = s; lnred[MG_NQ + q] = a; }
     }
-    mg_barrier();
+    wa_barrier_lds();
     if (tslot >= 0) mg_trace(A, lane == 0, tslot + 4, mg_now());
     float mean = 0.0f;
     // every wave takes the same decision from the same six partial sums (the gather waves need the mean, the others the barrier count)
@@ -242,7 +159,7 @@ __device__ __forceinline__ void mg_ln3(mg_kargs A, mg_ctl & c, gu64 * edge /* nu
             for (int k = 0; k < NP3; ++k) if (i0 + lane + 64 * k < i1) same &= wa_mean_indifferent(xv[k], mean, mean_hi);
             if (lane == 0) ((int *) (lnred + 3 * MG_NQ))[q] = __all(same) ? 1 : 0;
         }
-        mg_barrier();
+        wa_barrier_lds();
         const int * fl = (const int *) (lnred + 3 * MG_NQ);
         need_seq = !(fl[0] & fl[1] & fl[2] & fl[3] & fl[4] & fl[5]);
     }
@@ -258,7 +175,7 @@ __device__ __forceinline__ void mg_ln3(mg_kargs A, mg_ctl & c, gu64 * edge /* nu
         s2 = wave_sum_d(s2);
         if (lane == 0) lnred[2 * MG_NQ + q] = s2;
     }
-    mg_barrier();
+    wa_barrier_lds();
     if (tslot >= 0) mg_trace(A, lane == 0, tslot + 5, mg_now());
     if (q >= 0) {
         double s2 = ((lnred[12] + lnred[13]) + (lnred[14] + lnred[15])) + (lnred[16] + lnred[17]);
@@ -285,15 +202,15 @@ __device__ __forceinline__ void mg_ln3(mg_kargs A, mg_ctl & c, gu64 * edge /* nu
         }
         if (tslot >= 0) mg_trace(A, lane == 0, tslot + 2, mg_now());
     }
-    mg_barrier();
+    wa_barrier_lds();
 }
 
 // wave(s): copy the packed-F16 granules [i0, i1) (two halfs each) into LDS once they are all valid
 template <int NPL>
-__device__ __forceinline__ void mg_gather_h2(mg_ctl & c, gu64 * edge, int i0, int i1, int lane, unsigned * dst32, unsigned code, mg_kargs A = nullptr,
+__device__ __forceinline__ void mg_gather_h2(mo_ctl & c, gu64 * edge, int i0, int i1, int lane, unsigned * dst32, unsigned code, mg_kargs A = nullptr,
                                              int tslot = -1) {
     unsigned v[NPL];
-    const unsigned sp = mg_sweep<NPL>(edge, [&](int k) { const int i = i0 + lane + 64 * k; return i < i1 ? i : -1; }, c, lane, v, code);
+    const unsigned sp = mo_sweep<MO_POLL_OWN, NPL>(edge, [&](int k) { const int i = i0 + lane + 64 * k; return i < i1 ? i : -1; }, c, lane, v, code);
     if (tslot >= 0) { mg_trace(A, lane == 0, tslot, mg_now()); mg_trace(A, lane == 0, tslot + 1, sp); }
 #pragma unroll
     for (int k = 0; k < NPL; ++k) { const int i = i0 + lane + 64 * k; if (i < i1) dst32[i] = v[k]; }
@@ -301,9 +218,9 @@ __device__ __forceinline__ void mg_gather_h2(mg_ctl & c, gu64 * edge, int i0, in
 
 // wave(s): copy the F32 granules [i0, i1) into LDS once they are all valid
 template <int NPL>
-__device__ __forceinline__ void mg_gather_f32(mg_ctl & c, gu64 * edge, int i0, int i1, int lane, float * dst, unsigned code, mg_kargs A = nullptr, int tslot = -1) {
+__device__ __forceinline__ void mg_gather_f32(mo_ctl & c, gu64 * edge, int i0, int i1, int lane, float * dst, unsigned code, mg_kargs A = nullptr, int tslot = -1) {
     unsigned v[NPL];
-    const unsigned sp = mg_sweep<NPL>(edge, [&](int k) { const int i = i0 + lane + 64 * k; return i < i1 ? i : -1; }, c, lane, v, code);
+    const unsigned sp = mo_sweep<MO_POLL_OWN, NPL>(edge, [&](int k) { const int i = i0 + lane + 64 * k; return i < i1 ? i : -1; }, c, lane, v, code);
     if (tslot >= 0) { mg_trace(A, lane == 0, tslot, mg_now()); mg_trace(A, lane == 0, tslot + 1, sp); }
 #pragma unroll
     for (int k = 0; k < NPL; ++k) { const int i = i0 + lane + 64 * k; if (i < i1) dst[i] = __uint_as_float(v[k]); }
@@ -311,10 +228,10 @@ __device__ __forceinline__ void mg_gather_f32(mg_ctl & c, gu64 * edge, int i0, i
 
 // wave(s): the F32 granules [i0, i1) (whole 32-element blocks) quantised to Q8_0 into the activation row in LDS once they are all valid
 template <int NPL>
-__device__ __forceinline__ void mg_gather_q8(mg_ctl & c, gu64 * edge, int i0, int i1, int lane, wa_f16 * xin, int nb, unsigned code, mg_kargs A = nullptr,
+__device__ __forceinline__ void mg_gather_q8(mo_ctl & c, gu64 * edge, int i0, int i1, int lane, wa_f16 * xin, int nb, unsigned code, mg_kargs A = nullptr,
                                              int tslot = -1) {
     unsigned v[NPL];
-    const unsigned sp = mg_sweep<NPL>(edge, [&](int k) { const int i = i0 + lane + 64 * k; return i < i1 ? i : -1; }, c, lane, v, code);
+    const unsigned sp = mo_sweep<MO_POLL_OWN, NPL>(edge, [&](int k) { const int i = i0 + lane + 64 * k; return i < i1 ? i : -1; }, c, lane, v, code);
     if (tslot >= 0) { mg_trace(A, lane == 0, tslot, mg_now()); mg_trace(A, lane == 0, tslot + 1, sp); }
     const int ln = mq_fresh(lane);
     unsigned * q32 = (unsigned *) mq_xq(xin) + ((ln & 31) >> 2) * mq_ld(nb) + (i0 >> 5) + (ln >> 5);
@@ -325,10 +242,10 @@ __device__ __forceinline__ void mg_gather_q8(mg_ctl & c, gu64 * edge, int i0, in
 
 // wave(s): blocks that were quantised by their producer - 9 granules per block (quads 0..7, scale) - copied into the activation row in LDS
 template <int NPL>
-__device__ __forceinline__ void mg_gather_qb(mg_ctl & c, gu64 * edge, int i0, int i1, int lane, wa_f16 * xin, int nb, unsigned code, mg_kargs A = nullptr,
+__device__ __forceinline__ void mg_gather_qb(mo_ctl & c, gu64 * edge, int i0, int i1, int lane, wa_f16 * xin, int nb, unsigned code, mg_kargs A = nullptr,
                                              int tslot = -1) {
     unsigned v[NPL];
-    const unsigned sp = mg_sweep<NPL>(edge, [&](int k) { const int i = i0 + lane + 64 * k; return i < i1 ? i : -1; }, c, lane, v, code);
+    const unsigned sp = mo_sweep<MO_POLL_OWN, NPL>(edge, [&](int k) { const int i = i0 + lane + 64 * k; return i < i1 ? i : -1; }, c, lane, v, code);
     if (tslot >= 0) { mg_trace(A, lane == 0, tslot, mg_now()); mg_trace(A, lane == 0, tslot + 1, sp); }
 #pragma unroll
     for (int k = 0; k < NPL; ++k) {
@@ -629,58 +546,15 @@ __device__ __forceinline__ unsigned mg_pub_h2(gu64 * edge, unsigned seq, bool va
 #define MG_GELU_OFF  (MG_LNRED_OFF + 256)
 #define MG_PICK_OFF  (MG_GELU_OFF + 131072)        // behind every role's LDS (the GEMV role's is the largest)
 #define MG_PICK_BYTES 512
-struct mg_best { float v; int i; };
-__device__ __forceinline__ void mg_best_merge(mg_best & a, float v, int i) { if (v > a.v || (v == a.v && i < a.i)) { a.v = v; a.i = i; } }
-__device__ __forceinline__ void mg_best_wave(mg_best & a) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { const float v = __shfl_xor(a.v, o, WAVE); const int i = __shfl_xor(a.i, o, WAVE); mg_best_merge(a, v, i); }
-}
-__device__ __forceinline__ int mg_decide(const mg_best & bt, const mg_best & bs, float s_ts, int token_beg) {
-    // whisper.cpp:6309-6333: timestamp mass above every text token => a timestamp; else the arg-max of everything allowed
-    if (!(bs.v > -INFINITY)) return bt.v > -INFINITY ? bt.i : 0;
-    if (!(bt.v > -INFINITY)) return bs.i;
-    if (__logf(s_ts) + bs.v > bt.v) return bs.i;
-    return bs.v > bt.v ? bs.i : bt.i;
-}
 __device__ __forceinline__ void mg_pick(mg_kargs A, int lane, int * pk) {
-    int token = A->token, last = A->s_last, penult = A->s_penult, seek_delta = A->s_seek_delta, has_ts = A->s_has_ts;
-    if (A->spec) {
-        const GAS int * ps = (const GAS int *) A->ps_in;
-        const GAS unsigned * rec = (const GAS unsigned *) A->rec_in;
-        penult = ps[0]; seek_delta = ps[2]; has_ts = ps[3];
-        mg_best bt = { -INFINITY, 0x7fffffff }, bs = { -INFINITY, 0x7fffffff };
-        // every record (n_rec <= 256: four per lane) in ONE round of loads - a loop over them paid a cold global round trip per
-        // iteration, 4.4 us at the head of every launch
-        u32x4 ra[4]; unsigned rb[4];
-        const int nr = A->n_rec;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int g = lane + 64 * j, gg = g < nr ? g : 0;
-            ra[j] = *(const GAS u32x4 *) (rec + gg * 8); rb[j] = rec[gg * 8 + 4];
-        }
-#pragma unroll
-        for (int j = 0; j < 4; ++j) if (lane + 64 * j < nr) {
-            mg_best_merge(bt, __uint_as_float(ra[j].x), (int) ra[j].y);
-            mg_best_merge(bs, __uint_as_float(ra[j].z), (int) ra[j].w);
-        }
-        mg_best_wave(bt); mg_best_wave(bs);
-        float s = 0.0f;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) if (lane + 64 * j < nr) {
-            const float m = __uint_as_float(ra[j].z);
-            if (m > -INFINITY) s += __uint_as_float(rb[j]) * __expf(m - bs.v);
-        }
-        s = wave_sum(s);
-        token = mg_decide(bt, bs, s, A->token_beg);
-        last = token;
-        if (token > A->token_beg) { seek_delta = 2 * (token - A->token_beg); has_ts = 1; }
-    }
+    mo_pick p = { A->token, A->s_last, A->s_penult, A->s_seek_delta, A->s_has_ts };
+    if (A->spec) mo_pick_merge(p, A->rec_in, A->ps_in, A->n_rec, A->token_beg, lane);
     if (lane == 0) {
-        pk[0] = token; pk[1] = last; pk[2] = penult; pk[3] = seek_delta; pk[4] = has_ts;
+        mo_pick_put(pk, p);
         if (blockIdx.x == 0) {
             GAS int * po = (GAS int *) A->ps_out;
-            po[0] = last; po[1] = penult; po[2] = seek_delta; po[3] = has_ts;
-            ((GAS int *) A->logits)[A->n_vocab + 1] = token;          // behind the logits and the status word: the token this launch decoded
+            po[MO_PS_LAST] = p.last; po[MO_PS_PENULT] = p.penult; po[MO_PS_SEEK_DELTA] = p.seek_delta; po[MO_PS_HAS_TS] = p.has_ts;
+            ((GAS int *) A->logits)[A->n_vocab + 1] = p.token;        // behind the logits and the status word: the token this launch decoded
         }
     }
 }
@@ -700,7 +574,7 @@ __device__ __forceinline__ void mg_prefetch_logits(mg_kargs A, unsigned (&pf)[96
     have_pf = true;
 }
 template <int NP3, int NS, bool Q = false>
-__device__ __forceinline__ void mg_final(mg_kargs A, mg_ctl & c, unsigned char * smem, unsigned (&pf)[96], bool have_pf, const float (&gw)[NP3],
+__device__ __forceinline__ void mg_final(mg_kargs A, mo_ctl & c, unsigned char * smem, unsigned (&pf)[96], bool have_pf, const float (&gw)[NP3],
                                          const float (&gb)[NP3], int lane, int wave) {
     float  * xf  = (float *) smem;
     wa_f16 * xin = (wa_f16 *) (smem + WA_MEGA_MAX_D * 4);
@@ -710,16 +584,8 @@ __device__ __forceinline__ void mg_final(mg_kargs A, mg_ctl & c, unsigned char *
                    blockIdx.x == 0 && wave == 0 ? (A->n_layer * 8) * 8 : -1, ((const int *) (smem + MG_PICK_OFF))[0]);
     const int NG = (n_vocab + 7) >> 3;
     GAS float * logits = (GAS float *) A->logits;
-    // sampling state after this launch's token -> which logits the next pick may choose (whisper.cpp:6264-6302)
-    const int * pk = (const int *) (smem + MG_PICK_OFF);
-    const int beg = A->token_beg, eot = A->token_eot;
-    const int st_last = pk[1], st_penult = pk[2], st_seek = pk[3], st_has = pk[4];
-    const bool last_ts = st_last >= beg, penult_ts = st_penult < 0 || st_penult >= beg;
-    const bool no_ts = last_ts && penult_ts, no_text = last_ts && !penult_ts;
-    const int ts_min = st_has ? beg + st_seek / 2 : beg;
+    mo_cand cd = mo_cand_init((const int *) (smem + MG_PICK_OFF), A->token_beg, A->token_eot);      // the state after this launch's token
     const GAS unsigned * smask = (const GAS unsigned *) A->smask;
-    mg_best bt = { -INFINITY, 0x7fffffff }, bs = { -INFINITY, 0x7fffffff };
-    float s_ts = 0.0f;
     // row groups g(j) = wg + nwg (wave + 8 j) of this wave, two weight buffers: the loads of group j + 1 fly during group j
     unsigned pf2[96];
     const int ns = d >> 5;
@@ -738,17 +604,7 @@ __device__ __forceinline__ void mg_final(mg_kargs A, mg_ctl & c, unsigned char *
         float r;
         if constexpr (Q) r = mq_hsum8(mq_chain<NS>(buf, qwl(j), qdl(j), valid, 0, ns, (const int *) mq_xq(xin) + (lane & 7) * mq_ld(ns), mq_xd(xin), 0.0f, ns <= MQ_PF));
         else r = mg_dot8<NS>(buf, wrow(j), valid, ns, xin, lane & 7, ns <= 48);
-        if (valid && (lane & 7) == 0) {
-            logits[row] = r;
-            if (!((mw >> (row & 31)) & 1u)) {
-                if (row >= beg) {
-                    if (!no_ts && row >= ts_min) {
-                        if (r > bs.v) { s_ts = s_ts * __expf(bs.v - r) + 1.0f; bs.v = r; bs.i = row; }
-                        else s_ts += __expf(r - bs.v);
-                    }
-                } else if (!(no_text && row < eot)) mg_best_merge(bt, r, row);
-            }
-        }
+        if (valid && (lane & 7) == 0) { logits[row] = r; mo_cand_add(cd, r, row, mw); }
     };
     if (!have_pf && grp(0) < NG) load(0, pf);
     for (int j = 0; grp(j) < NG; j += 2) {
@@ -758,29 +614,7 @@ __device__ __forceinline__ void mg_final(mg_kargs A, mg_ctl & c, unsigned char *
         if (grp(j + 2) < NG) load(j + 2, pf);
         one(j + 1, pf2);
     }
-    {   // this workgroup's record
-        unsigned * rb = (unsigned *) (smem + MG_PICK_OFF + 64);
-        const float m_loc = bs.v;
-        mg_best_wave(bt); mg_best_wave(bs);
-        float sw = m_loc > -INFINITY ? s_ts * __expf(m_loc - bs.v) : 0.0f;
-        sw = wave_sum(sw);
-        if (lane == 0) { rb[wave * 8 + 0] = __float_as_uint(bt.v); rb[wave * 8 + 1] = (unsigned) bt.i; rb[wave * 8 + 2] = __float_as_uint(bs.v);
-                         rb[wave * 8 + 3] = (unsigned) bs.i; rb[wave * 8 + 4] = __float_as_uint(sw); }
-        mg_barrier();
-        if (wave == 0) {
-            mg_best t2 = { -INFINITY, 0x7fffffff }, s2 = { -INFINITY, 0x7fffffff };
-            float sl = 0.0f, ml = -INFINITY;
-            if (lane < MG_NW) { t2.v = __uint_as_float(rb[lane * 8 + 0]); t2.i = (int) rb[lane * 8 + 1]; s2.v = __uint_as_float(rb[lane * 8 + 2]); s2.i = (int) rb[lane * 8 + 3];
-                                sl = __uint_as_float(rb[lane * 8 + 4]); ml = s2.v; }
-            mg_best_wave(t2); mg_best_wave(s2);
-            float sg = ml > -INFINITY ? sl * __expf(ml - s2.v) : 0.0f;
-            sg = wave_sum(sg);
-            if (lane == 0) {
-                GAS unsigned * ro = (GAS unsigned *) A->rec_out + (size_t) wg * 8;
-                ro[0] = __float_as_uint(t2.v); ro[1] = (unsigned) t2.i; ro[2] = __float_as_uint(s2.v); ro[3] = (unsigned) s2.i; ro[4] = __float_as_uint(sg);
-            }
-        }
-    }
+    mo_cand_record(cd, (unsigned *) (smem + MG_PICK_OFF + 64), A->rec_out + (size_t) wg * MO_REC_WORDS, lane, wave);      // this workgroup's record
     mg_trace(A, blockIdx.x == 0 && wave == 0 && lane == 0, (A->n_layer * 8) * 8 + 3, mg_now());
     if (A->dbg) { mg_trace(A, blockIdx.x == 0 && wave == 0 && lane == 0, 3022, (unsigned) clock64()); mg_trace(A, blockIdx.x == 0 && wave == 0 && lane == 0, 3023, mg_now()); }
     // this launch ran: the host accepts a step only with its own number behind the logits (a launch that never started leaves the status word 0 too)
@@ -799,12 +633,12 @@ __device__ __forceinline__ void mg_final(mg_kargs A, mg_ctl & c, unsigned char *
 template <int NP3, int NS, bool Q = false, bool CQ = false>        // CQ: see below (k_decode_mega_cq only)
 __device__ __forceinline__ void mg_role_gemv(mg_kargs A_, int idx_) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const mg_kargs A = mg_uniform(A_);
+    const mg_kargs A = mo_uniform(A_);
     int lane = threadIdx.x & 63;
 #define MG_FRESH() do { lane = mq_fresh(lane); } while (0)      /* see mq_fresh: nothing lane-derived lives across phases */
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int wg = __builtin_amdgcn_readfirstlane(idx_), nG = (int) gridDim.x - 5 * A->n_head;
-    mg_ctl c; c.status = (gu32 *) A->status; c.seq = A->seq; c.dead = false;
+    mo_ctl c; c.status = (gu32 *) A->status; c.seq = A->seq; c.dead = false;
     mg_chaos_start(c.seq);
     mg_trace(A, wg == 0 && wave == 0 && (threadIdx.x & 63) == 0, (A->n_layer * 8) * 8 + 6, mg_now());        // entry
     if (A->dbg) { mg_trace(A, wg == 0 && wave == 0 && (threadIdx.x & 63) == 0, 3020, (unsigned) clock64()); mg_trace(A, wg == 0 && wave == 0 && (threadIdx.x & 63) == 0, 3021, mg_now()); }
@@ -814,12 +648,11 @@ __device__ __forceinline__ void mg_role_gemv(mg_kargs A_, int idx_) {
     // Quantised, d <= 768: the first MLP product is owned by WHOLE Q8_0 blocks - workgroup b < 4d / 32 has rows 32 b .. 32 b + 31, eight per
     // wave 1..4 -, so that the block leaves already quantised (8 quads + scale: 9 granules instead of 32 F32 values, and no consumer
     // quantises it again).  The four waves meet over an LDS counter; the last one to arrive quantises and publishes.
-    constexpr bool QB = Q && !BIG && MG_DEFER;
-    // Wide models (d > 768), second form of the schedule: FC1 has a prefetched owner for every group (waves 1, 2 | 3, 4 after their P6 products |
+    constexpr bool QB = Q && !BIG;
+    // Wide models (BIG): FC1 has a prefetched owner for every group (waves 1, 2 | 3, 4 after their P6 products |
     // 6, 7, which hold no logits rows until the last layer), and waves 3, 4 ask for the first half of their FC2 rows right after FC1 - an assist
     // that fetches on demand exposes an HBM round trip per group (P7 5.3 -> ~1.5 us, P8 5.9 -> ~4 us per layer on large-v3).
-    constexpr bool BIGP = BIG && MG_DEFER;
-    static_assert(!CQ || (!Q && !BIG && MG_DEFER), "the CQ form is the F16 small-width schedule");
+    static_assert(!CQ || (!Q && !BIG), "the CQ form is the F16 small-width schedule");
     // (fc1x / fc1cnt sit in the xin area at byte 7 MAX_D = 8960 .. 9092.  The whole-block form runs for d <= 768 only (QB = Q && !BIG): the widest thing
     //  ever written into xin there is the FC2 operand - quants [4d <= 3072] bytes at 0, block scales [4d / 32 <= 96] floats at 6 MAX_D = 7680 .. 8064 -, so
     //  no gather reaches byte 8960; the counter is never reset, only compared modulo 4.)
@@ -858,8 +691,8 @@ __device__ __forceinline__ void mg_role_gemv(mg_kargs A_, int idx_) {
     else if (wave == 3)         t = mg_mk8<Q, NS>(pf, Ly[0].out_w, Ly[0].out_d, Ly[0].out_b, nullptr, d, d, row_d, r_d, 0, lane);
     else if (wave == 4 && !CQ)  t = mg_mk8<Q, NS>(pf, Ly[0].cq_w, Ly[0].cq_d, Ly[0].cq_b, nullptr, d, d, row_d, r_d, 0, lane);
     else if (wave == 5)         t = mg_mk16<Q, 4 * NS>(pf, Ly[0].fc2_w, Ly[0].fc2_d, Ly[0].fc2_b, d, d4, row_d, r_d, 0, lane);
-    else if (wave >= 6 && !((BIGP || CQ) && L > 0)) mg_prefetch_logits<NS, Q>(A, pf, have_pf, lane, wave);      // held until the final phase (wide form: they own FC1 rows, CQ: QKV rows; the logits rows come in the last layer)
-    mg_barrier();                   // the picked token is in LDS for the three embedding waves
+    else if (wave >= 6 && !((BIG || CQ) && L > 0)) mg_prefetch_logits<NS, Q>(A, pf, have_pf, lane, wave);      // held until the final phase (wide form: they own FC1 rows, CQ: QKV rows; the logits rows come in the last layer)
+    wa_barrier_lds();                   // the picked token is in LDS for the three embedding waves
     mg_trace(A, wg == 0 && wave == 0 && lane == 0, (A->n_layer * 8) * 8 + 7, mg_now());
     if (wave >= 3 && wave <= 5) {   // GELU table -> LDS by LDS-DMA (no registers, nothing waits here); first needed by FC1 of layer 0
         const GAS u32x4 * src = (const GAS u32x4 *) A->gelu;
@@ -881,12 +714,11 @@ __device__ __forceinline__ void mg_role_gemv(mg_kargs A_, int idx_) {
         mg_ln3<NP3, Q>(A, c, l == 0 ? nullptr : mg_edge(A, l - 1, E_X3), gw, gb, mg_slot(wave, MG_EX_P1), lane, xf, xinB, lnred, 100u + l, wg == 0 && wave == 0 ? (l * 8 + 0) * 8 : -1, pk[0]);
         MG_FRESH();
         if (!CQ) mg_ln_params<NP3>(gw, gb, Y.ln2_w, Y.ln2_b, d, mg_slot(wave, MG_EX_P4), lane);
-        if (MG_DEFER && l > 0 && wave == 5) t = mg_mk16<Q, 4 * NS>(pf, Y.fc2_w, Y.fc2_d, Y.fc2_b, d, d4, row_d, r_d, 0, lane);      // deferred from the previous layer's P8
+        if (l > 0 && wave == 5) t = mg_mk16<Q, 4 * NS>(pf, Y.fc2_w, Y.fc2_d, Y.fc2_b, d, d4, row_d, r_d, 0, lane);      // deferred from the previous layer's P8
         // (Wide models give a workgroup more row groups than the one per wave that is prefetched.  The waves idle in a phase then
         //  assist: they take the extra groups on demand - overwriting the rows they hold for a later phase - and fetch those again
         //  afterwards, long before that phase.  ggml-small and below: one group per wave, nothing changes.)
         if (CQ ? wave >= 6 : wave == 1 || wave == 2 || (BIG && (wave == 3 || wave == 4))) {
-            const bool own = !BIG || wave <= 2;
             bool assisted = false;
             gu64 * eq = mg_edge(A, l, E_QKV);
             for (int grp = CQ ? wave - 6 : wave - 1; grp < g_qkv; grp += BIG ? 4 : 2) {
@@ -903,8 +735,7 @@ __device__ __forceinline__ void mg_role_gemv(mg_kargs A_, int idx_) {
                 }
             }
             mg_trace(A, wg == 0 && wave == (CQ ? 6 : 1) && lane == 0, (l * 8 + 0) * 8 + 3, mg_now());
-            if (own && !MG_DEFER) t = mg_mk8<Q, NS>(pf, Y.fc1_w, Y.fc1_d, Y.fc1_b, nullptr, d4, d, row_ff, r_ff, wave - 1, lane);
-            else if (assisted) t = wave == 3 ? mg_mk8<Q, NS>(pf, Y.out_w, Y.out_d, Y.out_b, nullptr, d, d, row_d, r_d, 0, lane)
+            if (assisted) t = wave == 3 ? mg_mk8<Q, NS>(pf, Y.out_w, Y.out_d, Y.out_b, nullptr, d, d, row_d, r_d, 0, lane)
                                              : mg_mk8<Q, NS>(pf, Y.cq_w, Y.cq_d, Y.cq_b, nullptr, d, d, row_d, r_d, 0, lane);
         }
         // ---------------- P3: self-attention out-projection + residual ----------------
@@ -914,11 +745,11 @@ __device__ __forceinline__ void mg_role_gemv(mg_kargs A_, int idx_) {
             if constexpr (Q) { if (qs >= 0) mg_gather_qb<1>(c, mg_edge(A, l, E_AO), j0, j1, lane, xin, d >> 5, 200u + l, A, wg == 0 && wave == 0 ? (l * 8 + 1) * 8 : -1); }
             else if (qs >= 0) mg_gather_h2<2>(c, mg_edge(A, l, E_AO), j0, j1, lane, (unsigned *) xin, 200u + l, A, wg == 0 && wave == 0 ? (l * 8 + 1) * 8 : -1);
         }
-        mg_barrier();
+        wa_barrier_lds();
         MG_FRESH();
-        // (MG_DEFER: a wave's next weights are requested only once the CU's NEXT gather is over - a poll queued behind 24-48 KB of
+        // (A wave's next weights are requested only once the CU's NEXT gather is over - a poll queued behind 24-48 KB of
         //  weight loads waits for them: hand-off-1to1 costs 0.8 us with quiet endpoints, 2.3-3.5 behind 8-15 streaming waves.)
-        if (MG_DEFER && (wave == 1 || wave == 2)) t = mg_mk8<Q, NS>(pf, Y.fc1_w, Y.fc1_d, Y.fc1_b, nullptr, d4, d, QB ? 32 * wg : row_ff, QB ? 32 : r_ff, wave - 1, lane);
+        if (wave == 1 || wave == 2) t = mg_mk8<Q, NS>(pf, Y.fc1_w, Y.fc1_d, Y.fc1_b, nullptr, d4, d, QB ? 32 * wg : row_ff, QB ? 32 : r_ff, wave - 1, lane);
         if (wave == 3 || (BIG && wave == 5)) {        // wave 5 assists (it holds this layer's FC2 rows, next needed in P8)
             const bool own = !BIG || wave == 3;
             bool assisted = false;
@@ -932,8 +763,7 @@ __device__ __forceinline__ void mg_role_gemv(mg_kargs A_, int idx_) {
             }
             mg_trace(A, wg == 0 && own && lane == 0, (l * 8 + 1) * 8 + 3, mg_now());
             if (A->dbg && l == MG_WGTRACE_LAYER) mg_trace(A, own && lane == 0, 1024 + wg * 8 + 3, mg_now());
-            if (own && !MG_DEFER) t = mg_mk8<Q, NS>(pf, Y.co_w, Y.co_d, Y.co_b, nullptr, d, d, row_d, r_d, 0, lane);
-            else if (assisted) t = mg_mk16<Q, 4 * NS>(pf, Y.fc2_w, Y.fc2_d, Y.fc2_b, d, d4, row_d, r_d, 0, lane);
+            if (assisted) t = mg_mk16<Q, 4 * NS>(pf, Y.fc2_w, Y.fc2_d, Y.fc2_b, d, d4, row_d, r_d, 0, lane);
         }
         // ---------------- P4: LayerNorm + cross query (CQ: x -> the residual row only) ----------------
         MG_FRESH();
@@ -944,7 +774,7 @@ __device__ __forceinline__ void mg_role_gemv(mg_kargs A_, int idx_) {
             const int qs = mg_slot(wave, MG_EX_X1), sg = mg_seg(d), i0 = qs * sg, i1 = min(d, i0 + sg);
             if (qs >= 0) mg_gather_f32<NP3>(c, mg_edge(A, l, E_X1), i0, i1, lane, xf, 300u + l, A,
                                             wave == 0 ? (wg == 0 ? (l * 8 + 2) * 8 : (A->dbg && l == MG_WGTRACE_LAYER ? 1024 + wg * 8 : -1)) : -1);
-            mg_barrier();
+            wa_barrier_lds();
             MG_FRESH();
             if (wave == 4) t = mg_mk8<Q, NS>(pf, Y.co_w, Y.co_d, Y.co_b, nullptr, d, d, row_d, r_d, 0, lane);
             else if (wave == 3 || wave >= 6) {
@@ -956,8 +786,8 @@ __device__ __forceinline__ void mg_role_gemv(mg_kargs A_, int idx_) {
         mg_ln3<NP3, Q>(A, c, mg_edge(A, l, E_X1), gw, gb, mg_slot(wave, MG_EX_P4), lane, xf, xinB, lnred, 300u + l,
                        wave == 0 ? (wg == 0 ? (l * 8 + 2) * 8 : (A->dbg && l == MG_WGTRACE_LAYER ? 1024 + wg * 8 : -1)) : -1);
         MG_FRESH();
-        if (MG_DEFER && !CQ && wave == 3) t = mg_mk8<Q, NS>(pf, Y.co_w, Y.co_d, Y.co_b, nullptr, d, d, row_d, r_d, 0, lane);
-        if (BIGP && wave >= 6 && wave - 2 < g_ff) t = mg_mk8<Q, NS>(pf, Y.fc1_w, Y.fc1_d, Y.fc1_b, nullptr, d4, d, row_ff, r_ff, wave - 2, lane);      // FC1 groups 4, 5 (the next gather is a cross-attention away)
+        if (!CQ && wave == 3) t = mg_mk8<Q, NS>(pf, Y.co_w, Y.co_d, Y.co_b, nullptr, d, d, row_d, r_d, 0, lane);
+        if (BIG && wave >= 6 && wave - 2 < g_ff) t = mg_mk8<Q, NS>(pf, Y.fc1_w, Y.fc1_d, Y.fc1_b, nullptr, d4, d, row_ff, r_ff, wave - 2, lane);      // FC1 groups 4, 5 (the next gather is a cross-attention away)
         mg_ln_params<NP3>(gw, gb, Y.ln3_w, Y.ln3_b, d, mg_slot(wave, MG_EX_P7), lane);
         if (!CQ && (wave == 4 || (BIG && wave == 3))) {        // wave 3 assists (it holds this layer's cross-attention output rows, next needed in P6)
             const bool own = !BIG || wave == 4;
@@ -973,10 +803,7 @@ __device__ __forceinline__ void mg_role_gemv(mg_kargs A_, int idx_) {
             mg_trace(A, wg == 0 && own && lane == 0, (l * 8 + 2) * 8 + 3, mg_now());
             if (A->dbg && l == MG_WGTRACE_LAYER) mg_trace(A, own && lane == 0, 1024 + wg * 8 + 6, mg_now());
             if (QB) t = mg_mk8<Q, NS>(pf, Y.fc1_w, Y.fc1_d, Y.fc1_b, nullptr, d4, d, 32 * wg, 32, 3, lane);      // its eight rows of the block; next needed in P7
-            else if (own && !MG_DEFER) {
-                if (l + 1 < L) t = mg_mk8<Q, NS>(pf, Ly[l + 1].cq_w, Ly[l + 1].cq_d, Ly[l + 1].cq_b, nullptr, d, d, row_d, r_d, 0, lane);
-                else mg_prefetch_logits<NS, Q>(A, pf, have_pf, lane, wave);
-            } else if (assisted) t = mg_mk8<Q, NS>(pf, Y.co_w, Y.co_d, Y.co_b, nullptr, d, d, row_d, r_d, 0, lane);
+            else if (assisted) t = mg_mk8<Q, NS>(pf, Y.co_w, Y.co_d, Y.co_b, nullptr, d, d, row_d, r_d, 0, lane);
         }
         // ---------------- P6: cross-attention out-projection + residual ----------------
         MG_FRESH();
@@ -985,9 +812,9 @@ __device__ __forceinline__ void mg_role_gemv(mg_kargs A_, int idx_) {
             if constexpr (Q) { if (qs >= 0) mg_gather_qb<1>(c, mg_edge(A, l, E_AO2), j0, j1, lane, xin, d >> 5, 400u + l, A, wg == 0 && wave == 0 ? (l * 8 + 3) * 8 : -1); }
             else if (qs >= 0) mg_gather_h2<2>(c, mg_edge(A, l, E_AO2), j0, j1, lane, (unsigned *) xin, 400u + l, A, wg == 0 && wave == 0 ? (l * 8 + 3) * 8 : -1);
         }
-        mg_barrier();
+        wa_barrier_lds();
         MG_FRESH();
-        if (MG_DEFER && !QB && !BIGP && !CQ && wave == 4) {
+        if (!QB && !BIG && !CQ && wave == 4) {
             if (l + 1 < L) t = mg_mk8<Q, NS>(pf, Ly[l + 1].cq_w, Ly[l + 1].cq_d, Ly[l + 1].cq_b, nullptr, d, d, row_d, r_d, 0, lane);
             else mg_prefetch_logits<NS, Q>(A, pf, have_pf, lane, wave);
         }
@@ -1006,12 +833,9 @@ __device__ __forceinline__ void mg_role_gemv(mg_kargs A_, int idx_) {
             if (A->dbg && l == MG_WGTRACE_LAYER) mg_trace(A, own && lane == 0, 4096 + wg * 8 + 3, mg_now());
             if (QB) t = mg_mk8<Q, NS>(pf, Y.fc1_w, Y.fc1_d, Y.fc1_b, nullptr, d4, d, 32 * wg, 32, 2, lane);
             else if (CQ) { if (l + 1 >= L) mg_prefetch_logits<NS, Q>(A, pf, have_pf, lane, wave); }      // (the next rows: after the next P4)
-            else if (BIGP) {                 // FC1 group 2 (wave 3) / 3 (wave 4), used in P7
+            else if (BIG) {                 // FC1 group 2 (wave 3) / 3 (wave 4), used in P7
                 if (wave - 1 < g_ff) t = mg_mk8<Q, NS>(pf, Y.fc1_w, Y.fc1_d, Y.fc1_b, nullptr, d4, d, row_ff, r_ff, wave - 1, lane);
                 else big_next(wave);
-            } else if (own && !MG_DEFER) {
-                if (l + 1 < L) t = mg_mk8<Q, NS>(pf, Ly[l + 1].out_w, Ly[l + 1].out_d, Ly[l + 1].out_b, nullptr, d, d, row_d, r_d, 0, lane);
-                else mg_prefetch_logits<NS, Q>(A, pf, have_pf, lane, wave);
             } else if (assisted) {
                 if (l + 1 < L) t = mg_mk8<Q, NS>(pf, Ly[l + 1].cq_w, Ly[l + 1].cq_d, Ly[l + 1].cq_b, nullptr, d, d, row_d, r_d, 0, lane);
                 else mg_prefetch_logits<NS, Q>(A, pf, have_pf, lane, wave);
@@ -1023,7 +847,7 @@ __device__ __forceinline__ void mg_role_gemv(mg_kargs A_, int idx_) {
         mg_ln3<NP3, Q>(A, c, mg_edge(A, l, E_X2), gw, gb, mg_slot(wave, MG_EX_P7), lane, xf, xinB, lnred, 500u + l,
                        wave == 0 ? (wg == 0 ? (l * 8 + 4) * 8 : (A->dbg && l == MG_WGTRACE_LAYER ? 4096 + wg * 8 : -1)) : -1);
         MG_FRESH();
-        if (MG_DEFER && !QB && !BIGP && !CQ && wave == 3) {
+        if (!QB && !BIG && !CQ && wave == 3) {
             if (l + 1 < L) t = mg_mk8<Q, NS>(pf, Ly[l + 1].out_w, Ly[l + 1].out_d, Ly[l + 1].out_b, nullptr, d, d, row_d, r_d, 0, lane);
             else mg_prefetch_logits<NS, Q>(A, pf, have_pf, lane, wave);
         }
@@ -1043,18 +867,13 @@ __device__ __forceinline__ void mg_role_gemv(mg_kargs A_, int idx_) {
                 if (lane == 0) arrived = __hip_atomic_fetch_add(fc1cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                 arrived = (unsigned) __builtin_amdgcn_readfirstlane((int) arrived);
                 asm volatile("" ::: "memory");
-                if ((arrived & 3u) == 3u && 32 * wg < d4) {               // all 32 values are there: quantize_row_q8_0 of the block (as mq_put), by lanes 0..31
+                if ((arrived & 3u) == 3u && 32 * wg < d4) {               // all 32 values are there: quantize_row_q8_0 of the block, by lanes 0..31
                     MG_CHAOS_AT(52u);
-                    const float y = fc1x[lane & 31];
-                    float a = fabsf(y);
-                    a = fmaxf(a, dpp_f32<0x128>(a)); a = fmaxf(a, dpp_f32<0x124>(a)); a = fmaxf(a, dpp_f32<0x122>(a)); a = fmaxf(a, dpp_f32<0x121>(a));
-                    a = fmaxf(a, __shfl_xor(a, 16, 32));
-                    const float dq = a / 127.f, id = a != 0.0f ? 127.f / a : 0.0f;
-                    const unsigned q = (unsigned) (int) rintf(y * id) & 0xffu;
-                    const unsigned w = q | (dpp_u32<0x101>(q) << 8) | (dpp_u32<0x102>(q) << 16) | (dpp_u32<0x103>(q) << 24);
+                    float dq;
+                    const unsigned w = mq_quant32(fc1x[lane & 31], dq);
                     gu64 * eb = mg_edge(A, l, E_HF) + (size_t) wg * 9;
                     if (lane < 32 && (lane & 3) == 0) gr_store(eb + (lane >> 2), seq, w);
-                    if (lane == 0) gr_store(eb + 8, seq, __float_as_uint(h2f(f2h(dq))));
+                    if (lane == 0) gr_store(eb + 8, seq, __float_as_uint(dq));
                     mg_trace(A, wg == 0 && lane == 0, (l * 8 + 4) * 8 + 3, mg_now());
                 }
                 if (wave == 3) {
@@ -1065,7 +884,7 @@ __device__ __forceinline__ void mg_role_gemv(mg_kargs A_, int idx_) {
                     else mg_prefetch_logits<NS, Q>(A, pf, have_pf, lane, wave);
                 }
             }
-        } else if (BIGP) {
+        } else if (BIG) {
             if ((wave >= 1 && wave <= 4) || wave >= 6) {
                 gu64 * eh = mg_edge(A, l, E_HF);
                 for (int grp = wave <= 4 ? wave - 1 : wave - 2; grp < g_ff; grp += 6) {
@@ -1084,7 +903,6 @@ __device__ __forceinline__ void mg_role_gemv(mg_kargs A_, int idx_) {
             }
         } else
         if (wave == 1 || wave == 2 || (BIG && (wave == 3 || wave == 4))) {        // waves 3, 4 assist (they hold the next layer's out-projection / cross-query rows)
-            const bool own = !BIG || wave <= 2;
             bool assisted = false;
             gu64 * eh = mg_edge(A, l, E_HF);
             for (int grp = wave - 1; grp < g_ff; grp += BIG ? 4 : 2) {
@@ -1099,10 +917,7 @@ __device__ __forceinline__ void mg_role_gemv(mg_kargs A_, int idx_) {
             }
             mg_trace(A, wg == 0 && wave == 1 && lane == 0, (l * 8 + 4) * 8 + 3, mg_now());
             if (A->dbg && l == MG_WGTRACE_LAYER) mg_trace(A, wave == 1 && lane == 0, 4096 + wg * 8 + 6, mg_now());
-            if (own && !MG_DEFER) {
-                if (l + 1 < L) t = mg_mk8<Q, NS>(pf, Ly[l + 1].qkv_w, Ly[l + 1].qkv_d, Ly[l + 1].qkv_b, Ly[l + 1].qkv_s, 3 * d, d, row_qkv, r_qkv, wave - 1, lane);
-                else mg_prefetch_logits<NS, Q>(A, pf, have_pf, lane, wave);
-            } else if (CQ) {
+            if (CQ) {
                 if (l + 1 >= L) mg_prefetch_logits<NS, Q>(A, pf, have_pf, lane, wave);      // (the next FC1 rows: after the next P3)
             } else if (assisted) {
                 if (l + 1 >= L) mg_prefetch_logits<NS, Q>(A, pf, have_pf, lane, wave);
@@ -1114,15 +929,15 @@ __device__ __forceinline__ void mg_role_gemv(mg_kargs A_, int idx_) {
         MG_FRESH();
         {   // the widest hand-off (2d granules)
             const int ng = QB ? 9 * (d4 >> 5) : Q ? d4 : 2 * d;
-            const int qs = mg_slot(wave, QB || BIGP ? MG_EX_HFQ : MG_EX_HF), sg = mg_seg(ng), i0 = qs * sg, i1 = min(ng, i0 + sg);
+            const int qs = mg_slot(wave, QB || BIG ? MG_EX_HFQ : MG_EX_HF), sg = mg_seg(ng), i0 = qs * sg, i1 = min(ng, i0 + sg);
             if constexpr (QB) { if (qs >= 0) mg_gather_qb<3>(c, mg_edge(A, l, E_HF), i0, i1, lane, xin, d4 >> 5, 600u + l, A, wg == 0 && wave == 0 ? (l * 8 + 5) * 8 : -1); }
             else if constexpr (Q) { if (qs >= 0) mg_gather_q8<(NP3 == MG_NP3 ? 14 : 8)>(c, mg_edge(A, l, E_HF), i0, i1, lane, xin, d4 >> 5, 600u + l, A, wg == 0 && wave == 0 ? (l * 8 + 5) * 8 : -1); }
             else if (qs >= 0) mg_gather_h2<7>(c, mg_edge(A, l, E_HF), i0, i1, lane, (unsigned *) xin, 600u + l, A, wg == 0 && wave == 0 ? (l * 8 + 5) * 8 : -1);
         }
-        mg_barrier();
+        wa_barrier_lds();
         MG_FRESH();
         mg_trace(A, wg == 0 && wave == 5 && lane == 0, (l * 8 + 5) * 8 + 4, mg_now());
-        if (MG_DEFER && !CQ && (wave == 1 || wave == 2)) {
+        if (!CQ && (wave == 1 || wave == 2)) {
             if (l + 1 < L) t = mg_mk8<Q, NS>(pf, Ly[l + 1].qkv_w, Ly[l + 1].qkv_d, Ly[l + 1].qkv_b, Ly[l + 1].qkv_s, 3 * d, d, row_qkv, r_qkv, wave - 1, lane);
             else mg_prefetch_logits<NS, Q>(A, pf, have_pf, lane, wave);
         }
@@ -1131,7 +946,7 @@ __device__ __forceinline__ void mg_role_gemv(mg_kargs A_, int idx_) {
             bool assisted = false;
             gu64 * ex = mg_edge(A, l, E_X3);
             for (int grp = own ? 0 : wave - 2; grp < g_d16; grp += BIG ? 3 : 1) {
-                if (grp >= (BIGP ? 3 : 1)) t = mg_mk16<Q, 4 * NS>(pf, Y.fc2_w, Y.fc2_d, Y.fc2_b, d, d4, row_d, r_d, grp, lane);      // (wide form: groups 1, 2 were asked for after FC1)
+                if (grp >= (BIG ? 3 : 1)) t = mg_mk16<Q, 4 * NS>(pf, Y.fc2_w, Y.fc2_d, Y.fc2_b, d, d4, row_d, r_d, grp, lane);      // (wide form: groups 1, 2 were asked for after FC1)
                 if (grp >= 1) assisted = true;
                 MG_CHAOS_AT(8u);
                 float v = mg_do16<Q, 4 * NS>(pf, t, d4 >> 5, xin, lane);
@@ -1139,10 +954,8 @@ __device__ __forceinline__ void mg_role_gemv(mg_kargs A_, int idx_) {
                 if (t.valid && (lane & 15) == MG_RES16(Q)) gr_store(ex + t.row, seq, __float_as_uint(v + xf[t.row]));
             }
             mg_trace(A, wg == 0 && own && lane == 0, (l * 8 + 5) * 8 + 3, mg_now());
-            if (own && (!MG_DEFER || l + 1 >= L)) {
-                if (l + 1 < L) t = mg_mk16<Q, 4 * NS>(pf, Ly[l + 1].fc2_w, Ly[l + 1].fc2_d, Ly[l + 1].fc2_b, d, d4, row_d, r_d, 0, lane);
-                else mg_prefetch_logits<NS, Q>(A, pf, have_pf, lane, wave);
-            } else if (assisted) {
+            if (own && l + 1 >= L) mg_prefetch_logits<NS, Q>(A, pf, have_pf, lane, wave);      // (its next FC2 rows: after the next layer's P1)
+            else if (assisted) {
                 if (l + 1 >= L) mg_prefetch_logits<NS, Q>(A, pf, have_pf, lane, wave);
                 else t = wave == 3 ? mg_mk8<Q, NS>(pf, Ly[l + 1].out_w, Ly[l + 1].out_d, Ly[l + 1].out_b, nullptr, d, d, row_d, r_d, 0, lane)
                                    : mg_mk8<Q, NS>(pf, Ly[l + 1].cq_w, Ly[l + 1].cq_d, Ly[l + 1].cq_b, nullptr, d, d, row_d, r_d, 0, lane);
@@ -1173,23 +986,8 @@ __device__ __forceinline__ mg_att_smem mg_att_carve(unsigned char * base, int ma
 }
 
 
-// one key's score from its two 16-byte pieces (lane a of the key's 4-lane group): k_attn_exact's arithmetic
-__device__ __forceinline__ float mg_score(const u32x4 & ka, const u32x4 & kb, const float (&qa)[8], const float (&qb)[8], float scale) {
-    const wa_f16 * k8a = (const wa_f16 *) &ka, * k8b = (const wa_f16 *) &kb;
-    float v[8];
-#pragma unroll
-    for (int l = 0; l < 8; ++l) {
-        float t = fmaf(h2f(k8a[l]), qa[l], 0.0f);
-        t = fmaf(h2f(k8b[l]), qb[l], t);
-        t = t + dpp_f32<0x4e>(t);                // quad_perm [2,3,0,1]: s[j] + s[j+2]
-        v[l] = t + dpp_f32<0xb1>(t);             // quad_perm [1,0,3,2]: (s0+s2) + (s1+s3)
-    }
-    const float t0 = v[0] + v[4], t1 = v[1] + v[5], t2 = v[2] + v[6], t3 = v[3] + v[7];
-    return ((t0 + t1) + (t2 + t3)) * scale;
-}
-
 // final tree over the 32 partial-sum chains + F64 leftovers, by threads 0..63 (tid = d_head index); then publish
-template <bool Q = false>                 // Q: the result leaves in F32, one granule per element (the out-projection quantises it from F32)
+template <bool Q = false>                 // Q: the outputs leave as two Q8_0 blocks (mo_attn_publish)
 __device__ __forceinline__ void mg_attn_finish(const float * part, const wa_f16 * vleft /* [nl][64] */, const wa_f16 * p16, int np, int nl,
                                                gu64 * edge, int h, unsigned seq, int tid, double * dbl0, double * dbl1 /* LDS, [16][64] each */,
                                                mg_kargs A = nullptr, int tslot = -1) {
@@ -1222,7 +1020,7 @@ __device__ __forceinline__ void mg_attn_finish(const float * part, const wa_f16 
         sumf = (double) wa_tree32(s32);
         if (tslot >= 0) mg_trace(A, tid == 0, tslot + 1, mg_now() + (sumf == 1e300 ? 1u : 0u));
     }
-    mg_barrier();
+    wa_barrier_lds();
     if (tid < 64) {
         double dv[32];
 #pragma unroll
@@ -1231,24 +1029,7 @@ __device__ __forceinline__ void mg_attn_finish(const float * part, const wa_f16 
 #pragma unroll
         for (int cc = 0; cc < 32; ++cc) sumf += dv[cc];
         if (tslot >= 0) mg_trace(A, tid == 0, tslot + 2, mg_now() + (sumf == 1e300 ? 1u : 0u));
-        if constexpr (Q) {
-            // The head's 64 outputs are two Q8_0 blocks of the out-projection's operand (quantize_row_q8_0, arch/x86/quants.c): quantised
-            // HERE, once, instead of by every consumer - a block leaves as 8 quads + its scale (9 granules instead of 32 F32 values).
-            const float y = (float) sumf;
-            float a = fabsf(y);
-            a = fmaxf(a, dpp_f32<0x128>(a)); a = fmaxf(a, dpp_f32<0x124>(a)); a = fmaxf(a, dpp_f32<0x122>(a)); a = fmaxf(a, dpp_f32<0x121>(a));
-            a = fmaxf(a, __shfl_xor(a, 16, 32));
-            const float dsc = a / 127.f, id = a != 0.0f ? 127.f / a : 0.0f;
-            const unsigned q = (unsigned) (int) rintf(y * id) & 0xffu;
-            const unsigned w = q | (dpp_u32<0x101>(q) << 8) | (dpp_u32<0x102>(q) << 16) | (dpp_u32<0x103>(q) << 24);      // row_shl:1..3: the quad of lanes 4k..4k+3 in lane 4k
-            gu64 * eb = edge + (size_t) (2 * h + (tid >> 5)) * 9;
-            if ((tid & 3) == 0) gr_store(eb + ((tid & 31) >> 2), seq, w);
-            if ((tid & 31) == 0) gr_store(eb + 8, seq, __float_as_uint(h2f(f2h(dsc))));
-        } else {
-        const unsigned hv = (unsigned) f2h((float) sumf);
-        const unsigned hi = dpp_u32<0x101>(hv);          // row_shl:1: lane i reads lane i+1
-        if ((tid & 1) == 0) gr_store(edge + ((h * 64 + tid) >> 1), seq, (hv & 0xffffu) | (hi << 16));
-        }
+        mo_attn_publish<Q>((float) sumf, edge, h, seq, tid);
     }
 }
 
@@ -1285,11 +1066,11 @@ __device__ __forceinline__ void mg_attn_finish16(const float * part, const doubl
 template <bool Q = false>
 __device__ __forceinline__ void mg_role_self(mg_kargs A_, int idx_) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const mg_kargs A = mg_uniform(A_);
+    const mg_kargs A = mo_uniform(A_);
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int h = __builtin_amdgcn_readfirstlane(idx_);
-    mg_ctl c; c.status = (gu32 *) A->status; c.seq = A->seq; c.dead = false;
+    mo_ctl c; c.status = (gu32 *) A->status; c.seq = A->seq; c.dead = false;
     mg_chaos_start(c.seq);
 
     wa_f16 * Ks = (wa_f16 *) smem;                                  // [512][64]
@@ -1318,17 +1099,17 @@ __device__ __forceinline__ void mg_role_self(mg_kargs A_, int idx_) {
                 if (idx < n16) { *(u32x4 *) (Ks + (size_t) idx * 8) = tk[j]; *(u32x4 *) (Vs + (size_t) idx * 8) = tv[j]; }
             }
         }
-        mg_barrier();
+        wa_barrier_lds();
         if (wave == 0) {    // q | k | v of this head: three runs of 32 packed granules
             unsigned v[2];
-            const unsigned sp = mg_sweep<2>(mg_edge(A, l, E_QKV), [&](int k) {
+            const unsigned sp = mo_sweep<MO_POLL_OWN, 2>(mg_edge(A, l, E_QKV), [&](int k) {
                 if (k == 0) return (lane < 32 ? 0 : (d >> 1)) + h * 32 + (lane & 31);
                 return lane < 32 ? d + h * 32 + lane : -1; }, c, lane, v, 1000u + l);
             mg_trace(A, h == 0 && lane == 0, (l * 8 + 6) * 8 + 0, mg_now()); mg_trace(A, h == 0 && lane == 0, (l * 8 + 6) * 8 + 1, sp);
             if (lane < 32) { ((unsigned *) M.qs)[lane] = v[0]; ((unsigned *) (Vs + (size_t) kv_head * 64))[lane] = v[1]; }
             else ((unsigned *) (Ks + (size_t) kv_head * 64))[lane - 32] = v[0];
         }
-        mg_barrier();
+        wa_barrier_lds();
         // ---- scores: 4 lanes per key ----
         float lmax = -INFINITY;
         {
@@ -1338,7 +1119,7 @@ __device__ __forceinline__ void mg_role_self(mg_kargs A_, int idx_) {
             for (int c0 = 0; c0 < n_kv; c0 += MG_THREADS / 4) {
                 const int cc = c0 + kslot, cl = cc < n_kv ? cc : n_kv - 1;
                 const u32x4 ka = *(const u32x4 *) (Ks + (size_t) cl * 64 + 8 * a), kb = *(const u32x4 *) (Ks + (size_t) cl * 64 + 32 + 8 * a);
-                const float r = mg_score(ka, kb, qa, qb, 1.0f);
+                const float r = mo_score(ka, kb, qa, qb, 1.0f);
                 if (cc < n_kv) { if (a == 0) M.sc[cc] = r; lmax = fmaxf(lmax, r); }
             }
         }
@@ -1347,7 +1128,7 @@ __device__ __forceinline__ void mg_role_self(mg_kargs A_, int idx_) {
             // exp + the 8-lane group tree + F64 partial sums; every thread certifies the total and scales its own cell
             lmax = wave_max(lmax);
             if (lane == 0) M.red[wave] = lmax;
-            mg_barrier();
+            wa_barrier_lds();
             float mx = M.red[0];
 #pragma unroll
             for (int k = 1; k < MG_NW; ++k) mx = fmaxf(mx, M.red[k]);
@@ -1364,15 +1145,13 @@ __device__ __forceinline__ void mg_role_self(mg_kargs A_, int idx_) {
             }
             ps = wave_sum_d(ps);
             if (lane == 0) M.redd[wave] = ps;
-            mg_barrier();
+            wa_barrier_lds();
             const double tot = ((M.redd[0] + M.redd[1]) + (M.redd[2] + M.redd[3])) + ((M.redd[4] + M.redd[5]) + (M.redd[6] + M.redd[7]));
-            // (the reference adds the ng + (n % 8) addends one after the other in F64: error <= (ng + 7) u S; this sum is a tree of depth <= 16 over the SAME addends:
-            //  error <= 16 u S; together (ng + 8 + 16) u S - not twice the reference's bound, which sent twice as many soft-maxes back to the launch sequence)
-            const double delta = (double) (ng + 8 + 16) * 0x1p-53 * tot * 1.000001;
-            const float ilo = (float) (1.0 / (tot + delta)), ihi = (float) (1.0 / (tot - delta));
+            float ilo, ihi;
+            wa_softmax_bounds(tot, ng, ilo, ihi);
             if (ilo != ihi && tid == 0 && !c.dead) __hip_atomic_store(c.status, (unsigned) WA_MEGA_REDO, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             if (tid < n_kv) M.p16[tid] = f2h(e * ilo);
-            mg_barrier();
+            wa_barrier_lds();
         }
         mg_trace(A, h == 0 && tid == 0, (l * 8 + 6) * 8 + 5, mg_now());
         MG_CHAOS_ID(1000 + h, 21u, c.seq);
@@ -1389,12 +1168,12 @@ __device__ __forceinline__ void mg_role_self(mg_kargs A_, int idx_) {
 #pragma unroll
             for (int i = 0; i < 4; ++i) M.part[(r0 + i) * 64 + lane] = acc[i];
         }
-        mg_barrier();
+        wa_barrier_lds();
         // (the 8 KB behind cell WA_MEGA_KV_ROOM of the K and of the V copy are free: the host sends longer contexts through the launch sequence)
         mg_attn_finish<Q>(M.part, Vs + (size_t) np * 64, M.p16, np, n_kv - np, mg_edge(A, l, E_AO), h, c.seq, tid, (double *) (Ks + WA_MEGA_KV_ROOM * 64),
                           (double *) (Vs + WA_MEGA_KV_ROOM * 64), A, A->dbg && h == 0 && l == MG_WGTRACE_LAYER ? 3004 : -1);
         mg_trace(A, h == 0 && tid == 0, (l * 8 + 6) * 8 + 3, mg_now());
-        mg_barrier();
+        wa_barrier_lds();
     }
     unsigned pf[96];
     bool have_pf = false;
@@ -1441,7 +1220,7 @@ __device__ __forceinline__ void mg_role_self(mg_kargs A_, int idx_) {
 //
 // X1 (k_decode_mega_cq only): the ONE-EXCHANGE form.  The three exchanges above are store-to-load round trips that compute nothing
 // (0.64 + 1.00 + 1.28 us per layer); they exist because scores, soft-max and P V chains are all split by cells.  Here only the scores are:
-//   * K stays split by cells (mg_score unchanged); a quarter publishes each score as a granule at index = cell the moment it is computed
+//   * K stays split by cells (mo_score unchanged); a quarter publishes each score as a granule at index = cell the moment it is computed
 //     and all eight waves gather the other quarters' (<= 1128 granules), keeping the running maximum: every quarter holds all T scores;
 //   * every quarter runs the WHOLE soft-max identically: same maximum, same wa_expf / wa_expf_libm split at n8, ops.cpp's 8-lane group
 //     tree, the F64 total over the same addends (certificate below), the same WA_MEGA_REDO decision, all F16 probabilities in its own LDS;
@@ -1454,13 +1233,13 @@ template <bool Q = false, int CQ = -1, bool X1 = false>
 __device__ __forceinline__ void mg_role_cross(mg_kargs A_, int idx_) {
     static_assert(!X1 || (CQ >= 0 && !Q), "the one-exchange form is the F16 d = 768 kernel's");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const mg_kargs A = mg_uniform(A_);
+    const mg_kargs A = mo_uniform(A_);
     int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int H = A->n_head;
     const int ci = __builtin_amdgcn_readfirstlane(idx_);
     const int h = ci >> 2, w = ci & 3;
-    mg_ctl c; c.status = (gu32 *) A->status; c.seq = A->seq; c.dead = false;
+    mo_ctl c; c.status = (gu32 *) A->status; c.seq = A->seq; c.dead = false;
     mg_chaos_start(c.seq);
     const unsigned seq = c.seq;
 
@@ -1505,11 +1284,11 @@ __device__ __forceinline__ void mg_role_cross(mg_kargs A_, int idx_) {
         gu64 * X0 = (gu64 *) A->cross_gr + (size_t) h * MG_CGR + (X1 ? MG_CGR_XCC1 : MG_CGR_XCC);
         if (lane == 0) gr_store(X0 + w, seq, xcc);
         unsigned v[1];
-        mg_sweep<1>(X0, [&](int) { return lane < 4 ? lane : -1; }, c, lane, v, 2900u);
+        mo_sweep<MO_POLL_OWN, 1>(X0, [&](int) { return lane < 4 ? lane : -1; }, c, lane, v, 2900u);
         const bool same = lane >= 4 || v[0] == xcc;
         if (lane == 0) bc[2] = __builtin_amdgcn_ballot_w64(same) == ~0ull && !c.dead ? 1.0f : 0.0f;
     }
-    mg_barrier();
+    wa_barrier_lds();
     const bool local = bc[2] != 0.0f;
     const __attribute__((address_space(4))) wa_mega_layer * Ly = (const __attribute__((address_space(4))) wa_mega_layer *) A->layers;
     float  * xf    = (float *) (smem + MG_CX_XF);
@@ -1571,12 +1350,12 @@ __device__ __forceinline__ void mg_role_cross(mg_kargs A_, int idx_) {
         } else if (wave == 0) {
             unsigned v[1];
             mg_trace(A, ci == 0 && lane == 0, (l * 8 + 7) * 8 + 2, mg_now());
-            const unsigned sp = mg_sweep<1>(mg_edge(A, l, E_QC), [&](int) { return lane < 32 ? h * 32 + lane : -1; }, c, lane, v, 2000u + l);
+            const unsigned sp = mo_sweep<MO_POLL_OWN, 1>(mg_edge(A, l, E_QC), [&](int) { return lane < 32 ? h * 32 + lane : -1; }, c, lane, v, 2000u + l);
             mg_trace(A, ci == 0 && lane == 0, (l * 8 + 7) * 8 + 0, mg_now()); mg_trace(A, ci == 0 && lane == 0, (l * 8 + 7) * 8 + 1, sp);
             if (A->dbg && l == MG_WGTRACE_LAYER && w == 0) mg_trace(A, lane == 0, 3200 + h, mg_now());
             if (lane < 32) ((unsigned *) qs)[lane] = v[0];
         }
-        mg_barrier();
+        wa_barrier_lds();
 #define MG_CX(k) do { if (A->dbg && l == MG_WGTRACE_LAYER) mg_trace(A, ci == 0 && tid == 0, 3010 + (k), mg_now()); } while (0)
         if constexpr (X1) {
         MG_CX(0);
@@ -1590,7 +1369,7 @@ __device__ __forceinline__ void mg_role_cross(mg_kargs A_, int idx_) {
 #pragma unroll
             for (int p = 0; p < 3; ++p) {
                 const int o = p * 128 + ks, cc = 32 * (o >> 3) + 8 * w + (o & 7);
-                const float r = mg_score(ka[p], kb[p], qa, qb, kq_scale);
+                const float r = mo_score(ka[p], kb[p], qa, qb, kq_scale);
                 if (cc < T) {
                     if (a == 0) { gr_store_l(X + cc, seq, __float_as_uint(r), local); sc[cc] = r; }
                     lmax = fmaxf(lmax, r);
@@ -1603,7 +1382,7 @@ __device__ __forceinline__ void mg_role_cross(mg_kargs A_, int idx_) {
         {
             unsigned v[3];
             const auto other = [&](int k) { const int cg = tid + 512 * k; return cg < T && ((cg >> 3) & 3) != w ? cg : -1; };
-            mg_sweep<3>(X, other, c, lane, v, 2400u + l);
+            mo_sweep<MO_POLL_OWN, 3>(X, other, c, lane, v, 2400u + l);
 #pragma unroll
             for (int k = 0; k < 3; ++k) {
                 const int cg = other(k);
@@ -1613,7 +1392,7 @@ __device__ __forceinline__ void mg_role_cross(mg_kargs A_, int idx_) {
         lmax = wave_max(lmax);
         if (lane == 0) red[wave] = lmax;
         MG_CX(2);
-        mg_barrier();
+        wa_barrier_lds();
         MG_CX(3);
         mg_trace(A, ci == 0 && tid == 0, (l * 8 + 7) * 8 + 4, mg_now());
         MG_CHAOS_ID(2000 + ci, 34u, seq);
@@ -1638,16 +1417,14 @@ __device__ __forceinline__ void mg_role_cross(mg_kargs A_, int idx_) {
             if (lane == 0) redd[wave] = ps;
         }
         MG_CX(4);
-        mg_barrier();
+        wa_barrier_lds();
         mg_trace(A, ci == 0 && tid == 0, (l * 8 + 7) * 8 + 5, mg_now());
         {
             const double tot = ((redd[0] + redd[1]) + (redd[2] + redd[3])) + ((redd[4] + redd[5]) + (redd[6] + redd[7]));
-            // (the reference adds the ng + (n % 8) addends one after the other in F64: error <= (ng + 7) u S; this sum is a tree over the SAME
-            //  addends - <= 3 per thread in series (depth 2), wave_sum_d (6), the eight waves (3): depth 11 <= 16, error <= 16 u S; together
-            //  (ng + 8 + 16) u S as in the three-exchange form.  Every thread of every quarter forms the same total from the same values in
-            //  the same order, so all four take the same decision.)
-            const double delta = (double) (ng + 8 + 16) * 0x1p-53 * tot * 1.000001;
-            const float ilo = (float) (1.0 / (tot + delta)), ihi = (float) (1.0 / (tot - delta));
+            // (wa_softmax_bounds' tree here: <= 3 addends per thread in series (depth 2), wave_sum_d (6), the eight waves (3): depth 11 <= 16.
+            //  Every thread of every quarter forms the same total from the same values in the same order, so all four take the same decision.)
+            float ilo, ihi;
+            wa_softmax_bounds(tot, ng, ilo, ihi);
             if (ilo != ihi && tid == 0 && !c.dead) __hip_atomic_store(c.status, (unsigned) WA_MEGA_REDO, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 #pragma unroll
             for (int k = 0; k < 3; ++k) {
@@ -1660,7 +1437,7 @@ __device__ __forceinline__ void mg_role_cross(mg_kargs A_, int idx_) {
             }
         }
         MG_CX(5);
-        mg_barrier();
+        wa_barrier_lds();
         MG_CX(6);
         MG_CHAOS_ID(2000 + ci, 32u, seq);
         // ---- P V: thread = (chain r = tid / 16, own output j = tid % 16); then the leftover cell r's product for output j (vec.cpp:221-223) ----
@@ -1682,7 +1459,7 @@ __device__ __forceinline__ void mg_role_cross(mg_kargs A_, int idx_) {
             dbl[tid] = (double) (r < nlo ? pr : -0.0f);
         }
         mg_trace(A, ci == 0 && tid == 0, (l * 8 + 7) * 8 + 6, mg_now());
-        mg_barrier();
+        wa_barrier_lds();
         mg_trace(A, ci == 0 && tid == 0, (l * 8 + 7) * 8 + 7, mg_now());
         mg_attn_finish16(part, dbl, mg_edge(A, l, E_AO2), 64 * h + 16 * w, seq, tid, A, A->dbg && ci == 0 && l == MG_WGTRACE_LAYER ? 3000 : -1);
         mg_trace(A, ci == 0 && tid == 0, (l * 8 + 7) * 8 + 3, mg_now());
@@ -1699,14 +1476,14 @@ __device__ __forceinline__ void mg_role_cross(mg_kargs A_, int idx_) {
 #pragma unroll
             for (int p = 0; p < 3; ++p) {
                 const int o = p * 128 + ks, cc = 32 * (o >> 3) + 8 * w + (o & 7);
-                const float r = mg_score(ka[p], kb[p], qa, qb, kq_scale);
+                const float r = mo_score(ka[p], kb[p], qa, qb, kq_scale);
                 if (cc < T) { if (a == 0) sc[o] = r; lmax = fmaxf(lmax, r); }
             }
         }
         lmax = wave_max(lmax);
         if (lane == 0) red[wave] = lmax;
         MG_CX(1);
-        mg_barrier();
+        wa_barrier_lds();
         MG_CX(2);
         if (wave == 0) {        // (1) maxima of the four workgroups
             float m = red[0];
@@ -1714,13 +1491,13 @@ __device__ __forceinline__ void mg_role_cross(mg_kargs A_, int idx_) {
             for (int k = 1; k < MG_NW; ++k) m = fmaxf(m, red[k]);
             if (lane == 0) gr_store_l(X + MG_CGR_MAX + w, seq, __float_as_uint(m), local);
             unsigned v[1];
-            mg_sweep<1>(X + MG_CGR_MAX, [&](int) { return lane < 4 ? lane : -1; }, c, lane, v, 2100u + l);
+            mo_sweep<MO_POLL_OWN, 1>(X + MG_CGR_MAX, [&](int) { return lane < 4 ? lane : -1; }, c, lane, v, 2100u + l);
             float g = lane < 4 ? __uint_as_float(v[0]) : -INFINITY;
             g = fmaxf(g, dpp_f32<0x4e>(g)); g = fmaxf(g, dpp_f32<0xb1>(g));      // max over lanes 0..3
             if (lane == 0) bc[0] = g;
             MG_CX(3);
         }
-        mg_barrier();
+        wa_barrier_lds();
         mg_trace(A, ci == 0 && tid == 0, (l * 8 + 7) * 8 + 4, mg_now());
         const float mx = bc[0];
         // ---- exp, group sums (8-lane tree = ops.cpp's), F64 partial sum: thread = one own cell (ops.cpp:4792-4818, vec.cpp:257-308) ----
@@ -1740,28 +1517,26 @@ __device__ __forceinline__ void mg_role_cross(mg_kargs A_, int idx_) {
             if (lane == 0) redd[wave] = ps;
         }
         MG_CX(4);
-        mg_barrier();
+        wa_barrier_lds();
         if (wave == 0) {        // (2) partial sums -> total, certified
             const double ps = ((redd[0] + redd[1]) + (redd[2] + redd[3])) + ((redd[4] + redd[5]) + (redd[6] + redd[7]));
             const u64 pb = (u64) __double_as_longlong(ps);
             if (lane == 0) { gr_store_l(X + MG_CGR_SUM + 2 * w, seq, (unsigned) pb, local); gr_store_l(X + MG_CGR_SUM + 2 * w + 1, seq, (unsigned) (pb >> 32), local); }
             unsigned v[1];
-            mg_sweep<1>(X + MG_CGR_SUM, [&](int) { return lane < 8 ? lane : -1; }, c, lane, v, 2200u + l);
+            mo_sweep<MO_POLL_OWN, 1>(X + MG_CGR_SUM, [&](int) { return lane < 8 ? lane : -1; }, c, lane, v, 2200u + l);
             double tot = 0.0;
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 const unsigned lo = __builtin_amdgcn_readlane(v[0], 2 * k), hi = __builtin_amdgcn_readlane(v[0], 2 * k + 1);
                 tot += __longlong_as_double((long long) (((u64) hi << 32) | lo));
             }
-            // (the reference adds the ng + (n % 8) addends one after the other in F64: error <= (ng + 7) u S; this sum is a tree of depth <= 16 over the SAME addends:
-            //  error <= 16 u S; together (ng + 8 + 16) u S - not twice the reference's bound, which sent twice as many soft-maxes back to the launch sequence)
-            const double delta = (double) (ng + 8 + 16) * 0x1p-53 * tot * 1.000001;
-            const float ilo = (float) (1.0 / (tot + delta)), ihi = (float) (1.0 / (tot - delta));
+            float ilo, ihi;
+            wa_softmax_bounds(tot, ng, ilo, ihi);
             if (ilo != ihi && lane == 0 && !c.dead) __hip_atomic_store(c.status, (unsigned) WA_MEGA_REDO, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             if (lane == 0) bc[1] = ilo;
             MG_CX(5);
         }
-        mg_barrier();
+        wa_barrier_lds();
         mg_trace(A, ci == 0 && tid == 0, (l * 8 + 7) * 8 + 5, mg_now());
         const float inv = bc[1];
         if (tid < 8 * MG_CSTEPS) {
@@ -1772,7 +1547,7 @@ __device__ __forceinline__ void mg_role_cross(mg_kargs A_, int idx_) {
                 if (cc >= np) { if (w == 0) pleft[cc - np] = ph; else gr_store_l(X + MG_CGR_PART + (w - 1) * 576 + 512 + (tid & 7), seq, (unsigned) ph, local); }
             }
         }
-        mg_barrier();
+        wa_barrier_lds();
         MG_CX(6);
         MG_CHAOS_ID(2000 + ci, 32u, seq);
         // ---- P V: wave = own chain (cells 32 s + 8 w + wave), lane = d_head index ----
@@ -1792,12 +1567,12 @@ __device__ __forceinline__ void mg_role_cross(mg_kargs A_, int idx_) {
                 const int ww = (wave - 1) >> 1, half = (wave - 1) & 1;       // source workgroup ww + 1, rows [4 half, 4 half + 4) of its 8 chains
                 gu64 * src = X + MG_CGR_PART + ww * 576;
                 unsigned v[5];
-                mg_sweep<5>(src, [&](int k) { return k < 4 ? half * 256 + 64 * k + lane : (half == 0 && lane < 8 && 8 * (ww + 1) + lane < nl ? 512 + lane : -1); }, c, lane, v, 2300u + l);
+                mo_sweep<MO_POLL_OWN, 5>(src, [&](int k) { return k < 4 ? half * 256 + 64 * k + lane : (half == 0 && lane < 8 && 8 * (ww + 1) + lane < nl ? 512 + lane : -1); }, c, lane, v, 2300u + l);
 #pragma unroll
                 for (int k = 0; k < 4; ++k) part[(8 * (ww + 1) + 4 * half + k) * 64 + lane] = __uint_as_float(v[k]);
                 if (half == 0 && lane < 8) { const int cc = 8 * (ww + 1) + lane; if (cc < nl) pleft[cc] = (wa_f16) v[4]; }
             }
-            mg_barrier();
+            wa_barrier_lds();
             mg_trace(A, ci == 0 && tid == 0, (l * 8 + 7) * 8 + 7, mg_now());
             mg_attn_finish<Q>(part, vleft, pleft - np, np, nl, mg_edge(A, l, E_AO2), h, seq, tid, (double *) (smem + 16384), (double *) (smem + 24576), A,
                               A->dbg && ci == 0 && l == MG_WGTRACE_LAYER ? 3000 : -1);
@@ -1805,7 +1580,7 @@ __device__ __forceinline__ void mg_role_cross(mg_kargs A_, int idx_) {
             if (A->dbg && l == MG_WGTRACE_LAYER) mg_trace(A, tid == 0, 3100 + h, mg_now());
         }
         }
-        mg_barrier();
+        wa_barrier_lds();
     }
     unsigned pf[96];
     bool have_pf = false;
@@ -1862,7 +1637,7 @@ bool wa_launch_decode_mega(hipStream_t s, const wa_mega_args & a, int n_wg) {
             hipFuncSetAttribute((const void *) k_decode_mega_q, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds) != hipSuccess) return false;
         attr_set[dev & 63] = true;
     }
-    if (MG_DEFER && !a.quant && a.d == 768) return wa_launch_decode_mega_cq(s, a, n_wg, lds);
+    if (!a.quant && a.d == 768) return wa_launch_decode_mega_cq(s, a, n_wg, lds);
     if (a.quant) hipLaunchKernelGGL(k_decode_mega_q, dim3(n_wg), dim3(MG_THREADS), lds, s, a);
     else         hipLaunchKernelGGL(k_decode_mega, dim3(n_wg), dim3(MG_THREADS), lds, s, a);
     return hipGetLastError() == hipSuccess;

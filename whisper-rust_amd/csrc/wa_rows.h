@@ -30,8 +30,8 @@ struct wa_rows_row {                 // where ONE token row's state lives (layer
     // the launch leaves per-workgroup candidate records of the row's logits under the reference's logit rules (approximated: the host verifies
     // every token); with spec != 0 the row's token is picked from the records and state its previous pass left, not taken from `token`.
     int spec;
-    const unsigned * rec_in; unsigned * rec_out;      // [n_workgroups][8]: {max text logit, id, max timestamp logit, id, sum exp(ts - max ts)}
-    const int * ps_in; int * ps_out;                  // {last token, token before it (-1: none), seek_delta, has_ts}; ps_out[4] = the token this launch decoded
+    const unsigned * rec_in; unsigned * rec_out;      // [n_workgroups][8]: {max text logit, id, max timestamp logit, id, sum exp(ts - max ts)} (wa_one_launch_dev.h: MO_REC_*)
+    const int * ps_in; int * ps_out;                  // {last token, token before it (-1: none), seek_delta, has_ts}; ps_out[4] = the token this launch decoded (MO_PS_*)
     const unsigned * smask;                           // bit i set: token i is suppressed for the row's whole call; null: no records
     int s_last, s_penult, s_seek_delta, s_has_ts;     // spec == 0: the state after `token`, from the host
 };

@@ -7,52 +7,24 @@
 // then the final LayerNorm and the logits rows.  A product phase = [gather or LayerNorm into LDS] -> barrier -> products; the weight
 // chunk of a phase was requested by wave 7 at the barrier of the phase before (LDS-DMA into the other slot) and is waited for by wave 7
 // alone, right before the barrier that starts the products.
-#include "wa_device.h"
+#include "wa_one_launch_dev.h"
 #include "wa_rows.h"
 #include <algorithm>
 
-typedef unsigned long long u64;
-#define GAS __attribute__((address_space(1)))
 #define LAS __attribute__((address_space(3)))
-typedef GAS u64 gu64;
-typedef GAS unsigned gu32;
-typedef const GAS wa_f16 * gch;
-typedef const GAS float * gcf;
-typedef _Float16 half4v __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
 typedef const __attribute__((address_space(4))) wa_rows_args * mb_kargs;
 typedef const __attribute__((address_space(4))) wa_mega_layer * mb_layers;
-__device__ __forceinline__ mb_kargs mb_uniform(mb_kargs p) {
-    const unsigned long long v = (unsigned long long) p;
-    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned) v), hi = __builtin_amdgcn_readfirstlane((unsigned) (v >> 32));
-    return (mb_kargs) (((unsigned long long) hi << 32) | lo);
-}
 
 #define MB_THREADS 512
 #define MB_NW 8
 #define MB_NCW 7                  // waves that compute products; wave 7 streams the weights
-#define MB_SPIN_LIMIT 20000u      // polls (~0.5 us each, ~10 ms) before a hand-off is declared dead (the host pauses the form and tries again later)
 #define MB_TRACE_LAYER 5
 #define MB_PAD 64                 // bytes behind every weight row in LDS: consecutive rows start 16 banks apart
 
-enum { E_QKV = 0, E_AO, E_X1, E_QC, E_AO2, E_X2, E_HF, E_X3 };
-
-struct mb_ctl { gu32 * status; unsigned seq; bool dead; };
-
-__device__ __forceinline__ void gr_store(gu64 * g, unsigned seq, unsigned v) {
-    __hip_atomic_store(g, ((u64) seq << 32) | (u64) v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ u64 gr_load(gu64 * g) { return __hip_atomic_load(g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-template <int CTRL>
-__device__ __forceinline__ unsigned dpp_u32(unsigned v) { return (unsigned) __builtin_amdgcn_update_dpp(0, (int) v, CTRL, 0xf, 0xf, true); }
-
-__device__ __forceinline__ void mb_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 // the barrier in front of a product phase: wave 7's LDS-DMA of this phase's weights has landed
 __device__ __forceinline__ void mb_barrier_w(int wave) {
     if (wave == MB_NW - 1) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    mb_barrier();
+    wa_barrier_lds();
 }
 
 // optional timeline (tools/rows_trace.py): 100 MHz wall-clock ticks of one workgroup, 32 stamps per layer
@@ -60,16 +32,10 @@ __device__ __forceinline__ void mb_trace(mb_kargs A, bool who, int slot) {
     if (A->dbg && who) ((GAS unsigned *) A->dbg)[slot] = (unsigned) wall_clock64();
 }
 
-// MB_CHAOS (the test build, libwhisper_chaos.so): waves and whole workgroups stall at random for ~25 us in front of products, units and gathers,
-// so that the rest of the workgroup - and of the grid - runs far ahead of them.  Results must not change.
-#ifdef MB_CHAOS
-__device__ __forceinline__ void mb_chaos(unsigned a, unsigned b, unsigned c_, unsigned phase, unsigned seq) {
-    unsigned h = (a * 2654435761u) ^ (b * 40503u) ^ (c_ * 2246822519u) ^ (phase * 3266489917u) ^ (seq * 668265263u);
-    h ^= h >> 15; h *= 2246822519u; h ^= h >> 13;
-    if ((h & 7u) == 0u) for (int i = 0; i < 8; ++i) __builtin_amdgcn_s_sleep(127);
-}
-#define MB_CHAOS_AT(phase) mb_chaos((unsigned) blockIdx.x, (unsigned) (threadIdx.x >> 6), (unsigned) l, (phase), seq)
-#define MB_CHAOS_WG(phase) mb_chaos((unsigned) blockIdx.x, 99u, (unsigned) l, (phase), seq)
+// (test build, WA_CHAOS) waves and whole workgroups stall at random in front of products, units and gathers
+#ifdef WA_CHAOS
+#define MB_CHAOS_AT(phase) mo_chaos((unsigned) blockIdx.x, (unsigned) (threadIdx.x >> 6), (unsigned) l, (phase), seq)
+#define MB_CHAOS_WG(phase) mo_chaos((unsigned) blockIdx.x, 99u, (unsigned) l, (phase), seq)
 #else
 #define MB_CHAOS_AT(phase) do { } while (0)
 #define MB_CHAOS_WG(phase) do { } while (0)
@@ -79,38 +45,14 @@ __device__ __forceinline__ gu64 * mb_edge(mb_kargs A, int layer, int e) {
     return (gu64 *) A->granules + ((size_t) layer * WA_MEGA_EDGES + e) * ((size_t) A->B * A->row_gr);
 }
 
-// One wave polls the granules idx(0..NPL-1) (idx < 0: none) until every tag equals this launch's sequence number (as wa_mega.hip: mg_sweep).
-template <int NPL, typename F>
-__device__ __forceinline__ void mb_sweep(gu64 * g, F idx, mb_ctl & c, int lane, unsigned (&v)[NPL], unsigned code) {
-    for (unsigned spins = 0;; ++spins) {
-        bool ok = true;
-#pragma unroll
-        for (int k = 0; k < NPL; ++k) {      // unconditional loads (a lane without a granule reads granule 0): predicated ones are issued one round trip at a time
-            const int i = idx(k);
-            const u64 x = gr_load(g + (i >= 0 ? i : 0)); v[k] = (unsigned) x; ok &= i < 0 || (unsigned) (x >> 32) == c.seq;
-        }
-        if (__all(ok) || c.dead) return;
-        if ((spins & 127u) == 127u) {
-            const unsigned st = __builtin_amdgcn_readfirstlane(__hip_atomic_load(c.status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-            if (st != 0u) { c.dead = true; return; }
-            if (spins >= MB_SPIN_LIMIT) {
-                if (lane == 0) __hip_atomic_store(c.status, code, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                c.dead = true;
-                return;
-            }
-        }
-        __builtin_amdgcn_s_sleep(1);
-    }
-}
-
 // all 512 threads: `per_row` granules of each of B token rows of `edge` (row b's run starts at b * row_gr), eight per thread and round,
 // handed to store(b, j, value) once valid
 template <int NPL, typename ST>
-__device__ __forceinline__ void mb_gather(mb_ctl & c, gu64 * edge, int B, int per_row, int row_gr, int tid, int lane, ST store, unsigned code) {
+__device__ __forceinline__ void mb_gather(mo_ctl & c, gu64 * edge, int B, int per_row, int row_gr, int tid, int lane, ST store, unsigned code) {
     const int total = B * per_row;
     for (int base = 0; base < total; base += MB_THREADS * NPL) {
         unsigned v[NPL];
-        mb_sweep<NPL>(edge, [&](int k) { const int i = base + tid + MB_THREADS * k; if (i >= total) return -1; const int b = i / per_row; return b * row_gr + (i - b * per_row); },
+        mo_sweep<MO_POLL_ALL, NPL>(edge, [&](int k) { const int i = base + tid + MB_THREADS * k; if (i >= total) return -1; const int b = i / per_row; return b * row_gr + (i - b * per_row); },
                     c, lane, v, code);
 #pragma unroll
         for (int k = 0; k < NPL; ++k) { const int i = base + tid + MB_THREADS * k; if (i < total) { const int b = i / per_row; store(b, i - b * per_row, v[k]); } }
@@ -227,21 +169,9 @@ __device__ __forceinline__ void mb_dot16(const unsigned char * wrow, const wa_f1
 // -------------------------------------------------------------------------------------------------
 typedef int   mq_i4 __attribute__((ext_vector_type(4)));
 typedef float mq_f4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ int mq_ld(int nb) { return nb | 8; }                                   // words between the quad rows u of an operand row
 __host__ __device__ __forceinline__ size_t mq_row_bytes(int nb) { return (size_t) 32 * (nb | 8) + (size_t) 4 * nb; }
 __device__ __forceinline__ unsigned * mq_quads(unsigned char * op, int nb, int u) { return (unsigned *) op + u * mq_ld(nb); }
 __device__ __forceinline__ float * mq_scales(unsigned char * op, int nb) { return (float *) (op + (size_t) 32 * mq_ld(nb)); }
-// quantize_row_q8_0 (arch/x86/quants.c) of a 32-element block held one value per lane of a half-wave (as wa_q8_store): the quad of lanes
-// 4k..4k+3 packed over DPP into lane 4k; returns the block's scale (rounded through F16).  All lanes take part.
-__device__ __forceinline__ unsigned mq_quant32(float y, float & dq) {
-    float a = fabsf(y);
-    a = fmaxf(a, dpp_f32<0x128>(a)); a = fmaxf(a, dpp_f32<0x124>(a)); a = fmaxf(a, dpp_f32<0x122>(a)); a = fmaxf(a, dpp_f32<0x121>(a));
-    a = fmaxf(a, __shfl_xor(a, 16, 32));
-    const float id = a != 0.0f ? 127.f / a : 0.0f;
-    dq = h2f(f2h(a / 127.f));
-    const unsigned q = (unsigned) (int) rintf(y * id) & 0xffu;
-    return q | (dpp_u32<0x101>(q) << 8) | (dpp_u32<0x102>(q) << 16) | (dpp_u32<0x103>(q) << 24);      // row_shl:1..3
-}
 template <int BC>
 __device__ __forceinline__ void mb_dotq8(const unsigned char * wq, const unsigned char * wd, const unsigned char * xop, size_t op_bytes, int u, int nb,
                                          int b0, int B, float (&res)[BC]) {
@@ -317,7 +247,7 @@ __device__ __forceinline__ double mb_seq_sum(const float (&xv)[NP], int d, bool 
     return t;
 }
 template <int NP, bool Q = false>         // Q: the normalised row leaves as Q8_0 (the next product's operand), not as F16
-__device__ __forceinline__ void mb_ln_row(mb_kargs A, mb_ctl & c, gu64 * edge_row /* null: embeddings */, const float * lnp /* LDS: gamma | beta, each d floats in whole KB */, const float * gw_g, const float * gb_g /* global, when non-null */,
+__device__ __forceinline__ void mb_ln_row(mb_kargs A, mo_ctl & c, gu64 * edge_row /* null: embeddings */, const float * lnp /* LDS: gamma | beta, each d floats in whole KB */, const float * gw_g, const float * gb_g /* global, when non-null */,
                                           int b, int lane_, wa_f16 * dst, float * xres_b, int row_d, int r_d, unsigned code, int token = 0, bool tw = false, int tslot = 0) {
     // (nothing derived from the lane index may live across calls: hoisted out of the layer loop the per-element LDS addresses went to scratch, and every
     //  reload waits for the vector-memory queue)
@@ -327,7 +257,7 @@ __device__ __forceinline__ void mb_ln_row(mb_kargs A, mb_ctl & c, gu64 * edge_ro
     float xv[NP];
     if (edge_row) {
         unsigned v[NP];
-        mb_sweep<NP>(edge_row, [&](int k) { const int i = lane + 64 * k; return i < d ? i : -1; }, c, lane, v, code);
+        mo_sweep<MO_POLL_ALL, NP>(edge_row, [&](int k) { const int i = lane + 64 * k; return i < d ? i : -1; }, c, lane, v, code);
 #pragma unroll
         for (int k = 0; k < NP; ++k) xv[k] = (lane + 64 * k < d) ? __uint_as_float(v[k]) : 0.0f;
     } else {                    // k_dec_embed: token embedding + positional embedding
@@ -445,22 +375,8 @@ __device__ __forceinline__ unsigned mb_pack_h2(unsigned h) { return (h & 0xffffu
 // -------------------------------------------------------------------------------------------------
 #define MB_ATT_BYTES 34816          /* self-attention unit: 28160; cross-attention unit: 17408 + 2 x 8192 of F64 for its finish */
 
-__device__ __forceinline__ float mb_score(const u32x4 & ka, const u32x4 & kb, const float (&qa)[8], const float (&qb)[8], float scale) {
-    const wa_f16 * k8a = (const wa_f16 *) &ka, * k8b = (const wa_f16 *) &kb;
-    float v[8];
-#pragma unroll
-    for (int l = 0; l < 8; ++l) {
-        float t = fmaf(h2f(k8a[l]), qa[l], 0.0f);
-        t = fmaf(h2f(k8b[l]), qb[l], t);
-        t = t + dpp_f32<0x4e>(t);                // quad_perm [2,3,0,1]: s[j] + s[j+2]
-        v[l] = t + dpp_f32<0xb1>(t);             // quad_perm [1,0,3,2]: (s0+s2) + (s1+s3)
-    }
-    const float t0 = v[0] + v[4], t1 = v[1] + v[5], t2 = v[2] + v[6], t3 = v[3] + v[7];
-    return ((t0 + t1) + (t2 + t3)) * scale;
-}
-
-// the head's 64 outputs from the 32 chain sums + the leftover cells in F64, index order (vec.cpp:221-223), by threads 0..63; published packed.
-// Q: the 64 outputs are two Q8_0 blocks of the out-projection's operand: quantised HERE, once (8 quads + the scale = 9 granules per block).
+// the head's 64 outputs from the 32 chain sums + the leftover cells in F64, index order (vec.cpp:221-223), by threads 0..63; published packed
+// (Q: as two Q8_0 blocks)
 template <bool Q = false>
 __device__ __forceinline__ void mb_attn_finish(const float * part, const wa_f16 * vleft /* [nl][64] LDS */, const wa_f16 * pleft /* [nl] */, int nl,
                                                gu64 * edge_row, int h, unsigned seq, int tid) {
@@ -470,17 +386,7 @@ __device__ __forceinline__ void mb_attn_finish(const float * part, const wa_f16 
         for (int r = 0; r < 32; ++r) s32[r] = part[r * 64 + tid];
         double sumf = (double) wa_tree32(s32);
         for (int cc = 0; cc < nl; ++cc) sumf += (double) (h2f(vleft[cc * 64 + tid]) * h2f(pleft[cc]));
-        if constexpr (Q) {
-            float dq;
-            const unsigned w = mq_quant32((float) sumf, dq);
-            gu64 * eb = edge_row + (size_t) (2 * h + (tid >> 5)) * 9;
-            if ((tid & 3) == 0) gr_store(eb + ((tid & 31) >> 2), seq, w);
-            if ((tid & 31) == 0) gr_store(eb + 8, seq, __float_as_uint(dq));
-        } else {
-            const unsigned hv = (unsigned) f2h((float) sumf);
-            const unsigned hi = dpp_u32<0x101>(hv);          // row_shl:1: lane i reads lane i + 1
-            if ((tid & 1) == 0) gr_store(edge_row + ((h * 64 + tid) >> 1), seq, (hv & 0xffffu) | (hi << 16));
-        }
+        mo_attn_publish<Q>((float) sumf, edge_row, h, seq, tid);
     }
 }
 
@@ -490,7 +396,7 @@ __device__ __forceinline__ void mb_attn_finish(const float * part, const wa_f16 
 // its cache (earlier tokens of a small batch; other beams, which the mask hides) - arrive as granules, like the query.
 // -------------------------------------------------------------------------------------------------
 template <bool Q = false>
-__device__ __forceinline__ void mb_unit_self(mb_kargs A, mb_ctl & c, unsigned char * area, int l, int b, int h, int tid, bool tw = false) {
+__device__ __forceinline__ void mb_unit_self(mb_kargs A, mo_ctl & c, unsigned char * area, int l, int b, int h, int tid, bool tw = false) {
 #define MB_TS(k) mb_trace(A, tw, 4096 + l * 16 + (k))
     MB_TS(0);
     const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -535,7 +441,7 @@ __device__ __forceinline__ void mb_unit_self(mb_kargs A, mb_ctl & c, unsigned ch
         if (same) {
             unsigned v[2];
             gu64 * e = mb_edge(A, l, E_QKV) + (size_t) wave * A->row_gr;
-            mb_sweep<2>(e, [&](int k) {
+            mo_sweep<MO_POLL_ALL, 2>(e, [&](int k) {
                 if (k == 0) return (lane < 32 ? (d >> 1) : d) + h * 32 + (lane & 31);
                 return wave == b && lane < 32 ? h * 32 + lane : -1; }, c, lane, v, 1000u + l);
             if (lane < 32) ((unsigned *) (knew + wave * 64))[lane] = v[0]; else ((unsigned *) (vnew + wave * 64))[lane - 32] = v[0];
@@ -544,7 +450,7 @@ __device__ __forceinline__ void mb_unit_self(mb_kargs A, mb_ctl & c, unsigned ch
         if (lane == 0) ncl[wave] = same && A->rows[wave].kv_head < n_kv ? A->rows[wave].kv_head : -1;
     } else if (lane == 0) ncl[wave] = -1;
     MB_TS(1);
-    mb_barrier();
+    wa_barrier_lds();
     MB_TS(2);
     int nc[8];
 #pragma unroll
@@ -577,7 +483,7 @@ __device__ __forceinline__ void mb_unit_self(mb_kargs A, mb_ctl & c, unsigned ch
             for (int p = 0; p < 4; ++p) {
                 if (c0 + p * (MB_THREADS / 4) >= n_kv) break;       // (uniform: a block of 128 cells behind the row's last one - with 110 cells three of the four)
                 const int cc = c0 + p * (MB_THREADS / 4) + kslot;
-                float r = mb_score(ka[p], kb[p], qa, qb, 1.0f);
+                float r = mo_score(ka[p], kb[p], qa, qb, 1.0f);
                 if (cc < n_kv && new_of(cc) < 0) {       // (a cell written by this launch: below, from its granules)
                     if (mk[p]) r = -INFINITY;
                     if (a == 0) sc[cc] = r;
@@ -589,7 +495,7 @@ __device__ __forceinline__ void mb_unit_self(mb_kargs A, mb_ctl & c, unsigned ch
             const int j = tid >> 2, cc = nc[0] * (j == 0) + nc[1] * (j == 1) + nc[2] * (j == 2) + nc[3] * (j == 3) + nc[4] * (j == 4) + nc[5] * (j == 5) + nc[6] * (j == 6) + nc[7] * (j == 7);
             const bool act = cc >= 0 && new_of(cc) == j;
             const u32x4 kna = *(const u32x4 *) (knew + j * 64 + 8 * a), knb = *(const u32x4 *) (knew + j * 64 + 32 + 8 * a);
-            float r = mb_score(kna, knb, qa, qb, 1.0f);
+            float r = mo_score(kna, knb, qa, qb, 1.0f);
             if (act) {
                 if (mrow && mrow[cc]) r = -INFINITY;
                 if (a == 0) sc[cc] = r;
@@ -600,7 +506,7 @@ __device__ __forceinline__ void mb_unit_self(mb_kargs A, mb_ctl & c, unsigned ch
     lmax = wave_max(lmax);
     if (lane == 0) red[wave] = lmax;
     MB_TS(3);
-    mb_barrier();
+    wa_barrier_lds();
     MB_TS(4);
     float mx = red[0];
 #pragma unroll
@@ -626,12 +532,10 @@ __device__ __forceinline__ void mb_unit_self(mb_kargs A, mb_ctl & c, unsigned ch
         }
         ps = wave_sum_d(ps);
         if (lane == 0) redd[wave] = ps;
-        mb_barrier();
+        wa_barrier_lds();
         const double sum = ((redd[0] + redd[1]) + (redd[2] + redd[3])) + ((redd[4] + redd[5]) + (redd[6] + redd[7]));
-        // (the reference adds the ng + (n % 8) addends one after the other in F64: error <= (ng + 7) u S; this sum is a tree of depth <= 16 over the SAME addends:
-        //  error <= 16 u S; together (ng + 8 + 16) u S - not twice the reference's bound, which sent twice as many soft-maxes back to the launch sequence)
-        const double delta = (double) (ng + 8 + 16) * 0x1p-53 * sum * 1.000001;
-        const float ilo = (float) (1.0 / (sum + delta)), ihi = (float) (1.0 / (sum - delta));
+        float ilo, ihi;
+        wa_softmax_bounds(sum, ng, ilo, ihi);
         inv = ilo;
         if (ilo != ihi) {       // (~1e-9 per soft-max; the same for every thread) the reference's order, by one thread
             if (tid == 0) {
@@ -640,7 +544,7 @@ __device__ __forceinline__ void mb_unit_self(mb_kargs A, mb_ctl & c, unsigned ch
                 for (int cc = n8; cc < n_kv; ++cc) so += (double) sc[cc];
                 *s_inv = (float) (1.0 / so);
             }
-            mb_barrier();
+            wa_barrier_lds();
             inv = *s_inv;
         }
     }
@@ -654,7 +558,7 @@ __device__ __forceinline__ void mb_unit_self(mb_kargs A, mb_ctl & c, unsigned ch
             *(u32x4 *) (vleft + (size_t) tid * 8) = j >= 0 ? *(const u32x4 *) (vnew + j * 64 + (tid & 7) * 8) : *(const GAS u32x4 *) (vp + (size_t) cc * d + (tid & 7) * 8);
         }
     }
-    mb_barrier();
+    wa_barrier_lds();
     MB_TS(6);
     // ---- P V: chains r = cell mod 32 (4 per wave), lane = d_head index ----
     {
@@ -682,10 +586,10 @@ __device__ __forceinline__ void mb_unit_self(mb_kargs A, mb_ctl & c, unsigned ch
         for (int i = 0; i < 4; ++i) part[(r0 + i) * 64 + lane] = acc[i];
     }
     MB_TS(7);
-    mb_barrier();
+    wa_barrier_lds();
     mb_attn_finish<Q>(part, vleft, p16 + np, nl, mb_edge(A, l, E_AO) + (size_t) b * A->row_gr, h, c.seq, tid);
     MB_TS(8);
-    mb_barrier();
+    wa_barrier_lds();
     MB_TS(9);
 #undef MB_TS
 }
@@ -726,7 +630,7 @@ __device__ __forceinline__ void mb_cross_load(mb_kargs A, int l, int b, int h, i
 }
 
 template <bool Q, int P>
-__device__ __forceinline__ void mb_unit_cross(mb_kargs A, mb_ctl & c, unsigned char * area, int l, int b, int h, int w, int tid, bool tw, const mb_cross_regs<P> & R) {
+__device__ __forceinline__ void mb_unit_cross(mb_kargs A, mo_ctl & c, unsigned char * area, int l, int b, int h, int w, int tid, bool tw, const mb_cross_regs<P> & R) {
     constexpr int NCH = 32 / P, CPW = 4 / P, NK = NCH * MB_CSTEPS;          // chains of this part, chains per wave, local cell slots
     const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const unsigned seq = c.seq;
@@ -756,11 +660,11 @@ __device__ __forceinline__ void mb_unit_cross(mb_kargs A, mb_ctl & c, unsigned c
     }
     if (wave == 0) {
         unsigned v[1];
-        mb_sweep<1>(mb_edge(A, l, E_QC) + (size_t) b * A->row_gr, [&](int) { return lane < 32 ? h * 32 + lane : -1; }, c, lane, v, 2000u + l);
+        mo_sweep<MO_POLL_ALL, 1>(mb_edge(A, l, E_QC) + (size_t) b * A->row_gr, [&](int) { return lane < 32 ? h * 32 + lane : -1; }, c, lane, v, 2000u + l);
         if (lane < 32) ((unsigned *) qs)[lane] = v[0];
         MB_TC(1);
     }
-    mb_barrier();
+    wa_barrier_lds();
     MB_TC(2);
     // ---- scores of the own cells ----
     float lmax = -INFINITY;
@@ -771,26 +675,26 @@ __device__ __forceinline__ void mb_unit_cross(mb_kargs A, mb_ctl & c, unsigned c
 #pragma unroll
         for (int p = 0; p < 12 / P; ++p) {
             const int o = p * 128 + ks, cc = 32 * (o / NCH) + NCH * w + (o % NCH);
-            const float r = mb_score(R.ka[p], R.kb[p], qa, qb, kq_scale);
+            const float r = mo_score(R.ka[p], R.kb[p], qa, qb, kq_scale);
             if (cc < T) { if (a == 0) sc[o] = r; lmax = fmaxf(lmax, r); }
         }
     }
     lmax = wave_max(lmax);
     if (lane == 0) red[wave] = lmax;
     MB_TC(3);
-    mb_barrier();
+    wa_barrier_lds();
     if (wave == 0) {        // (1) maxima of the parts
         float m = red[0];
 #pragma unroll
         for (int k = 1; k < MB_NW; ++k) m = fmaxf(m, red[k]);
         if (lane == 0) gr_store(X + MB_CGR_MAX + w, seq, __float_as_uint(m));
         unsigned v[1];
-        mb_sweep<1>(X + MB_CGR_MAX, [&](int) { return lane < P ? lane : -1; }, c, lane, v, 2100u + l);
+        mo_sweep<MO_POLL_ALL, 1>(X + MB_CGR_MAX, [&](int) { return lane < P ? lane : -1; }, c, lane, v, 2100u + l);
         float g = lane < P ? __uint_as_float(v[0]) : -INFINITY;
         g = fmaxf(g, dpp_f32<0x4e>(g)); g = fmaxf(g, dpp_f32<0xb1>(g));      // max over lanes 0..3
         if (lane == 0) bc[0] = g;
     }
-    mb_barrier();
+    wa_barrier_lds();
     MB_TC(4);
     const float mx = bc[0];
     // ---- exp, group sums (8-lane tree = ops.cpp's), F64 partial sum: a thread per own cell (ops.cpp:4792-4818, vec.cpp:257-308) ----
@@ -812,21 +716,21 @@ __device__ __forceinline__ void mb_unit_cross(mb_kargs A, mb_ctl & c, unsigned c
         if (lane == 0) redd[wave] = ps;
     }
     MB_TC(5);
-    mb_barrier();
+    wa_barrier_lds();
     if (wave == 0) {        // (2) partial sums -> total, certified
         const double ps = ((redd[0] + redd[1]) + (redd[2] + redd[3])) + ((redd[4] + redd[5]) + (redd[6] + redd[7]));
         const u64 pb = (u64) __double_as_longlong(ps);
         if (lane == 0) { gr_store(X + MB_CGR_SUM + 2 * w, seq, (unsigned) pb); gr_store(X + MB_CGR_SUM + 2 * w + 1, seq, (unsigned) (pb >> 32)); }
         unsigned v[1];
-        mb_sweep<1>(X + MB_CGR_SUM, [&](int) { return lane < 2 * P ? lane : -1; }, c, lane, v, 2200u + l);
+        mo_sweep<MO_POLL_ALL, 1>(X + MB_CGR_SUM, [&](int) { return lane < 2 * P ? lane : -1; }, c, lane, v, 2200u + l);
         double tot = 0.0;
 #pragma unroll
         for (int k = 0; k < P; ++k) {
             const unsigned lo = __builtin_amdgcn_readlane(v[0], 2 * k), hi = __builtin_amdgcn_readlane(v[0], 2 * k + 1);
             tot += __longlong_as_double((long long) (((u64) hi << 32) | lo));
         }
-        const double delta = (double) (ng + 8 + 16) * 0x1p-53 * tot * 1.000001;      // (as in the self-attention unit: reference (ng + 7) u S + this tree's 16 u S)
-        const float ilo = (float) (1.0 / (tot + delta)), ihi = (float) (1.0 / (tot - delta));
+        float ilo, ihi;
+        wa_softmax_bounds(tot, ng, ilo, ihi);
         float inv_ = ilo;
         if (ilo != ihi || A->force_inorder) {       // the order could matter (~3e-5 per soft-max; the same decision in every part: they hold the same total)
             if constexpr (P == 4) {
@@ -849,7 +753,7 @@ __device__ __forceinline__ void mb_unit_cross(mb_kargs A, mb_ctl & c, unsigned c
                     gr_store(XI + 64 * w + s_, seq, __float_as_uint(pv));
                 }
                 unsigned vi[4];
-                mb_sweep<4>(XI, [&](int k) { return 64 * k + lane; }, c, lane, vi, 2250u + l);
+                mo_sweep<MO_POLL_ALL, 4>(XI, [&](int k) { return 64 * k + lane; }, c, lane, vi, 2250u + l);
 #pragma unroll
                 for (int k = 0; k < 4; ++k) io[64 * k + lane] = __uint_as_float(vi[k]);
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");       // (this wave's own LDS writes, read back below)
@@ -864,7 +768,7 @@ __device__ __forceinline__ void mb_unit_cross(mb_kargs A, mb_ctl & c, unsigned c
         }
         if (lane == 0) bc[1] = inv_;
     }
-    mb_barrier();
+    wa_barrier_lds();
     MB_TC(6);
     const float inv = bc[1];
     gu64 * XP = X + MB_CGR_PART;
@@ -880,7 +784,7 @@ __device__ __forceinline__ void mb_unit_cross(mb_kargs A, mb_ctl & c, unsigned c
             }
         }
     }
-    mb_barrier();
+    wa_barrier_lds();
     MB_TC(7);
     // ---- P V: wave = own chains (cells 32 s + NCH w + CPW wave + c), lane = d_head index ----
 #pragma unroll
@@ -898,13 +802,13 @@ __device__ __forceinline__ void mb_unit_cross(mb_kargs A, mb_ctl & c, unsigned c
     if (w == 0) {           // (3) gather the other parts' chain sums and leftover probabilities, finish the head
         constexpr int NG_ = (P - 1) * NCH * 64;          // 1536 (quarters) or 1024 (halves) chain sums
         unsigned v[NG_ / MB_THREADS + 1];
-        mb_sweep<NG_ / MB_THREADS + 1>(XP, [&](int k) {
+        mo_sweep<MO_POLL_ALL, NG_ / MB_THREADS + 1>(XP, [&](int k) {
             if (k < NG_ / MB_THREADS) return tid + MB_THREADS * k;
             return tid < (P - 1) * NCH && NCH + tid < nl ? NG_ + tid : -1; }, c, lane, v, 2300u + l);
 #pragma unroll
         for (int k = 0; k < NG_ / MB_THREADS; ++k) part[NCH * 64 + tid + MB_THREADS * k] = __uint_as_float(v[k]);      // (part ww's chain r = global chain NCH ww + r)
         if (tid < (P - 1) * NCH && NCH + tid < nl) pleft[NCH + tid] = (wa_f16) v[NG_ / MB_THREADS];
-        mb_barrier();
+        wa_barrier_lds();
         MB_TC(9);
         // finish: the leftover cells (vec.cpp:221-223: F64, index order) spread over waves 1..7 - five cells each, for the 64 outputs, every product
         // ONE v_fma_mix_f32 (F16 x F16 is exact in F32; with a -0.0 addend it is the multiplication's float), parked in LDS as F64 - while wave 0 runs
@@ -931,7 +835,7 @@ __device__ __forceinline__ void mb_unit_cross(mb_kargs A, mb_ctl & c, unsigned c
             for (int r = 0; r < 32; ++r) s32[r] = part[r * 64 + tid];
             sumf = (double) wa_tree32(s32);
         }
-        mb_barrier();
+        wa_barrier_lds();
         if (tid < 64) {
             double dv[32];
 #pragma unroll
@@ -939,22 +843,11 @@ __device__ __forceinline__ void mb_unit_cross(mb_kargs A, mb_ctl & c, unsigned c
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int cc = 0; cc < 32; ++cc) sumf += dv[cc];
-            gu64 * edge_row = mb_edge(A, l, E_AO2) + (size_t) b * A->row_gr;
-            if constexpr (Q) {
-                float dq;
-                const unsigned wq_ = mq_quant32((float) sumf, dq);
-                gu64 * eb = edge_row + (size_t) (2 * h + (tid >> 5)) * 9;
-                if ((tid & 3) == 0) gr_store(eb + ((tid & 31) >> 2), seq, wq_);
-                if ((tid & 31) == 0) gr_store(eb + 8, seq, __float_as_uint(dq));
-            } else {
-                const unsigned hv = (unsigned) f2h((float) sumf);
-                const unsigned hi = dpp_u32<0x101>(hv);
-                if ((tid & 1) == 0) gr_store(edge_row + ((h * 64 + tid) >> 1), seq, (hv & 0xffffu) | (hi << 16));
-            }
+            mo_attn_publish<Q>((float) sumf, mb_edge(A, l, E_AO2) + (size_t) b * A->row_gr, h, seq, tid);
         }
         MB_TC(10);
     }
-    mb_barrier();
+    wa_barrier_lds();
 }
 
 // -------------------------------------------------------------------------------------------------
@@ -1136,102 +1029,34 @@ __device__ __forceinline__ void mb_logits_q(mb_kargs A, const unsigned char * xo
 }
 
 // -------------------------------------------------------------------------------------------------
-// next-token prediction per row (wa_mega.hip: mg_pick / mg_final's records; the host re-derives every token from the logits with the reference's
-// rules - this arithmetic is a prediction only).  mb_pick: one wave, the row's token and the sampling state after it -> pk[0..4].
+// next-token prediction per row (the protocol and its records: wa_one_launch_dev.h).  mb_pick: one wave, the row's token and the sampling state
+// after it -> pk (MO_PK_*).
 // -------------------------------------------------------------------------------------------------
-struct mb_best { float v; int i; };
-__device__ __forceinline__ void mb_best_merge(mb_best & a, float v, int i) { if (v > a.v || (v == a.v && i < a.i)) { a.v = v; a.i = i; } }
-__device__ __forceinline__ void mb_best_wave(mb_best & a) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { const float v = __shfl_xor(a.v, o, WAVE); const int i = __shfl_xor(a.i, o, WAVE); mb_best_merge(a, v, i); }
-}
 __device__ __forceinline__ void mb_pick(mb_kargs A, int b, int lane, int * pk, int n_rec) {
-    int token = A->rows[b].token, last = A->rows[b].s_last, penult = A->rows[b].s_penult, seek_delta = A->rows[b].s_seek_delta, has_ts = A->rows[b].s_has_ts;
-    if (A->rows[b].spec) {
-        const GAS int * ps = (const GAS int *) A->rows[b].ps_in;
-        const GAS unsigned * rec = (const GAS unsigned *) A->rows[b].rec_in;
-        penult = ps[0]; seek_delta = ps[2]; has_ts = ps[3];
-        mb_best bt = { -INFINITY, 0x7fffffff }, bs = { -INFINITY, 0x7fffffff };
-        u32x4 ra[4]; unsigned rb[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {           // every record (n_rec <= 256: four per lane) in ONE round of loads
-            const int g = lane + 64 * j, gg = g < n_rec ? g : 0;
-            ra[j] = *(const GAS u32x4 *) (rec + gg * 8); rb[j] = rec[gg * 8 + 4];
-        }
-#pragma unroll
-        for (int j = 0; j < 4; ++j) if (lane + 64 * j < n_rec) {
-            mb_best_merge(bt, __uint_as_float(ra[j].x), (int) ra[j].y);
-            mb_best_merge(bs, __uint_as_float(ra[j].z), (int) ra[j].w);
-        }
-        mb_best_wave(bt); mb_best_wave(bs);
-        float sm = 0.0f;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) if (lane + 64 * j < n_rec) {
-            const float m = __uint_as_float(ra[j].z);
-            if (m > -INFINITY) sm += __uint_as_float(rb[j]) * __expf(m - bs.v);
-        }
-        sm = wave_sum(sm);
-        // whisper.cpp:6309-6333: timestamp mass above every text token => a timestamp; else the arg-max of everything allowed
-        if (!(bs.v > -INFINITY)) token = bt.v > -INFINITY ? bt.i : 0;
-        else if (!(bt.v > -INFINITY)) token = bs.i;
-        else if (__logf(sm) + bs.v > bt.v) token = bs.i;
-        else token = bs.v > bt.v ? bs.i : bt.i;
-        last = token;
-        if (token > A->token_beg) { seek_delta = 2 * (token - A->token_beg); has_ts = 1; }
-    }
+    mo_pick p = { A->rows[b].token, A->rows[b].s_last, A->rows[b].s_penult, A->rows[b].s_seek_delta, A->rows[b].s_has_ts };
+    if (A->rows[b].spec) mo_pick_merge(p, A->rows[b].rec_in, A->rows[b].ps_in, n_rec, A->token_beg, lane);
     if (lane == 0) {
-        pk[0] = token; pk[1] = last; pk[2] = penult; pk[3] = seek_delta; pk[4] = has_ts;
+        mo_pick_put(pk, p);
         if (blockIdx.x == 0 && A->rows[b].ps_out) {
             GAS int * po = (GAS int *) A->rows[b].ps_out;
-            po[0] = last; po[1] = penult; po[2] = seek_delta; po[3] = has_ts; po[4] = token;
+            po[MO_PS_LAST] = p.last; po[MO_PS_PENULT] = p.penult; po[MO_PS_SEEK_DELTA] = p.seek_delta; po[MO_PS_HAS_TS] = p.has_ts; po[MO_PS_TOKEN] = p.token;
         }
-        if (blockIdx.x == 0 && A->tok_out) ((GAS int *) A->tok_out)[b] = token;
+        if (blockIdx.x == 0 && A->tok_out) ((GAS int *) A->tok_out)[b] = p.token;
     }
 }
 // candidate records of logits row m (token row br) from this workgroup's share of the logits, kept in LDS by mb_logits (lg [BT][256]); all threads
 __device__ __forceinline__ void mb_record(mb_kargs A, int br, const float * lg_m, const int * pk, unsigned * scratch /* LDS [8][8] */, int tid) {
     const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wg = blockIdx.x, n_vocab = A->n_vocab, beg = A->token_beg, eot = A->token_eot;
+    const int n_vocab = A->n_vocab;
     const GAS unsigned * smask = (const GAS unsigned *) A->rows[br].smask;
-    const int st_last = pk[1], st_penult = pk[2], st_seek = pk[3], st_has = pk[4];
-    const bool last_ts = st_last >= beg, penult_ts = st_penult < 0 || st_penult >= beg;
-    const bool no_ts = last_ts && penult_ts, no_text = last_ts && !penult_ts;
-    const int ts_min = st_has ? beg + st_seek / 2 : beg;
-    mb_best bt = { -INFINITY, 0x7fffffff }, bs = { -INFINITY, 0x7fffffff };
-    float s_ts = 0.0f;
+    mo_cand cd = mo_cand_init(pk, A->token_beg, A->token_eot);
     int g1; const int g0 = mb_share(n_vocab, &g1);
     if (tid < 256) {        // local row li  <->  vocabulary row 8 g0 + li (mb_share)
         const int li = tid, row = 8 * g0 + li;
-        if (row < n_vocab && row < 8 * g1) {
-            const float r = lg_m[li];
-            const unsigned mw = smask[row >> 5];
-            if (!((mw >> (row & 31)) & 1u)) {
-                if (row >= beg) { if (!no_ts && row >= ts_min) { bs.v = r; bs.i = row; s_ts = 1.0f; } }
-                else if (!(no_text && row < eot)) { bt.v = r; bt.i = row; }
-            }
-        }
+        if (row < n_vocab && row < 8 * g1) mo_cand_add(cd, lg_m[li], row, smask[row >> 5]);
     }
-    const float m_loc = bs.v;
-    mb_best_wave(bt); mb_best_wave(bs);
-    float sw = m_loc > -INFINITY ? s_ts * __expf(m_loc - bs.v) : 0.0f;
-    sw = wave_sum(sw);
-    if (lane == 0) { scratch[wave * 8 + 0] = __float_as_uint(bt.v); scratch[wave * 8 + 1] = (unsigned) bt.i; scratch[wave * 8 + 2] = __float_as_uint(bs.v);
-                     scratch[wave * 8 + 3] = (unsigned) bs.i; scratch[wave * 8 + 4] = __float_as_uint(sw); }
-    mb_barrier();
-    if (wave == 0) {
-        mb_best t2 = { -INFINITY, 0x7fffffff }, s2 = { -INFINITY, 0x7fffffff };
-        float sl = 0.0f, ml = -INFINITY;
-        if (lane < MB_NW) { t2.v = __uint_as_float(scratch[lane * 8 + 0]); t2.i = (int) scratch[lane * 8 + 1]; s2.v = __uint_as_float(scratch[lane * 8 + 2]); s2.i = (int) scratch[lane * 8 + 3];
-                            sl = __uint_as_float(scratch[lane * 8 + 4]); ml = s2.v; }
-        mb_best_wave(t2); mb_best_wave(s2);
-        float sg = ml > -INFINITY ? sl * __expf(ml - s2.v) : 0.0f;
-        sg = wave_sum(sg);
-        if (lane == 0) {
-            GAS unsigned * ro = (GAS unsigned *) A->rows[br].rec_out + (size_t) wg * 8;
-            ro[0] = __float_as_uint(t2.v); ro[1] = (unsigned) t2.i; ro[2] = __float_as_uint(s2.v); ro[3] = (unsigned) s2.i; ro[4] = __float_as_uint(sg);
-        }
-    }
-    mb_barrier();
+    mo_cand_record(cd, scratch, A->rows[br].rec_out + (size_t) blockIdx.x * MO_REC_WORDS, lane, wave);
+    wa_barrier_lds();           // (the next row's record takes the same scratch)
 }
 
 // -------------------------------------------------------------------------------------------------
@@ -1242,11 +1067,11 @@ struct mb_phase { const wa_f16 * W; const float * D; const float * bias; const f
 template <int NP, bool Q>
 __device__ __forceinline__ void mb_body(mb_kargs A_) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const mb_kargs A = mb_uniform(A_);
+    const mb_kargs A = mo_uniform(A_);
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wg = blockIdx.x, nwg = gridDim.x;
-    mb_ctl c; c.status = (gu32 *) A->status; c.seq = A->seq; c.dead = false;
+    mo_ctl c; c.status = (gu32 *) A->status; c.seq = A->seq; c.dead = false;
     const unsigned seq = c.seq;
     const int d = A->d, L = A->n_layer, B = A->B, H = A->n_head, d4 = 4 * d, RG = A->row_gr;
     const mb_layers Ly = (mb_layers) A->layers;
@@ -1376,7 +1201,7 @@ __device__ __forceinline__ void mb_body(mb_kargs A_) {
 
     if (wave == MB_NW - 1 && L > 0) request(0, 0, 0, 0);
     if (wave < B) mb_pick(A, wave, lane, pk + 8 * wave, min(nwg, 256));      // the rows' tokens: given, or picked from the records their previous passes left
-    mb_barrier();
+    wa_barrier_lds();
 #define MB_T(k) do { mb_trace(A, tw, l * 32 + (k)); mb_trace(A, tid == 0 && l == MB_TRACE_LAYER, 8192 + wg * 16 + (k)); } while (0)      /* every workgroup at ONE layer */
     for (int l = 0; l < L; ++l) {
         const __attribute__((address_space(4))) wa_mega_layer & Y = Ly[l];
@@ -1503,7 +1328,7 @@ __device__ __forceinline__ void mb_body(mb_kargs A_) {
             (void) ck_row;
         });
         if constexpr (Q) {      // this workgroup's block of every token row: quantize_row_q8_0, published as 9 granules (wave b: row b)
-            mb_barrier();
+            wa_barrier_lds();
             if (wave < B && 32 * wg < d4) {
                 float dq;
                 const unsigned w = mq_quant32(fc1x[wave * 32 + (lane & 31)], dq);
@@ -1547,7 +1372,7 @@ __device__ __forceinline__ void mb_body(mb_kargs A_) {
     bool want_rec = false;
     for (int m = 0; m < n_out; ++m) want_rec = want_rec || A->rows[A->out_row[m]].smask != nullptr;
     float * lg = (float *) area;            // (the gathered-inputs area holds nothing any more) the workgroup's logits, staged for whole-line stores and the records
-    mb_barrier();
+    wa_barrier_lds();
     if constexpr (Q) {
         if (n_out <= 2) mb_logits_q<2>(A, xinB, opB, n_out, lane, wave, pf0, lg); else if (n_out <= 4) mb_logits_q<4>(A, xinB, opB, n_out, lane, wave, pf0, lg);
         else if (n_out <= 5) mb_logits_q<5>(A, xinB, opB, n_out, lane, wave, pf0, lg); else mb_logits_q<8>(A, xinB, opB, n_out, lane, wave, pf0, lg);
@@ -1555,7 +1380,7 @@ __device__ __forceinline__ void mb_body(mb_kargs A_) {
         if (n_out <= 2) mb_logits<2>(A, (const wa_f16 *) xinB, n_out, lane, wave, pf0, lg); else if (n_out <= 4) mb_logits<4>(A, (const wa_f16 *) xinB, n_out, lane, wave, pf0, lg);
         else if (n_out <= 5) mb_logits<5>(A, (const wa_f16 *) xinB, n_out, lane, wave, pf0, lg); else mb_logits<8>(A, (const wa_f16 *) xinB, n_out, lane, wave, pf0, lg);
     }
-    mb_barrier();
+    wa_barrier_lds();
     mb_logits_out(A, lg, n_out, tid);
     if (want_rec) {          // candidate records of every row that asked for them (the next pass of its chunk picks its token from them)
         for (int m = 0; m < n_out; ++m) {
