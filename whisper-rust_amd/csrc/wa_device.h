@@ -102,6 +102,8 @@ __device__ __forceinline__ float wa_gelu(float x, const wa_f16 * __restrict__ ta
 // (qs [row][el / 4][block][el % 4], qd [row][block]).  All 32 lanes of the half-wave must be active.
 // qsum set (the same for the whole wave): the row is the Q8_1 operand of a Q4_1 / Q5_1 product (quantize_row_q8_1, same file), which
 // carries qsum [row][block] = f16(d * (float) sum of the block's quants) besides - d the F32 quotient BEFORE it is rounded to F16.
+// Outside the contract: a block with 0 < max|x| < 2^-120 (127 / max|x| overflows, and the conversion of inf / NaN to an integer gives
+// another value here than in the reference's AVX2 code) and NaN inputs.  An all-zero block (+0 or -0) is inside it: id = 0, every quant 0.
 __device__ __forceinline__ void wa_q8_store(float y, int row, int blk, int el, int nb, int8_t * __restrict__ qs, float * __restrict__ qd,
                                             float * __restrict__ qsum = nullptr) {
     float a = fabsf(y);
