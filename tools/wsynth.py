@@ -23,6 +23,7 @@ SHAPES = {
     "s128":   dict(d=128,  heads=2,  enc=3,  dec=4,  n_mels=80,  n_vocab=51865),
     "s128u":  dict(d=128,  heads=2,  enc=3,  dec=4,  n_mels=80,  n_vocab=51865, vocab="utf8"),   # s128 with multi-byte token texts (synth_vocab)
     "s192":   dict(d=192,  heads=3,  enc=2,  dec=2 + 1, n_mels=80, n_vocab=51865),   # d not a multiple of 128: tile guards
+    "s256":   dict(d=256,  heads=4,  enc=2,  dec=3,  n_mels=80,  n_vocab=51865),      # the smallest width the K formats (256-value blocks) can hold
     "w1280":  dict(d=1280, heads=20, enc=1,  dec=3,  n_mels=128, n_vocab=51866),      # large-v3's width with few layers: the wide-model paths
     "m1024":  dict(d=1024, heads=16, enc=1,  dec=3,  n_mels=80,  n_vocab=51865),      # medium's width and head count with few layers (config 4's products)
     # real Whisper shapes (SURVEY.md §8 header)
@@ -245,7 +246,7 @@ def model_path(shape_name: str, seed: int = 0, cache_dir: str | None = None, ove
 def quant_model_path(shape_name: str, qtype: str, seed: int = 0, cache_dir: str | None = None, overrides: dict | None = None,
                      tag: str | None = None) -> str:
     """Path of the cached quantised version of a synthetic model (qtype: any name the tool knows - "q5_0", "q8_0", "q5_1", "q4_1",
-    "q4_0", ...), produced on first use by the REFERENCE's own quantizer
+    "q4_0", "q5_k", "q6_k", ...), produced on first use by the REFERENCE's own quantizer
     (examples/quantize, compiled by oracle/Makefile into oracle/_ref/quantize-ref; test infrastructure only)."""
     import subprocess
     src = model_path(shape_name, seed, cache_dir, overrides, tag)

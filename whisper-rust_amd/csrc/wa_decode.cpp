@@ -187,23 +187,33 @@ static void decode_launch_quant(whisper_context & ctx, whisper_state & st, int n
     const int n_vocab = hp.n_vocab, d = hp.n_text_state, H = hp.n_text_head;
     const int T = audio_ctx(st);
     hipStream_t s = st.stream;
+    // Q5_K / Q6_K (wa_quantk.hip): Q8_K operand rows; LayerNorm, attention and GELU hand over F32 (d_q32a / d_q32b) and one more launch quantises.
+    const bool QK = wa_wtype_k(m.wtype);
+    auto quant = [&](const float * A, int lda, int M, int K) {
+        if (QK) wa_launch_quantize_q8_K(s, A, lda, M, K, st.d_q8, st.d_q8d, st.d_q8bs);
+        else    wa_launch_quantize_q8_0(s, A, lda, M, K, st.d_q8, st.d_q8d, st.d_q8s);
+    };
     auto qmul = [&](wa_epi_mode mode, const wa_lin & L, int M, const wa_epi & e) {      // operand already in d_q8 / d_q8d
-        wa_launch_qgemm_exact(s, mode, st.d_q8, st.d_q8d, M, L.qs, L.qd, L.n_out, L.n_in, e, st.d_q8s, L.qm);
+        if (QK) wa_launch_kgemm_exact(s, mode, m.wtype, st.d_q8, st.d_q8d, st.d_q8bs, M, L.qs, L.qsc, L.qd, L.qm, L.n_out, L.n_in, e);
+        else    wa_launch_qgemm_exact(s, mode, st.d_q8, st.d_q8d, M, L.qs, L.qd, L.n_out, L.n_in, e, st.d_q8s, L.qm);
     };
     auto qlin = [&](wa_epi_mode mode, const float * A, int lda, const wa_lin & L, int M, const wa_epi & e) {
-        wa_launch_quantize_q8_0(s, A, lda, M, L.n_in, st.d_q8, st.d_q8d, st.d_q8s);
+        quant(A, lda, M, L.n_in);
         qmul(mode, L, M, e);
     };
     auto ln_q = [&](const float * x, int rows, const wa_ln & ln) {
-        if (rows == 1 && d <= 2048) wa_launch_ln_q8_row(s, x, d, ln.w, ln.b, hp.eps, st.d_q8, st.d_q8d, st.d_q8s);
+        if (QK) { wa_launch_layernorm_exact(s, x, d, rows, d, ln.w, ln.b, hp.eps, nullptr, 0, st.d_q32a, d); quant(st.d_q32a, d, rows, d); }
+        else if (rows == 1 && d <= 2048) wa_launch_ln_q8_row(s, x, d, ln.w, ln.b, hp.eps, st.d_q8, st.d_q8d, st.d_q8s);
         else wa_launch_layernorm_exact(s, x, d, rows, d, ln.w, ln.b, hp.eps, nullptr, 0, nullptr, 0, st.d_q8, st.d_q8d, st.d_q8s);
     };
-    wa_launch_dec_embed_q(s, st.d_tok, st.d_pos, n_tokens, d, m.te_q.qs, m.te_q.qd, m.d_pe, st.d_dx, m.te_q.qm);
+    if (QK) wa_launch_dec_embed_k(s, m.wtype, st.d_tok, st.d_pos, n_tokens, d, m.te_q.qs, m.te_q.qsc, m.te_q.qd, m.te_q.qm, m.d_pe, st.d_dx);
+    else wa_launch_dec_embed_q(s, st.d_tok, st.d_pos, n_tokens, d, m.te_q.qs, m.te_q.qd, m.d_pe, st.d_dx, m.te_q.qm);
     const float KQscale = pow(float(64), -0.25);
     const size_t kv_layer = (size_t) kv.size * d, cross_layer = (size_t) H * st.cross_tpad * 64;
     // second operand buffer (upper half of d_q8 / d_q8d) for the one product whose output is quantised by its own launch
     int8_t * q8b = st.d_q8 + (size_t) st.q8_rows * 2 * d; float * q8bd = st.d_q8d + (size_t) st.q8_rows * 2 * d / 32;
-    const wa_q8_rows q8r{ st.d_q8, st.d_q8d, st.d_q8s };      // where attention hands its rows over
+    const wa_q8_rows q8r = QK ? wa_q8_rows() : wa_q8_rows{ st.d_q8, st.d_q8d, st.d_q8s };      // where attention hands its rows over
+    float * att32 = QK ? st.d_q32a : nullptr;                 // K formats: in F32, to the Q8_K quantiser
     float * q8bs = st.d_q8s ? st.d_q8s + (size_t) st.q8_rows * 2 * d / 32 : nullptr;
     for (int il = 0; il < hp.n_text_layer; ++il) {
         const auto & L = m.dec[il];
@@ -215,7 +225,8 @@ static void decode_launch_quant(whisper_context & ctx, whisper_state & st, int n
             qmul(WA_EPI_DEC_QKV, L.qkv, n_tokens, e);
         }
         wa_launch_attn_exact(s, st.d_dq, d, kv.k + il * kv_layer, 64, d, kv.v + il * kv_layer, 64, d, H, n_tokens, n_kv, mask, 1.0f,
-                             st.d_att_partial, st.d_att_pleft, st.d_dao, d, nullptr, dyn, nullptr, q8r);
+                             st.d_att_partial, st.d_att_pleft, st.d_dao, d, nullptr, dyn, att32, q8r);
+        if (QK) quant(st.d_q32a, d, n_tokens, d);
         { wa_epi e; e.bias = L.out.b; e.out = st.d_dx; e.ldo = d; e.resid = st.d_dx; e.ldr = d; qmul(WA_EPI_RESID, L.out, n_tokens, e); }
         ln_q(st.d_dx, n_tokens, L.cross_ln);
         { wa_epi e; e.bias = L.cross_q.b; e.out = st.d_dq; e.ldo = d; qmul(WA_EPI_F16, L.cross_q, n_tokens, e); }
@@ -224,11 +235,12 @@ static void decode_launch_quant(whisper_context & ctx, whisper_state & st, int n
             qk_out = st.d_aheads_qk + (size_t) st.aheads_slot[il] * n_tokens * H * T;
         wa_launch_attn_exact(s, st.d_dq, d, st.d_cross_k + il * cross_layer, (size_t) st.cross_tpad * 64, 64, st.d_cross_v + il * cross_layer,
                              (size_t) st.cross_tpad * 64, 64, H, n_tokens, T, nullptr, KQscale, st.d_att_partial, st.d_att_pleft, st.d_dao, d, qk_out,
-                             nullptr, nullptr, q8r);
+                             nullptr, att32, q8r);
+        if (QK) quant(st.d_q32a, d, n_tokens, d);
         { wa_epi e; e.bias = L.cross_out.b; e.out = st.d_dx; e.ldo = d; e.resid = st.d_dx; e.ldr = d; qmul(WA_EPI_RESID, L.cross_out, n_tokens, e); }
         ln_q(st.d_dx, n_tokens, L.mlp_ln);
         wa_epi e2; e2.bias = L.fc2.b; e2.out = st.d_dx; e2.ldo = d; e2.resid = st.d_dx; e2.ldr = d;
-        if (n_tokens == 1) {
+        if (n_tokens == 1 && !QK) {
             wa_launch_qgemv_gelu_q8(s, st.d_q8, st.d_q8d, L.fc1.qs, L.fc1.qd, 4 * d, d, L.fc1.b, m.d_gelu, q8b, q8bd, st.d_q8s, L.fc1.qm, q8bs);
             wa_launch_qgemm_exact(s, WA_EPI_RESID, q8b, q8bd, 1, L.fc2.qs, L.fc2.qd, d, 4 * d, e2, q8bs, L.fc2.qm);
         } else {
@@ -239,8 +251,10 @@ static void decode_launch_quant(whisper_context & ctx, whisper_state & st, int n
     if (n_rows) {       // final LayerNorm of the flagged rows (packed), then the logits product over the quantised token embedding
         const int nb = d >> 5;
         for (int i = 0; i < n_rows; ++i)
-            wa_launch_layernorm_exact(s, st.d_dx + (size_t) h_rows[i] * d, d, 1, d, m.d_ln.w, m.d_ln.b, hp.eps, nullptr, 0, nullptr, 0,
+            if (QK) wa_launch_layernorm_exact(s, st.d_dx + (size_t) h_rows[i] * d, d, 1, d, m.d_ln.w, m.d_ln.b, hp.eps, nullptr, 0, st.d_q32a + (size_t) i * d, d);
+            else wa_launch_layernorm_exact(s, st.d_dx + (size_t) h_rows[i] * d, d, 1, d, m.d_ln.w, m.d_ln.b, hp.eps, nullptr, 0, nullptr, 0,
                                       st.d_q8 + (size_t) i * d, st.d_q8d + (size_t) i * nb, st.d_q8s ? st.d_q8s + (size_t) i * nb : nullptr);
+        if (QK) quant(st.d_q32a, d, n_rows, d);
         wa_epi e; e.out = st.d_logits; e.ldo = n_vocab;
         qmul(WA_EPI_F32, m.te_q, n_rows, e);
     }

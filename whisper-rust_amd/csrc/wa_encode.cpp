@@ -107,7 +107,7 @@ bool wa_state_alloc(whisper_context & ctx, whisper_state & st) {
         const int dt = hp.n_text_state, Ht = hp.n_text_head;
         st.mega_form = wa_launch_form(!(g && g[0] == '1') && ctx.model.d_mega_layers && ctx.model.n_loaded > 0 && dt == Ht * 64 && dt % 128 == 0 &&
                                       dt <= WA_MEGA_MAX_D && hp.n_audio_ctx <= 1500 && ctx.model.n_cu >= 5 * Ht + 16 && tpad <= WA_MEGA_MAX_T &&
-                                      !wa_wtype_has_min(ctx.model.wtype));      // (Q4_1 / Q5_1: no one-launch kernel yet - every pass is the launch sequence)
+                                      !wa_wtype_has_min(ctx.model.wtype) && !wa_wtype_k(ctx.model.wtype));      // (Q4_1 / Q5_1, Q5_K / Q6_K: no one-launch kernel - every pass is the launch sequence)
         if (st.mega_form.enabled()) {
             // logits of the step and, right behind them, the status word: one device-to-host copy per token
             if (!dev_alloc(st.d_mega_cgr, (size_t) hp.n_text_layer * Ht * WA_MEGA_CGR)) return false;
@@ -133,6 +133,7 @@ bool wa_state_alloc(whisper_context & ctx, whisper_state & st) {
         if (!dev_alloc(st.d_q32a, (size_t) tpad * d) || !dev_alloc(st.d_q32b, (size_t) tpad * 4 * d) || !dev_alloc(st.d_q8, (size_t) tpad * 4 * d) ||
             !dev_alloc(st.d_q8d, (size_t) tpad * 4 * d / 32)) return false;
         if (wa_wtype_has_min(ctx.model.wtype) && !dev_alloc(st.d_q8s, (size_t) tpad * 4 * d / 32)) return false;
+        if (wa_wtype_k(ctx.model.wtype) && !dev_alloc(st.d_q8bs, (size_t) tpad * 4 * d / 16)) return false;      // Q8_K rows: K bytes, K / 256 scales, K / 16 sums
         st.q8_rows = tpad;
     }
     if (!dev_alloc(st.d_im2col, std::max((size_t) 2 * T * 3 * hp.n_mels, (size_t) T * 3 * d) + 64)) return false;
@@ -161,7 +162,7 @@ void wa_state_release(whisper_state & st) {
     dev_free(st.d_tok); dev_free(st.d_pos); dev_free(st.d_cell); dev_free(st.d_rows); dev_free(st.d_mask);
     dev_free(st.d_dx); dev_free(st.d_dxn); dev_free(st.d_dqkv); dev_free(st.d_dao); dev_free(st.d_dff); dev_free(st.d_dq);
     if (st.dec_graph) { (void) hipGraphExecDestroy(st.dec_graph); st.dec_graph = nullptr; }
-    dev_free(st.d_q32a); dev_free(st.d_q32b); dev_free(st.d_q8); dev_free(st.d_q8d); dev_free(st.d_q8s);
+    dev_free(st.d_q32a); dev_free(st.d_q32b); dev_free(st.d_q8); dev_free(st.d_q8d); dev_free(st.d_q8s); dev_free(st.d_q8bs);
     dev_free(st.d_mega_gr); dev_free(st.d_mega_cgr); dev_free(st.d_mega_out); st.d_mega_status = nullptr;
     dev_free(st.d_mega_out2); dev_free(st.d_mega_smask);
     dev_free(st.d_rows_gr); dev_free(st.d_rows_cgr); dev_free(st.d_rows_status);
@@ -305,31 +306,44 @@ bool wa_encode(whisper_context & ctx, whisper_state & st, int mel_offset, ggml_a
         // Quantised model: every 2-D weight is Q5_0 / Q8_0 (Q4_1 / Q5_1) and the reference multiplies it with the Q8_0 (Q8_1) form of the
         // F32 activation row (wa_quant.hip).  Same sequence as below; the operands of the products stay F32 until they are quantised.
         // d_q8s is null unless the weights carry a block minimum: then every quantising launch writes the block sums there too.
+        // Q5_K / Q6_K (wa_quantk.hip): the operand rows are Q8_K; LayerNorm and attention hand over F32 (d_q32a) and one more launch quantises.
+        const bool QK = wa_wtype_k(m.wtype);
+        auto quant = [&](const float * A, int lda, int M, int K) {
+            if (QK) wa_launch_quantize_q8_K(s, A, lda, M, K, st.d_q8, st.d_q8d, st.d_q8bs);
+            else    wa_launch_quantize_q8_0(s, A, lda, M, K, st.d_q8, st.d_q8d, st.d_q8s);
+        };
         auto qmul = [&](wa_epi_mode mode, const wa_lin & L, int M, const wa_epi & e) {       // operand rows already in d_q8 / d_q8d
-            wa_launch_qgemm_exact(s, mode, st.d_q8, st.d_q8d, M, L.qs, L.qd, L.n_out, L.n_in, e, st.d_q8s, L.qm);
+            if (QK) wa_launch_kgemm_exact(s, mode, m.wtype, st.d_q8, st.d_q8d, st.d_q8bs, M, L.qs, L.qsc, L.qd, L.qm, L.n_out, L.n_in, e);
+            else    wa_launch_qgemm_exact(s, mode, st.d_q8, st.d_q8d, M, L.qs, L.qd, L.n_out, L.n_in, e, st.d_q8s, L.qm);
         };
         auto qlin = [&](wa_epi_mode mode, const float * A, int lda, const wa_lin & L, int M, const wa_epi & e) {
-            wa_launch_quantize_q8_0(s, A, lda, M, L.n_in, st.d_q8, st.d_q8d, st.d_q8s);
+            quant(A, lda, M, L.n_in);
             qmul(mode, L, M, e);
+        };
+        auto ln_q = [&](const wa_ln & ln) {
+            if (QK) { wa_launch_layernorm_exact(s, st.d_x, d, T, d, ln.w, ln.b, hp.eps, nullptr, 0, st.d_q32a, d); quant(st.d_q32a, d, T, d); }
+            else wa_launch_layernorm_exact(s, st.d_x, d, T, d, ln.w, ln.b, hp.eps, nullptr, 0, nullptr, 0, st.d_q8, st.d_q8d, st.d_q8s);
         };
         for (int il = 0; il < hp.n_audio_layer; ++il) {
             const auto & L = m.enc[il];
             // (LayerNorm and attention quantise their F32 result rows themselves: wa_q8_store)
-            wa_launch_layernorm_exact(s, st.d_x, d, T, d, L.attn_ln.w, L.attn_ln.b, hp.eps, nullptr, 0, nullptr, 0, st.d_q8, st.d_q8d, st.d_q8s);
+            ln_q(L.attn_ln);
             static const bool no_mfma_attn = getenv("WHISPER_AMD_NO_EXACT_MFMA") != nullptr;
             if (st.d_attn_p && T >= 128 && !no_mfma_attn) {
                 // q, k, v are F16 here whatever the weight type (whisper.cpp:2181-2202): the reference-order attention on the matrix cores as for an
                 // F16 model (Q | K row-major, V transposed); its F32 result is quantised for the out-projection by one more launch
                 { wa_epi e; e.bias = L.qkv.b; e.out = st.d_qk; e.ldo = 2 * d; e.out2 = st.d_vt; e.ldo2 = tpad; e.split0 = 2 * d; qmul(WA_EPI_ENC_QKV, L.qkv, T, e); }
                 wa_launch_attn_exact_mfma(s, st.d_qk, 2 * d, st.d_vt, tpad, T, d, H, KQscale, st.d_attn_p, st.d_attn_pl, (T + 127) & ~127, st.d_ao, d, st.d_q32a);
-                wa_launch_quantize_q8_0(s, st.d_q32a, d, T, d, st.d_q8, st.d_q8d, st.d_q8s);
+                quant(st.d_q32a, d, T, d);
             } else {
             { wa_epi e; e.bias = L.qkv.b; e.out = st.d_ff; e.ldo = 3 * d; qmul(WA_EPI_F16, L.qkv, T, e); }
             wa_launch_attn_exact(s, st.d_ff, 3 * d, st.d_ff + d, 64, 3 * d, st.d_ff + 2 * d, 64, 3 * d, H, T, T, nullptr, KQscale,
-                                 st.d_att_partial, st.d_att_pleft, st.d_ao, d, nullptr, nullptr, nullptr, wa_q8_rows{ st.d_q8, st.d_q8d, st.d_q8s });
+                                 st.d_att_partial, st.d_att_pleft, st.d_ao, d, nullptr, nullptr, QK ? st.d_q32a : nullptr,
+                                 QK ? wa_q8_rows() : wa_q8_rows{ st.d_q8, st.d_q8d, st.d_q8s });
+            if (QK) quant(st.d_q32a, d, T, d);
             }
             { wa_epi e; e.bias = L.out.b; e.out = st.d_x; e.ldo = d; e.resid = st.d_x; e.ldr = d; qmul(WA_EPI_RESID, L.out, T, e); }
-            wa_launch_layernorm_exact(s, st.d_x, d, T, d, L.mlp_ln.w, L.mlp_ln.b, hp.eps, nullptr, 0, nullptr, 0, st.d_q8, st.d_q8d, st.d_q8s);
+            ln_q(L.mlp_ln);
             { wa_epi e; e.bias = L.fc1.b; e.gelu = m.d_gelu; e.out = st.d_q32b; e.ldo = 4 * d; qmul(WA_EPI_GELU_F32, L.fc1, T, e); }
             { wa_epi e; e.bias = L.fc2.b; e.out = st.d_x; e.ldo = d; e.resid = st.d_x; e.ldr = d; qlin(WA_EPI_RESID, st.d_q32b, 4 * d, L.fc2, T, e); }
         }

@@ -14,6 +14,7 @@
 #include "wa_internal.h"
 #include "wa_mega.h"
 #include "wa_quant1.h"
+#include "wa_quantk.h"
 
 #include <cmath>
 #include <cstring>
@@ -34,7 +35,8 @@ inline float gelu_f32(float x) {
 struct slot {             // where a named tensor goes
     int    kind;          // 0 raw copy, 1 conv weight re-order ([oc][ic][3] -> [oc][3][ic], row stride ld),
                           // 2 quantised blocks -> kernel layout (off = signed quant bytes [row][8][block][4], off3 = scales [row][block],
-                          //   off4 = minimums [row][block] of the formats that have one)
+                          //   off4 = minimums [row][block] of the formats that have one; K formats, 256-value blocks (wa_quantk.h): off = quants
+                          //   [row][8][block][8][4], off5 = scale bytes [row][block][16], off3 = d [row][block], off4 = dmin [row][block] of Q5_K)
     size_t off;           // byte offset in the arena
     int    type;          // expected ggml type: 0 f32, 1 f16
     int64_t ne[3];        // expected ne[] (fastest first)
@@ -42,6 +44,7 @@ struct slot {             // where a named tensor goes
     size_t off2 = 0;      // kind 1: byte offset of the second, unpermuted copy (ggml im2col order)
     size_t off3 = 0;
     size_t off4 = 0;
+    size_t off5 = 0;
     bool   seen = false;
 };
 
@@ -106,13 +109,14 @@ bool wa_model_load(whisper_model_loader * loader, whisper_context & wctx) {
                      hp.n_text_ctx, hp.n_vocab);
             return false;
         }
-        // ftype % 1000 names the type of the 2-D weights (whisper.cpp:1567-1573; ggml_ftype: 1 F16, 3 Q4_1, 7 Q8_0, 8 Q5_0, 9 Q5_1).  ftype 0
+        // ftype % 1000 names the type of the 2-D weights (whisper.cpp:1567-1573; ggml_ftype: 1 F16, 3 Q4_1, 7 Q8_0, 8 Q5_0, 9 Q5_1, 13 Q5_K, 14 Q6_K - for the
+        // K formats the ftype number is the ggml type number too).  ftype 0
         // (all-F32) aborts in the reference's own conv path; Q4_0 runs through the reference's repacked 8-row product, a
-        // summation order of its own that is not restated here; the other quantised formats are not built.
+        // summation order of its own that is not restated here, and so does Q4_K; the other quantised formats (Q2_K, Q3_K, ...) are not built.
         const int ft = hp.ftype % 1000;
-        model.wtype = ft == 1 ? 1 : ft == 8 ? 6 : ft == 7 ? 8 : ft == 3 ? 3 : ft == 9 ? 7 : -1;
+        model.wtype = ft == 1 ? 1 : ft == 8 ? 6 : ft == 7 ? 8 : ft == 3 ? 3 : ft == 9 ? 7 : ft == 13 ? 13 : ft == 14 ? 14 : -1;
         if (model.wtype < 0) {
-            WA_ERROR("%s: unsupported ftype %d (this backend loads F16, Q8_0, Q5_0, Q5_1 and Q4_1 models)\n", __func__, hp.ftype);
+            WA_ERROR("%s: unsupported ftype %d (this backend loads F16, Q8_0, Q5_0, Q5_1, Q4_1, Q5_K and Q6_K models)\n", __func__, hp.ftype);
             return false;
         }
     }
@@ -181,6 +185,10 @@ bool wa_model_load(whisper_model_loader * loader, whisper_context & wctx) {
         WA_ERROR("%s: unsupported head size (kernels are built for d_head = 64, as in every Whisper model)\n", __func__);
         return false;
     }
+    if (wa_wtype_k(model.wtype) && d % WA_QK_K != 0) {      // every quantised row is d or 4 d long (tiny's 384 does not qualify)
+        WA_ERROR("%s: a %s model needs row lengths that are a multiple of 256, n_audio_state is %d\n", __func__, model.wtype == 13 ? "Q5_K" : "Q6_K", d);
+        return false;
+    }
     if (model.n_mel_filt != hp.n_mels) { WA_ERROR("%s: mel filter count %d != n_mels %d\n", __func__, model.n_mel_filt, hp.n_mels); return false; }
 
     // ---------------------------------------------------------------------------------------------
@@ -199,20 +207,30 @@ bool wa_model_load(whisper_model_loader * loader, whisper_context & wctx) {
     const size_t o_sincos  = ab.take(800 * F);
     const size_t o_gelu    = ab.take(65536 * H);
 
-    struct lin_off { size_t w, b, s; size_t qs = 0, qh = 0, qd = 0, qm = 0; };
-    const int QT = model.wtype;                                  // 1, 6, 8, 3 or 7
+    struct lin_off { size_t w, b, s; size_t qs = 0, qh = 0, qd = 0, qm = 0, qsc = 0; };
+    const int QT = model.wtype;                                  // 1, 6, 8, 3, 7, 13 or 14
     // Kernel layout of a quantised [n_out][n_in] matrix: the quants as signed bytes (Q5_0's 5-bit values are expanded once, here),
     // ordered [row][lane l = 0..7][block][4] - lane l of a row's 8-lane group owns elements 4l..4l+3 of EVERY block, so its bytes
     // are contiguous over the blocks (16-byte loads cover four blocks) - and the block scales [row][block] as F32.  Q4_1 / Q5_1: the
     // quants are the unsigned 4- / 5-bit values, and a third array holds the block minimums [row][block] as F32 (wa_quant1.h).
-    const bool QMIN = wa_wtype_has_min(QT);
+    // Q5_K / Q6_K (wa_quantk.h): 256-value blocks - quants [row][lane][block][group][4], 16 scale bytes and d (Q5_K: and dmin) per block.
+    const bool QMIN = wa_wtype_has_min(QT), QK = wa_wtype_k(QT);
     auto take_q = [&](lin_off & o, size_t n_out, size_t n_in) {
+        if (QK) {
+            o.qs = ab.take(n_out * n_in); o.qsc = ab.take(n_out * (n_in / 256) * 16); o.qd = ab.take(n_out * (n_in / 256) * 4);
+            if (QT == 13) o.qm = ab.take(n_out * (n_in / 256) * 4);
+            return;
+        }
         o.qs = ab.take(n_out * n_in); o.qh = 0; o.qd = ab.take(n_out * (n_in / 32) * 4);
         if (QMIN) o.qm = ab.take(n_out * (n_in / 32) * 4);
     };
     auto add_q = [&](const std::string & name, const lin_off & o, size_t row0, int64_t n_in, int64_t n_rows) {
         slot s; s.kind = 2; s.off = o.qs + row0 * (size_t) n_in; s.off2 = 0; s.off3 = o.qd + row0 * (size_t) (n_in / 32) * 4; s.type = QT;
         s.off4 = QMIN ? o.qm + row0 * (size_t) (n_in / 32) * 4 : 0;
+        if (QK) {
+            s.off3 = o.qd + row0 * (size_t) (n_in / 256) * 4; s.off4 = o.qm ? o.qm + row0 * (size_t) (n_in / 256) * 4 : 0;
+            s.off5 = o.qsc + row0 * (size_t) (n_in / 256) * 16;
+        }
         s.ne[0] = n_in; s.ne[1] = n_rows; s.ne[2] = 1; s.ld = 0;
         slots[name] = s;
     };
@@ -362,9 +380,28 @@ bool wa_model_load(whisper_model_loader * loader, whisper_context & wctx) {
             return false;
         }
         if (ttype != s.type) { WA_ERROR("%s: tensor '%s' has type %d in model file, expected %d\n", __func__, name.c_str(), ttype, s.type); return false; }
-        const size_t nbytes = s.type == 6 ? (size_t) nelements / 32 * 22 : s.type == 8 ? (size_t) nelements / 32 * 34 :
+        if (wa_qk_block_bytes(s.type) && s.ne[0] % WA_QK_K != 0) {
+            WA_ERROR("%s: tensor '%s' has rows of %d values, not a multiple of 256\n", __func__, name.c_str(), (int) s.ne[0]);
+            return false;
+        }
+        const size_t nbytes = wa_qk_block_bytes(s.type) ? (size_t) nelements / WA_QK_K * wa_qk_block_bytes(s.type) : s.type == 6 ? (size_t) nelements / 32 * 22 : s.type == 8 ? (size_t) nelements / 32 * 34 :
                               wa_q1_block_bytes(s.type) ? (size_t) nelements / 32 * wa_q1_block_bytes(s.type) : (size_t) nelements * (s.type == 0 ? F : H);
-        if (s.kind == 2) {        // block_q5_0 { f16 d; u32 qh; u8 qs[16] } / block_q8_0 { f16 d; i8 qs[32] } (ggml-common.h:187-214) -> arrays
+        if (s.kind == 2 && wa_qk_block_bytes(s.type)) {        // block_q5_K / block_q6_K -> the arrays of wa_quantk.h
+            tmp.resize(nbytes);
+            if (loader->read(loader->context, tmp.data(), nbytes) != nbytes) { WA_ERROR("%s: truncated tensor '%s'\n", __func__, name.c_str()); return false; }
+            const size_t bsz = wa_qk_block_bytes(s.type), nbr = (size_t) s.ne[0] / WA_QK_K, rows = (size_t) s.ne[1];
+            int8_t * qs = (int8_t *) (img.data() + s.off), * qsc = (int8_t *) (img.data() + s.off5);
+            float * qd = (float *) (img.data() + s.off3), * qm = s.off4 ? (float *) (img.data() + s.off4) : nullptr;
+            for (size_t r = 0; r < rows; ++r)
+                for (size_t b = 0; b < nbr; ++b) {
+                    int8_t v[256]; float dd, dm;
+                    wa_qk_unpack(s.type, tmp.data() + (r * nbr + b) * bsz, v, qsc + (r * nbr + b) * 16, dd, dm);
+                    qd[r * nbr + b] = dd;
+                    if (qm) qm[r * nbr + b] = dm;
+                    for (int g = 0; g < 8; ++g)
+                        for (int l = 0; l < 8; ++l) memcpy(qs + wa_qk_quant_index(r, nbr, b, 32 * g + 4 * l), v + 32 * g + 4 * l, 4);
+                }
+        } else if (s.kind == 2) {        // block_q5_0 { f16 d; u32 qh; u8 qs[16] } / block_q8_0 { f16 d; i8 qs[32] } (ggml-common.h:187-214) -> arrays
             tmp.resize(nbytes);
             if (loader->read(loader->context, tmp.data(), nbytes) != nbytes) { WA_ERROR("%s: truncated tensor '%s'\n", __func__, name.c_str()); return false; }
             //                          block_q4_1 / block_q5_1 carry a minimum too (wa_quant1.h: wa_q1_unpack)
@@ -428,7 +465,8 @@ bool wa_model_load(whisper_model_loader * loader, whisper_context & wctx) {
     auto LN = [&](ln_off o) { wa_ln r; r.w = PF(o.w); r.b = PF(o.b); return r; };
     auto LIN = [&](lin_off o, int n_out, int n_in) {
         wa_lin r; r.w = PH(o.w); r.b = PF(o.b); r.s = o.s ? PF(o.s) : nullptr; r.n_out = n_out; r.n_in = n_in;
-        if (o.qs) { r.w = nullptr; r.wtype = model.wtype; r.qs = (const int8_t *) (base + o.qs); r.qd = PF(o.qd); r.qm = o.qm ? PF(o.qm) : nullptr; }
+        if (o.qs) { r.w = nullptr; r.wtype = model.wtype; r.qs = (const int8_t *) (base + o.qs); r.qd = PF(o.qd); r.qm = o.qm ? PF(o.qm) : nullptr;
+                    r.qsc = o.qsc ? (const int8_t *) (base + o.qsc) : nullptr; }
         return r;
     };
 
