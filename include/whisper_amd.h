@@ -333,7 +333,7 @@ WHISPER_API int whisper_model_n_text_state (struct whisper_context * ctx);
 WHISPER_API int whisper_model_n_text_head  (struct whisper_context * ctx);
 WHISPER_API int whisper_model_n_text_layer (struct whisper_context * ctx);
 WHISPER_API int whisper_model_n_mels       (struct whisper_context * ctx);
-WHISPER_API int whisper_model_ftype        (struct whisper_context * ctx);   /* loadable: 1 F16, 7 Q8_0, 8 Q5_0, 9 Q5_1, 3 Q4_1, 13 Q5_K, 14 Q6_K */
+WHISPER_API int whisper_model_ftype        (struct whisper_context * ctx);   /* loadable: 1 F16, 7 Q8_0, 8 Q5_0, 9 Q5_1, 3 Q4_1, 10 Q2_K, 11 Q3_K, 13 Q5_K, 14 Q6_K */
 WHISPER_API int whisper_model_type         (struct whisper_context * ctx);
 WHISPER_API const char * whisper_model_type_readable(struct whisper_context * ctx);
 
@@ -484,7 +484,7 @@ WHISPER_API int whisper_amd_decode_step_probe(struct whisper_context * ctx, stru
 
 /* 1 when the state runs the single-token decoder pass as ONE persistent launch (wa_mega.hip), 0 when it replays the
  * captured launch sequence (WHISPER_AMD_NO_MEGA=1, unsupported shape, after a hand-off time-out, or a model whose weight format has no
- * one-launch kernel: Q5_1 / Q4_1 and Q5_K / Q6_K files run the launch sequence in every decode mode, and whisper_amd_rows_enabled is 0 too). */
+ * one-launch kernel: Q5_1 / Q4_1 and Q2_K / Q3_K / Q5_K / Q6_K files run the launch sequence in every decode mode, and whisper_amd_rows_enabled is 0 too). */
 WHISPER_API int whisper_amd_mega_enabled(struct whisper_state * state);
 /* Role of workgroup `wg` of the n_wg workgroups of the one-launch step for a model with n_head text heads (no device needed): role 0 =
  * weight streaming (index = its rank), 1 = self-attention of head `index`, 2 = cross-attention (index = 4 head + quarter). */

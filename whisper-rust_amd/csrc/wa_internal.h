@@ -71,14 +71,15 @@ struct wa_ln  { const float * w = nullptr; const float * b = nullptr; };
 // 6 Q5_0 / 8 Q8_0 / 3 Q4_1 / 7 Q5_1): qs = the quants as signed bytes [n_out][8][n_in/32][4] (element 4l + e of block b at [row][l][b][e];
 // the 4- and 5-bit values expanded at load), qd [n_out][n_in/32] the block scales widened from F16 to F32 (exact); Q4_1 / Q5_1 only
 // (wa_quant1.h): qm [n_out][n_in/32] the block minimums likewise, and the quants are the unsigned values 0..15 / 0..31.
-// K formats (wtype 13 Q5_K / 14 Q6_K, 256-value blocks; wa_quantk.h): qs [n_out][8][n_in/256][8][4] (Q6_K as q - 32, Q5_K 0..31), qsc
-// [n_out][n_in/256][16] the sub-block scale (and minimum) bytes, qd [n_out][n_in/256] the block's d and - Q5_K only - qm its dmin.
+// K formats (wtype 10 Q2_K / 11 Q3_K / 13 Q5_K / 14 Q6_K, 256-value blocks; wa_quantk.h): qs [n_out][8][n_in/256][8][4] (Q6_K as q - 32,
+// Q5_K 0..31, Q3_K -4..3, Q2_K 0..3), qsc [n_out][n_in/256][16] the sub-block scale (and minimum) bytes, qd [n_out][n_in/256] the block's d
+// and - Q5_K and Q2_K only - qm its dmin.
 struct wa_lin {
     const wa_f16 * w = nullptr; const float * b = nullptr; const float * s = nullptr; int n_out = 0, n_in = 0;
     int wtype = 1; const int8_t * qs = nullptr; const float * qd = nullptr; const float * qm = nullptr; const int8_t * qsc = nullptr;
 };
 inline bool wa_wtype_has_min(int wtype) { return wtype == 3 || wtype == 7; }     // Q4_1, Q5_1: multiplied with Q8_1 activation rows
-inline bool wa_wtype_k(int wtype) { return wtype == 13 || wtype == 14; }          // Q5_K, Q6_K: multiplied with Q8_K activation rows (wa_quantk.hip)
+inline bool wa_wtype_k(int wtype) { return wtype == 13 || wtype == 14 || wtype == 10 || wtype == 11; }   // Q5_K, Q6_K, Q2_K, Q3_K: multiplied with Q8_K activation rows (wa_quantk.hip)
 
 struct wa_enc_layer {
     wa_ln  attn_ln, mlp_ln;
@@ -100,7 +101,7 @@ struct wa_model {
     int n_mel_filt = 0, n_fft_filt = 0;
     std::vector<float> filters;     // host copy [n_mel][n_fft]
     int n_loaded = 0;               // 0 => header/vocab-only test model (ref: whisper.cpp:1959-1960)
-    int wtype = 1;                  // ggml type of the 2-D weight matrices: 1 F16, 6 Q5_0, 8 Q8_0, 3 Q4_1, 7 Q5_1, 13 Q5_K, 14 Q6_K (whisper.cpp:1567-1573)
+    int wtype = 1;                  // ggml type of the 2-D weight matrices: 1 F16, 6 Q5_0, 8 Q8_0, 3 Q4_1, 7 Q5_1, 10 Q2_K, 11 Q3_K, 13 Q5_K, 14 Q6_K (whisper.cpp:1567-1573)
 
     // ---- device (all inside `arena`) ----
     void * arena = nullptr; size_t arena_size = 0;
@@ -265,7 +266,7 @@ struct whisper_state {
     int      q8_rows = 0;
     float  * d_q8d  = nullptr;      // [tpad][4d / 32]
     float  * d_q8s  = nullptr;      // [tpad][4d / 32]  Q4_1 / Q5_1 models only: the Q8_1 block sums of those rows (wa_quant1.h), else null
-    // Q5_K / Q6_K models: d_q8 holds Q8_K rows (K bytes each, wa_quantk.h order), d_q8d their K / 256 scales, and
+    // K-format models: d_q8 holds Q8_K rows (K bytes each, wa_quantk.h order), d_q8d their K / 256 scales, and
     int16_t * d_q8bs = nullptr;     // [tpad][4d / 16]  their 16-element sums; else null
 
     // hipGraph of the single-token decoder pass (launch-bound inner loop); parameters that change per token live in d_dyn

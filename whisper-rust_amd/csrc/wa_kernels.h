@@ -126,15 +126,15 @@ void wa_launch_qgemv_gelu_q8(hipStream_t stream, const int8_t * xq, const float 
 void wa_launch_dec_embed_q(hipStream_t stream, const int32_t * tok, const int32_t * pos, int n_tokens, int d, const int8_t * wq, const float * wd,
                            const float * pe, float * x, const float * wm = nullptr);
 
-// ---- Q5_K / Q6_K weights (wa_quantk.hip; the arithmetic and the layout are stated in wa_quantk.h): ggml's K-format x Q8_K products in the
-// reference's AVX2 order.  wtype = ggml type 13 (Q5_K) or 14 (Q6_K); K % 256 == 0.  A weight matrix is wq int8 [N][8][K/256][8][4], wsc int8
-// [N][K/256][16], wd f32 [N][K/256] and - Q5_K only, else null - wdm f32 [N][K/256]; an activation row is xq (the same quant order), xd f32
+// ---- Q2_K / Q3_K / Q5_K / Q6_K weights (wa_quantk.hip; the arithmetic and the layout are stated in wa_quantk.h): ggml's K-format x Q8_K products
+// in the reference's AVX2 order.  wtype = ggml type 10 (Q2_K), 11 (Q3_K), 13 (Q5_K) or 14 (Q6_K); K % 256 == 0.  A weight matrix is wq int8
+// [N][8][K/256][8][4], wsc int8 [N][K/256][16], wd f32 [N][K/256] and - Q5_K and Q2_K only, else null - wdm f32 [N][K/256]; an activation row is xq (the same quant order), xd f32
 // [K/256] and xbs int16 [K/16].
 // quantize_row_q8_K: x f32 [rows][ldx] (ldx % 4 == 0, 16-byte aligned rows) -> qs, qd, qbs
 void wa_launch_quantize_q8_K(hipStream_t stream, const float * x, int ldx, int rows, int K, int8_t * qs, float * qd, int16_t * qbs);
-// C[M][N] = xq . Wq^T in ggml_vec_dot_q5_K_q8_K / q6_K_q8_K order, any M; the epilogues of wa_launch_qgemm_exact
+// C[M][N] = xq . Wq^T in ggml_vec_dot_q2_K_q8_K / q3_K_q8_K / q5_K_q8_K / q6_K_q8_K order, any M; the epilogues of wa_launch_qgemm_exact
 void wa_launch_kgemm_exact(hipStream_t stream, wa_epi_mode mode, int wtype, const int8_t * xq, const float * xd, const int16_t * xbs, int M, const int8_t * wq,
                            const int8_t * wsc, const float * wd, const float * wdm, int N, int K, const wa_epi & e);
-// token embedding rows of such a matrix (dequantize_row_q5_K / q6_K) + positional embedding
+// token embedding rows of such a matrix (dequantize_row_q2_K / q3_K / q5_K / q6_K) + positional embedding
 void wa_launch_dec_embed_k(hipStream_t stream, int wtype, const int32_t * tok, const int32_t * pos, int n_tokens, int d, const int8_t * wq, const int8_t * wsc,
                            const float * wd, const float * wdm, const float * pe, float * x);

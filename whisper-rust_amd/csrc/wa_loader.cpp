@@ -36,7 +36,7 @@ struct slot {             // where a named tensor goes
     int    kind;          // 0 raw copy, 1 conv weight re-order ([oc][ic][3] -> [oc][3][ic], row stride ld),
                           // 2 quantised blocks -> kernel layout (off = signed quant bytes [row][8][block][4], off3 = scales [row][block],
                           //   off4 = minimums [row][block] of the formats that have one; K formats, 256-value blocks (wa_quantk.h): off = quants
-                          //   [row][8][block][8][4], off5 = scale bytes [row][block][16], off3 = d [row][block], off4 = dmin [row][block] of Q5_K)
+                          //   [row][8][block][8][4], off5 = scale bytes [row][block][16], off3 = d [row][block], off4 = dmin [row][block] of Q5_K / Q2_K)
     size_t off;           // byte offset in the arena
     int    type;          // expected ggml type: 0 f32, 1 f16
     int64_t ne[3];        // expected ne[] (fastest first)
@@ -109,14 +109,14 @@ bool wa_model_load(whisper_model_loader * loader, whisper_context & wctx) {
                      hp.n_text_ctx, hp.n_vocab);
             return false;
         }
-        // ftype % 1000 names the type of the 2-D weights (whisper.cpp:1567-1573; ggml_ftype: 1 F16, 3 Q4_1, 7 Q8_0, 8 Q5_0, 9 Q5_1, 13 Q5_K, 14 Q6_K - for the
+        // ftype % 1000 names the type of the 2-D weights (whisper.cpp:1567-1573; ggml_ftype: 1 F16, 3 Q4_1, 7 Q8_0, 8 Q5_0, 9 Q5_1, 10 Q2_K, 11 Q3_K, 13 Q5_K, 14 Q6_K - for the
         // K formats the ftype number is the ggml type number too).  ftype 0
         // (all-F32) aborts in the reference's own conv path; Q4_0 runs through the reference's repacked 8-row product, a
-        // summation order of its own that is not restated here, and so does Q4_K; the other quantised formats (Q2_K, Q3_K, ...) are not built.
+        // summation order of its own that is not restated here, and so does Q4_K; the other quantised formats (the IQ family) are not built.
         const int ft = hp.ftype % 1000;
-        model.wtype = ft == 1 ? 1 : ft == 8 ? 6 : ft == 7 ? 8 : ft == 3 ? 3 : ft == 9 ? 7 : ft == 13 ? 13 : ft == 14 ? 14 : -1;
+        model.wtype = ft == 1 ? 1 : ft == 8 ? 6 : ft == 7 ? 8 : ft == 3 ? 3 : ft == 9 ? 7 : ft == 13 ? 13 : ft == 14 ? 14 : ft == 10 ? 10 : ft == 11 ? 11 : -1;
         if (model.wtype < 0) {
-            WA_ERROR("%s: unsupported ftype %d (this backend loads F16, Q8_0, Q5_0, Q5_1, Q4_1, Q5_K and Q6_K models)\n", __func__, hp.ftype);
+            WA_ERROR("%s: unsupported ftype %d (this backend loads F16, Q8_0, Q5_0, Q5_1, Q4_1, Q2_K, Q3_K, Q5_K and Q6_K models)\n", __func__, hp.ftype);
             return false;
         }
     }
@@ -186,7 +186,7 @@ bool wa_model_load(whisper_model_loader * loader, whisper_context & wctx) {
         return false;
     }
     if (wa_wtype_k(model.wtype) && d % WA_QK_K != 0) {      // every quantised row is d or 4 d long (tiny's 384 does not qualify)
-        WA_ERROR("%s: a %s model needs row lengths that are a multiple of 256, n_audio_state is %d\n", __func__, model.wtype == 13 ? "Q5_K" : "Q6_K", d);
+        WA_ERROR("%s: a %s model needs row lengths that are a multiple of 256, n_audio_state is %d\n", __func__, model.wtype == 13 ? "Q5_K" : model.wtype == 14 ? "Q6_K" : model.wtype == 10 ? "Q2_K" : "Q3_K", d);
         return false;
     }
     if (model.n_mel_filt != hp.n_mels) { WA_ERROR("%s: mel filter count %d != n_mels %d\n", __func__, model.n_mel_filt, hp.n_mels); return false; }
@@ -208,17 +208,17 @@ bool wa_model_load(whisper_model_loader * loader, whisper_context & wctx) {
     const size_t o_gelu    = ab.take(65536 * H);
 
     struct lin_off { size_t w, b, s; size_t qs = 0, qh = 0, qd = 0, qm = 0, qsc = 0; };
-    const int QT = model.wtype;                                  // 1, 6, 8, 3, 7, 13 or 14
+    const int QT = model.wtype;                                  // 1, 6, 8, 3, 7, 10, 11, 13 or 14
     // Kernel layout of a quantised [n_out][n_in] matrix: the quants as signed bytes (Q5_0's 5-bit values are expanded once, here),
     // ordered [row][lane l = 0..7][block][4] - lane l of a row's 8-lane group owns elements 4l..4l+3 of EVERY block, so its bytes
     // are contiguous over the blocks (16-byte loads cover four blocks) - and the block scales [row][block] as F32.  Q4_1 / Q5_1: the
     // quants are the unsigned 4- / 5-bit values, and a third array holds the block minimums [row][block] as F32 (wa_quant1.h).
-    // Q5_K / Q6_K (wa_quantk.h): 256-value blocks - quants [row][lane][block][group][4], 16 scale bytes and d (Q5_K: and dmin) per block.
+    // K formats (wa_quantk.h): 256-value blocks - quants [row][lane][block][group][4], 16 scale bytes and d (Q5_K, Q2_K: and dmin) per block.
     const bool QMIN = wa_wtype_has_min(QT), QK = wa_wtype_k(QT);
     auto take_q = [&](lin_off & o, size_t n_out, size_t n_in) {
         if (QK) {
             o.qs = ab.take(n_out * n_in); o.qsc = ab.take(n_out * (n_in / 256) * 16); o.qd = ab.take(n_out * (n_in / 256) * 4);
-            if (QT == 13) o.qm = ab.take(n_out * (n_in / 256) * 4);
+            if (wa_qk_has_min(QT)) o.qm = ab.take(n_out * (n_in / 256) * 4);
             return;
         }
         o.qs = ab.take(n_out * n_in); o.qh = 0; o.qd = ab.take(n_out * (n_in / 32) * 4);
@@ -386,7 +386,7 @@ bool wa_model_load(whisper_model_loader * loader, whisper_context & wctx) {
         }
         const size_t nbytes = wa_qk_block_bytes(s.type) ? (size_t) nelements / WA_QK_K * wa_qk_block_bytes(s.type) : s.type == 6 ? (size_t) nelements / 32 * 22 : s.type == 8 ? (size_t) nelements / 32 * 34 :
                               wa_q1_block_bytes(s.type) ? (size_t) nelements / 32 * wa_q1_block_bytes(s.type) : (size_t) nelements * (s.type == 0 ? F : H);
-        if (s.kind == 2 && wa_qk_block_bytes(s.type)) {        // block_q5_K / block_q6_K -> the arrays of wa_quantk.h
+        if (s.kind == 2 && wa_qk_block_bytes(s.type)) {        // block_q2_K / q3_K / q5_K / q6_K -> the arrays of wa_quantk.h
             tmp.resize(nbytes);
             if (loader->read(loader->context, tmp.data(), nbytes) != nbytes) { WA_ERROR("%s: truncated tensor '%s'\n", __func__, name.c_str()); return false; }
             const size_t bsz = wa_qk_block_bytes(s.type), nbr = (size_t) s.ne[0] / WA_QK_K, rows = (size_t) s.ne[1];

@@ -1,4 +1,4 @@
-// wa_quantk.hip - Q5_K / Q6_K weights (ggml K formats, 256-value blocks) in the reference's order.  The arithmetic is stated in host
+// wa_quantk.hip - Q2_K / Q3_K / Q5_K / Q6_K weights (ggml K formats, 256-value blocks) in the reference's order.  The arithmetic is stated in host
 // code in wa_quantk.h; these kernels restate it.
 //
 // With such a matrix the reference quantises the F32 activation row to Q8_K (quantize_row_q8_K_ref: the scale comes from the FIRST
@@ -15,6 +15,13 @@
 // Layout (wa_quantk.h, made at load by wa_loader.cpp): quants int8 [row][lane][block][group][4] - a lane's 32 bytes of a block are two
 // 16-byte loads -, scale bytes [row][block][16] (Q6_K: the lane's half first / second eight; Q5_K: scales, then minimums), d / dmin f32
 // [row][block].  Activation rows: the same quant order, d f32 [row][block], the 16-element sums int16 [row][block][16].
+// Q3_K, unpacked at load (quants -4..3, signed 6-bit scales in Q6_K's order, one d), IS a Q6_K matrix: it runs the Q6_K instantiations.
+// Q2_K (quants 0..3; scale bytes in Q6_K's order, the scale in the low nibble and the minimum in the high one; d and dmin) is a format of
+// its own (WK_Q2): the minimums go into the LANE accumulators, per block before the product term and by an fma of their own,
+//     acc[l] = fma( -d_x * f32(dmin_w), (float) (m[2 l] * bsums[2 l] + m[2 l + 1] * bsums[2 l + 1]), acc[l] ),  then the fma above,
+// and lane l's two minimums are bytes l and 8 + l of the block's 16: no exchange between lanes, with one activation row or with eight.
+// This file is compiled twice: wa_quantk.o holds everything but Q2_K, wa_quantk_q2.o (-DWA_QK_Q2_TU) the Q2_K instantiations of the two
+// products and their launcher - a code object of their own beside the fourteen + fourteen of Q5_K / Q6_K.
 #include "wa_device.h"
 
 typedef int wk_i4 __attribute__((ext_vector_type(4)));
@@ -38,22 +45,23 @@ __device__ __forceinline__ float wk_from_lane(float v, int m) {      // lane 0 o
         case 5: return dpp_f32<0x105>(v); case 6: return dpp_f32<0x106>(v); case 7: return dpp_f32<0x107>(v); default: return v;
     }
 }
-// byte g (0..7) of the scale pair s: signed (Q6_K) or unsigned (Q5_K, values <= 63)
-template <bool SIGNED> __device__ __forceinline__ int wk_byte(wk_i2 s, int g) {
+enum { WK_Q6 = 0, WK_Q5 = 1, WK_Q2 = 2 };      // the weight format of an instantiation (Q3_K runs as WK_Q6)
+// byte g (0..7) of the scale pair s: signed (Q6_K), unsigned (Q5_K, values <= 63) or its low nibble (Q2_K)
+template <int F> __device__ __forceinline__ int wk_byte(wk_i2 s, int g) {
     const int w = g < 4 ? s.x : s.y, sh = 8 * (g & 3);
-    return SIGNED ? (w << (24 - sh)) >> 24 : (int) (((unsigned) w >> sh) & 0xffu);
+    return F == WK_Q6 ? (w << (24 - sh)) >> 24 : (int) (((unsigned) w >> sh) & (F == WK_Q2 ? 0xfu : 0xffu));
 }
 // the integer sum of one lane over one 256-value block: 8 groups, quads w0 | w1 against x0 | x1, scale bytes s
-template <bool SIGNED> __device__ __forceinline__ int wk_block(wk_i4 w0, wk_i4 w1, wk_i4 x0, wk_i4 x1, wk_i2 s) {
+template <int F> __device__ __forceinline__ int wk_block(wk_i4 w0, wk_i4 w1, wk_i4 x0, wk_i4 x1, wk_i2 s) {
     int t = 0;
-    t += wk_byte<SIGNED>(s, 0) * __builtin_amdgcn_sdot4(w0.x, x0.x, 0, false);
-    t += wk_byte<SIGNED>(s, 1) * __builtin_amdgcn_sdot4(w0.y, x0.y, 0, false);
-    t += wk_byte<SIGNED>(s, 2) * __builtin_amdgcn_sdot4(w0.z, x0.z, 0, false);
-    t += wk_byte<SIGNED>(s, 3) * __builtin_amdgcn_sdot4(w0.w, x0.w, 0, false);
-    t += wk_byte<SIGNED>(s, 4) * __builtin_amdgcn_sdot4(w1.x, x1.x, 0, false);
-    t += wk_byte<SIGNED>(s, 5) * __builtin_amdgcn_sdot4(w1.y, x1.y, 0, false);
-    t += wk_byte<SIGNED>(s, 6) * __builtin_amdgcn_sdot4(w1.z, x1.z, 0, false);
-    t += wk_byte<SIGNED>(s, 7) * __builtin_amdgcn_sdot4(w1.w, x1.w, 0, false);
+    t += wk_byte<F>(s, 0) * __builtin_amdgcn_sdot4(w0.x, x0.x, 0, false);
+    t += wk_byte<F>(s, 1) * __builtin_amdgcn_sdot4(w0.y, x0.y, 0, false);
+    t += wk_byte<F>(s, 2) * __builtin_amdgcn_sdot4(w0.z, x0.z, 0, false);
+    t += wk_byte<F>(s, 3) * __builtin_amdgcn_sdot4(w0.w, x0.w, 0, false);
+    t += wk_byte<F>(s, 4) * __builtin_amdgcn_sdot4(w1.x, x1.x, 0, false);
+    t += wk_byte<F>(s, 5) * __builtin_amdgcn_sdot4(w1.y, x1.y, 0, false);
+    t += wk_byte<F>(s, 6) * __builtin_amdgcn_sdot4(w1.z, x1.z, 0, false);
+    t += wk_byte<F>(s, 7) * __builtin_amdgcn_sdot4(w1.w, x1.w, 0, false);
     return t;
 }
 
@@ -61,6 +69,7 @@ template <bool SIGNED> __device__ __forceinline__ int wk_block(wk_i4 w0, wk_i4 w
 // quantize_row_q8_K_ref: one wave per 256-value block, lane i holds elements 4 i .. 4 i + 3.  The arg-max keeps the FIRST index on ties
 // (opposite signs included): strictly-greater inside the lane, then the lowest lane that holds the wave's maximum.
 // -------------------------------------------------------------------------------------------------
+#ifndef WA_QK_Q2_TU
 __global__ __launch_bounds__(256) void k_quantize_q8_K(const float * __restrict__ x, int ldx, int rows, int K, int8_t * __restrict__ qs,
                                                        float * __restrict__ qd, int16_t * __restrict__ qbs) {
     const int nb = K >> 8;
@@ -97,18 +106,20 @@ void wa_launch_quantize_q8_K(hipStream_t stream, const float * x, int ldx, int r
     const long nblk = (long) rows * (K >> 8);
     hipLaunchKernelGGL(k_quantize_q8_K, dim3((unsigned) ((nblk + 3) / 4)), dim3(256), 0, stream, x, ldx, rows, K, qs, qd, qbs);
 }
+#endif
 
 // -------------------------------------------------------------------------------------------------
 // M == 1 (the decode step): grid = ceil(N / 8) single-wave workgroups, 8 output rows x 8 lanes each; no LDS.
 // One output row per 8 lanes: the row's dot product with the activation row (valid in lane l == 0 of the group).
 // -------------------------------------------------------------------------------------------------
-template <bool Q5>
+template <int F>
 __device__ __forceinline__ float wk_row_dot(const int8_t * __restrict__ xq, const float * __restrict__ xd, const int16_t * __restrict__ xbs,
                                             const int8_t * __restrict__ wq, const int8_t * __restrict__ wsc, const float * __restrict__ wd,
                                             const float * __restrict__ wdm, int nn, int nb, int l) {
     const wk_i4 * wl = (const wk_i4 *) (wq + ((size_t) nn * 8 + l) * nb * 32);
     const wk_i4 * xl = (const wk_i4 *) (xq + (size_t) l * nb * 32);
-    // Q6_K: the lane's half of the 16 scales; Q5_K: the 8 scales (the minimums are the second eight)
+    constexpr bool Q5 = F == WK_Q5;
+    // Q6_K, Q2_K: the lane's half of the 16 scales; Q5_K: the 8 scales (the minimums are the second eight)
     const int8_t * sl = wsc + (size_t) nn * nb * 16 + (Q5 ? 0 : 8 * (l >> 2));
     const float * dl = wd + (size_t) nn * nb;
     float acc = 0.0f, summs = 0.0f;
@@ -118,7 +129,14 @@ __device__ __forceinline__ float wk_row_dot(const int8_t * __restrict__ xq, cons
         const wk_i2 s = *(const wk_i2 *) (sl + 16 * b);
         const float dx = xd[b];
         const float dd = dx * dl[b];
-        const int t = wk_block<!Q5>(w0, w1, x0, x1, s);
+        const int t = wk_block<F>(w0, w1, x0, x1, s);
+        if (F == WK_Q2) {                 // this lane's sub-blocks 2 l and 2 l + 1: bytes l and 8 + l of the block's scales, the minimum in the high nibble
+            const uint8_t * sb = (const uint8_t *) wsc + ((size_t) nn * nb + b) * 16;
+            const int bs2 = *(const int *) (xbs + 16 * b + 2 * l);
+            const int mins = (int) (sb[l] >> 4) * ((bs2 << 16) >> 16) + (int) (sb[8 + l] >> 4) * (bs2 >> 16);
+            const float dn = -dx * wdm[(size_t) nn * nb + b];
+            acc = fmaf(dn, (float) mins, acc);
+        }
         acc = fmaf(dd, (float) t, acc);
         if (Q5) {
             const int mb = (int) (unsigned char) sl[16 * b + 8 + l];                   // this lane's group: m[l] * (bsums[2 l] + bsums[2 l + 1])
@@ -133,7 +151,7 @@ __device__ __forceinline__ float wk_row_dot(const int8_t * __restrict__ xq, cons
     return Q5 ? v + summs : v;
 }
 
-template <int EPI, bool Q5>
+template <int EPI, int F>
 __global__ __launch_bounds__(64) void k_kgemv_exact(const int8_t * __restrict__ xq, const float * __restrict__ xd, const int16_t * __restrict__ xbs,
                                                     const int8_t * __restrict__ wq, const int8_t * __restrict__ wsc, const float * __restrict__ wd,
                                                     const float * __restrict__ wdm, int N, int K, wa_epi e) {
@@ -142,18 +160,19 @@ __global__ __launch_bounds__(64) void k_kgemv_exact(const int8_t * __restrict__ 
     const int nn = n < N ? n : N - 1;
     wa_epi_pre pre;
     if (l == 0) pre = epi_preload<EPI>(e, 0, nn);
-    const float v = wk_row_dot<Q5>(xq, xd, xbs, wq, wsc, wd, wdm, nn, K >> 8, l);
+    const float v = wk_row_dot<F>(xq, xd, xbs, wq, wsc, wd, wdm, nn, K >> 8, l);
     if (l == 0 && n < N) epi_apply<EPI>(e, 0, n, v, pre);
 }
 
 // -------------------------------------------------------------------------------------------------
 // C[M][N] = xq Wq^T, M > 1; grid = (ceil(N / 32), ceil(M / 8)); 256 threads = 32 output rows x 8 lanes; the 8 activation rows in LDS
 // -------------------------------------------------------------------------------------------------
-template <int EPI, bool Q5>
+template <int EPI, int F>
 __global__ __launch_bounds__(256) void k_kgemm_exact(const int8_t * __restrict__ xq, const float * __restrict__ xd, const int16_t * __restrict__ xbs, int M,
                                                      const int8_t * __restrict__ wq, const int8_t * __restrict__ wsc, const float * __restrict__ wd,
                                                      const float * __restrict__ wdm, int N, int K, wa_epi e) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];       // xs int8 [8][K] (kernel layout) | xds f32 [8][K/256] | Q5: xgs i32 [8][K/256][8]
+    constexpr bool Q5 = F == WK_Q5;                                            // | Q2: xgs = the rows' 16-element sums in pairs, i16 x 2 [8][K/256][8]
     const int nb = K >> 8;
     int8_t * xs = (int8_t *) smem;
     float * xds = (float *) (smem + (size_t) 8 * K);
@@ -177,6 +196,11 @@ __global__ __launch_bounds__(256) void k_kgemm_exact(const int8_t * __restrict__
             if (m < mt) { const int bs2 = *(const int *) (xbs + (size_t) (m0 + m) * nb * 16 + 2 * r); s = ((bs2 << 16) >> 16) + (bs2 >> 16); }
             xgs[c] = s;
         }
+    if (F == WK_Q2)
+        for (int c = tid; c < 8 * nb * 8; c += 256) {          // bsums[2 l] | bsums[2 l + 1] << 16, as they lie in memory
+            const int m = c / (nb * 8), r = c - m * (nb * 8);
+            xgs[c] = m < mt ? *(const int *) (xbs + (size_t) (m0 + m) * nb * 16 + 2 * r) : 0;
+        }
     __syncthreads();
     const int n = blockIdx.x * 32 + (tid >> 3);
     const int nn = n < N ? n : N - 1;
@@ -195,17 +219,28 @@ __global__ __launch_bounds__(256) void k_kgemm_exact(const int8_t * __restrict__
         const wk_i4 w0 = wl[2 * b], w1 = wl[2 * b + 1];
         const wk_i2 s = *(const wk_i2 *) (sl + 16 * b + (Q5 ? 0 : 8 * (l >> 2)));
         const float dw = dl[b];
+        int ma = 0, mb = 0; float dwm = 0.0f;        // Q2: the minimums of this lane's sub-blocks 2 l and 2 l + 1, and the block's dmin
+        if (F == WK_Q2) {
+            const uint8_t * sb = (const uint8_t *) sl + 16 * b;
+            ma = sb[l] >> 4; mb = sb[8 + l] >> 4; dwm = wdm[(size_t) nn * nb + b];
+        }
 #pragma unroll
         for (int m = 0; m < 8; ++m) {
             const wk_i4 x0 = xl[(size_t) m * (K >> 4) + 2 * b], x1 = xl[(size_t) m * (K >> 4) + 2 * b + 1];
-            const float dd = xds[m * nb + b] * dw;
-            acc[m] = fmaf(dd, (float) wk_block<!Q5>(w0, w1, x0, x1, s), acc[m]);
+            const float dx = xds[m * nb + b];
+            const float dd = dx * dw;
+            if (F == WK_Q2) {                        // the lane owns acc[m] of every activation row: the minimum term first, then the product term
+                const int bs2 = xgs[(m * nb + b) * 8 + l];
+                const float dn = -dx * dwm;
+                acc[m] = fmaf(dn, (float) (ma * ((bs2 << 16) >> 16) + mb * (bs2 >> 16)), acc[m]);
+            }
+            acc[m] = fmaf(dd, (float) wk_block<F>(w0, w1, x0, x1, s), acc[m]);
         }
         if (Q5) {
             const wk_i2 mm = *(const wk_i2 *) (sl + 16 * b + 8);
             const wk_i4 g0 = *(const wk_i4 *) (xgs + (l * nb + b) * 8), g1 = *(const wk_i4 *) (xgs + (l * nb + b) * 8 + 4);
-            const int tot = wk_byte<false>(mm, 0) * g0.x + wk_byte<false>(mm, 1) * g0.y + wk_byte<false>(mm, 2) * g0.z + wk_byte<false>(mm, 3) * g0.w +
-                            wk_byte<false>(mm, 4) * g1.x + wk_byte<false>(mm, 5) * g1.y + wk_byte<false>(mm, 6) * g1.z + wk_byte<false>(mm, 7) * g1.w;
+            const int tot = wk_byte<WK_Q5>(mm, 0) * g0.x + wk_byte<WK_Q5>(mm, 1) * g0.y + wk_byte<WK_Q5>(mm, 2) * g0.z + wk_byte<WK_Q5>(mm, 3) * g0.w +
+                            wk_byte<WK_Q5>(mm, 4) * g1.x + wk_byte<WK_Q5>(mm, 5) * g1.y + wk_byte<WK_Q5>(mm, 6) * g1.z + wk_byte<WK_Q5>(mm, 7) * g1.w;
             const float dm = -xds[l * nb + b] * wdm[(size_t) nn * nb + b];
             const float p = dm * (float) tot;
             summs = summs + p;
@@ -219,29 +254,43 @@ __global__ __launch_bounds__(256) void k_kgemm_exact(const int8_t * __restrict__
     }
 }
 
-void wa_launch_kgemm_exact(hipStream_t s, wa_epi_mode mode, int wtype, const int8_t * xq, const float * xd, const int16_t * xbs, int M, const int8_t * wq,
-                           const int8_t * wsc, const float * wd, const float * wdm, int N, int K, const wa_epi & e) {
+// one format's instantiations: M == 1 the one-row kernel, else the 8-row kernel with its LDS (the Q8_K rows; Q5_K, Q2_K: and their sums)
+template <int F>
+static void wk_launch(hipStream_t s, wa_epi_mode mode, const int8_t * xq, const float * xd, const int16_t * xbs, int M, const int8_t * wq,
+                      const int8_t * wsc, const float * wd, const float * wdm, int N, int K, const wa_epi & e) {
     const dim3 grid((N + 31) / 32, (M + 7) / 8);
-    const bool q5 = wtype == 13;
-    const size_t lds = (size_t) 8 * K + (size_t) 8 * (K >> 8) * sizeof(float) + (q5 ? (size_t) 8 * (K >> 8) * 8 * sizeof(int) : 0);
-#define WA_CASE_K(E, Q5) { \
-        if (M == 1) { hipLaunchKernelGGL((k_kgemv_exact<E, Q5>), dim3((N + 7) / 8), dim3(64), 0, s, xq, xd, xbs, wq, wsc, wd, wdm, N, K, e); break; } \
-        if (lds > 48 * 1024) (void) hipFuncSetAttribute((const void *) k_kgemm_exact<E, Q5>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds); \
-        hipLaunchKernelGGL((k_kgemm_exact<E, Q5>), grid, dim3(256), lds, s, xq, xd, xbs, M, wq, wsc, wd, wdm, N, K, e); }
-#define WA_CASE(E) case E: if (q5) WA_CASE_K(E, true) else WA_CASE_K(E, false) break;
+    const size_t lds = (size_t) 8 * K + (size_t) 8 * (K >> 8) * sizeof(float) + (F != WK_Q6 ? (size_t) 8 * (K >> 8) * 8 * sizeof(int) : 0);
+#define WA_CASE(E) case E: { \
+        if (M == 1) { hipLaunchKernelGGL((k_kgemv_exact<E, F>), dim3((N + 7) / 8), dim3(64), 0, s, xq, xd, xbs, wq, wsc, wd, wdm, N, K, e); break; } \
+        if (lds > 48 * 1024) (void) hipFuncSetAttribute((const void *) k_kgemm_exact<E, F>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds); \
+        hipLaunchKernelGGL((k_kgemm_exact<E, F>), grid, dim3(256), lds, s, xq, xd, xbs, M, wq, wsc, wd, wdm, N, K, e); } break;
     switch (mode) {
         WA_CASE(WA_EPI_F16) WA_CASE(WA_EPI_ENC_QKV) WA_CASE(WA_EPI_GELU_F32) WA_CASE(WA_EPI_RESID) WA_CASE(WA_EPI_F32) WA_CASE(WA_EPI_CROSS_KV) WA_CASE(WA_EPI_DEC_QKV)
         default: break;
     }
 #undef WA_CASE
-#undef WA_CASE_K
+}
+
+#ifdef WA_QK_Q2_TU
+void wa_launch_kgemm_q2(hipStream_t s, wa_epi_mode mode, const int8_t * xq, const float * xd, const int16_t * xbs, int M, const int8_t * wq,
+                        const int8_t * wsc, const float * wd, const float * wdm, int N, int K, const wa_epi & e) {
+    wk_launch<WK_Q2>(s, mode, xq, xd, xbs, M, wq, wsc, wd, wdm, N, K, e);
+}
+#else
+void wa_launch_kgemm_q2(hipStream_t s, wa_epi_mode mode, const int8_t * xq, const float * xd, const int16_t * xbs, int M, const int8_t * wq,
+                        const int8_t * wsc, const float * wd, const float * wdm, int N, int K, const wa_epi & e);      // wa_quantk_q2.o
+void wa_launch_kgemm_exact(hipStream_t s, wa_epi_mode mode, int wtype, const int8_t * xq, const float * xd, const int16_t * xbs, int M, const int8_t * wq,
+                           const int8_t * wsc, const float * wd, const float * wdm, int N, int K, const wa_epi & e) {
+    if (wtype == 13) wk_launch<WK_Q5>(s, mode, xq, xd, xbs, M, wq, wsc, wd, wdm, N, K, e);
+    else if (wtype == 10) wa_launch_kgemm_q2(s, mode, xq, xd, xbs, M, wq, wsc, wd, wdm, N, K, e);
+    else wk_launch<WK_Q6>(s, mode, xq, xd, xbs, M, wq, wsc, wd, wdm, N, K, e);        // Q6_K, and Q3_K as the loader unpacks it
 }
 
 // -------------------------------------------------------------------------------------------------
-// ggml_get_rows on the quantised token embedding (dequantize_row_q6_K: (d * sc) * q; dequantize_row_q5_K: (d * sc) * q, then
-// - (dmin * m): no fma) + positional embedding
+// ggml_get_rows on the quantised token embedding (dequantize_row_q6_K / q3_K: (d * sc) * q; dequantize_row_q5_K / q2_K: (d * sc) * q,
+// then - (dmin * m): no fma) + positional embedding.  fmt: WK_Q6 (Q6_K, Q3_K), WK_Q5 or WK_Q2
 // -------------------------------------------------------------------------------------------------
-__global__ void k_dec_embed_k(const int32_t * __restrict__ tok, const int32_t * __restrict__ pos, int n_tokens, int d, int q5,
+__global__ void k_dec_embed_k(const int32_t * __restrict__ tok, const int32_t * __restrict__ pos, int n_tokens, int d, int fmt,
                               const int8_t * __restrict__ wq, const int8_t * __restrict__ wsc, const float * __restrict__ wd, const float * __restrict__ wdm,
                               const float * __restrict__ pe, float * __restrict__ x) {
     const int j = blockIdx.x;
@@ -252,9 +301,15 @@ __global__ void k_dec_embed_k(const int32_t * __restrict__ tok, const int32_t * 
         const int8_t * sc = wsc + ((size_t) t * nb + b) * 16;
         const float db = wd[(size_t) t * nb + b];
         float v;
-        if (q5) {
+        if (fmt == WK_Q5) {
             const float d1 = db * (float) (int) (unsigned char) sc[el >> 5];
             const float m1 = wdm[(size_t) t * nb + b] * (float) (int) (unsigned char) sc[8 + (el >> 5)];
+            const float tq = d1 * (float) q;
+            v = tq - m1;
+        } else if (fmt == WK_Q2) {
+            const int sb = (int) (unsigned char) sc[8 * ((el >> 4) & 1) + (el >> 5)];
+            const float d1 = db * (float) (sb & 15);
+            const float m1 = wdm[(size_t) t * nb + b] * (float) (sb >> 4);
             const float tq = d1 * (float) q;
             v = tq - m1;
         } else {
@@ -266,5 +321,6 @@ __global__ void k_dec_embed_k(const int32_t * __restrict__ tok, const int32_t * 
 }
 void wa_launch_dec_embed_k(hipStream_t stream, int wtype, const int32_t * tok, const int32_t * pos, int n_tokens, int d, const int8_t * wq, const int8_t * wsc,
                            const float * wd, const float * wdm, const float * pe, float * x) {
-    hipLaunchKernelGGL(k_dec_embed_k, dim3(n_tokens), dim3(256), 0, stream, tok, pos, n_tokens, d, wtype == 13 ? 1 : 0, wq, wsc, wd, wdm, pe, x);
+    hipLaunchKernelGGL(k_dec_embed_k, dim3(n_tokens), dim3(256), 0, stream, tok, pos, n_tokens, d, wtype == 13 ? WK_Q5 : wtype == 10 ? WK_Q2 : WK_Q6, wq, wsc, wd, wdm, pe, x);
 }
+#endif
