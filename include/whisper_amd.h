@@ -518,14 +518,19 @@ WHISPER_API int whisper_amd_rows_step_probe(struct whisper_context * ctx, struct
 /* Chunk-parallel transcription on ONE device (the reference's model: one state + thread per chunk, whisper.cpp:7771-7806):
  * runs `n_chunks` independent whisper_full_with_state jobs, each on its own state / HIP stream / host thread; mel, encoder and
  * prompts overlap on the device, and the single-token decode steps of the chunks are served in LOCK STEP - one decoder pass reads
- * every weight row once for all chunks' tokens (F16 models; up to 8 rows per pass).  Results are those of each chunk alone.
+ * every weight row once for all chunks' tokens (up to 8 rows per pass; F16 models, and Q5_0 / Q8_0 models where the several-rows one-launch
+ * step of wa_rows.hip takes the shape - the members of any other group decode their tokens alone).
+ * Results are those of each chunk alone.
  * samples[i] may be host or device pointers.  Returns 0 or the first non-zero per-chunk code. */
 WHISPER_API int whisper_amd_full_batch(struct whisper_context * ctx, struct whisper_state ** states, int n_chunks,
                                        struct whisper_full_params params, const float * const * samples, const int * n_samples);
-/* how the last whisper_amd_full_batch call on this context decoded: lock-step passes and the token rows they served */
+/* how the last whisper_amd_full_batch or whisper_full_parallel call on this context decoded: lock-step passes and the token rows they served */
 WHISPER_API void whisper_amd_batch_stats(struct whisper_context * ctx, long * steps, long * rows);
 /* ... and how many of those passes were ONE launch (wa_rows.hip) rather than the launch sequence */
 WHISPER_API long whisper_amd_batch_one_launch(struct whisper_context * ctx);
+/* ... and how many of them DELIVERED their rows to the members, as one launch or through the launch sequence (`steps` counts every pass the
+ * group formed; the passes not counted here ended with each member decoding its token alone) */
+WHISPER_API long whisper_amd_batch_served(struct whisper_context * ctx);
 
 #ifdef __cplusplus
 }

@@ -2,7 +2,7 @@
 for a kernel trace of that job:   rocprofv3 --kernel-trace --output-format csv -d <dir> -- python3 tools/chunks8_probe.py [model=small] [chunks=8] [reps=2]
 With a trace directory as 4th argument instead (no GPU needed):  python3 tools/chunks8_probe.py - - - <dir>  prints the timeline of the rows kernel
 in the LAST repetition: launches, mean duration, mean gap between consecutive launches, and what ran before the first of them."""
-import csv, glob, os, sys, time
+import csv, ctypes as C, glob, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools")); sys.path.insert(0, os.path.join(ROOT, "whisper-rust_amd"))
 
@@ -58,7 +58,9 @@ name = sys.argv[1] if len(sys.argv) > 1 else "small"
 NB = int(sys.argv[2]) if len(sys.argv) > 2 else 8
 reps = int(sys.argv[3]) if len(sys.argv) > 3 else 2
 os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
-lib = W.load_library(os.environ.get("WA_LIB")); W.set_log_callback(lib, lambda l, t: sys.stderr.write(t) if l >= 3 else None)
+lib = W.load_library(os.environ.get("WA_LIB"))
+lib.whisper_amd_batch_stats.argtypes = [C.c_void_p, C.POINTER(C.c_long), C.POINTER(C.c_long)]
+W.set_log_callback(lib, lambda l, t: sys.stderr.write(t) if l >= 3 else None)
 mp = wsynth.quant_model_path(*name.split(":")) if ":" in name else wsynth.model_path(name)
 ctx = W.WhisperContext.new_with_params(mp, W.WhisperContextParameters(lib), lib=lib)
 fp = W.FullParams(lib, best_of=1, temperature_inc=0.0, language="en", no_context=True)
@@ -68,4 +70,8 @@ for r in range(reps):
     t1 = time.perf_counter()
     W.full_batch(ctx, tst, fp, pcm)
     dt = time.perf_counter() - t1
-    print("rep %d: %d chunks in %.1f ms = %.1fx real time" % (r, NB, 1e3 * dt, 30.0 * NB / dt), flush=True)
+    steps, rows = C.c_long(0), C.c_long(0)
+    lib.whisper_amd_batch_stats(ctx.ptr, C.byref(steps), C.byref(rows))
+    served = int(lib.whisper_amd_batch_served(ctx.ptr)) if hasattr(lib, "whisper_amd_batch_served") else -1      # (-1: a library from before the counter)
+    print("rep %d: %d chunks in %.1f ms = %.1fx real time; %d passes (%.0f per second), %d rows, %d as one launch, %d served by the group"
+          % (r, NB, 1e3 * dt, 30.0 * NB / dt, steps.value, steps.value / dt, rows.value, int(lib.whisper_amd_batch_one_launch(ctx.ptr)), served), flush=True)

@@ -64,6 +64,7 @@ void whisper_amd_abi_sizes(size_t out[6]) {
 // how the last whisper_amd_full_batch call on this context decoded: lock-step passes and the token rows they served
 void whisper_amd_batch_stats(struct whisper_context * ctx, long * steps, long * rows) { if (ctx) { *steps = ctx->batch_steps; *rows = ctx->batch_rows; } }
 long whisper_amd_batch_one_launch(struct whisper_context * ctx) { return ctx ? ctx->batch_one_launch : 0; }
+long whisper_amd_batch_served(struct whisper_context * ctx) { return ctx ? ctx->batch_served : 0; }
 
 } // extern "C"
 
@@ -608,15 +609,20 @@ struct wa_batch_groups {
         if (const char * g = getenv("WHISPER_AMD_BATCH_GROUP")) group = std::max(2, std::min(WA_MAX_DECODERS, atoi(g)));
         for (size_t i0 = 0; i0 < members.size() && !off; i0 += group) {
             const size_t n = std::min((size_t) group, members.size() - i0);
-            wa_batcher * b = wa_batcher_create(*ctx, (int) n);       // null for a group of one / a quantised model: those chunks decode on their own
+            wa_batcher * b = wa_batcher_create(*ctx, (int) n);       // null for a group of one: that chunk decodes on its own (the members of a quantised group too, unless the one-launch form serves it)
             bats.push_back(b);
             for (size_t i = i0; i < i0 + n; ++i) members[i]->batcher = b;
         }
     }
     ~wa_batch_groups() {
         for (auto * st : members) st->batcher = nullptr;
-        ctx->batch_steps = ctx->batch_rows = ctx->batch_one_launch = 0;
-        for (auto * b : bats) if (b) { long st_ = 0, rw_ = 0, ol_ = 0; wa_batcher_stats(b, &st_, &rw_, &ol_); ctx->batch_steps += st_; ctx->batch_rows += rw_; ctx->batch_one_launch += ol_; wa_batcher_destroy(b); }
+        ctx->batch_steps = ctx->batch_rows = ctx->batch_one_launch = ctx->batch_served = 0;
+        for (auto * b : bats) if (b) {
+            long st_ = 0, rw_ = 0, ol_ = 0, sv_ = 0;
+            wa_batcher_stats(b, &st_, &rw_, &ol_, &sv_);
+            ctx->batch_steps += st_; ctx->batch_rows += rw_; ctx->batch_one_launch += ol_; ctx->batch_served += sv_;
+            wa_batcher_destroy(b);
+        }
     }
 };
 

@@ -559,6 +559,7 @@ struct wa_batcher {
     int n_members = 0;                              // threads that may still submit
     wa_bslot slots[WA_MAX_DECODERS];
     long n_steps = 0, n_rows = 0, n_one_launch = 0;       // passes, the token rows they served, passes that were ONE launch (wa_rows.hip)
+    long n_served = 0;                                    // passes whose rows the group delivered (the others ended with the members decoding alone)
     int64_t t_pass_us = 0, t_gap_us = 0, t_last_end = 0, t_created = 0, t_first = 0;   // (WHISPER_AMD_BATCH_TRACE) time inside the synchronous passes / between them
     // asynchronous passes (the one-launch form): two sets of output buffers, alternating; pass n may overwrite set n & 1 because every member
     // has collected pass n - 2 before it asks for the step that pass n serves
@@ -581,7 +582,7 @@ struct wa_batcher {
 // takes a free one (or makes one), wa_batcher_destroy hands it back; whisper_free releases them (wa_batcher_free_all).
 static std::mutex & batcher_cache_mutex() { static std::mutex m; return m; }
 static void batcher_reset(wa_batcher & b, int n_members) {
-    b.n_members = n_members; b.n_steps = b.n_rows = b.n_one_launch = 0; b.t_pass_us = b.t_gap_us = b.t_last_end = 0; b.t_created = wa_time_us(); b.t_first = 0; b.n_ahead = b.n_picks = 0;
+    b.n_members = n_members; b.n_steps = b.n_rows = b.n_one_launch = b.n_served = 0; b.t_pass_us = b.t_gap_us = b.t_last_end = 0; b.t_created = wa_time_us(); b.t_first = 0; b.n_ahead = b.n_picks = 0;
     for (auto & sl : b.slots) { sl.st = nullptr; sl.q.clear(); sl.ahead = false; }
 }
 wa_batcher * wa_batcher_create(whisper_context & ctx, int n_members) {
@@ -631,7 +632,9 @@ void wa_batcher_free_all(whisper_context & ctx) {
     { std::lock_guard<std::mutex> lk(batcher_cache_mutex()); all.swap(ctx.batcher_cache); }
     for (void * b : all) wa_batcher_release((wa_batcher *) b);
 }
-void wa_batcher_stats(const wa_batcher * b, long * steps, long * rows, long * one_launch) { if (b) { *steps = b->n_steps; *rows = b->n_rows; if (one_launch) *one_launch = b->n_one_launch; } }
+void wa_batcher_stats(const wa_batcher * b, long * steps, long * rows, long * one_launch, long * served) {
+    if (b) { *steps = b->n_steps; *rows = b->n_rows; if (one_launch) *one_launch = b->n_one_launch; if (served) *served = b->n_served; }
+}
 
 // the request of a member that the next pass serves: its oldest one that no pass serves yet (null: none)
 static wa_breq * batcher_next(wa_bslot & sl) {
@@ -752,7 +755,7 @@ static void batcher_run_sync(wa_batcher & b, wa_bslot ** run, int B, int T, uint
     }
     // every member copies ITS row out on its own thread (the staging buffer is not written again before all of them are back with their next requests)
     for (int i = 0; i < B; ++i) { wa_breq & r = *batcher_next(*run[i]); r.pass = -2; r.row = i; r.result = ok ? 1 : -1; }
-    b.n_steps += 1; b.n_rows += B;
+    b.n_steps += 1; b.n_rows += B; if (ok) b.n_served += 1;
     b.t_last_end = wa_time_us();
     b.t_pass_us += b.t_last_end - t_begin;
 }
@@ -826,7 +829,7 @@ static int batcher_collect(wa_batcher & b, wa_bslot & sl, int * token_used) {
                                     tk[0], tk[1], tk[2], tk[3], tk[4], tk[5], tk[6], tk[7], b.h_out[par][0], b.h_out[par][1], b.h_out[par][2], b.h_out[par][3]); }
             (void) hipMemsetAsync(b.d_stat[par], 0, sizeof(unsigned), bs.stream);
             if (ps.status != WA_MEGA_REDO) form_timed_out(bs.rows_form, "several-rows one-launch step (lock-step group)", ps.status);
-        } else b.bst->n_rows_steps += 1;
+        } else { b.bst->n_rows_steps += 1; b.n_served += 1; }
     }
     const bool ok = ps.ok && b.h_stat[par][12 + r.row] == 0;
     const unsigned status = ps.ok ? b.h_stat[par][12 + r.row] : ps.status;      // (WA_MEGA_REDO for THIS row: its member has the step redone, the others go on)

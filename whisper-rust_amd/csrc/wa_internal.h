@@ -139,7 +139,7 @@ struct whisper_context {
     std::vector<void *> batcher_cache;    // idle lock-step batchers (wa_decode.cpp), kept between whisper_amd_full_batch / whisper_full_parallel calls
     std::shared_ptr<const wa_grammar_vocab> grammar_vocab;     // the vocabulary's code points, decoded by the first call that brings a grammar (wa_full.cpp)
     std::mutex grammar_vocab_m;
-    long batch_steps = 0, batch_rows = 0, batch_one_launch = 0; // the last whisper_amd_full_batch call: lock-step passes, the token rows they served, passes that were one launch
+    long batch_steps = 0, batch_rows = 0, batch_one_launch = 0, batch_served = 0; // the last whisper_amd_full_batch / whisper_full_parallel call: lock-step passes formed, their token rows, passes that were one launch, passes that delivered their rows
 };
 
 // ---------------------------------------------------------------------------------------------
@@ -374,7 +374,7 @@ void wa_batcher_leave(wa_batcher * b);
 void wa_batcher_destroy(wa_batcher * b);          // hands the batcher back to its context's cache
 void wa_batcher_release(wa_batcher * b);          // frees it
 void wa_batcher_free_all(whisper_context & ctx);  // whisper_free
-void wa_batcher_stats(const wa_batcher * b, long * steps, long * rows, long * one_launch = nullptr);
+void wa_batcher_stats(const wa_batcher * b, long * steps, long * rows, long * one_launch = nullptr, long * served = nullptr);
 bool wa_state_alloc(whisper_context & ctx, whisper_state & st);
 void wa_state_release(whisper_state & st);
 bool wa_kv_self_realloc(whisper_context & ctx, whisper_state & st, int n_cells);

@@ -18,6 +18,7 @@
 // runs that chain redundantly (one v_mul + one v_add per block); with 8 activation rows lane l of the group runs the chain of activation
 // row l and hands it to lane 0 over DPP.  The minimums wm [row][block] and the sums xs [row][block] are read like the scales.
 #include "wa_device.h"
+#include <cstdlib>
 
 // -------------------------------------------------------------------------------------------------
 // quantize_row_q8_0: one 32-lane half-wave per block.  The quants are written in the kernel layout of the weights
@@ -189,6 +190,81 @@ __global__ __launch_bounds__(64) void k_qgemv_exact(const int8_t * __restrict__ 
     if (l == 0 && n < N) epi_apply<EPI>(e, 0, n, v, pre);
 }
 
+// -------------------------------------------------------------------------------------------------
+// M = R = 2..8 (a beam / best_of step, a small batch): the one-row kernel's shape - grid = ceil(N / 8) single-wave workgroups, 8 output
+// rows x 8 lanes, no LDS, 16 blocks of weight loads in flight - with R accumulators: the lane's weight quads and scales are loaded ONCE per four
+// blocks and meet the R activation rows, which every wave reads from L2 with the same 16-byte pattern (R K bytes, shared by all workgroups).
+// Per (activation row, output) the arithmetic is WQ_BLOCK / WQ_MIN block after block, as in k_qgemm_exact: the results are the same bits.
+// Against k_qgemm_exact (32 output rows per workgroup, one load group in flight) a narrow matrix gets 4 x the workgroups: N = 768 -> 96, not 24.
+// With a minimum, lane l of an output row's group runs the chain of activation row min(l, R - 1) and hands it to lane 0 (as k_qgemm_exact).
+// -------------------------------------------------------------------------------------------------
+template <int EPI, bool Q1, int R>
+__global__ __launch_bounds__(64) void k_qgemv_rows(const int8_t * __restrict__ xq, const float * __restrict__ xd, const int8_t * __restrict__ wq,
+                                                   const float * __restrict__ wd, int N, int K, wa_epi e, const float * __restrict__ xsum,
+                                                   const float * __restrict__ wm) {
+    const int tid = threadIdx.x, l = tid & 7, nb = K >> 5;
+    const int n = blockIdx.x * 8 + (tid >> 3);
+    const int nn = n < N ? n : N - 1;
+    wa_epi_pre pre[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) if (l == 0) pre[r] = epi_preload<EPI>(e, r, nn);
+    const int * wl = (const int *) wq + ((size_t) nn * 8 + l) * nb;
+    const float * dl = wd + (size_t) nn * nb;
+    const int * xl = (const int *) xq + (size_t) l * nb;            // row r: + r * (K >> 2)
+    const float * ml = Q1 ? wm + (size_t) nn * nb : dl;
+    const float * sl = Q1 ? xsum + (size_t) (l < R ? l : R - 1) * nb : xd;
+    float acc[R];
+    float summs = 0.0f;
+#pragma unroll
+    for (int r = 0; r < R; ++r) acc[r] = 0.0f;
+    if ((nb & 3) == 0) {
+        wq_i4 wn[4]; wq_f4 dn[4], mn[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int bj = min(4 * j, nb - 4);
+            wn[j] = *(const wq_i4 *) (wl + bj); dn[j] = *(const wq_f4 *) (dl + bj);
+            if (Q1) mn[j] = *(const wq_f4 *) (ml + bj);
+        }
+        for (int b = 0; b < nb; b += 16) {
+            wq_i4 w[4]; wq_f4 dw[4], mw[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) { w[j] = wn[j]; dw[j] = dn[j]; if (Q1) mw[j] = mn[j]; }
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int bj = min(b + 16 + 4 * j, nb - 4);
+                wn[j] = *(const wq_i4 *) (wl + bj); dn[j] = *(const wq_f4 *) (dl + bj);
+                if (Q1) mn[j] = *(const wq_f4 *) (ml + bj);
+            }
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int bj = min(b + 4 * j, nb - 4);                 // (clamped: the loads of a round's four groups go out together, whatever the guard below says)
+                wq_i4 x[R]; wq_f4 dx[R], sx;
+#pragma unroll
+                for (int r = 0; r < R; ++r) { x[r] = *(const wq_i4 *) (xl + (size_t) r * (K >> 2) + bj); dx[r] = *(const wq_f4 *) (xd + (size_t) r * nb + bj); }
+                if (Q1) sx = *(const wq_f4 *) (sl + bj);
+                if (b + 4 * j < nb) {
+#pragma unroll
+                    for (int r = 0; r < R; ++r) WQ_STEP4(acc[r], w[j], dw[j], x[r], dx[r]);
+                    if (Q1) WQ_MIN4(summs, mw[j], sx);
+                }
+            }
+        }
+    } else {
+        for (int b = 0; b < nb; ++b) {
+            const int w = wl[b]; const float dw = dl[b];
+#pragma unroll
+            for (int r = 0; r < R; ++r) WQ_BLOCK(acc[r], w, dw, xl[(size_t) r * (K >> 2) + b], xd[(size_t) r * nb + b]);
+            if (Q1) WQ_MIN(summs, ml[b], sl[b]);
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        float v = wq_hsum8(acc[r]);
+        if (Q1) v = v + wq_from_lane(summs, r);
+        if (l == 0 && n < N) epi_apply<EPI>(e, r, n, v, pre[r]);
+    }
+}
+
 // the first MLP product of the decode step: 4 waves = 32 output rows = one Q8_0 block of the GELU output (N % 32 == 0)
 template <bool Q1>
 __global__ __launch_bounds__(256) void k_qgemv_gelu_q8(const int8_t * __restrict__ xq, const float * __restrict__ xd, const int8_t * __restrict__ wq,
@@ -210,8 +286,30 @@ void wa_launch_qgemv_gelu_q8(hipStream_t s, const int8_t * xq, const float * xd,
     else    hipLaunchKernelGGL(k_qgemv_gelu_q8<false>, dim3(N / 32), dim3(256), 0, s, xq, xd, wq, wd, N, K, bias, gelu, oq, oqd, xs, wm, oqs);
 }
 
-void wa_launch_qgemm_exact(hipStream_t s, wa_epi_mode mode, const int8_t * xq, const float * xd, int M, const int8_t * wq, const float * wd, int N, int K,
-                           const wa_epi & e, const float * xs, const float * wm) {
+// The default rule: every product of 2..8 rows goes to the few-rows kernel.  Measured on the MI355X (M = 5 and 8 at d = 768 and 1280, the logits
+// product at d = 768 with 5 rows) it is the faster one for every product timed; the other row counts and widths follow those points unmeasured.
+// WHISPER_AMD_NO_FEW_ROWS=1 (read once per process) goes back.
+static bool few_rows_rule(int M) {
+    static const bool off = getenv("WHISPER_AMD_NO_FEW_ROWS") != nullptr;
+    return !off && M >= 2 && M <= 8;
+}
+// route 0: the rule above picks the kernel; 1: k_qgemm_exact (k_qgemv_exact for M == 1) whatever it says; 2: k_qgemv_rows wherever it exists (M = 2..8, the
+// epilogues of the decoder) - the kernel tests compare the two
+void wa_launch_qgemm_exact_route(hipStream_t s, wa_epi_mode mode, const int8_t * xq, const float * xd, int M, const int8_t * wq, const float * wd, int N, int K,
+                                 const wa_epi & e, const float * xs, const float * wm, int route) {
+    const bool few = M >= 2 && M <= 8 && route != 1 && (route == 2 || few_rows_rule(M));
+    if (few) {
+#define WA_ROWS_R(E, Q1, R) case R: hipLaunchKernelGGL((k_qgemv_rows<E, Q1, R>), dim3((N + 7) / 8), dim3(64), 0, s, xq, xd, wq, wd, N, K, e, xs, wm); return;
+#define WA_ROWS_Q(E, Q1) switch (M) { WA_ROWS_R(E, Q1, 2) WA_ROWS_R(E, Q1, 3) WA_ROWS_R(E, Q1, 4) WA_ROWS_R(E, Q1, 5) WA_ROWS_R(E, Q1, 6) WA_ROWS_R(E, Q1, 7) WA_ROWS_R(E, Q1, 8) default: break; }
+#define WA_ROWS_E(E) case E: if (wm) WA_ROWS_Q(E, true) else WA_ROWS_Q(E, false) break;
+        switch (mode) {        // (the encoder's epilogues never see so few rows: they stay with k_qgemm_exact)
+            WA_ROWS_E(WA_EPI_F16) WA_ROWS_E(WA_EPI_GELU_F32) WA_ROWS_E(WA_EPI_RESID) WA_ROWS_E(WA_EPI_F32) WA_ROWS_E(WA_EPI_DEC_QKV)
+            default: break;
+        }
+#undef WA_ROWS_E
+#undef WA_ROWS_Q
+#undef WA_ROWS_R
+    }
     const dim3 grid((N + 31) / 32, (M + 7) / 8);
     const size_t lds = (size_t) 8 * K + (size_t) (wm ? 16 : 8) * (K >> 5) * sizeof(float);
 #define WA_CASE_Q(E, Q1) { \
@@ -225,6 +323,10 @@ void wa_launch_qgemm_exact(hipStream_t s, wa_epi_mode mode, const int8_t * xq, c
     }
 #undef WA_CASE
 #undef WA_CASE_Q
+}
+void wa_launch_qgemm_exact(hipStream_t s, wa_epi_mode mode, const int8_t * xq, const float * xd, int M, const int8_t * wq, const float * wd, int N, int K,
+                           const wa_epi & e, const float * xs, const float * wm) {
+    wa_launch_qgemm_exact_route(s, mode, xq, xd, M, wq, wd, N, K, e, xs, wm, 0);
 }
 
 // -------------------------------------------------------------------------------------------------

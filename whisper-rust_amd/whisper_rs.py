@@ -260,6 +260,8 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         proto("whisper_amd_rows_stats", None, P, C.POINTER(C.c_long))
         proto("whisper_amd_rows_enabled", I, P)
         proto("whisper_amd_batch_one_launch", C.c_long, P)
+    if hasattr(lib, "whisper_amd_batch_served"):
+        proto("whisper_amd_batch_served", C.c_long, P)
     _LIBS[path] = lib
     return lib
 
