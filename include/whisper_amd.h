@@ -532,6 +532,32 @@ WHISPER_API long whisper_amd_batch_one_launch(struct whisper_context * ctx);
  * group formed; the passes not counted here ended with each member decoding its token alone) */
 WHISPER_API long whisper_amd_batch_served(struct whisper_context * ctx);
 
+/* DTW token timestamps, the alignment alone (wa_dtw.cpp): normalise over tokens, median over audio with reflect padding, mean over heads,
+ * DTW table and backtrace over a caller's own cross-attention probabilities - what whisper_full does after its extra decoder pass when
+ * dtw_token_timestamps is set.  qk is a host cube [n_heads][n_tokens][n_ctx] F32 of which the first n_audio_tokens frames are used; rows
+ * [sot_len, n_tokens - 1) enter the table (N = n_tokens - sot_len - 1 rows, M = n_audio_tokens columns).
+ * where = 0: the host function.  where = 1: the device kernels (wa_dtw.hip); the cube is uploaded into the state's capture buffer and runs
+ * through the launchers of the product path, on the state's stream.  Both give the same path, pair for pair.
+ * Returns the path length (at most N + M) and copies up to `cap` pairs (token index, time index; one time index = 20 ms), or
+ *   WHISPER_AMD_DTW_REFUSED    the arguments are refused by both paths: an even or non-positive medfilt_width, M <= medfilt_width, M > n_ctx,
+ *                              N <= 0, no heads, null pointers, another `where`;
+ *   WHISPER_AMD_DTW_NOT_TAKEN  where = 1 and the device path does not take them: it serves medfilt_width 7 and n_tokens up to the state's
+ *                              decoder rows (the text context rounded up to 64);
+ *   WHISPER_AMD_DTW_HIP_ERROR  a HIP call failed.
+ * Nothing is written on a negative return.
+ * whisper_amd_dtw_stats: out = { DTW calls served by the device path, calls served by the host path, device-path attempts that fell back to
+ * the host path } since the state was created, whisper_full's calls and whisper_amd_dtw_path's alike.  WHISPER_AMD_DTW_HOST=1 in the environment
+ * when a state is created makes whisper_full take the host path on that state.
+ * whisper_amd_dtw_timings: out = { wall time in us of whisper_full's DTW post-processing on this state, from the end of the decoder pass to
+ * t_dtw placed, number of such calls } (tools/dtw_probe.py). */
+#define WHISPER_AMD_DTW_REFUSED   (-1)
+#define WHISPER_AMD_DTW_NOT_TAKEN (-2)
+#define WHISPER_AMD_DTW_HIP_ERROR (-3)
+WHISPER_API int  whisper_amd_dtw_path(struct whisper_state * state, const float * qk, int n_heads, int n_tokens, int n_ctx, int n_audio_tokens,
+                                      int sot_len, int medfilt_width, int where, int32_t * path_tok, int32_t * path_time, int cap);
+WHISPER_API void whisper_amd_dtw_stats(struct whisper_state * state, long out[3]);
+WHISPER_API void whisper_amd_dtw_timings(struct whisper_state * state, int64_t out[2]);
+
 #ifdef __cplusplus
 }
 #endif

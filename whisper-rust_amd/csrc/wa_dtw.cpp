@@ -3,16 +3,66 @@
 // ref: whisper_exp_compute_token_level_timestamps_dtw whisper.cpp:8772-8933, dtw_and_backtrace 8647-8731,
 // median_filter 8737-8770, alignment-head selection 1190-1303, QK capture in the decoder graph 2737-2752 / 2838-2845.
 //
-// Device part: one extra decoder pass over [sot, lang, not, text..., eot] whose cross-attention kernels also write
-// their F32 soft-max probabilities (k_attn_exact's qk_out).  Only the alignment heads are copied back.  The rest
-// (normalise over tokens, 7-wide median over audio, mean over heads, DTW + backtrace) is host post-processing on a
-// [tokens x frames/2 x heads] cube, as in the reference, in the same arithmetic order (F64 sums of ggml_norm/ggml_mean).
+// One extra decoder pass over [sot, lang, not, text..., eot] whose cross-attention kernels also write their F32 soft-max probabilities
+// (k_attn_exact's qk_out) into the state's capture buffer [layer slot][token][head][n_audio_ctx].  The rest - normalise over tokens, 7-wide
+// median over audio, mean over heads, DTW table - runs on the device too (wa_dtw.hip), on the state's stream, reading the alignment heads in
+// place through a table of (slot, head) offsets; the trace (one byte per cell) comes back to a pinned buffer and the backtrace runs here.
+// A device call that fits the state's grow-only buffers allocates nothing, issues nothing on the null stream and waits for the stream once.
+// The same arithmetic on the host (wa_dtw_host.cpp, the reference's order: F64 sums of ggml_norm / ggml_mean) serves every other shape, any
+// HIP error on the way, and WHISPER_AMD_DTW_HOST=1 (read when the state is created).
 #include "wa_internal.h"
+#include "wa_dtw_host.h"
+#include "wa_kernels.h"
 
-#include <algorithm>
-#include <cmath>
 #include <cstring>
-#include <thread>
+
+static size_t dtw_pad256(size_t n) { return (n + 255) / 256 * 256; }
+
+// the capture buffer, grow-only (a larger one replaces it only while the state's stream is idle: every caller has waited for its last pass)
+static bool dtw_reserve_capture(whisper_state & st, size_t n_floats) {
+    if (n_floats <= st.aheads_qk_cap && st.d_aheads_qk) return true;
+    if (st.d_aheads_qk) { (void) hipFree(st.d_aheads_qk); st.d_aheads_qk = nullptr; st.aheads_qk_cap = 0; }
+    if (!WA_HIP_OK(hipMalloc((void **) &st.d_aheads_qk, n_floats * sizeof(float)))) { st.d_aheads_qk = nullptr; return false; }
+    st.aheads_qk_cap = n_floats;
+    return true;
+}
+
+static bool dtw_device_takes(const whisper_state & st, int n_tokens, int M, int sot_len, int medfilt_width) {
+    const int N = n_tokens - sot_len - 1;
+    return medfilt_width == 7 && M > 7 && N > 0 && N <= WA_DTW_MAX_N && n_tokens <= st.dec_mpad;
+}
+
+// The device path on x(k, t, j) = d_x[head_off[k] + t * tok_stride + j]: the path length, or WA_DTW_HIP_ERROR.  One stream synchronise.
+static int dtw_device_path(whisper_state & st, const float * d_x, const long long * head_off, long long tok_stride, int n_heads, int n_tokens, int M,
+                           int sot_len, wa_dtw_path_t & path) {
+    const int N = n_tokens - sot_len - 1;
+    const size_t nd = (size_t) N + M - 1;
+    const size_t o_mean = dtw_pad256((size_t) n_heads * sizeof(long long)), o_scale = o_mean + dtw_pad256((size_t) n_heads * M * sizeof(float)),
+                 o_cost = o_scale + dtw_pad256((size_t) n_heads * M * sizeof(float)), o_trace = o_cost + dtw_pad256(nd * N * sizeof(float)),
+                 d_need = o_trace + dtw_pad256(nd * N), h_need = o_mean + dtw_pad256(nd * N);
+    if (d_need > st.d_dtw_cap) {
+        if (st.d_dtw) { (void) hipFree(st.d_dtw); st.d_dtw = nullptr; st.d_dtw_cap = 0; }
+        if (!WA_HIP_OK(hipMalloc((void **) &st.d_dtw, d_need))) { st.d_dtw = nullptr; return WA_DTW_HIP_ERROR; }
+        st.d_dtw_cap = d_need;
+    }
+    if (h_need > st.h_dtw_cap) {
+        if (st.h_dtw) { (void) hipHostFree(st.h_dtw); st.h_dtw = nullptr; st.h_dtw_cap = 0; }
+        if (!WA_HIP_OK(hipHostMalloc((void **) &st.h_dtw, h_need))) { st.h_dtw = nullptr; return WA_DTW_HIP_ERROR; }
+        st.h_dtw_cap = h_need;
+    }
+    hipStream_t s = st.stream;
+    memcpy(st.h_dtw, head_off, (size_t) n_heads * sizeof(long long));
+    uint8_t * h_trace = st.h_dtw + o_mean, * d_trace = st.d_dtw + o_trace;
+    if (!WA_HIP_OK(hipMemcpyAsync(st.d_dtw, st.h_dtw, (size_t) n_heads * sizeof(long long), hipMemcpyHostToDevice, s))) return WA_DTW_HIP_ERROR;
+    wa_launch_dtw(s, d_x, (const long long *) st.d_dtw, tok_stride, n_heads, n_tokens, sot_len, M, (float *) (st.d_dtw + o_mean), (float *) (st.d_dtw + o_scale),
+                  (float *) (st.d_dtw + o_cost), d_trace);
+    const bool launched = WA_HIP_OK(hipGetLastError());
+    const bool copied = launched && WA_HIP_OK(hipMemcpyAsync(h_trace, d_trace, nd * N, hipMemcpyDeviceToHost, s));
+    if (!WA_HIP_OK(hipStreamSynchronize(s)) || !copied) return WA_DTW_HIP_ERROR;
+    // cell (i, j) of the table at [(i - 1 + j - 1) * N + (i - 1)]
+    wa_dtw_backtrace(h_trace, (long long) N + 1, (long long) N, N, M, path);
+    return (int) path.size();
+}
 
 void wa_dtw_timestamps(whisper_context * ctx, whisper_state * st, const whisper_full_params & params, int i_segment, size_t n_segments,
                        int seek, int n_frames, int medfilt_width) {
@@ -38,13 +88,13 @@ void wa_dtw_timestamps(whisper_context * ctx, whisper_state * st, const whisper_
     const int n_tokens = (int) tokens.size();
     if (n_tokens > st->dec_mpad) { WA_WARN("%s: too many tokens for DTW (%d)\n", __func__, n_tokens); return; }
 
-    // capture buffer: [layer slot][token][head][n_audio_ctx] F32 for the layers that own alignment heads
+    // capture buffer: [layer slot][token][head][n_audio_ctx] F32 for the layers that own alignment heads; sized for a multiple of 64 tokens
+    // so that a longer window seldom replaces it
     std::vector<int> slot(hp.n_text_layer, -1);
     int n_slots = 0;
     for (int il = 0; il < hp.n_text_layer; ++il) if (!st->aheads[il].empty()) slot[il] = n_slots++;
     const size_t per_layer = (size_t) n_tokens * H * n_audio_ctx;
-    if (st->d_aheads_qk) { (void) hipFree(st->d_aheads_qk); st->d_aheads_qk = nullptr; }
-    if (!WA_HIP_OK(hipMalloc((void **) &st->d_aheads_qk, per_layer * n_slots * sizeof(float)))) return;
+    if (!dtw_reserve_capture(*st, (size_t) std::min(st->dec_mpad, wa_pad(n_tokens, 64)) * H * n_audio_ctx * n_slots)) return;
 
     // the decoder pass (whisper.cpp:8823-8829)
     wa_kv_clear(st->kv_self);
@@ -58,119 +108,39 @@ void wa_dtw_timestamps(whisper_context * ctx, whisper_state * st, const whisper_
     // wa_decode indexes the capture buffer by layer; give it a slot table through aheads_slot
     st->aheads_slot = slot;
     const bool ok = wa_decode(*ctx, *st, b, true, nullptr, nullptr);
-    if (!ok) { WA_ERROR("%s: decoder pass failed\n", __func__); (void) hipFree(st->d_aheads_qk); st->d_aheads_qk = nullptr; return; }
+    if (!ok) { WA_ERROR("%s: decoder pass failed\n", __func__); return; }
+    const int64_t t_post = wa_time_us();
 
-    // copy back the alignment heads only: data[t + n_tokens*(j + n_audio_ctx*k)] (layout of aheads_cross_QKs, whisper.cpp:8844-8856)
+    // the alignment heads in the capture buffer, head k at (slot, head): x(k, t, j) = d_aheads_qk[head_off[k] + t * H * n_audio_ctx + j]
     const int n_heads = st->aheads_n;
     const int n_audio_tokens = n_frames / 2;
-    if (n_audio_tokens <= 0) { (void) hipFree(st->d_aheads_qk); st->d_aheads_qk = nullptr; return; }
-    std::vector<float> rows((size_t) n_tokens * n_audio_ctx);
-    std::vector<float> w((size_t) n_tokens * n_audio_tokens * n_heads);     // w[t + n_tokens*(j + n_audio_tokens*k)]
-    int k = 0;
-    for (int il = 0; il < hp.n_text_layer; ++il) {
-        for (int h : st->aheads[il]) {
-            const float * src = st->d_aheads_qk + (size_t) slot[il] * per_layer + (size_t) h * n_audio_ctx;
-            if (!WA_HIP_OK(hipMemcpy2D(rows.data(), (size_t) n_audio_ctx * sizeof(float), src, (size_t) H * n_audio_ctx * sizeof(float),
-                                       (size_t) n_audio_ctx * sizeof(float), n_tokens, hipMemcpyDeviceToHost))) return;
-            for (int j = 0; j < n_audio_tokens; ++j)
-                for (int t = 0; t < n_tokens; ++t) w[t + (size_t) n_tokens * (j + (size_t) n_audio_tokens * k)] = rows[(size_t) t * n_audio_ctx + j];
-            ++k;
-        }
-    }
-    (void) hipFree(st->d_aheads_qk); st->d_aheads_qk = nullptr;
-
-    // Per alignment head (independent: spread over a few host threads - a medium model's 32 heads x 223 tokens x 750 frames took ~0.5 s
-    // in one thread with a sort per median):
-    //   ggml_norm over the token axis, eps 1e-9 (whisper.cpp:8864, ops.cpp:3225-3242), in place in w[.][j][t];
-    //   7-wide median over the audio axis with reflect padding, per token (whisper.cpp:8737-8770) -> med[kk][t][j].  The median of 7 is a
-    //   13-exchange selection network on a transposed copy of the head (rows of frames: it vectorises); other widths sort.
+    if (n_audio_tokens <= 0) return;
+    std::vector<long long> head_off;
+    for (int il = 0; il < hp.n_text_layer; ++il)
+        for (int h : st->aheads[il]) head_off.push_back((long long) ((size_t) slot[il] * per_layer + (size_t) h * n_audio_ctx));
+    const long long tok_stride = (long long) H * n_audio_ctx;
     if (medfilt_width >= n_audio_tokens) { WA_WARN("%s: too few audio frames for the median filter\n", __func__); return; }
-    std::vector<float> med((size_t) n_heads * n_tokens * n_audio_tokens);  // med[kk][t][j]
-    auto one_head = [&](int kk) {
-        for (int j = 0; j < n_audio_tokens; ++j) {
-            float * x = &w[(size_t) n_tokens * (j + (size_t) n_audio_tokens * kk)];
-            double sum = 0.0;
-            for (int t = 0; t < n_tokens; ++t) sum += (double) x[t];
-            const float mean = sum / n_tokens;
-            double sum2 = 0.0;
-            for (int t = 0; t < n_tokens; ++t) { const float v = x[t] - mean; x[t] = v; sum2 += (double) (v * v); }
-            const float variance = sum2 / n_tokens;
-            const float scale = 1.0f / sqrtf(variance + 1e-9f);
-            for (int t = 0; t < n_tokens; ++t) x[t] = x[t] * scale;
-        }
-        const int hw = medfilt_width / 2, M_ = n_audio_tokens;
-        std::vector<float> row((size_t) M_ + 2 * hw), filt((size_t) medfilt_width);
-        for (int t = 0; t < n_tokens; ++t) {
-            for (int j = 0; j < M_; ++j) row[hw + j] = w[t + (size_t) n_tokens * (j + (size_t) M_ * kk)];
-            for (int o = 1; o <= hw; ++o) { row[hw - o] = row[hw + o]; row[hw + M_ - 1 + o] = row[hw + M_ - 1 - o]; }      // reflect (idx -> -idx, 2 (M - 1) - idx)
-            float * out = &med[((size_t) kk * n_tokens + t) * M_];
-            if (medfilt_width == 7) {
-                const float * r = row.data();
-                for (int j = 0; j < M_; ++j) {
-                    float p0 = r[j], p1 = r[j + 1], p2 = r[j + 2], p3 = r[j + 3], p4 = r[j + 4], p5 = r[j + 5], p6 = r[j + 6];
-#define WA_CX(a, b) do { const float lo_ = std::min(a, b), hi_ = std::max(a, b); a = lo_; b = hi_; } while (0)
-                    WA_CX(p0, p5); WA_CX(p0, p3); WA_CX(p1, p6); WA_CX(p2, p4); WA_CX(p0, p1); WA_CX(p3, p5); WA_CX(p2, p6);
-                    WA_CX(p2, p3); WA_CX(p3, p6); WA_CX(p4, p5); WA_CX(p1, p4); WA_CX(p1, p3); WA_CX(p3, p4);
-#undef WA_CX
-                    out[j] = p3;
-                }
-            } else {
-                for (int j = 0; j < M_; ++j) {
-                    std::copy(row.begin() + j, row.begin() + j + medfilt_width, filt.begin());
-                    std::sort(filt.begin(), filt.end());
-                    out[j] = filt[filt.size() / 2];
-                }
-            }
-        }
-    };
-    {
-        const int n_thr = std::max(1, std::min(n_heads, 8));
-        std::vector<std::thread> th;
-        for (int i = 1; i < n_thr; ++i) th.emplace_back([&, i] { for (int kk = i; kk < n_heads; kk += n_thr) one_head(kk); });
-        for (int kk = 0; kk < n_heads; kk += n_thr) one_head(kk);
-        for (auto & t_ : th) t_.join();
+    if (!wa_dtw_args_ok(n_heads, n_tokens, n_audio_ctx, n_audio_tokens, (int) sot_len, medfilt_width)) return;      // (N <= 0)
+
+    wa_dtw_path_t path;                                   // (token index, time index)
+    bool served = false;
+    if (!st->dtw_host && dtw_device_takes(*st, n_tokens, n_audio_tokens, (int) sot_len, medfilt_width)) {
+        served = dtw_device_path(*st, st->d_aheads_qk, head_off.data(), tok_stride, n_heads, n_tokens, n_audio_tokens, (int) sot_len, path) >= 0;
+        if (served) st->n_dtw_device++; else { st->n_dtw_fallback++; WA_WARN("%s: the device path failed, taking the host path\n", __func__); }
     }
-    // mean over heads (F64 sum in head order, ops.cpp:2033-2041 / vec.h:908-914), times -1
-    std::vector<float> cost_in((size_t) n_tokens * n_audio_tokens);          // x[t][j]
-    for (int t = 0; t < n_tokens; ++t)
-        for (int j = 0; j < n_audio_tokens; ++j) {
-            double sum = 0.0;
-            for (int kk = 0; kk < n_heads; ++kk) sum += (double) med[((size_t) kk * n_tokens + t) * n_audio_tokens + j];
-            float v = (float) sum;
-            v /= (float) n_heads;
-            cost_in[(size_t) t * n_audio_tokens + j] = v * -1.0f;
+    if (!served) {
+        // copy back the alignment heads only, the frames in use: cube[k][t][j]
+        const int M_ = n_audio_tokens;
+        std::vector<float> cube((size_t) n_heads * n_tokens * M_);
+        std::vector<long long> off_h(n_heads);
+        for (int k = 0; k < n_heads; ++k) {
+            off_h[k] = (long long) k * n_tokens * M_;
+            if (!WA_HIP_OK(hipMemcpy2D(cube.data() + off_h[k], (size_t) M_ * sizeof(float), st->d_aheads_qk + head_off[k], (size_t) tok_stride * sizeof(float),
+                                       (size_t) M_ * sizeof(float), n_tokens, hipMemcpyDeviceToHost))) return;
         }
-
-    // drop the sot sequence and eot (whisper.cpp:8880-8882): rows [sot_len, n_tokens - 1)
-    const int N = n_tokens - (int) sot_len - 1, M = n_audio_tokens;
-    if (N <= 0) return;
-    auto X = [&](int i, int j) { return cost_in[(size_t) (i + sot_len) * n_audio_tokens + j]; };
-
-    // DTW + backtrace (whisper.cpp:8647-8731)
-    std::vector<float> cost((size_t) (N + 1) * (M + 1), INFINITY);
-    std::vector<int32_t> trace((size_t) (N + 1) * (M + 1), -1);
-    auto C = [&](int i, int j) -> float & { return cost[(size_t) j * (N + 1) + i]; };
-    auto TR = [&](int i, int j) -> int32_t & { return trace[(size_t) j * (N + 1) + i]; };
-    C(0, 0) = 0.0f;
-    for (int j = 1; j < M + 1; ++j)
-        for (int i = 1; i < N + 1; ++i) {
-            const float c0 = C(i - 1, j - 1), c1 = C(i - 1, j), c2 = C(i, j - 1);
-            float c; int32_t t;
-            if (c0 < c1 && c0 < c2) { c = c0; t = 0; } else if (c1 < c0 && c1 < c2) { c = c1; t = 1; } else { c = c2; t = 2; }
-            C(i, j) = X(i - 1, j - 1) + c;
-            TR(i, j) = t;
-        }
-    for (int j = 0; j < M + 1; ++j) TR(0, j) = 2;
-    for (int i = 0; i < N + 1; ++i) TR(i, 0) = 1;
-    std::vector<std::pair<int32_t, int32_t>> path;       // (token index, time index), built backwards
-    {
-        int i = N, j = M;
-        while (i > 0 || j > 0) {
-            path.emplace_back(i - 1, j - 1);
-            const int32_t t = TR(i, j);
-            if (t == 0) { --i; --j; } else if (t == 1) { --i; } else if (t == 2) { --j; } else break;
-        }
-        std::reverse(path.begin(), path.end());
+        const wa_dtw_view v = { cube.data(), off_h.data(), n_heads, (long long) M_, n_tokens, M_ };
+        if (wa_dtw_host_path(v, M_, (int) sot_len, medfilt_width, path) < 0) return;
+        st->n_dtw_host++;
     }
 
     // place the timestamps on the text tokens of the new segments (whisper.cpp:8894-8920)
@@ -197,4 +167,39 @@ void wa_dtw_timestamps(whisper_context * ctx, whisper_state * st, const whisper_
             ++tok_i;
         }
     }
+    st->t_dtw_post_us += wa_time_us() - t_post; st->n_dtw_post++;
 }
+
+// ---- the alignment alone (include/whisper_amd.h) ----
+int whisper_amd_dtw_path(struct whisper_state * st, const float * qk, int n_heads, int n_tokens, int n_ctx, int n_audio_tokens, int sot_len,
+                         int medfilt_width, int where, int32_t * path_tok, int32_t * path_time, int cap) {
+    if (!st || !qk || (where != 0 && where != 1)) return WA_DTW_REFUSED;
+    if (!wa_dtw_args_ok(n_heads, n_tokens, n_ctx, n_audio_tokens, sot_len, medfilt_width)) return WA_DTW_REFUSED;
+    std::vector<long long> head_off(n_heads);
+    for (int k = 0; k < n_heads; ++k) head_off[k] = (long long) k * n_tokens * n_ctx;
+    wa_dtw_path_t path;
+    int n;
+    if (where == 0) {
+        const wa_dtw_view v = { qk, head_off.data(), n_heads, (long long) n_ctx, n_tokens, n_ctx };
+        n = wa_dtw_host_path(v, n_audio_tokens, sot_len, medfilt_width, path);
+        if (n >= 0) st->n_dtw_host++;
+    } else {
+        if (!dtw_device_takes(*st, n_tokens, n_audio_tokens, sot_len, medfilt_width)) return WA_DTW_NOT_TAKEN;
+        if (!st->ctx || !WA_HIP_OK(hipSetDevice(st->ctx->device))) return WA_DTW_HIP_ERROR;
+        // the cube takes the capture buffer's place; the launchers are the product path's
+        const size_t n_cube = (size_t) n_heads * n_tokens * n_ctx;
+        if (!dtw_reserve_capture(*st, n_cube)) return WA_DTW_HIP_ERROR;
+        if (!WA_HIP_OK(hipMemcpyAsync(st->d_aheads_qk, qk, n_cube * sizeof(float), hipMemcpyHostToDevice, st->stream))) return WA_DTW_HIP_ERROR;
+        n = dtw_device_path(*st, st->d_aheads_qk, head_off.data(), (long long) n_ctx, n_heads, n_tokens, n_audio_tokens, sot_len, path);
+        if (n >= 0) st->n_dtw_device++; else st->n_dtw_fallback++;
+    }
+    if (n < 0) return n;
+    for (int i = 0; i < n && i < cap; ++i) {
+        if (path_tok)  path_tok[i]  = path[i].first;
+        if (path_time) path_time[i] = path[i].second;
+    }
+    return n;
+}
+
+void whisper_amd_dtw_stats(struct whisper_state * st, long out[3]) { out[0] = st->n_dtw_device; out[1] = st->n_dtw_host; out[2] = st->n_dtw_fallback; }
+void whisper_amd_dtw_timings(struct whisper_state * st, int64_t out[2]) { out[0] = st->t_dtw_post_us; out[1] = st->n_dtw_post; }

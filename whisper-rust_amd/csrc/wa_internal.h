@@ -341,6 +341,14 @@ struct whisper_state {
     std::vector<int> aheads_slot;          // per text layer: slot in d_aheads_qk during the DTW pass (-1: none)
     std::vector<float> aheads_cross_QKs_data;
     int aheads_n = 0;
+    // DTW post-processing on the device (wa_dtw.cpp / wa_dtw.hip).  The capture buffer d_aheads_qk and these work areas are grow-only: sized on
+    // first use, kept between calls, freed with the state.
+    size_t aheads_qk_cap = 0;                               // floats in d_aheads_qk
+    uint8_t * d_dtw = nullptr; size_t d_dtw_cap = 0;        // head table | mean | scale | cost | trace
+    uint8_t * h_dtw = nullptr; size_t h_dtw_cap = 0;        // pinned: head table (up) | trace (down)
+    bool dtw_host = false;                                  // WHISPER_AMD_DTW_HOST=1 when the state was created: the host path only
+    long n_dtw_device = 0, n_dtw_host = 0, n_dtw_fallback = 0;      // calls served by the device path / by the host path / device attempts that fell back
+    int64_t t_dtw_post_us = 0; long n_dtw_post = 0;         // whisper_full's DTW calls: wall time from the end of the decoder pass to t_dtw placed
 };
 // the form a state's single-token run-ahead window (wa_spec_*) runs on, is gated on and is charged with its time-outs
 inline wa_launch_form & wa_window_form(whisper_state & st) { return st.single_via_rows ? st.rows_form : st.mega_form; }

@@ -141,3 +141,11 @@ void wa_launch_kgemm_exact(hipStream_t stream, wa_epi_mode mode, int wtype, cons
 // token embedding rows of such a matrix (dequantize_row_q2_K / q3_K / q5_K / q6_K) + positional embedding
 void wa_launch_dec_embed_k(hipStream_t stream, int wtype, const int32_t * tok, const int32_t * pos, int n_tokens, int d, const int8_t * wq, const int8_t * wsc,
                            const float * wd, const float * wdm, const float * pe, float * x);
+
+// ---- DTW token timestamps (wa_dtw.hip): normalise over tokens, 7-wide median over audio, mean over heads, cost / trace table ----
+#define WA_DTW_MAX_N 512         // most table rows N = n_tokens - sot_len - 1: one thread of ONE workgroup each
+// x(k, t, j) = x[head_off[k] + t * tok_stride + j] (device; wa_dtw_host.h: wa_dtw_view), k < n_heads, t < n_tokens, j < M; M > 7, N <= WA_DTW_MAX_N.
+// Work areas: mean, scale f32 [n_heads][M]; cost f32 [(N + M - 1)][N], cell (i + 1, j + 1)'s cost_in at [(i + j) * N + i]; trace u8 likewise, the
+// result: 0 / 1 / 2 per cell of the table (cells outside it are not written).  Three launches; arguments outside the limits launch nothing.
+void wa_launch_dtw(hipStream_t stream, const float * x, const long long * head_off, long long tok_stride, int n_heads, int n_tokens, int sot_len, int M,
+                   float * mean, float * scale, float * cost, uint8_t * trace);

@@ -262,9 +262,15 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         proto("whisper_amd_batch_one_launch", C.c_long, P)
     if hasattr(lib, "whisper_amd_batch_served"):
         proto("whisper_amd_batch_served", C.c_long, P)
+    if hasattr(lib, "whisper_amd_dtw_path"):
+        proto("whisper_amd_dtw_path", I, P, C.POINTER(F), I, I, I, I, I, I, I, C.POINTER(C.c_int32), C.POINTER(C.c_int32), I)
+        proto("whisper_amd_dtw_stats", None, P, C.POINTER(C.c_long))
+        proto("whisper_amd_dtw_timings", None, P, C.POINTER(C.c_int64))
     _LIBS[path] = lib
     return lib
 
+
+DTW_REFUSED, DTW_NOT_TAKEN, DTW_HIP_ERROR = -1, -2, -3      # whisper_amd_dtw_path's codes (include/whisper_amd.h)
 
 _KEEP_LOG_CB = {}
 
@@ -480,6 +486,31 @@ class WhisperState:
         """Extension: (decoder passes of several token rows served by the one-launch form, passes sent back to the launch sequence)."""
         out = (C.c_long * 2)()
         self.lib.whisper_amd_rows_stats(self.ptr, out)
+        return int(out[0]), int(out[1])
+
+    def dtw_path(self, qk: np.ndarray, n_audio_tokens: int, sot_len: int, medfilt_width: int = 7, where: int = 0, cap: int = None, fill: int = -1):
+        """Extension (whisper_amd_dtw_path): the DTW alignment alone over a host cube qk [n_heads][n_tokens][n_ctx] F32.  where = 0: the host
+        function, 1: the device kernels.  Returns (the path length or a DTW_* code, token indices, time indices); the two arrays have `cap`
+        entries (default N + M), pre-filled with `fill`, of which the first min(length, cap) are the path."""
+        qk = np.ascontiguousarray(qk, dtype=np.float32)
+        n_heads, n_tokens, n_ctx = qk.shape
+        if cap is None:
+            cap = max(1, n_tokens + n_audio_tokens)
+        tok, tim = np.full(cap, fill, dtype=np.int32), np.full(cap, fill, dtype=np.int32)
+        r = self.lib.whisper_amd_dtw_path(self.ptr, qk.ctypes.data_as(C.POINTER(C.c_float)), n_heads, n_tokens, n_ctx, n_audio_tokens, sot_len, medfilt_width,
+                                          where, tok.ctypes.data_as(C.POINTER(C.c_int32)), tim.ctypes.data_as(C.POINTER(C.c_int32)), cap)
+        return r, tok, tim
+
+    def dtw_stats(self) -> tuple:
+        """Extension: DTW calls on this state (served by the device path, served by the host path, device-path attempts that fell back)."""
+        out = (C.c_long * 3)()
+        self.lib.whisper_amd_dtw_stats(self.ptr, out)
+        return int(out[0]), int(out[1]), int(out[2])
+
+    def dtw_timings(self) -> tuple:
+        """Extension: (wall time in us of full()'s DTW post-processing on this state - decoder pass done to t_dtw placed -, number of such calls)."""
+        out = (C.c_int64 * 2)()
+        self.lib.whisper_amd_dtw_timings(self.ptr, out)
         return int(out[0]), int(out[1])
 
     def n_len(self) -> int:
