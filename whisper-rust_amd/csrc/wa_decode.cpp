@@ -195,7 +195,10 @@ static void decode_launch_quant(whisper_context & ctx, whisper_state & st, int n
     };
     auto qmul = [&](wa_epi_mode mode, const wa_lin & L, int M, const wa_epi & e) {      // operand already in d_q8 / d_q8d
         if (QK) wa_launch_kgemm_exact(s, mode, m.wtype, st.d_q8, st.d_q8d, st.d_q8bs, M, L.qs, L.qsc, L.qd, L.qm, L.n_out, L.n_in, e);
-        else    wa_launch_qgemm_exact(s, mode, st.d_q8, st.d_q8d, M, L.qs, L.qd, L.n_out, L.n_in, e, st.d_q8s, L.qm);
+        else {
+            if (M > 8) (wa_qgemm_exact_kernel(mode, M, L.n_out, L.n_in, e, 0) == 3 ? st.n_qgemm_mfma : st.n_qgemm_exact) += 1;
+            wa_launch_qgemm_exact(s, mode, st.d_q8, st.d_q8d, M, L.qs, L.qd, L.n_out, L.n_in, e, st.d_q8s, L.qm);
+        }
     };
     auto qlin = [&](wa_epi_mode mode, const float * A, int lda, const wa_lin & L, int M, const wa_epi & e) {
         quant(A, lda, M, L.n_in);

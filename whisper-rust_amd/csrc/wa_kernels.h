@@ -117,9 +117,12 @@ void wa_launch_quantize_q8_0(hipStream_t stream, const float * x, int ldx, int r
 // C[M][N] = xq . Wq^T, ggml_vec_dot_q5_0_q8_0 / q8_0_q8_0 / q4_1_q8_1 / q5_1_q8_1 order; wq int8 [N][8][K/32][4], wd f32 [N][K/32] (wa_internal.h: wa_lin); any M
 void wa_launch_qgemm_exact(hipStream_t stream, wa_epi_mode mode, const int8_t * xq, const float * xd, int M, const int8_t * wq, const float * wd, int N, int K,
                            const wa_epi & e, const float * xs = nullptr, const float * wm = nullptr);
-// the same with the kernel named (0: the launcher's own rule - what wa_launch_qgemm_exact does; 1: the general kernel; 2: the few-rows kernel, M = 2..8)
+// the same with the kernel named (0: the launcher's own rule - what wa_launch_qgemm_exact does; 1: the general kernel; 2: the few-rows kernel, M = 2..8;
+// 3: the matrix-core kernel k_qgemm_mfma, M >= 9 and e.rowp null)
 void wa_launch_qgemm_exact_route(hipStream_t stream, wa_epi_mode mode, const int8_t * xq, const float * xd, int M, const int8_t * wq, const float * wd, int N, int K,
                                  const wa_epi & e, const float * xs, const float * wm, int route);
+// the kernel that launcher takes for a product and a route: 1 k_qgemm_exact (k_qgemv_exact for M == 1), 2 k_qgemv_rows, 3 k_qgemm_mfma
+int wa_qgemm_exact_kernel(wa_epi_mode mode, int M, int N, int K, const wa_epi & e, int route);
 // one row (K <= 2048, K % 32 == 0): LayerNorm in reference order, quantised to Q8_0 row 0 of (qs, qd), by one 256-thread block
 void wa_launch_ln_q8_row(hipStream_t stream, const float * x, int K, const float * w, const float * b, float eps, int8_t * qs, float * qd, float * qsum = nullptr);
 // M == 1: GELU(x Wq^T + bias) quantised to Q8_0 straight away (the operand of the second MLP product); N % 32 == 0

@@ -9,6 +9,7 @@
 // token), the three DPP exchanges reproduce hsum_float_8.  Up to 8 activation rows share one pass over the weights.
 // The weights are stored for this access pattern at load (wa_loader.cpp: signed bytes, [row][lane][block][4]).
 // Bit-identical to the reference engine on the Q5_0 / Q8_0 goldens (tests/test_parity_gpu.py).
+// Products of more than 8 activation rows take the integer sums from the int8 matrix cores instead (k_qgemm_mfma below): same chains, same bits.
 //
 // Q4_1 / Q5_1 (template flag Q1; the arithmetic is stated in host code in wa_quant1.h): the quants are the unsigned 4- / 5-bit values
 // (0..31 fits a signed byte, so the same v_dot4_i32_i8), the weight is q * d + m, and the reference multiplies with a Q8_1 row, whose
@@ -131,6 +132,117 @@ __global__ __launch_bounds__(256) void k_qgemm_exact(const int8_t * __restrict__
         float v = wq_hsum8(acc[m]);
         if (Q1) v = v + wq_from_lane(summs, m);
         if (l == 0 && n < N && m < mt) epi_apply<EPI>(e, m0 + m, n, v, pre[m]);
+    }
+}
+
+// -------------------------------------------------------------------------------------------------
+// The same product on the int8 matrix cores, M > 8.  v_mfma_i32_16x16x4_4b_i8 computes FOUR independent 16 x 16 products with K = 4 bytes; its
+// operand and result mapping, confirmed on the MI355X by tools/micro/mfma_i8_blocks.hip (one-hot rows, random bytes, one-hot K-bytes):
+//     A: lane L holds the four K-bytes of block L / 16, row L % 16          B: lane L holds the four K-bytes of block L / 16, column L % 16
+//     D: register 4 blk + r of lane L is block blk, row 4 (L / 16) + r, column L % 16
+// Here block = lane-sum index: the int at ((const int *) q)[(row * 8 + l) * nb + b] of the kernel layout IS one operand, rows = activation rows,
+// columns = weight rows, and two instructions (l = 0..3, l = 4..7) give all eight integer lane sums of a 16 x 16 output tile for one quant block -
+// exact, as any integer order is.  Every lane then holds, for its column and its rows, the eight sums of the reference's eight AVX2 lanes:
+// f32(dw) * f32(dx) is rounded once per (row, column, block), the eight chains acc[l] = fma(dw dx, (float) sum_l, acc[l]) run block after block, and
+// hsum_float_8 is lane-local (no DPP).  Q1: the lane runs the minimum chains of its (row, column) pairs.  Bit-identical to k_qgemm_exact.
+// Two forms of one body (RS = result rows a lane works on), 256 threads each:
+//   RS = 4  grid (ceil(N / 64), ceil(M / 16)): the 4 waves are 4 column tiles of one row tile, every lane keeps all four rows the instruction
+//           gives it (32 chains) - the fewest VALU operations per output; for grids that fill the chip (the encoder).
+//   RS = 1  grid (ceil(N / 16), ceil(M / 16)): the 4 waves share ONE tile; wave w feeds the instruction the rows 4 i + w in the places 4 i .. 4 i + 3,
+//           so its register r = 0 holds row 4 (L / 16) + w, and works on that row only (8 chains; the other registers repeat it and are not
+//           read).  The integer work is done four times over in the otherwise idle matrix pipe; the VALU chain of a wave - which is what a
+//           prompt pass of a few row tiles waits for - is a quarter as long.
+// The row tile's scales (and Q8_1 block sums) are staged in LDS once - the kernel's only barrier; the quants come straight from global memory / L2
+// (the 4 waves' common operand rows meet in the vector cache), the next four blocks' loads in flight while the current four are worked on.
+// Nothing waits for another workgroup.  Rows beyond M and columns beyond N read the last valid row / column and store nothing.
+// -------------------------------------------------------------------------------------------------
+typedef int wq_i16 __attribute__((ext_vector_type(16)));
+
+// one quant block of the tile: s0 / s1 = the lane sums l = 0..3 / 4..7 (register 4 t + r: l = t (+ 4), row r of the lane's)
+#define WQ_MFMA_BLOCK(acc, summs, A0, A1, B0, B1, DW, DX, MW, SX) do { \
+        const wq_i16 wq_z = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; \
+        const wq_i16 s0 = __builtin_amdgcn_mfma_i32_16x16x4i8((A0), (B0), wq_z, 0, 0, 0); \
+        const wq_i16 s1 = __builtin_amdgcn_mfma_i32_16x16x4i8((A1), (B1), wq_z, 0, 0, 0); \
+        _Pragma("unroll") for (int r = 0; r < RS; ++r) { \
+            const float wq_p = (DW) * (DX)[r]; \
+            _Pragma("unroll") for (int t = 0; t < 4; ++t) { \
+                acc[r][t]     = fmaf(wq_p, (float) s0[4 * t + r], acc[r][t]); \
+                acc[r][4 + t] = fmaf(wq_p, (float) s1[4 * t + r], acc[r][4 + t]); \
+            } \
+            if (Q1) WQ_MIN(summs[r], (MW), (SX)[r]); \
+        } } while (0)
+
+template <int EPI, bool Q1, int RS>
+__global__ __launch_bounds__(256, RS == 1 ? 4 : Q1 ? 2 : 3) void k_qgemm_mfma(const int8_t * __restrict__ xq, const float * __restrict__ xd, int M,
+                                                                              const int8_t * __restrict__ wq, const float * __restrict__ wd, int N, int K, wa_epi e,
+                                                                              const float * __restrict__ xsum, const float * __restrict__ wm) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];       // the row tile's scales xds f32 [16][K/32] | Q1: its block sums xss f32 [16][K/32]
+    const int nb = K >> 5;
+    float * xds = (float *) smem, * xss = xds + 16 * nb;
+    const int lane = threadIdx.x & 63, c = lane & 15, g = lane >> 4, wv = threadIdx.x >> 6;
+    const int m0 = blockIdx.y * 16, n0 = (RS == 4 ? blockIdx.x * 4 + wv : blockIdx.x) * 16;
+    for (int i = threadIdx.x; i < 16 * nb; i += 256) {
+        const int r = i / nb, b = i - r * nb;
+        const size_t src = (size_t) min(m0 + r, M - 1) * nb + b;
+        xds[i] = xd[src];
+        if (Q1) xss[i] = xsum[src];
+    }
+    __syncthreads();                                       // the kernel's only barrier, before any wave leaves
+    if (n0 >= N) return;                                   // (a whole wave)
+    const int n = n0 + c, nn = n < N ? n : N - 1;
+    const int ma = min(RS == 4 ? m0 + c : m0 + (c & ~3) + wv, M - 1);         // the activation row whose bytes this lane feeds
+    const int r0 = RS == 4 ? 4 * g : 4 * g + wv;                                // the tile rows r0 .. r0 + RS - 1 are this lane's results
+    wa_epi_pre pre[RS];
+#pragma unroll
+    for (int r = 0; r < RS; ++r) pre[r] = epi_preload<EPI>(e, min(m0 + r0 + r, M - 1), nn);
+    // 32-bit element offsets from the (uniform) array bases: the launcher sends no product here whose arrays they could not index
+    const unsigned xo = ((unsigned) ma * 8 + g) * nb, wo = ((unsigned) nn * 8 + g) * nb, h = 4 * (unsigned) nb;      // l = g; l = 4 + g: + h
+    const unsigned so = (unsigned) nn * nb;
+    const int * xi = (const int *) xq, * wi = (const int *) wq;
+    const float * wmn = Q1 ? wm : wd;
+    const float * dxl = xds + r0 * nb, * sxl = Q1 ? xss + r0 * nb : dxl;          // the lane's rows in LDS: row r at + r nb
+    float acc[RS][8], summs[RS];
+#pragma unroll
+    for (int r = 0; r < RS; ++r) {
+        summs[r] = 0.0f;
+#pragma unroll
+        for (int t = 0; t < 8; ++t) acc[r][t] = 0.0f;
+    }
+    if ((nb & 3) == 0) {
+        wq_i4 a0n = *(const wq_i4 *) (xi + xo), a1n = *(const wq_i4 *) (xi + xo + h), b0n = *(const wq_i4 *) (wi + wo), b1n = *(const wq_i4 *) (wi + wo + h);
+        wq_f4 dn = *(const wq_f4 *) (wd + so), mn = dn;
+        if (Q1) mn = *(const wq_f4 *) (wmn + so);
+        for (int b = 0; b < nb; b += 4) {
+            const wq_i4 a0 = a0n, a1 = a1n, b0 = b0n, b1 = b1n; const wq_f4 dw = dn, mw = mn;
+            const unsigned bn = (unsigned) min(b + 4, nb - 4);
+            a0n = *(const wq_i4 *) (xi + xo + bn); a1n = *(const wq_i4 *) (xi + xo + h + bn);
+            b0n = *(const wq_i4 *) (wi + wo + bn); b1n = *(const wq_i4 *) (wi + wo + h + bn);
+            dn = *(const wq_f4 *) (wd + so + bn);
+            if (Q1) mn = *(const wq_f4 *) (wmn + so + bn);
+            wq_f4 dx4[RS], sx4[RS];
+#pragma unroll
+            for (int r = 0; r < RS; ++r) { dx4[r] = *(const wq_f4 *) (dxl + r * nb + b); sx4[r] = dx4[r]; if (Q1) sx4[r] = *(const wq_f4 *) (sxl + r * nb + b); }
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                float dx[RS], sx[RS];
+#pragma unroll
+                for (int r = 0; r < RS; ++r) { dx[r] = dx4[r][j]; sx[r] = sx4[r][j]; }
+                WQ_MFMA_BLOCK(acc, summs, a0[j], a1[j], b0[j], b1[j], dw[j], dx, mw[j], sx);
+            }
+        }
+    } else {
+        for (int b = 0; b < nb; ++b) {
+            float dx[RS], sx[RS];
+#pragma unroll
+            for (int r = 0; r < RS; ++r) { dx[r] = dxl[r * nb + b]; sx[r] = sxl[r * nb + b]; }
+            WQ_MFMA_BLOCK(acc, summs, xi[xo + b], xi[xo + h + b], wi[wo + b], wi[wo + h + b], wd[so + b], dx, wmn[so + b], sx);
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < RS; ++r) {
+        float v = ((acc[r][0] + acc[r][4]) + (acc[r][2] + acc[r][6])) + ((acc[r][1] + acc[r][5]) + (acc[r][3] + acc[r][7]));       // hsum_float_8
+        if (Q1) v = v + summs[r];
+        if (n < N && m0 + r0 + r < M) epi_apply<EPI>(e, m0 + r0 + r, n, v, pre[r]);
     }
 }
 
@@ -293,11 +405,45 @@ static bool few_rows_rule(int M) {
     static const bool off = getenv("WHISPER_AMD_NO_FEW_ROWS") != nullptr;
     return !off && M >= 2 && M <= 8;
 }
-// route 0: the rule above picks the kernel; 1: k_qgemm_exact (k_qgemv_exact for M == 1) whatever it says; 2: k_qgemv_rows wherever it exists (M = 2..8, the
-// epilogues of the decoder) - the kernel tests compare the two
+// The matrix-core rule: every product of more than 8 rows whose rows belong to one state.  Measured on the MI355X k_qgemm_mfma is the
+// faster one for every shape class timed.  WHISPER_AMD_NO_QMFMA=1 (read once per process) goes back to k_qgemm_exact.
+static bool qmfma_rule(int M, int N, int K) {
+    static const bool off = getenv("WHISPER_AMD_NO_QMFMA") != nullptr;
+    (void) N; (void) K;
+    return !off && M >= 9;
+}
+// the kernel a route gives a product: 1 k_qgemm_exact (k_qgemv_exact for M == 1), 2 k_qgemv_rows, 3 k_qgemm_mfma
+int wa_qgemm_exact_kernel(wa_epi_mode mode, int M, int N, int K, const wa_epi & e, int route) {
+    const bool few_mode = mode == WA_EPI_F16 || mode == WA_EPI_GELU_F32 || mode == WA_EPI_RESID || mode == WA_EPI_F32 || mode == WA_EPI_DEC_QKV;
+    if (M >= 2 && M <= 8 && few_mode && route != 1 && (route == 2 || few_rows_rule(M))) return 2;       // (route 3 below 9 rows: the rule's kernel)
+    const bool idx32 = (long long) (M > N ? M : N) * K < (1ll << 33);         // k_qgemm_mfma indexes the quants by 32-bit int offsets
+    if (M >= 9 && !e.rowp && idx32 && route != 1 && route != 2 && (route == 3 || qmfma_rule(M, N, K))) return 3;
+    return 1;
+}
+// route 0: the rules above pick the kernel; 1: k_qgemm_exact (k_qgemv_exact for M == 1) whatever they say; 2: k_qgemv_rows wherever it exists (M = 2..8, the
+// epilogues of the decoder); 3: k_qgemm_mfma wherever it applies (M >= 9, no rowp) - the kernel tests compare them
 void wa_launch_qgemm_exact_route(hipStream_t s, wa_epi_mode mode, const int8_t * xq, const float * xd, int M, const int8_t * wq, const float * wd, int N, int K,
                                  const wa_epi & e, const float * xs, const float * wm, int route) {
-    const bool few = M >= 2 && M <= 8 && route != 1 && (route == 2 || few_rows_rule(M));
+    const int kernel = wa_qgemm_exact_kernel(mode, M, N, K, e, route);
+    if (kernel == 3) {
+        // the form with four rows per lane where its 64-column workgroups still give every CU two of them (the encoder); the one-row form for the
+        // few row tiles of a prompt pass, which would leave most of the chip idle otherwise and wait for long single waves
+        const bool wide = (long) ((N + 63) / 64) * ((M + 15) / 16) >= 512;
+        const dim3 grid(wide ? (N + 63) / 64 : (N + 15) / 16, (M + 15) / 16);
+        const size_t lds = (size_t) (wm ? 32 : 16) * (K >> 5) * sizeof(float);           // <= 20 KiB at K = 5120
+#define WA_MFMA_L(E, Q1, RS) hipLaunchKernelGGL((k_qgemm_mfma<E, Q1, RS>), grid, dim3(256), lds, s, xq, xd, M, wq, wd, N, K, e, xs, wm)
+#define WA_CASE(E) case E: if (wm) { if (wide) WA_MFMA_L(E, true, 4); else WA_MFMA_L(E, true, 1); } \
+                           else    { if (wide) WA_MFMA_L(E, false, 4); else WA_MFMA_L(E, false, 1); } \
+                           break;
+        switch (mode) {
+            WA_CASE(WA_EPI_F16) WA_CASE(WA_EPI_ENC_QKV) WA_CASE(WA_EPI_GELU_F32) WA_CASE(WA_EPI_RESID) WA_CASE(WA_EPI_F32) WA_CASE(WA_EPI_CROSS_KV) WA_CASE(WA_EPI_DEC_QKV)
+            default: break;
+        }
+#undef WA_CASE
+#undef WA_MFMA_L
+        return;
+    }
+    const bool few = kernel == 2;
     if (few) {
 #define WA_ROWS_R(E, Q1, R) case R: hipLaunchKernelGGL((k_qgemv_rows<E, Q1, R>), dim3((N + 7) / 8), dim3(64), 0, s, xq, xd, wq, wd, N, K, e, xs, wm); return;
 #define WA_ROWS_Q(E, Q1) switch (M) { WA_ROWS_R(E, Q1, 2) WA_ROWS_R(E, Q1, 3) WA_ROWS_R(E, Q1, 4) WA_ROWS_R(E, Q1, 5) WA_ROWS_R(E, Q1, 6) WA_ROWS_R(E, Q1, 7) WA_ROWS_R(E, Q1, 8) default: break; }

@@ -266,6 +266,8 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         proto("whisper_amd_dtw_path", I, P, C.POINTER(F), I, I, I, I, I, I, I, C.POINTER(C.c_int32), C.POINTER(C.c_int32), I)
         proto("whisper_amd_dtw_stats", None, P, C.POINTER(C.c_long))
         proto("whisper_amd_dtw_timings", None, P, C.POINTER(C.c_int64))
+    if hasattr(lib, "whisper_amd_qgemm_stats"):
+        proto("whisper_amd_qgemm_stats", None, P, C.POINTER(C.c_long))
     _LIBS[path] = lib
     return lib
 
@@ -481,6 +483,12 @@ class WhisperState:
         if r < 0:
             raise WhisperError("GenericError", r)
         return r, np.array(probs[:], dtype=np.float32)
+
+    def qgemm_stats(self) -> tuple:
+        """Extension: (quantised products of more than 8 rows served by the int8 matrix-core kernel, served by k_qgemm_exact) since the state was created."""
+        out = (C.c_long * 2)()
+        self.lib.whisper_amd_qgemm_stats(self.ptr, out)
+        return int(out[0]), int(out[1])
 
     def rows_stats(self) -> tuple:
         """Extension: (decoder passes of several token rows served by the one-launch form, passes sent back to the launch sequence)."""
