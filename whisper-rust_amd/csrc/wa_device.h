@@ -218,7 +218,8 @@ static __device__ const unsigned long long WA_EXP2F_T[32] = {
     0x3feeff76f2fb5e47ULL, 0x3fef199bdd85529cULL, 0x3fef3720dcef9069ULL, 0x3fef5818dcfba487ULL, 0x3fef7c97337b9b5fULL,
     0x3fefa4afa2a490daULL, 0x3fefd0765b6e4540ULL,
 };
-__device__ __forceinline__ float wa_expf_libm(float x) {
+// `tab`: WA_EXP2F_T or a copy of it (a latency-bound caller keeps one in LDS: the entry's index depends on x, so the read is in series)
+__device__ __forceinline__ float wa_expf_libm_tab(float x, const unsigned long long * tab) {
     if (!(x >= -0x1.9fe368p6f)) return 0.0f;            // underflow and -inf (arguments here are always <= 0)
     const double InvLn2N = 0x1.71547652b82fep+0 * 32;
     const double C0 = 0x1.c6af84b912394p-5 / 32 / 32 / 32, C1 = 0x1.ebfce50fac4f3p-3 / 32 / 32, C2 = 0x1.62e42ff0c52d6p-1 / 32;
@@ -228,7 +229,7 @@ __device__ __forceinline__ float wa_expf_libm(float x) {
     const unsigned long long ki = (unsigned long long) __double_as_longlong(kd);
     kd = kd - SHIFT;
     const double r = z - kd;
-    const unsigned long long t = WA_EXP2F_T[ki & 31] + (ki << 47);
+    const unsigned long long t = tab[ki & 31] + (ki << 47);
     const double s = __longlong_as_double((long long) t);
     z = fma(C0, r, C1);
     const double r2 = r * r;
@@ -237,6 +238,7 @@ __device__ __forceinline__ float wa_expf_libm(float x) {
     y = y * s;
     return (float) y;
 }
+__device__ __forceinline__ float wa_expf_libm(float x) { return wa_expf_libm_tab(x, WA_EXP2F_T); }
 
 // -------------------------------------------------------------------------------------------------
 // certified F64 sums (LayerNorm / soft-max denominators), shared by wa_exact.hip, wa_mega.hip and wa_rows.hip

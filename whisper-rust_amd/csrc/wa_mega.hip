@@ -1063,7 +1063,7 @@ __device__ __forceinline__ void mg_attn_finish16(const float * part, const doubl
 // role: self-attention of head h (whisper.cpp:2636-2651), every layer.  The K/V cells of earlier tokens are copied
 // into LDS while the GEMV workgroups are busy with the previous phases; the new cell arrives with the query.
 // -------------------------------------------------------------------------------------------------
-template <bool Q = false>
+template <bool Q = false, bool NF = false>        // NF: the serial path of k_decode_mega_cq (below); the other kernels keep the first form
 __device__ __forceinline__ void mg_role_self(mg_kargs A_, int idx_) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const mg_kargs A = mo_uniform(A_);
@@ -1079,6 +1079,9 @@ __device__ __forceinline__ void mg_role_self(mg_kargs A_, int idx_) {
     const int d = A->d, n_kv = A->n_kv, kv_head = A->kv_head, L = A->n_layer;
     const int a = tid & 3, kslot = tid >> 2;
     if (wave == 0) mg_pick(A, lane, (int *) (smem + MG_PICK_OFF));
+    // (NF) wa_expf_libm's table, which every tail cell reads at an index that depends on its score: in LDS (M.gs: 256 bytes the role has no
+    // other use for) instead of global memory; visible behind the first barrier below
+    if constexpr (NF) { if (tid < 32) ((unsigned long long *) M.gs)[tid] = WA_EXP2F_T[tid]; }
     for (int l = 0; l < L; ++l) {
         {   // cells of earlier tokens -> LDS (row kv_head is stale here and replaced below)
             const gch kc = (gch) A->kv_k + (size_t) l * A->kv_layer_stride + h * 64;
@@ -1109,6 +1112,95 @@ __device__ __forceinline__ void mg_role_self(mg_kargs A_, int idx_) {
             if (lane < 32) { ((unsigned *) M.qs)[lane] = v[0]; ((unsigned *) (Vs + (size_t) kv_head * 64))[lane] = v[1]; }
             else ((unsigned *) (Ks + (size_t) kv_head * 64))[lane - 32] = v[0];
         }
+        if constexpr (NF) {
+        // ---- the serial path of k_decode_mega_cq; the arithmetic is the first form's (below) ----
+        // n_kv <= 64 (a launch argument: the same in every wave): wave 0 alone runs gather -> scores -> soft-max with no barrier in between -
+        // what it wrote to LDS it reads back itself, in program order, and cell c stays in lane c from its score to its probability -; the
+        // other waves wait at the barrier in front of P V.  Longer contexts: all eight waves compute scores, which reach their cell's thread
+        // behind the barrier that exchanges the waves' maxima; the round of the F64 partial sums remains too.  Every wave meets the same
+        // barriers on either path: `one` and `has` are wave-uniform and no barrier stands inside a branch on `has`.
+        const bool one = n_kv <= 64;
+        if (!one) wa_barrier_lds();
+        else asm volatile("" ::: "memory");         // (wave 0's own LDS writes above stay ahead of its reads below: the words are read back as F16)
+        MG_CHAOS_ID(1000 + h, 22u, c.seq);
+        const bool has = 64 * wave < n_kv;          // this wave holds cells 64 wave .. 64 wave + 63 from the soft-max on
+        // ---- scores: 4 lanes per key (mo_score); every lane of a key's four ends with its score ----
+        float r = -INFINITY, lmax = -INFINITY;      // the score of cell tid; the maximum of this thread's keys
+        if (!one || wave == 0) {
+            float qa[8], qb[8];
+#pragma unroll
+            for (int i = 0; i < 8; ++i) { qa[i] = h2f(M.qs[8 * a + i]); qb[i] = h2f(M.qs[32 + 8 * a + i]); }
+            if (one) {      // wave 0, sub-pass j = keys 16 j + quad
+                float rj[4] = { 0.0f, 0.0f, 0.0f, 0.0f };
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    if (16 * j < n_kv) {
+                        const int cc = 16 * j + (lane >> 2), cl = cc < n_kv ? cc : n_kv - 1;
+                        const u32x4 ka = *(const u32x4 *) (Ks + (size_t) cl * 64 + 8 * a), kb = *(const u32x4 *) (Ks + (size_t) cl * 64 + 32 + 8 * a);
+                        rj[j] = mo_score(ka, kb, qa, qb, 1.0f);
+                    }
+                }
+                // lane 4 q + a keeps sub-pass a's score (cell 16 a + q); ONE permute then brings cell `lane` from lane 4 (lane & 15) + (lane >> 4)
+                const float mine = a == 0 ? rj[0] : a == 1 ? rj[1] : a == 2 ? rj[2] : rj[3];
+                const float got = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(4 * (4 * (lane & 15) + (lane >> 4)), __builtin_bit_cast(int, mine)));
+                if (tid < n_kv) r = lmax = got;
+            } else {        // every wave, 128 keys a pass; a score reaches its cell's thread through LDS behind the barrier the maxima need anyway
+                for (int c0 = 0; c0 < n_kv; c0 += MG_THREADS / 4) {
+                    const int cc = c0 + kslot, cl = cc < n_kv ? cc : n_kv - 1;
+                    const u32x4 ka = *(const u32x4 *) (Ks + (size_t) cl * 64 + 8 * a), kb = *(const u32x4 *) (Ks + (size_t) cl * 64 + 32 + 8 * a);
+                    const float sc = mo_score(ka, kb, qa, qb, 1.0f);
+                    if (cc < n_kv) { if (a == 0) M.sc[cc] = sc; lmax = fmaxf(lmax, sc); }
+                }
+            }
+        }
+        mg_trace(A, h == 0 && tid == 0, (l * 8 + 6) * 8 + 4, mg_now());
+        MG_CHAOS_ID(1000 + h, 23u, c.seq);
+        {   // soft_max (ops.cpp:4792-4818, vec.cpp:257-308), cell tid in thread tid
+            // the wave's maximum by DPP (exact in any order): row_ror 8, 4, 2, 1, then the four rows
+            lmax = fmaxf(lmax, dpp_f32<0x128>(lmax)); lmax = fmaxf(lmax, dpp_f32<0x124>(lmax));
+            lmax = fmaxf(lmax, dpp_f32<0x122>(lmax)); lmax = fmaxf(lmax, dpp_f32<0x121>(lmax));
+            {
+                const int b = __builtin_bit_cast(int, lmax);
+                const float m0 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(b, 0)), m1 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(b, 16));
+                const float m2 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(b, 32)), m3 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(b, 48));
+                lmax = fmaxf(fmaxf(m0, m1), fmaxf(m2, m3));
+            }
+            float mx = lmax;
+            if (!one) {
+                if (lane == 0) M.red[wave] = lmax;
+                wa_barrier_lds();
+                mx = M.red[0];
+#pragma unroll
+                for (int k = 1; k < MG_NW; ++k) mx = fmaxf(mx, M.red[k]);
+                if (tid < n_kv) r = M.sc[tid];
+            }
+            const int n8 = n_kv & ~7, ng = n8 >> 3;
+            float e = 0.0f;
+            double ps = 0.0;
+            if (has) {
+                if (tid < n_kv) e = tid < n8 ? wa_expf(r - mx) : wa_expf_libm_tab(r - mx, (const unsigned long long *) M.gs);
+                float t = e + dpp_f32<0x104>(e);        // lanes r = 0..3 of a group of 8 cells: e[r] + e[r+4]
+                t = t + dpp_f32<0x102>(t);              // r = 0: (e0+e4)+(e2+e6)   r = 1: (e1+e5)+(e3+e7)
+                t = t + dpp_f32<0x101>(t);              // r = 0: the group sum in ops.cpp's order
+                if (tid < n8) ps = (tid & 7) == 0 ? (double) t : 0.0;
+                else if (tid < n_kv) ps = (double) e;   // the n % 8 tail cells
+                ps = wave_sum_d(ps);
+            }
+            double tot = ps;                            // (one: wave 0 holds every addend; the tree below adds seven +0.0 to it)
+            if (!one) {
+                if (lane == 0) M.redd[wave] = ps;
+                wa_barrier_lds();
+                tot = ((M.redd[0] + M.redd[1]) + (M.redd[2] + M.redd[3])) + ((M.redd[4] + M.redd[5]) + (M.redd[6] + M.redd[7]));
+            }
+            if (has) {
+                float ilo, ihi;
+                wa_softmax_bounds(tot, ng, ilo, ihi);
+                if (ilo != ihi && tid == 0 && !c.dead) __hip_atomic_store(c.status, (unsigned) WA_MEGA_REDO, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if (tid < n_kv) M.p16[tid] = f2h(e * ilo);
+            }
+            wa_barrier_lds();
+        }
+        } else {
         wa_barrier_lds();
         // ---- scores: 4 lanes per key ----
         float lmax = -INFINITY;
@@ -1153,10 +1245,49 @@ __device__ __forceinline__ void mg_role_self(mg_kargs A_, int idx_) {
             if (tid < n_kv) M.p16[tid] = f2h(e * ilo);
             wa_barrier_lds();
         }
+        }
         mg_trace(A, h == 0 && tid == 0, (l * 8 + 6) * 8 + 5, mg_now());
         MG_CHAOS_ID(1000 + h, 21u, c.seq);
-        // ---- P V: chains r = cell mod 32 (4 per wave), lane = d_head index ----
         const int np = n_kv & ~31, nsteps = np >> 5;
+        if constexpr (NF) {
+        // ---- P V: chains r = cell mod 32, 4 per wave.  A lane holds TWO outputs (2 o2, 2 o2 + 1) of TWO chains (r0 + hw, r0 + 2 + hw; hw = its
+        // half-wave): a step is two 4-byte V reads - the halves read neighbouring rows, i.e. all 64 banks - and one 8-byte read of the step's
+        // four probabilities, 3 LDS instructions where one output per lane took 8; the phase was bound by their issue (8 waves, one LDS pipe).
+        // Blocks of four steps have every read in flight before the first fmaf; each chain's fmaf sequence is the one of vec.cpp:169-219. ----
+        {
+            const int r0 = wave * 4, hw = lane >> 5, o2 = lane & 31;
+            float acc[2][2] = { { 0.0f, 0.0f }, { 0.0f, 0.0f } };
+            const wa_f16 * vbase = Vs + (size_t) (r0 + hw) * 64 + 2 * o2;
+            auto block = [&](auto nk, int s0) {
+                constexpr int NK = decltype(nk)::value;
+                unsigned va[NK], vb[NK];
+                u32x2 pp[NK];
+#pragma unroll
+                for (int k = 0; k < NK; ++k) {
+                    va[k] = *(const unsigned *) (vbase + (size_t) (s0 + k) * 32 * 64);
+                    vb[k] = *(const unsigned *) (vbase + (size_t) (s0 + k) * 32 * 64 + 2 * 64);
+                    pp[k] = *(const u32x2 *) (M.p16 + (s0 + k) * 32 + r0);
+                }
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int k = 0; k < NK; ++k) {
+                    const float pa = h2f((wa_f16) (hw ? pp[k].x >> 16 : pp[k].x & 0xffffu)), pb = h2f((wa_f16) (hw ? pp[k].y >> 16 : pp[k].y & 0xffffu));
+                    acc[0][0] = fmaf(h2f((wa_f16) (va[k] & 0xffffu)), pa, acc[0][0]); acc[0][1] = fmaf(h2f((wa_f16) (va[k] >> 16)), pa, acc[0][1]);
+                    acc[1][0] = fmaf(h2f((wa_f16) (vb[k] & 0xffffu)), pb, acc[1][0]); acc[1][1] = fmaf(h2f((wa_f16) (vb[k] >> 16)), pb, acc[1][1]);
+                }
+            };
+            int s0 = 0;
+            for (; s0 + 4 <= nsteps; s0 += 4) block(std::integral_constant<int, 4>(), s0);
+            const int rem = nsteps - s0;        // (wave-uniform)
+            if (rem == 3) block(std::integral_constant<int, 3>(), s0);
+            else if (rem == 2) block(std::integral_constant<int, 2>(), s0);
+            else if (rem == 1) block(std::integral_constant<int, 1>(), s0);
+            *(float2 *) (M.part + (r0 + hw) * 64 + 2 * o2) = make_float2(acc[0][0], acc[0][1]);
+            *(float2 *) (M.part + (r0 + 2 + hw) * 64 + 2 * o2) = make_float2(acc[1][0], acc[1][1]);
+        }
+        mg_trace(A, h == 0 && tid == 0, (l * 8 + 6) * 8 + 6, mg_now());
+        } else {
+        // ---- P V: chains r = cell mod 32 (4 per wave), lane = d_head index ----
         {
             float acc[4] = { 0.0f, 0.0f, 0.0f, 0.0f };
             const int r0 = wave * 4;
@@ -1168,7 +1299,9 @@ __device__ __forceinline__ void mg_role_self(mg_kargs A_, int idx_) {
 #pragma unroll
             for (int i = 0; i < 4; ++i) M.part[(r0 + i) * 64 + lane] = acc[i];
         }
+        }
         wa_barrier_lds();
+        if constexpr (NF) mg_trace(A, h == 0 && tid == 0, (l * 8 + 6) * 8 + 7, mg_now());      // (timeline: the finish starts)
         // (the 8 KB behind cell WA_MEGA_KV_ROOM of the K and of the V copy are free: the host sends longer contexts through the launch sequence)
         mg_attn_finish<Q>(M.part, Vs + (size_t) np * 64, M.p16, np, n_kv - np, mg_edge(A, l, E_AO), h, c.seq, tid, (double *) (Ks + WA_MEGA_KV_ROOM * 64),
                           (double *) (Vs + WA_MEGA_KV_ROOM * 64), A, A->dbg && h == 0 && l == MG_WGTRACE_LAYER ? 3004 : -1);
@@ -1651,7 +1784,7 @@ __global__ __launch_bounds__(MG_THREADS) void k_decode_mega_cq(const wa_mega_arg
     mg_role_of((int) gridDim.x, A.n_head, (int) blockIdx.x, role, idx);
     const mg_kargs Ap = (mg_kargs) __builtin_amdgcn_kernarg_segment_ptr();
     if (role == 0)      mg_role_gemv<2, 24, false, true>(Ap, idx);
-    else if (role == 1) mg_role_self(Ap, idx);
+    else if (role == 1) mg_role_self<false, true>(Ap, idx);
     else                mg_role_cross<false, 24, true>(Ap, idx);
 }
 
