@@ -508,9 +508,10 @@ WHISPER_API int whisper_amd_seq_debug(struct whisper_context * ctx, struct whisp
  * out = { passes served by it, passes sent to the launch sequence after a status word } since the state was created. */
 WHISPER_API void whisper_amd_rows_stats(struct whisper_state * state, long out[2]);
 WHISPER_API int  whisper_amd_rows_enabled(struct whisper_state * state);
-/* Quantised models (Q5_0 / Q8_0 / Q4_1 / Q5_1): the products with more than 8 activation rows - the encoder, the cross K/V product, prompt passes,
- * DTW's extra pass - that this state launched since it was created: out = { served by the int8 matrix-core kernel (k_qgemm_mfma),
- * served by k_qgemm_exact }.  WHISPER_AMD_NO_QMFMA=1 in the environment sends all of them to the second. */
+/* Quantised models (Q5_0 / Q8_0 / Q4_1 / Q5_1 and the K formats Q2_K / Q3_K / Q5_K / Q6_K): the products with more than 8 activation rows - the
+ * encoder, the cross K/V product, prompt passes, DTW's extra pass - that this state launched since it was created: out = { served by the int8
+ * matrix-core kernel (k_qgemm_mfma; K formats: k_kgemm_mfma), served by k_qgemm_exact (K formats: k_kgemm_exact) }.  WHISPER_AMD_NO_QMFMA=1 in
+ * the environment sends all of them to the second. */
 WHISPER_API void whisper_amd_qgemm_stats(struct whisper_state * state, long out[2]);
 /* Debugging aid (tools/rows_check.py): B identical rows (token, position n_past) of this state through the several-rows step; copies out the
  * hand-off granules [n_text_layer][8][B][2 * n_text_state] and the logits [B][n_vocab].  Returns the status word (0 = ok), < 0: not available. */

@@ -316,8 +316,10 @@ bool wa_encode(whisper_context & ctx, whisper_state & st, int mel_offset, ggml_a
             else    wa_launch_quantize_q8_0(s, A, lda, M, K, st.d_q8, st.d_q8d, st.d_q8s);
         };
         auto qmul = [&](wa_epi_mode mode, const wa_lin & L, int M, const wa_epi & e) {       // operand rows already in d_q8 / d_q8d
-            if (QK) wa_launch_kgemm_exact(s, mode, m.wtype, st.d_q8, st.d_q8d, st.d_q8bs, M, L.qs, L.qsc, L.qd, L.qm, L.n_out, L.n_in, e);
-            else {
+            if (QK) {
+                if (M > 8) (wa_kgemm_kernel(mode, m.wtype, M, L.n_out, L.n_in, e, 0) == 3 ? st.n_qgemm_mfma : st.n_qgemm_exact) += 1;
+                wa_launch_kgemm_route(s, mode, m.wtype, st.d_q8, st.d_q8d, st.d_q8bs, M, L.qs, L.qsc, L.qd, L.qm, L.n_out, L.n_in, e, 0);
+            } else {
                 if (M > 8) (wa_qgemm_exact_kernel(mode, M, L.n_out, L.n_in, e, 0) == 3 ? st.n_qgemm_mfma : st.n_qgemm_exact) += 1;
                 wa_launch_qgemm_exact(s, mode, st.d_q8, st.d_q8d, M, L.qs, L.qd, L.n_out, L.n_in, e, st.d_q8s, L.qm);
             }

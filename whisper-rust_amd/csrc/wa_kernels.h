@@ -141,6 +141,12 @@ void wa_launch_quantize_q8_K(hipStream_t stream, const float * x, int ldx, int r
 // C[M][N] = xq . Wq^T in ggml_vec_dot_q2_K_q8_K / q3_K_q8_K / q5_K_q8_K / q6_K_q8_K order, any M; the epilogues of wa_launch_qgemm_exact
 void wa_launch_kgemm_exact(hipStream_t stream, wa_epi_mode mode, int wtype, const int8_t * xq, const float * xd, const int16_t * xbs, int M, const int8_t * wq,
                            const int8_t * wsc, const float * wd, const float * wdm, int N, int K, const wa_epi & e);
+// the same with the kernel named (wa_quantk_mfma.hip; 0: the launcher's own rule; 1: wa_launch_kgemm_exact whatever the rule says; 3: the matrix-core
+// kernel k_kgemm_mfma wherever it applies: M >= 9 and e.rowp null)
+void wa_launch_kgemm_route(hipStream_t stream, wa_epi_mode mode, int wtype, const int8_t * xq, const float * xd, const int16_t * xbs, int M, const int8_t * wq,
+                           const int8_t * wsc, const float * wd, const float * wdm, int N, int K, const wa_epi & e, int route);
+// the kernel that launcher takes for a product and a route: 1 k_kgemm_exact (k_kgemv_exact for M == 1), 3 k_kgemm_mfma
+int wa_kgemm_kernel(wa_epi_mode mode, int wtype, int M, int N, int K, const wa_epi & e, int route);
 // token embedding rows of such a matrix (dequantize_row_q2_K / q3_K / q5_K / q6_K) + positional embedding
 void wa_launch_dec_embed_k(hipStream_t stream, int wtype, const int32_t * tok, const int32_t * pos, int n_tokens, int d, const int8_t * wq, const int8_t * wsc,
                            const float * wd, const float * wdm, const float * pe, float * x);

@@ -22,17 +22,8 @@
 // and lane l's two minimums are bytes l and 8 + l of the block's 16: no exchange between lanes, with one activation row or with eight.
 // This file is compiled twice: wa_quantk.o holds everything but Q2_K, wa_quantk_q2.o (-DWA_QK_Q2_TU) the Q2_K instantiations of the two
 // products and their launcher - a code object of their own beside the fourteen + fourteen of Q5_K / Q6_K.
-#include "wa_device.h"
+#include "wa_quantk_dev.h"      // the vector types, wk_hsum8, the format enum WK_Q6 / WK_Q5 / WK_Q2 and wk_byte: shared with wa_quantk_mfma.hip
 
-typedef int wk_i4 __attribute__((ext_vector_type(4)));
-typedef int wk_i2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ float wk_hsum8(float v) {
-    v = v + dpp_f32<0x104>(v);          // row_shl:4  acc[l] + acc[l+4]
-    v = v + dpp_f32<0x102>(v);          // row_shl:2  (a0+a4)+(a2+a6) | (a1+a5)+(a3+a7)
-    v = v + dpp_f32<0x101>(v);          // row_shl:1  the two halves
-    return v;
-}
 __device__ __forceinline__ int wk_isum8(int v) {      // integer sum of an 8-lane group, valid in its lane 0 (any order is exact)
     v += __builtin_amdgcn_update_dpp(0, v, 0x104, 0xf, 0xf, true);
     v += __builtin_amdgcn_update_dpp(0, v, 0x102, 0xf, 0xf, true);
@@ -44,12 +35,6 @@ __device__ __forceinline__ float wk_from_lane(float v, int m) {      // lane 0 o
         case 1: return dpp_f32<0x101>(v); case 2: return dpp_f32<0x102>(v); case 3: return dpp_f32<0x103>(v); case 4: return dpp_f32<0x104>(v);
         case 5: return dpp_f32<0x105>(v); case 6: return dpp_f32<0x106>(v); case 7: return dpp_f32<0x107>(v); default: return v;
     }
-}
-enum { WK_Q6 = 0, WK_Q5 = 1, WK_Q2 = 2 };      // the weight format of an instantiation (Q3_K runs as WK_Q6)
-// byte g (0..7) of the scale pair s: signed (Q6_K), unsigned (Q5_K, values <= 63) or its low nibble (Q2_K)
-template <int F> __device__ __forceinline__ int wk_byte(wk_i2 s, int g) {
-    const int w = g < 4 ? s.x : s.y, sh = 8 * (g & 3);
-    return F == WK_Q6 ? (w << (24 - sh)) >> 24 : (int) (((unsigned) w >> sh) & (F == WK_Q2 ? 0xfu : 0xffu));
 }
 // the integer sum of one lane over one 256-value block: 8 groups, quads w0 | w1 against x0 | x1, scale bytes s
 template <int F> __device__ __forceinline__ int wk_block(wk_i4 w0, wk_i4 w1, wk_i4 x0, wk_i4 x1, wk_i2 s) {
