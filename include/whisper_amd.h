@@ -563,6 +563,16 @@ WHISPER_API int  whisper_amd_dtw_path(struct whisper_state * state, const float 
 WHISPER_API void whisper_amd_dtw_stats(struct whisper_state * state, long out[3]);
 WHISPER_API void whisper_amd_dtw_timings(struct whisper_state * state, int64_t out[2]);
 
+/* Model load (wa_loader.cpp).  By default the tensor bytes go to the device in pinned chunks while the next chunk is being read, and
+ * HIP kernels (wa_load.hip) write the kernel layouts straight into the weight arena; WHISPER_AMD_LOAD_HOST=1 in the environment WHEN A CONTEXT IS
+ * CREATED takes the host path instead (a host image of the arena, unpacked on the host, one upload).  Both leave the same arena, byte for byte.
+ * whisper_amd_arena_read: copies up to `cap` bytes of the weight arena from byte `offset` into `dst` (host) and returns the arena's size in bytes
+ *   (call with cap = 0 to size the buffer); -1 without a loaded model or when the copy fails.
+ * whisper_amd_load_stats: out = { path taken (0 host, 1 device), tensor bytes read from the loader, unpack kernels launched, microseconds in
+ *   loader->read for tensor bytes, microseconds waiting for the device, microseconds for the whole load }. */
+WHISPER_API int64_t whisper_amd_arena_read(struct whisper_context * ctx, int64_t offset, void * dst, int64_t cap);
+WHISPER_API void    whisper_amd_load_stats(struct whisper_context * ctx, int64_t out[6]);
+
 #ifdef __cplusplus
 }
 #endif

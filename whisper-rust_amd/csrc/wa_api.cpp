@@ -66,6 +66,20 @@ void whisper_amd_batch_stats(struct whisper_context * ctx, long * steps, long * 
 long whisper_amd_batch_one_launch(struct whisper_context * ctx) { return ctx ? ctx->batch_one_launch : 0; }
 long whisper_amd_batch_served(struct whisper_context * ctx) { return ctx ? ctx->batch_served : 0; }
 
+// the weight arena as the loader left it, and how the loader got there (wa_loader.cpp)
+int64_t whisper_amd_arena_read(struct whisper_context * ctx, int64_t offset, void * dst, int64_t cap) {
+    if (!ctx || !ctx->model.arena) return -1;
+    const int64_t size = (int64_t) ctx->model.arena_size;
+    if (dst && cap > 0 && offset >= 0 && offset < size) {
+        if (!WA_HIP_OK(hipSetDevice(ctx->device))) return -1;
+        if (!WA_HIP_OK(hipMemcpy(dst, (const uint8_t *) ctx->model.arena + offset, (size_t) std::min(cap, size - offset), hipMemcpyDeviceToHost))) return -1;
+    }
+    return size;
+}
+void whisper_amd_load_stats(struct whisper_context * ctx, int64_t out[6]) {
+    for (int i = 0; i < 6; ++i) out[i] = ctx ? ctx->load_stats[i] : 0;
+}
+
 } // extern "C"
 
 // -------------------------------------------------------------------------------------------------

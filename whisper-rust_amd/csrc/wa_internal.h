@@ -129,6 +129,7 @@ struct wa_model {
 
 struct whisper_context {
     int64_t t_load_us = 0, t_start_us = 0;
+    int64_t load_stats[6] = { 0, 0, 0, 0, 0, 0 };   // whisper_amd_load_stats: path, tensor bytes read, unpack kernels, us in loader->read, us waiting for the device, us in wa_model_load
     whisper_context_params params;
     int device = 0;
     bool exact = true;                    // !params.flash_attn: encoder/prompt in the reference's summation order (bit-exact)

@@ -11,13 +11,24 @@
 //     ONE GEMM over the encoder output,
 //   * conv weights re-ordered k-major ([oc][k][ic]) so conv1/conv2 read the activations as a plain
 //     strided view (no im2col buffer), conv1's K padded to a multiple of 32 with zeros.
+//
+// Where the tensor bytes go: by default through two pinned host buffers to the device, where the kernels of wa_load.hip write
+// the kernel layouts straight into the arena while the next chunk is being read; with WHISPER_AMD_LOAD_HOST=1 through a host image of the
+// arena, unpacked by the host functions (wa_quant1.h, wa_quantk.h, wa_load.h) and uploaded in one copy.  Both give the same arena, byte for byte.
 #include "wa_internal.h"
+#include "wa_load.h"
+#include "wa_load_plan.h"
 #include "wa_mega.h"
 #include "wa_quant1.h"
 #include "wa_quantk.h"
 
 #include <cmath>
+#include <cstdlib>
 #include <cstring>
+
+// bytes of one pinned host buffer and of one device staging buffer of the device load path (two of each); WHISPER_AMD_LOAD_CHUNK, read at
+// every load, overrides it (tests); never less than the longest row of the model.  Chosen by measurement: DESIGN.md 4.9.
+#define WA_LOAD_CHUNK_BYTES ((size_t) 4 << 20)
 
 namespace {
 
@@ -46,6 +57,59 @@ struct slot {             // where a named tensor goes
     size_t off4 = 0;
     size_t off5 = 0;
     bool   seen = false;
+};
+
+// The device load path's buffers: two pinned host buffers, two device staging buffers, one stream, one event per buffer.  The host fills
+// pin[cur] behind `used` while the stream still copies and unpacks what was placed before; next() switches buffers and waits until the
+// other one's last copy has left it.  Closing waits for the stream, then frees everything - and the arena too unless the load succeeded.
+struct load_pipe {
+    hipStream_t stream = nullptr;
+    uint8_t * pin[2] = { nullptr, nullptr }, * stage[2] = { nullptr, nullptr };
+    hipEvent_t ev[2] = { nullptr, nullptr };
+    bool pending[2] = { false, false };
+    size_t cap = 0, used = 0;     // bytes of a buffer the chunk planner may fill, bytes of pin[cur] taken
+    int cur = 0;
+    int64_t n_kernels = 0;
+    void ** arena = nullptr;
+    bool ok = false;
+
+    // cap: what a chunk may fill; alloc >= cap: the buffers' size (the constants' block may be longer than a chunk).  False, with nothing
+    // left allocated, when a buffer cannot be had.
+    bool open(size_t cap_, size_t alloc) {
+        cap = cap_;
+        bool got = hipStreamCreateWithFlags(&stream, hipStreamNonBlocking) == hipSuccess;
+        for (int i = 0; i < 2 && got; ++i)
+            got = hipHostMalloc((void **) &pin[i], alloc, hipHostMallocDefault) == hipSuccess && hipMalloc((void **) &stage[i], alloc) == hipSuccess &&
+                  hipEventCreateWithFlags(&ev[i], hipEventDisableTiming) == hipSuccess;
+        if (!got) { (void) hipGetLastError(); close(); }
+        return got;
+    }
+    bool next(int64_t & t_wait_us) {
+        if (!WA_HIP_OK(hipEventRecord(ev[cur], stream))) return false;
+        pending[cur] = true;
+        cur ^= 1; used = 0;
+        if (pending[cur]) {
+            const int64_t t0 = wa_time_us();
+            const bool done = WA_HIP_OK(hipEventSynchronize(ev[cur]));
+            t_wait_us += wa_time_us() - t0;
+            pending[cur] = false;
+            return done;
+        }
+        return true;
+    }
+    void close() {
+        if (stream) (void) hipStreamSynchronize(stream);
+        for (int i = 0; i < 2; ++i) {
+            if (pin[i]) (void) hipHostFree(pin[i]);
+            if (stage[i]) (void) hipFree(stage[i]);
+            if (ev[i]) (void) hipEventDestroy(ev[i]);
+            pin[i] = stage[i] = nullptr; ev[i] = nullptr; pending[i] = false;
+        }
+        if (stream) { (void) hipStreamDestroy(stream); stream = nullptr; }
+        if (!ok && arena && *arena) { (void) hipFree(*arena); *arena = nullptr; }
+        arena = nullptr;
+    }
+    ~load_pipe() { close(); }
 };
 
 struct arena_builder {
@@ -327,38 +391,150 @@ bool wa_model_load(whisper_model_loader * loader, whisper_context & wctx) {
     }
 
     // ---------------------------------------------------------------------------------------------
-    // host staging image of the arena
+    // where the bytes go: the device path (default) or the host path (WHISPER_AMD_LOAD_HOST=1, read at every load)
     // ---------------------------------------------------------------------------------------------
-    std::vector<uint8_t> img;
-    try { img.assign(ab.size, 0); } catch (...) { WA_ERROR("%s: out of host memory for %zu bytes\n", __func__, ab.size); return false; }
-
-    memcpy(img.data() + o_filters, model.filters.data(), model.filters.size() * F);
-    {   // Hann window and sin/cos tables exactly as whisper.cpp:3031-3047 (float cosf/sinf of a double argument)
-        float * hann = (float *) (img.data() + o_hann);
-        float * sc   = (float *) (img.data() + o_sincos);
+    // host-made constants: Hann window and sin/cos tables exactly as whisper.cpp:3031-3047 (float cosf/sinf of a double argument), the GELU
+    // table from the host's tanhf.  `tables` is an image of the arena's first bytes, [0, n_tables).
+    const size_t n_tables = o_gelu + 65536 * H;
+    auto fill_tables = [&](uint8_t * tables) {
+        memcpy(tables + o_filters, model.filters.data(), model.filters.size() * F);
+        float * hann = (float *) (tables + o_hann);
+        float * sc   = (float *) (tables + o_sincos);
         for (int i = 0; i < 400; ++i) {
             hann[i] = 0.5 * (1.0 - cosf((2.0 * M_PI * i) / 400));
             const double theta = (2 * M_PI * i) / 400;
             sc[i]       = sinf(theta);
             sc[400 + i] = cosf(theta);
         }
-        wa_f16 * g = (wa_f16 *) (img.data() + o_gelu);
+        wa_f16 * g = (wa_f16 *) (tables + o_gelu);
         for (int i = 0; i < 65536; ++i) g[i] = f2h_host(gelu_f32(h2f_host((wa_f16) i)));
-    }
+    };
     const float KQscale = pow(float(64), -0.25);   // whisper.cpp:2316, 2522
-    for (int i = 0; i < Ld; ++i) {
-        float * s = (float *) (img.data() + dof[i].qkv.s);
-        for (int c = 0; c < 3 * d; ++c) s[c] = c < 2 * d ? KQscale : 1.0f;
-        float * cs = (float *) (img.data() + o_ckv_s) + (size_t) i * 2 * d;
-        for (int c = 0; c < 2 * d; ++c) cs[c] = c < d ? KQscale : 1.0f;
+    // the per-column scales of a decoder layer's fused q|k|v, [3d]: q and k columns KQscale, v columns 1; columns [d, 3d) of it are the
+    // [2d] scales of a layer's cross k|v
+    auto fill_kq = [&](float * s) { for (int c = 0; c < 3 * d; ++c) s[c] = c < 2 * d ? KQscale : 1.0f; };
+
+    size_t row_bytes_max = 0;                     // the longest row of any tensor: no staging buffer may be smaller
+    auto slot_row_bytes = [&](const slot & s) -> size_t {
+        if (s.kind == 1) return (size_t) s.ne[1] * 3 * H;                                    // one output channel
+        if (s.kind == 2) return wa_qk_block_bytes(s.type) ? (size_t) s.ne[0] / WA_QK_K * wa_qk_block_bytes(s.type)
+                              : (size_t) s.ne[0] / 32 * (wa_q0_block_bytes(s.type) ? wa_q0_block_bytes(s.type) : wa_q1_block_bytes(s.type));
+        return (size_t) s.ne[0] * (s.type == 0 ? F : H);
+    };
+    for (const auto & kv : slots) row_bytes_max = std::max(row_bytes_max, slot_row_bytes(kv.second));
+
+    int64_t t_read_us = 0, t_wait_us = 0;
+    auto read_timed = [&](void * dst, size_t n) {
+        const int64_t t0 = wa_time_us();
+        const size_t got = loader->read(loader->context, dst, n);
+        t_read_us += wa_time_us() - t0;
+        return got;
+    };
+
+    load_pipe pipe;
+    std::vector<uint8_t> img;                     // host path: the host image of the arena
+    bool on_device = false;
+    {
+        const char * e = getenv("WHISPER_AMD_LOAD_HOST");
+        if (!(e && *e && strcmp(e, "0") != 0)) {
+            size_t chunk = WA_LOAD_CHUNK_BYTES;
+            if (const char * c = getenv("WHISPER_AMD_LOAD_CHUNK")) chunk = (size_t) std::max(1LL, std::min(atoll(c), 1LL << 30));
+            const size_t cap = wa_load_align(std::max(chunk, row_bytes_max)), n_consts = wa_load_align(n_tables) + (size_t) 3 * d * F;
+            if (!WA_HIP_OK(hipSetDevice(wctx.device))) return false;
+            on_device = pipe.open(cap, std::max(cap, n_consts));
+            if (!on_device) WA_WARN("%s: no pinned / staging buffers of %zu bytes - loading through the host image\n", __func__, cap);
+        }
     }
+    uint8_t * base = nullptr;
+    if (on_device) {
+        pipe.arena = &model.arena;
+        if (!WA_HIP_OK(hipMalloc(&model.arena, ab.size))) return false;
+        model.arena_size = ab.size;
+        base = (uint8_t *) model.arena;
+        // the host image was zero-initialised: conv1's padded columns and the alignment gaps stay zero
+        if (!WA_HIP_OK(hipMemsetAsync(base, 0, ab.size, pipe.stream))) return false;
+        // the constants: one copy up into staging buffer 0, placed from there
+        uint8_t * c = pipe.pin[0];
+        memset(c, 0, wa_load_align(n_tables));
+        fill_tables(c);
+        fill_kq((float *) (c + wa_load_align(n_tables)));
+        const uint8_t * dc = pipe.stage[0], * dkq = dc + wa_load_align(n_tables);
+        bool ok = WA_HIP_OK(hipMemcpyAsync(pipe.stage[0], c, wa_load_align(n_tables) + (size_t) 3 * d * F, hipMemcpyHostToDevice, pipe.stream)) &&
+                  WA_HIP_OK(hipMemcpyAsync(base, dc, n_tables, hipMemcpyDeviceToDevice, pipe.stream));
+        for (int i = 0; i < Ld && ok; ++i)
+            ok = WA_HIP_OK(hipMemcpyAsync(base + dof[i].qkv.s, dkq, (size_t) 3 * d * F, hipMemcpyDeviceToDevice, pipe.stream)) &&
+                 WA_HIP_OK(hipMemcpyAsync(base + o_ckv_s + (size_t) i * 2 * d * F, dkq + (size_t) d * F, (size_t) 2 * d * F, hipMemcpyDeviceToDevice, pipe.stream));
+        if (!ok || !pipe.next(t_wait_us)) return false;
+    } else {
+        try { img.assign(ab.size, 0); } catch (...) { WA_ERROR("%s: out of host memory for %zu bytes\n", __func__, ab.size); return false; }
+        fill_tables(img.data());
+        for (int i = 0; i < Ld; ++i) {
+            std::vector<float> kq((size_t) 3 * d);
+            fill_kq(kq.data());
+            memcpy(img.data() + dof[i].qkv.s, kq.data(), (size_t) 3 * d * F);
+            memcpy(img.data() + o_ckv_s + (size_t) i * 2 * d * F, kq.data() + d, (size_t) 2 * d * F);
+        }
+    }
+
+    // One tensor's bytes, host path: read whole, unpacked / re-ordered by the host functions into the image.  0, or 1: short read.
+    std::vector<uint8_t> tmp;
+    auto host_tensor = [&](const slot & s, size_t nbytes) -> int {
+        if (s.kind == 0) return read_timed(img.data() + s.off, nbytes) == nbytes ? 0 : 1;
+        tmp.resize(nbytes);
+        if (read_timed(tmp.data(), nbytes) != nbytes) return 1;
+        if (s.kind == 2 && wa_qk_block_bytes(s.type)) {        // block_q2_K / q3_K / q5_K / q6_K -> the arrays of wa_quantk.h
+            wa_qk_unpack_rows(s.type, tmp.data(), (size_t) s.ne[1], (size_t) s.ne[0] / WA_QK_K, (int8_t *) (img.data() + s.off), (int8_t *) (img.data() + s.off5),
+                              (float *) (img.data() + s.off3), s.off4 ? (float *) (img.data() + s.off4) : nullptr);
+        } else if (s.kind == 2) {        // block_q5_0 / block_q8_0, and block_q4_1 / block_q5_1 with their minimum (wa_quant1.h) -> arrays
+            wa_q32_unpack_rows(s.type, tmp.data(), (size_t) s.ne[1], (size_t) s.ne[0] / 32, (int8_t *) (img.data() + s.off), (float *) (img.data() + s.off3),
+                               s.off4 ? (float *) (img.data() + s.off4) : nullptr);
+        } else {        // file: [oc][ic][k] (k fastest) -> arena: [oc][k*IC + ic], row stride ld, and the file's order unchanged at off2
+            wa_conv_reorder_rows((const uint16_t *) tmp.data(), (size_t) s.ne[2], (int) s.ne[1], s.ld, (uint16_t *) (img.data() + s.off), (uint16_t *) (img.data() + s.off2));
+        }
+        return 0;
+    };
+    // Device path: the tensor in chunks of whole rows (wa_load_plan.h) through the pinned buffer being filled, each chunk copied up and
+    // unpacked on the stream while the next one is read.  0, 1: short read, 2: a HIP call failed (logged).
+    auto device_tensor = [&](const slot & s, size_t nbytes) -> int {
+        const size_t row_bytes = slot_row_bytes(s);
+        const auto plan = wa_load_plan(nbytes, row_bytes, pipe.cap, pipe.used);
+        if (plan.empty()) { WA_ERROR("wa_model_load: no chunk plan for %zu bytes in rows of %zu\n", nbytes, row_bytes); return 2; }
+        for (const wa_load_chunk & c : plan) {
+            const size_t bytes = c.rows * row_bytes;
+            if (pipe.used + bytes > pipe.cap && !pipe.next(t_wait_us)) return 2;
+            uint8_t * h = pipe.pin[pipe.cur] + pipe.used, * dv = pipe.stage[pipe.cur] + pipe.used;
+            if (read_timed(h, bytes) != bytes) return 1;
+            if (s.kind == 0) {
+                if (!WA_HIP_OK(hipMemcpyAsync(base + s.off + c.file_off, h, bytes, hipMemcpyHostToDevice, pipe.stream))) return 2;
+            } else {
+                if (!WA_HIP_OK(hipMemcpyAsync(dv, h, bytes, hipMemcpyHostToDevice, pipe.stream))) return 2;
+                int err;
+                if (s.kind == 1) {
+                    const size_t IC = (size_t) s.ne[1];
+                    err = wa_launch_load_conv(pipe.stream, (const uint16_t *) dv, c.rows, (int) IC, s.ld, (uint16_t *) (base + s.off) + c.row0 * (size_t) s.ld,
+                                              (uint16_t *) (base + s.off2) + c.row0 * IC * 3);
+                } else if (wa_qk_block_bytes(s.type)) {
+                    const size_t nb = (size_t) s.ne[0] / WA_QK_K;
+                    err = wa_launch_load_qk(pipe.stream, s.type, dv, c.rows, nb, (int8_t *) (base + s.off) + c.row0 * nb * WA_QK_K, (int8_t *) (base + s.off5) + c.row0 * nb * 16,
+                                            (float *) (base + s.off3) + c.row0 * nb, s.off4 ? (float *) (base + s.off4) + c.row0 * nb : nullptr);
+                } else {
+                    const size_t nb = (size_t) s.ne[0] / 32;
+                    err = wa_launch_load_q32(pipe.stream, s.type, dv, c.rows, nb, (int8_t *) (base + s.off) + c.row0 * nb * 32, (float *) (base + s.off3) + c.row0 * nb,
+                                             s.off4 ? (float *) (base + s.off4) + c.row0 * nb : nullptr);
+                }
+                if (!WA_HIP_OK((hipError_t) err)) return 2;
+                pipe.n_kernels++;
+            }
+            pipe.used = wa_load_align(pipe.used + bytes);
+        }
+        return 0;
+    };
 
     // ---------------------------------------------------------------------------------------------
     // tensor records
     // ---------------------------------------------------------------------------------------------
     size_t total_size = 0;
     model.n_loaded = 0;
-    std::vector<uint8_t> tmp;
     while (true) {
         int32_t n_dims = 0, length = 0, ttype = 0;
         rd(loader, n_dims); rd(loader, length); rd(loader, ttype);
@@ -386,58 +562,9 @@ bool wa_model_load(whisper_model_loader * loader, whisper_context & wctx) {
         }
         const size_t nbytes = wa_qk_block_bytes(s.type) ? (size_t) nelements / WA_QK_K * wa_qk_block_bytes(s.type) : s.type == 6 ? (size_t) nelements / 32 * 22 : s.type == 8 ? (size_t) nelements / 32 * 34 :
                               wa_q1_block_bytes(s.type) ? (size_t) nelements / 32 * wa_q1_block_bytes(s.type) : (size_t) nelements * (s.type == 0 ? F : H);
-        if (s.kind == 2 && wa_qk_block_bytes(s.type)) {        // block_q2_K / q3_K / q5_K / q6_K -> the arrays of wa_quantk.h
-            tmp.resize(nbytes);
-            if (loader->read(loader->context, tmp.data(), nbytes) != nbytes) { WA_ERROR("%s: truncated tensor '%s'\n", __func__, name.c_str()); return false; }
-            const size_t bsz = wa_qk_block_bytes(s.type), nbr = (size_t) s.ne[0] / WA_QK_K, rows = (size_t) s.ne[1];
-            int8_t * qs = (int8_t *) (img.data() + s.off), * qsc = (int8_t *) (img.data() + s.off5);
-            float * qd = (float *) (img.data() + s.off3), * qm = s.off4 ? (float *) (img.data() + s.off4) : nullptr;
-            for (size_t r = 0; r < rows; ++r)
-                for (size_t b = 0; b < nbr; ++b) {
-                    int8_t v[256]; float dd, dm;
-                    wa_qk_unpack(s.type, tmp.data() + (r * nbr + b) * bsz, v, qsc + (r * nbr + b) * 16, dd, dm);
-                    qd[r * nbr + b] = dd;
-                    if (qm) qm[r * nbr + b] = dm;
-                    for (int g = 0; g < 8; ++g)
-                        for (int l = 0; l < 8; ++l) memcpy(qs + wa_qk_quant_index(r, nbr, b, 32 * g + 4 * l), v + 32 * g + 4 * l, 4);
-                }
-        } else if (s.kind == 2) {        // block_q5_0 { f16 d; u32 qh; u8 qs[16] } / block_q8_0 { f16 d; i8 qs[32] } (ggml-common.h:187-214) -> arrays
-            tmp.resize(nbytes);
-            if (loader->read(loader->context, tmp.data(), nbytes) != nbytes) { WA_ERROR("%s: truncated tensor '%s'\n", __func__, name.c_str()); return false; }
-            //                          block_q4_1 / block_q5_1 carry a minimum too (wa_quant1.h: wa_q1_unpack)
-            const size_t bsz = s.type == 6 ? 22 : s.type == 8 ? 34 : wa_q1_block_bytes(s.type), nbr = (size_t) s.ne[0] / 32, rows = (size_t) s.ne[1];
-            int8_t * qs = (int8_t *) (img.data() + s.off); float * qd = (float *) (img.data() + s.off3);
-            float * qm = s.off4 ? (float *) (img.data() + s.off4) : nullptr;
-            for (size_t r = 0; r < rows; ++r)
-                for (size_t b = 0; b < nbr; ++b) {
-                    const uint8_t * blk = tmp.data() + (r * nbr + b) * bsz;
-                    wa_f16 dh; memcpy(&dh, blk, 2);
-                    qd[r * nbr + b] = h2f_host(dh);
-                    int8_t v[32];
-                    if (qm) wa_q1_unpack(s.type, blk, v, qd[r * nbr + b], qm[r * nbr + b]);
-                    else if (s.type == 6) {      // element j < 16: low nibble of qs[j], j + 16: high nibble; bit e of qh: fifth bit; value - 16
-                        uint32_t qh; memcpy(&qh, blk + 2, 4);
-                        for (int j = 0; j < 16; ++j) {
-                            v[j]      = (int8_t) ((int) ((blk[6 + j] & 0x0f) | (((qh >> j) & 1u) << 4)) - 16);
-                            v[j + 16] = (int8_t) ((int) ((blk[6 + j] >> 4)   | (((qh >> (j + 16)) & 1u) << 4)) - 16);
-                        }
-                    } else memcpy(v, blk + 2, 32);
-                    for (int l = 0; l < 8; ++l) memcpy(qs + ((r * 8 + l) * nbr + b) * 4, v + 4 * l, 4);
-                }
-        } else if (s.kind == 0) {
-            if (loader->read(loader->context, img.data() + s.off, nbytes) != nbytes) { WA_ERROR("%s: truncated tensor '%s'\n", __func__, name.c_str()); return false; }
-        } else {
-            tmp.resize(nbytes);
-            if (loader->read(loader->context, tmp.data(), nbytes) != nbytes) { WA_ERROR("%s: truncated tensor '%s'\n", __func__, name.c_str()); return false; }
-            // file: [oc][ic][k] (k fastest) -> arena: [oc][k*IC + ic], row stride ld
-            const int IC = (int) s.ne[1], OC = (int) s.ne[2];
-            const wa_f16 * src = (const wa_f16 *) tmp.data();
-            wa_f16 * dst = (wa_f16 *) (img.data() + s.off);
-            memcpy(img.data() + s.off2, tmp.data(), nbytes);
-            for (int oc = 0; oc < OC; ++oc)
-                for (int ic = 0; ic < IC; ++ic)
-                    for (int k = 0; k < 3; ++k) dst[(size_t) oc * s.ld + k * IC + ic] = src[((size_t) oc * IC + ic) * 3 + k];
-        }
+        const int rc = on_device ? device_tensor(s, nbytes) : host_tensor(s, nbytes);
+        if (rc == 1) { WA_ERROR("%s: truncated tensor '%s'\n", __func__, name.c_str()); return false; }
+        if (rc != 0) return false;
         s.seen = true;
         total_size += nbytes;
         model.n_loaded++;
@@ -451,15 +578,24 @@ bool wa_model_load(whisper_model_loader * loader, whisper_context & wctx) {
     }
 
     // ---------------------------------------------------------------------------------------------
-    // upload
+    // upload (host path), or the wait for the stream's last chunk (device path)
     // ---------------------------------------------------------------------------------------------
-    if (!WA_HIP_OK(hipSetDevice(wctx.device))) return false;
-    if (!WA_HIP_OK(hipMalloc(&model.arena, ab.size))) return false;
-    model.arena_size = ab.size;
-    if (!WA_HIP_OK(hipMemcpy(model.arena, img.data(), ab.size, hipMemcpyHostToDevice))) return false;
+    if (on_device) {
+        const int64_t t0 = wa_time_us();
+        const bool ok = WA_HIP_OK(hipStreamSynchronize(pipe.stream));
+        t_wait_us += wa_time_us() - t0;
+        if (!ok) return false;
+    } else {
+        if (!WA_HIP_OK(hipSetDevice(wctx.device))) return false;
+        if (!WA_HIP_OK(hipMalloc(&model.arena, ab.size))) return false;
+        model.arena_size = ab.size;
+        const int64_t t0 = wa_time_us();
+        if (!WA_HIP_OK(hipMemcpy(model.arena, img.data(), ab.size, hipMemcpyHostToDevice))) return false;
+        t_wait_us += wa_time_us() - t0;
+        base = (uint8_t *) model.arena;
+    }
     WA_INFO("%s: %12s total size = %8.2f MB\n", __func__, "HIP0", ab.size / 1e6);
 
-    uint8_t * base = (uint8_t *) model.arena;
     auto PF = [&](size_t o) { return (const float *) (base + o); };
     auto PH = [&](size_t o) { return (const wa_f16 *) (base + o); };
     auto LN = [&](ln_off o) { wa_ln r; r.w = PF(o.w); r.b = PF(o.b); return r; };
@@ -511,12 +647,18 @@ bool wa_model_load(whisper_model_loader * loader, whisper_context & wctx) {
         }
         if (Ld > 0) {
             if (!WA_HIP_OK(hipMalloc(&model.d_mega_layers, tab.size() * sizeof(wa_mega_layer)))) return false;
-            if (!WA_HIP_OK(hipMemcpy(model.d_mega_layers, tab.data(), tab.size() * sizeof(wa_mega_layer), hipMemcpyHostToDevice))) return false;
+            if (on_device) {      // on the loader's stream: nothing goes to the legacy stream once the pipeline has started
+                if (!WA_HIP_OK(hipMemcpyAsync(model.d_mega_layers, tab.data(), tab.size() * sizeof(wa_mega_layer), hipMemcpyHostToDevice, pipe.stream)) ||
+                    !WA_HIP_OK(hipStreamSynchronize(pipe.stream))) return false;
+            } else if (!WA_HIP_OK(hipMemcpy(model.d_mega_layers, tab.data(), tab.size() * sizeof(wa_mega_layer), hipMemcpyHostToDevice))) return false;
         }
         hipDeviceProp_t prop;
         if (WA_HIP_OK(hipGetDeviceProperties(&prop, wctx.device))) model.n_cu = prop.multiProcessorCount;
     }
 
+    if (on_device) { pipe.ok = true; pipe.close(); }        // the pinned and staging buffers go before the load returns
     wctx.t_load_us = wa_time_us() - t_start;
+    const int64_t stats[6] = { on_device ? 1 : 0, (int64_t) total_size, pipe.n_kernels, t_read_us, t_wait_us, wctx.t_load_us };
+    memcpy(wctx.load_stats, stats, sizeof(stats));
     return true;
 }

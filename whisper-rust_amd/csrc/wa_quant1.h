@@ -63,6 +63,37 @@ inline void wa_q1_unpack(int type, const uint8_t * blk, int8_t q[32], float & d,
     }
 }
 
+// The two formats without a minimum, block_q5_0 { f16 d; u32 qh; u8 qs[16]; } (22 bytes, ggml type 6) and block_q8_0 { f16 d; i8 qs[32]; }
+// (34 bytes, type 8; ggml-common.h:187-214): one block on file -> its 32 signed quants and scale.  Q5_0: element j < 16 is the low nibble
+// of qs[j], j + 16 the high nibble, bit e of qh the fifth bit, and the value is that minus 16.
+inline size_t wa_q0_block_bytes(int type) { return type == 6 ? 22 : type == 8 ? 34 : 0; }
+inline void wa_q0_unpack(int type, const uint8_t * blk, int8_t q[32], float & d) {
+    uint16_t dh; memcpy(&dh, blk, 2);
+    d = wa_q1_h2f(dh);
+    if (type == 6) {
+        uint32_t qh; memcpy(&qh, blk + 2, 4);
+        for (int j = 0; j < 16; ++j) {
+            q[j]      = (int8_t) ((int) ((blk[6 + j] & 0x0f) | (((qh >> j) & 1u) << 4)) - 16);
+            q[j + 16] = (int8_t) ((int) ((blk[6 + j] >> 4)   | (((qh >> (j + 16)) & 1u) << 4)) - 16);
+        }
+    } else memcpy(q, blk + 2, 32);
+}
+
+// `rows` rows of nb blocks of a 32-value format (type 6, 8, 3 or 7) on file -> the kernel layout the model loader writes: quants
+// [row][lane l = 0..7][block][4] (element 4 l + e of block b), scales [row][block] and - Q4_1 / Q5_1 only, else qm is null - minimums
+// [row][block].  THE definition of that layout: the host load path runs it, and the device unpack kernels (wa_load.hip) are held to it.
+inline void wa_q32_unpack_rows(int type, const uint8_t * src, size_t rows, size_t nb, int8_t * qs, float * qd, float * qm) {
+    const size_t bsz = wa_q0_block_bytes(type) ? wa_q0_block_bytes(type) : wa_q1_block_bytes(type);
+    for (size_t r = 0; r < rows; ++r)
+        for (size_t b = 0; b < nb; ++b) {
+            const uint8_t * blk = src + (r * nb + b) * bsz;
+            int8_t v[32];
+            if (qm) wa_q1_unpack(type, blk, v, qd[r * nb + b], qm[r * nb + b]);
+            else wa_q0_unpack(type, blk, v, qd[r * nb + b]);
+            for (int l = 0; l < 8; ++l) memcpy(qs + ((r * 8 + l) * nb + b) * 4, v + 4 * l, 4);
+        }
+}
+
 // dequantize_row_q4_1 / q5_1: q * d, then + m
 inline float wa_q1_dequant(int8_t q, float d, float m) { const float t = (float) q * d; return t + m; }
 

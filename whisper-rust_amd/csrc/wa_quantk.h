@@ -193,3 +193,18 @@ inline float wa_qk_dot(int type, int nb, const int8_t * wq, const int8_t * wsc, 
 inline size_t wa_qk_quant_index(size_t row, size_t nb, size_t b, int e) {
     return ((row * 8 + (size_t) ((e & 31) >> 2)) * nb + b) * 32 + (size_t) (e >> 5) * 4 + (size_t) (e & 3);
 }
+
+// `rows` rows of nb blocks of a K format on file -> the kernel layout above: quants, scale bytes, d and - Q5_K / Q2_K only, else qm is null -
+// dmin.  THE definition of what the model loader writes: the host load path runs it, and the device unpack kernels (wa_load.hip) are held to it.
+inline void wa_qk_unpack_rows(int type, const uint8_t * src, size_t rows, size_t nb, int8_t * qs, int8_t * qsc, float * qd, float * qm) {
+    const size_t bsz = wa_qk_block_bytes(type);
+    for (size_t r = 0; r < rows; ++r)
+        for (size_t b = 0; b < nb; ++b) {
+            int8_t v[256]; float dd, dm;
+            wa_qk_unpack(type, src + (r * nb + b) * bsz, v, qsc + (r * nb + b) * 16, dd, dm);
+            qd[r * nb + b] = dd;
+            if (qm) qm[r * nb + b] = dm;
+            for (int g = 0; g < 8; ++g)
+                for (int l = 0; l < 8; ++l) memcpy(qs + wa_qk_quant_index(r, nb, b, 32 * g + 4 * l), v + 32 * g + 4 * l, 4);
+        }
+}

@@ -268,6 +268,9 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         proto("whisper_amd_dtw_timings", None, P, C.POINTER(C.c_int64))
     if hasattr(lib, "whisper_amd_qgemm_stats"):
         proto("whisper_amd_qgemm_stats", None, P, C.POINTER(C.c_long))
+    if hasattr(lib, "whisper_amd_arena_read"):
+        proto("whisper_amd_arena_read", C.c_int64, P, C.c_int64, P, C.c_int64)
+        proto("whisper_amd_load_stats", None, P, C.POINTER(C.c_int64))
     _LIBS[path] = lib
     return lib
 
@@ -414,6 +417,22 @@ class WhisperContext:
         if n < 0:
             raise WhisperError("InvalidText", n)
         return list(arr[:n])
+
+    def load_stats(self) -> dict:
+        """Extension (whisper_amd_load_stats): how the model was loaded."""
+        out = (C.c_int64 * 6)()
+        self.lib.whisper_amd_load_stats(self.ptr, out)
+        return dict(zip(("path", "bytes_read", "kernels", "read_us", "wait_us", "load_us"), [int(v) for v in out]))
+
+    def arena(self) -> np.ndarray:
+        """Extension (whisper_amd_arena_read): the weight arena's bytes as the loader left them."""
+        size = self.lib.whisper_amd_arena_read(self.ptr, 0, None, 0)
+        if size < 0:
+            raise WhisperError("ArenaRead")
+        buf = np.empty(size, dtype=np.uint8)
+        if self.lib.whisper_amd_arena_read(self.ptr, 0, C.c_void_p(buf.ctypes.data), size) != size:
+            raise WhisperError("ArenaRead")
+        return buf
 
     def free(self):
         if self.ptr:
