@@ -513,6 +513,11 @@ WHISPER_API int  whisper_amd_rows_enabled(struct whisper_state * state);
  * matrix-core kernel (k_qgemm_mfma; K formats: k_kgemm_mfma), served by k_qgemm_exact (K formats: k_kgemm_exact) }.  WHISPER_AMD_NO_QMFMA=1 in
  * the environment sends all of them to the second. */
 WHISPER_API void whisper_amd_qgemm_stats(struct whisper_state * state, long out[2]);
+/* Quantised models: the products of 2..8 activation rows - beam-search and best_of steps, small whisper_decode batches - that this state issued (or
+ * captured into a graph: passes are captured once and replayed, so these count captures, not replays) since it was created: out = { taken by a
+ * few-rows kernel (k_qgemv_rows; K formats: k_kgemv_rows), taken by the general kernel (k_qgemm_exact; K formats: k_kgemm_exact) }.
+ * WHISPER_AMD_NO_FEW_ROWS=1 in the environment sends all of them to the second. */
+WHISPER_API void whisper_amd_few_rows_stats(struct whisper_state * state, long out[2]);
 /* Debugging aid (tools/rows_check.py): B identical rows (token, position n_past) of this state through the several-rows step; copies out the
  * hand-off granules [n_text_layer][8][B][2 * n_text_state] and the logits [B][n_vocab].  Returns the status word (0 = ok), < 0: not available. */
 WHISPER_API int whisper_amd_rows_debug(struct whisper_context * ctx, struct whisper_state * state, int B, int token, int n_past,

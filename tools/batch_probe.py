@@ -6,7 +6,7 @@ import wsynth, whisper_rs as W
 name = sys.argv[1] if len(sys.argv) > 1 else "small"
 n = int(sys.argv[2]) if len(sys.argv) > 2 else 5
 reps = int(sys.argv[3]) if len(sys.argv) > 3 else 50
-lib = W.load_library(); W.set_log_callback(lib, lambda l, t: sys.stderr.write(t) if l >= 3 else None)
+lib = W.load_library(os.environ.get("WA_LIB")); W.set_log_callback(lib, lambda l, t: sys.stderr.write(t) if l >= 3 else None)
 mp = wsynth.quant_model_path(*name.split(":")) if ":" in name else wsynth.model_path(name)      # "small:q5_1" = the quantised file
 ctx = W.WhisperContext.new_with_params(mp, W.WhisperContextParameters(lib, flash_attn=True), lib=lib)
 st = ctx.create_state(); st.pcm_to_mel(wsynth.synth_audio(480000, 0)); st.encode(0)

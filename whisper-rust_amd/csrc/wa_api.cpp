@@ -531,6 +531,7 @@ void whisper_amd_reset_timings(struct whisper_state * s) {
     s->n_spec_ok = s->n_spec_miss = 0;
 }
 void whisper_amd_overlap_stats(struct whisper_state * s, int out[2]) { out[0] = s->n_spec_ok; out[1] = s->n_spec_miss; }
+void whisper_amd_few_rows_stats(struct whisper_state * s, long out[2]) { out[0] = s ? s->n_few_rows : 0; out[1] = s ? s->n_few_general : 0; }
 void whisper_amd_qgemm_stats(struct whisper_state * s, long out[2]) { out[0] = s ? s->n_qgemm_mfma : 0; out[1] = s ? s->n_qgemm_exact : 0; }
 void whisper_reset_timings(struct whisper_context * ctx) {
     ctx->t_start_us = wa_time_us();

@@ -195,10 +195,14 @@ static void decode_launch_quant(whisper_context & ctx, whisper_state & st, int n
     };
     auto qmul = [&](wa_epi_mode mode, const wa_lin & L, int M, const wa_epi & e) {      // operand already in d_q8 / d_q8d
         if (QK) {
-            if (M > 8) (wa_kgemm_kernel(mode, m.wtype, M, L.n_out, L.n_in, e, 0) == 3 ? st.n_qgemm_mfma : st.n_qgemm_exact) += 1;
-            wa_launch_kgemm_route(s, mode, m.wtype, st.d_q8, st.d_q8d, st.d_q8bs, M, L.qs, L.qsc, L.qd, L.qm, L.n_out, L.n_in, e, 0);
+            const int kernel = wa_kgemm_few_kernel(mode, m.wtype, M, L.n_out, L.n_in, e, 0);      // 2: k_kgemv_rows (wa_quantk_rows.hip)
+            if (M > 8) (kernel == 3 ? st.n_qgemm_mfma : st.n_qgemm_exact) += 1;
+            else if (M >= 2) (kernel == 2 ? st.n_few_rows : st.n_few_general) += 1;
+            wa_launch_kgemm_few_route(s, mode, m.wtype, st.d_q8, st.d_q8d, st.d_q8bs, M, L.qs, L.qsc, L.qd, L.qm, L.n_out, L.n_in, e, 0);
         } else {
-            if (M > 8) (wa_qgemm_exact_kernel(mode, M, L.n_out, L.n_in, e, 0) == 3 ? st.n_qgemm_mfma : st.n_qgemm_exact) += 1;
+            const int kernel = wa_qgemm_exact_kernel(mode, M, L.n_out, L.n_in, e, 0);             // 2: k_qgemv_rows
+            if (M > 8) (kernel == 3 ? st.n_qgemm_mfma : st.n_qgemm_exact) += 1;
+            else if (M >= 2) (kernel == 2 ? st.n_few_rows : st.n_few_general) += 1;
             wa_launch_qgemm_exact(s, mode, st.d_q8, st.d_q8d, M, L.qs, L.qd, L.n_out, L.n_in, e, st.d_q8s, L.qm);
         }
     };

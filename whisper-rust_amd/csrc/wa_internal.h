@@ -298,6 +298,7 @@ struct whisper_state {
     unsigned * d_rows_status = nullptr;
     wa_launch_form rows_form;                      // on / paused / off (wa_one_launch.h)
     long n_rows_steps = 0, n_rows_fallback = 0;      // passes served by the one-launch form / sent to the launch sequence after a status
+    long n_few_rows = 0, n_few_general = 0;          // quantised products of 2..8 rows issued (or captured) by decode_launch_quant that a few-rows kernel took (k_qgemv_rows / k_kgemv_rows) / the general kernel
     long n_qgemm_mfma = 0, n_qgemm_exact = 0;        // quantised products of more than 8 rows served by k_qgemm_mfma / by k_qgemm_exact (wa_quant.hip; K formats: k_kgemm_mfma / k_kgemm_exact)
     struct wa_batcher * batcher = nullptr;   // set while this state is a member of a whisper_amd_full_batch call (wa_decode.cpp)
     bool solo_step = false;                  // the next plain step of a lock-step member is decoded by the member alone (its row of a pass asked to be redone by the launch sequence)

@@ -147,6 +147,12 @@ void wa_launch_kgemm_route(hipStream_t stream, wa_epi_mode mode, int wtype, cons
                            const int8_t * wsc, const float * wd, const float * wdm, int N, int K, const wa_epi & e, int route);
 // the kernel that launcher takes for a product and a route: 1 k_kgemm_exact (k_kgemv_exact for M == 1), 3 k_kgemm_mfma
 int wa_kgemm_kernel(wa_epi_mode mode, int wtype, int M, int N, int K, const wa_epi & e, int route);
+// the same with the few-rows kernel k_kgemv_rows beside them (wa_quantk_rows.hip: M = 2..8 in the modes F16, GELU_F32, RESID, F32, DEC_QKV).  Route 0: the
+// launchers' own rules; 1: never k_kgemv_rows; 2: k_kgemv_rows wherever it exists; anything it does not take goes to wa_launch_kgemm_route with the route
+void wa_launch_kgemm_few_route(hipStream_t stream, wa_epi_mode mode, int wtype, const int8_t * xq, const float * xd, const int16_t * xbs, int M, const int8_t * wq,
+                               const int8_t * wsc, const float * wd, const float * wdm, int N, int K, const wa_epi & e, int route);
+// the kernel that launcher takes for a product and a route: 2 k_kgemv_rows, else what wa_kgemm_kernel says
+int wa_kgemm_few_kernel(wa_epi_mode mode, int wtype, int M, int N, int K, const wa_epi & e, int route);
 // token embedding rows of such a matrix (dequantize_row_q2_K / q3_K / q5_K / q6_K) + positional embedding
 void wa_launch_dec_embed_k(hipStream_t stream, int wtype, const int32_t * tok, const int32_t * pos, int n_tokens, int d, const int8_t * wq, const int8_t * wsc,
                            const float * wd, const float * wdm, const float * pe, float * x);

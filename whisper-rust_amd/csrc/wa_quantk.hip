@@ -22,32 +22,13 @@
 // and lane l's two minimums are bytes l and 8 + l of the block's 16: no exchange between lanes, with one activation row or with eight.
 // This file is compiled twice: wa_quantk.o holds everything but Q2_K, wa_quantk_q2.o (-DWA_QK_Q2_TU) the Q2_K instantiations of the two
 // products and their launcher - a code object of their own beside the fourteen + fourteen of Q5_K / Q6_K.
-#include "wa_quantk_dev.h"      // the vector types, wk_hsum8, the format enum WK_Q6 / WK_Q5 / WK_Q2 and wk_byte: shared with wa_quantk_mfma.hip
+#include "wa_quantk_dev.h"      // the vector types, wk_hsum8, the format enum WK_Q6 / WK_Q5 / WK_Q2, wk_byte, wk_block and wk_from_lane: shared with wa_quantk_mfma.hip / wa_quantk_rows.hip
 
 __device__ __forceinline__ int wk_isum8(int v) {      // integer sum of an 8-lane group, valid in its lane 0 (any order is exact)
     v += __builtin_amdgcn_update_dpp(0, v, 0x104, 0xf, 0xf, true);
     v += __builtin_amdgcn_update_dpp(0, v, 0x102, 0xf, 0xf, true);
     v += __builtin_amdgcn_update_dpp(0, v, 0x101, 0xf, 0xf, true);
     return v;
-}
-__device__ __forceinline__ float wk_from_lane(float v, int m) {      // lane 0 of an 8-lane group reads lane m's value (m constant after unrolling)
-    switch (m) {
-        case 1: return dpp_f32<0x101>(v); case 2: return dpp_f32<0x102>(v); case 3: return dpp_f32<0x103>(v); case 4: return dpp_f32<0x104>(v);
-        case 5: return dpp_f32<0x105>(v); case 6: return dpp_f32<0x106>(v); case 7: return dpp_f32<0x107>(v); default: return v;
-    }
-}
-// the integer sum of one lane over one 256-value block: 8 groups, quads w0 | w1 against x0 | x1, scale bytes s
-template <int F> __device__ __forceinline__ int wk_block(wk_i4 w0, wk_i4 w1, wk_i4 x0, wk_i4 x1, wk_i2 s) {
-    int t = 0;
-    t += wk_byte<F>(s, 0) * __builtin_amdgcn_sdot4(w0.x, x0.x, 0, false);
-    t += wk_byte<F>(s, 1) * __builtin_amdgcn_sdot4(w0.y, x0.y, 0, false);
-    t += wk_byte<F>(s, 2) * __builtin_amdgcn_sdot4(w0.z, x0.z, 0, false);
-    t += wk_byte<F>(s, 3) * __builtin_amdgcn_sdot4(w0.w, x0.w, 0, false);
-    t += wk_byte<F>(s, 4) * __builtin_amdgcn_sdot4(w1.x, x1.x, 0, false);
-    t += wk_byte<F>(s, 5) * __builtin_amdgcn_sdot4(w1.y, x1.y, 0, false);
-    t += wk_byte<F>(s, 6) * __builtin_amdgcn_sdot4(w1.z, x1.z, 0, false);
-    t += wk_byte<F>(s, 7) * __builtin_amdgcn_sdot4(w1.w, x1.w, 0, false);
-    return t;
 }
 
 // -------------------------------------------------------------------------------------------------

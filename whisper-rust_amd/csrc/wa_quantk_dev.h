@@ -1,4 +1,4 @@
-// wa_quantk_dev.h - what the K-format kernels of wa_quantk.hip and wa_quantk_mfma.hip share on the device: the vector types, the weight format of
+// wa_quantk_dev.h - what the K-format kernels of wa_quantk.hip, wa_quantk_rows.hip and wa_quantk_mfma.hip share on the device: the vector types, the weight format of
 // an instantiation, how a sub-block scale byte is read, and the order of hsum_float_8 (across the 8 lanes of an output, or inside one lane).
 #pragma once
 #include "wa_device.h"
@@ -22,4 +22,23 @@ enum { WK_Q6 = 0, WK_Q5 = 1, WK_Q2 = 2 };      // the weight format of an instan
 template <int F> __device__ __forceinline__ int wk_byte(wk_i2 s, int g) {
     const int w = g < 4 ? s.x : s.y, sh = 8 * (g & 3);
     return F == WK_Q6 ? (w << (24 - sh)) >> 24 : (int) (((unsigned) w >> sh) & (F == WK_Q2 ? 0xfu : 0xffu));
+}
+__device__ __forceinline__ float wk_from_lane(float v, int m) {      // lane 0 of an 8-lane group reads lane m's value (m constant after unrolling)
+    switch (m) {
+        case 1: return dpp_f32<0x101>(v); case 2: return dpp_f32<0x102>(v); case 3: return dpp_f32<0x103>(v); case 4: return dpp_f32<0x104>(v);
+        case 5: return dpp_f32<0x105>(v); case 6: return dpp_f32<0x106>(v); case 7: return dpp_f32<0x107>(v); default: return v;
+    }
+}
+// the integer sum of one lane over one 256-value block: 8 groups, quads w0 | w1 against x0 | x1, scale bytes s
+template <int F> __device__ __forceinline__ int wk_block(wk_i4 w0, wk_i4 w1, wk_i4 x0, wk_i4 x1, wk_i2 s) {
+    int t = 0;
+    t += wk_byte<F>(s, 0) * __builtin_amdgcn_sdot4(w0.x, x0.x, 0, false);
+    t += wk_byte<F>(s, 1) * __builtin_amdgcn_sdot4(w0.y, x0.y, 0, false);
+    t += wk_byte<F>(s, 2) * __builtin_amdgcn_sdot4(w0.z, x0.z, 0, false);
+    t += wk_byte<F>(s, 3) * __builtin_amdgcn_sdot4(w0.w, x0.w, 0, false);
+    t += wk_byte<F>(s, 4) * __builtin_amdgcn_sdot4(w1.x, x1.x, 0, false);
+    t += wk_byte<F>(s, 5) * __builtin_amdgcn_sdot4(w1.y, x1.y, 0, false);
+    t += wk_byte<F>(s, 6) * __builtin_amdgcn_sdot4(w1.z, x1.z, 0, false);
+    t += wk_byte<F>(s, 7) * __builtin_amdgcn_sdot4(w1.w, x1.w, 0, false);
+    return t;
 }

@@ -268,6 +268,8 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         proto("whisper_amd_dtw_timings", None, P, C.POINTER(C.c_int64))
     if hasattr(lib, "whisper_amd_qgemm_stats"):
         proto("whisper_amd_qgemm_stats", None, P, C.POINTER(C.c_long))
+    if hasattr(lib, "whisper_amd_few_rows_stats"):
+        proto("whisper_amd_few_rows_stats", None, P, C.POINTER(C.c_long))
     if hasattr(lib, "whisper_amd_arena_read"):
         proto("whisper_amd_arena_read", C.c_int64, P, C.c_int64, P, C.c_int64)
         proto("whisper_amd_load_stats", None, P, C.POINTER(C.c_int64))
@@ -507,6 +509,12 @@ class WhisperState:
         """Extension: (quantised products of more than 8 rows served by the int8 matrix-core kernel, served by k_qgemm_exact) since the state was created."""
         out = (C.c_long * 2)()
         self.lib.whisper_amd_qgemm_stats(self.ptr, out)
+        return int(out[0]), int(out[1])
+
+    def few_rows_stats(self) -> tuple:
+        """Extension: (quantised products of 2..8 rows issued or captured that a few-rows kernel took, that the general kernel took) since the state was created."""
+        out = (C.c_long * 2)()
+        self.lib.whisper_amd_few_rows_stats(self.ptr, out)
         return int(out[0]), int(out[1])
 
     def rows_stats(self) -> tuple:
