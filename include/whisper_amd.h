@@ -524,6 +524,27 @@ WHISPER_API int whisper_amd_rows_debug(struct whisper_context * ctx, struct whis
                                        unsigned long long * granules_out, float * logits_out);
 /* Measurement helper (bench.py): average DEVICE time of one B-row step, row i on states[i]'s cells and encoder K / V (null = states[0]). */
 WHISPER_API int whisper_amd_rows_step_probe(struct whisper_context * ctx, struct whisper_state ** states, int B, int n_past, int n_iters, float * ms_per_step);
+/* Test entries (tests/test_rows_kernel_gpu.py): they hand the decoder the batches whisper_full builds and do the cell operations it does between them.
+ * None of them is on a decode path.
+ * whisper_amd_decode_batch: one decoder pass over n_tokens rows, each with its token, position, sequence id and logits flag, exactly as whisper_full
+ *   issues it; unlike whisper_decode_with_state it removes no cell first.  0 on success; row i's logits then stand at
+ *   whisper_get_logits_from_state(state) + i * n_vocab for every flagged i.
+ * whisper_amd_kv_op: the bookkeeping of the self-attention cells.  op 0: forget every cell; 1: remove sequence a from the cells at positions [p0, p1)
+ *   (a < 0: every sequence; p0 / p1 < 0: open end); 2: add sequence b to the cells of sequence a at positions [p0, p1); 3: a new, empty cache of `a`
+ *   cells, as whisper_full makes one for several decoders (at most 5120 cells; the state then counts as prepared for as many decoders as whisper_full's
+ *   rule, 512 cells x (decoders + 2), fits into `a`); 4, 5, 6: return the cells in use (n), the cell the next batch is tried at (head), the cache's
+ *   size.  -1: bad arguments or a failed allocation.
+ * whisper_amd_rows_fits: 1 where the several-rows one-launch step takes B rows of this model on this device, else 0.
+ * whisper_amd_rows_debug_rows: whisper_amd_rows_debug with a state, a token and a context length per row - row i attends over cells [0, n_past[i]] of
+ *   states[i] and that state's encoder K / V, and writes cell n_past[i] with the values a decode would write; the cell bookkeeping is left alone.  The
+ *   states are distinct and agree in cache size and audio context (-2 otherwise).  logits_out [B][n_vocab]; row_status_out [B]: 0, or 9000 for a row
+ *   that the launch sequence would redo.  Returns as whisper_amd_rows_debug. */
+WHISPER_API int whisper_amd_decode_batch(struct whisper_context * ctx, struct whisper_state * state, const whisper_token * tokens, const int32_t * pos,
+                                         const int32_t * seq_id, const int8_t * logits, int n_tokens);
+WHISPER_API int whisper_amd_kv_op(struct whisper_state * state, int op, int a, int b, int p0, int p1);
+WHISPER_API int whisper_amd_rows_fits(struct whisper_context * ctx, int B);
+WHISPER_API int whisper_amd_rows_debug_rows(struct whisper_context * ctx, struct whisper_state ** states, int B, const int * tokens, const int * n_past,
+                                            float * logits_out, unsigned * row_status_out);
 
 /* Chunk-parallel transcription on ONE device (the reference's model: one state + thread per chunk, whisper.cpp:7771-7806):
  * runs `n_chunks` independent whisper_full_with_state jobs, each on its own state / HIP stream / host thread; mel, encoder and

@@ -1240,6 +1240,95 @@ extern "C" int whisper_amd_rows_step_probe(struct whisper_context * ctx, struct 
     return 0;
 }
 
+// -------------------------------------------------------------------------------------------------
+// test entries (tests/test_rows_kernel_gpu.py): the batches whisper_full builds, the cell operations it does between them, and the several-rows
+// kernel with a token and a context length per row.  None of them is on a decode path.
+// -------------------------------------------------------------------------------------------------
+// A batch as whisper_full prepares it (token, position, sequence id and logits flag per row) through wa_decode; unlike whisper_decode_with_state it
+// removes no cell first.  0 on success; row i's logits then stand at whisper_get_logits_from_state(state) + i * n_vocab for every flagged i.
+extern "C" int whisper_amd_decode_batch(struct whisper_context * ctx, struct whisper_state * st, const whisper_token * tokens, const int32_t * pos,
+                                        const int32_t * seq_id, const int8_t * logits, int n_tokens) {
+    if (!ctx || !st || !tokens || !pos || !seq_id || !logits || n_tokens <= 0) return 1;
+    for (int i = 0; i < n_tokens; ++i) if (seq_id[i] < 0 || seq_id[i] >= 64) return 1;      // (wa_seq_set holds ids 0..63)
+    auto & b = st->batch;
+    b.n_tokens = n_tokens;
+    b.token.assign(tokens, tokens + n_tokens);
+    b.pos.assign(pos, pos + n_tokens);
+    b.seq_id.assign(seq_id, seq_id + n_tokens);
+    b.logits.assign(logits, logits + n_tokens);
+    st->defer_rows = false;
+    return wa_decode(*ctx, *st, b, false, nullptr, nullptr) ? 0 : 1;
+}
+
+// The cell bookkeeping of a state's self-attention cache.  op 0: wa_kv_clear; 1: wa_kv_seq_rm(a, p0, p1); 2: wa_kv_seq_cp(a -> b, p0, p1); 3: a new
+// cache of `a` cells (wa_kv_self_realloc, as whisper_full makes one for several decoders: the state then counts as prepared for as many decoders as
+// whisper_full's rule - 512 cells x (decoders + 2) - fits into `a`, so a later whisper_full call makes its own cache when it needs a larger one);
+// 4, 5, 6: the cache's n, head and size.  -1: a bad argument or a failed allocation.
+extern "C" int whisper_amd_kv_op(struct whisper_state * st, int op, int a, int b, int p0, int p1) {
+    if (!st) return -1;
+    auto & kv = st->kv_self;
+    switch (op) {
+        case 0: wa_kv_clear(kv); return 0;
+        case 1: wa_kv_seq_rm(kv, a, p0, p1); return 0;
+        case 2: if (a < 0 || a >= 64 || b < 0 || b >= 64) return -1; wa_kv_seq_cp(kv, a, b, p0, p1); return 0;
+        case 3: {
+            if (!st->ctx || a < 1 || !WA_HIP_OK(hipSetDevice(st->ctx->device)) || !WA_HIP_OK(hipStreamSynchronize(st->stream))) return -1;
+            const int unit = wa_pad(st->ctx->model.hp.n_text_ctx, 256);
+            st->kv_self_n_dec = 0;          // (nothing usable until the new cache stands)
+            if (!wa_kv_self_realloc(*st->ctx, *st, a)) return -1;
+            st->kv_self_n_dec = a >= 4 * unit ? std::min(a / unit - 2, (int) WA_MAX_DECODERS) : a >= unit ? 1 : 0;
+            return 0;
+        }
+        case 4: return (int) kv.n;
+        case 5: return (int) kv.head;
+        case 6: return (int) kv.size;
+        default: return -1;
+    }
+}
+
+// 1 where the several-rows kernel takes B rows of this model (wa_rows_lds_bytes at the workgroup count every launch uses), else 0
+extern "C" int whisper_amd_rows_fits(struct whisper_context * ctx, int B) {
+    if (!ctx || ctx->model.n_loaded == 0) return 0;
+    int slot = 0;
+    return wa_rows_lds_bytes(ctx->model.hp.n_text_state, B, std::min(ctx->model.n_cu, 256), ctx->model.wtype != 1 ? 1 : 0, &slot) != 0 ? 1 : 0;
+}
+
+// whisper_amd_rows_debug with a state, a token and a context length per row (the shape of a lock-step pass): row i attends over cells [0, n_past[i]]
+// of states[i] and that state's encoder K / V and writes cell n_past[i] with the values a decode would write; the cell bookkeeping is not touched.
+// The states are distinct and agree in cache size, padded and encoded audio context (-2 otherwise, and where the form does not take the shape).
+// logits_out [B][n_vocab], row_status_out [B] (0, or WA_MEGA_REDO for a row whose soft-max total could not be certified).
+extern "C" int whisper_amd_rows_debug_rows(struct whisper_context * ctx, struct whisper_state ** states, int B, const int * tokens, const int * n_past,
+                                           float * logits_out, unsigned * row_status_out) {
+    if (!ctx || !states || !tokens || !n_past || B < 1 || B > WA_ROWS_MAX) return B < 1 || B > WA_ROWS_MAX ? -2 : -1;
+    for (int i = 0; i < B; ++i) if (!states[i]) return -1;
+    if (!WA_HIP_OK(hipSetDevice(ctx->device))) return -1;
+    whisper_state & own = *states[0];
+    const auto & hp = ctx->model.hp;
+    wa_rows_row rows[WA_ROWS_MAX];
+    for (int i = 0; i < B; ++i) {
+        whisper_state & ms = *states[i];
+        for (int j = 0; j < i; ++j) if (states[j] == states[i]) return -2;
+        if (ms.ctx != ctx || ms.kv_self.size != own.kv_self.size || ms.cross_tpad != own.cross_tpad || encoded_ctx(ms) != encoded_ctx(own)) return -2;
+        if (n_past[i] < 0 || n_past[i] + 1 > (int) ms.kv_self.size || n_past[i] >= hp.n_text_ctx || tokens[i] < 0 || tokens[i] >= hp.n_vocab) return -2;
+        rows[i] = { ms.kv_self.k, ms.kv_self.v, ms.d_cross_k, ms.d_cross_v, nullptr, n_past[i] + 1, n_past[i], tokens[i], n_past[i] };
+        if (&ms != &own && !WA_HIP_OK(hipStreamSynchronize(ms.stream))) return -3;      // (its cells and encoder K / V were written on its own stream)
+    }
+    wa_rows_args a;
+    if (!rows_args(*ctx, own, a, B, rows, encoded_ctx(own), own.kv_self.size)) return -2;
+    a.logits = own.d_logits; a.status = own.d_rows_status; a.row_status = own.d_rows_status + 4;
+    wa_slot_guard slot(device_slot(ctx->device), true);
+    (void) hipMemsetAsync(own.d_rows_status + 4, 0, WA_ROWS_MAX * sizeof(unsigned), own.stream);
+    if (!wa_launch_decode_rows(own.stream, a, std::min(ctx->model.n_cu, 256))) return -4;
+    if (!WA_HIP_OK(hipStreamSynchronize(own.stream))) return -3;
+    if (logits_out) (void) hipMemcpy(logits_out, own.d_logits, (size_t) B * hp.n_vocab * 4, hipMemcpyDeviceToHost);
+    unsigned status[12] = { 0 };
+    (void) hipMemcpy(status, own.d_rows_status, sizeof(status), hipMemcpyDeviceToHost);
+    if (row_status_out) for (int i = 0; i < B; ++i) row_status_out[i] = status[4 + i];
+    if (status[0] != 0) (void) hipMemset(own.d_rows_status, 0, 4);
+    if (status[0] == 0 && status[1] != a.seq) return -5;
+    return (int) status[0];
+}
+
 extern "C" int whisper_amd_mega_enabled(struct whisper_state * st) { return st && st->mega_form.enabled() ? 1 : 0; }
 
 // The same step through the launch sequence, stage by stage, with every stage's output copied out in the granule

@@ -260,6 +260,11 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         proto("whisper_amd_rows_stats", None, P, C.POINTER(C.c_long))
         proto("whisper_amd_rows_enabled", I, P)
         proto("whisper_amd_batch_one_launch", C.c_long, P)
+    if hasattr(lib, "whisper_amd_decode_batch"):
+        proto("whisper_amd_decode_batch", I, P, P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int8), I)
+        proto("whisper_amd_kv_op", I, P, I, I, I, I, I)
+        proto("whisper_amd_rows_fits", I, P, I)
+        proto("whisper_amd_rows_debug_rows", I, P, C.POINTER(C.c_void_p), I, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(F), C.POINTER(C.c_uint))
     if hasattr(lib, "whisper_amd_batch_served"):
         proto("whisper_amd_batch_served", C.c_long, P)
     if hasattr(lib, "whisper_amd_dtw_path"):
@@ -460,6 +465,18 @@ def full_batch(ctx: "WhisperContext", states: Sequence["WhisperState"], params: 
     return r
 
 
+def rows_debug_rows(ctx: "WhisperContext", states: Sequence["WhisperState"], tokens: Sequence[int], n_past: Sequence[int]):
+    """Extension (whisper_amd_rows_debug_rows): the several-rows one-launch step with a state, a token and a context length per row.
+    Returns (return code, logits [B][n_vocab], row status words [B])."""
+    n = len(states)
+    logits = np.zeros((n, ctx.n_vocab()), dtype=np.float32)
+    status = np.full(n, 0xFFFFFFFF, dtype=np.uint32)
+    sp = (C.c_void_p * n)(*[s.ptr for s in states])
+    rc = ctx.lib.whisper_amd_rows_debug_rows(ctx.ptr, sp, n, (C.c_int * n)(*tokens), (C.c_int * n)(*n_past), logits.ctypes.data_as(C.POINTER(C.c_float)),
+                                             status.ctypes.data_as(C.POINTER(C.c_uint)))
+    return rc, logits, status
+
+
 class WhisperState:
     def __init__(self, ctx: WhisperContext, ptr: int):
         self.ctx, self.lib, self.ptr = ctx, ctx.lib, ptr
@@ -522,6 +539,27 @@ class WhisperState:
         out = (C.c_long * 2)()
         self.lib.whisper_amd_rows_stats(self.ptr, out)
         return int(out[0]), int(out[1])
+
+    def decode_batch(self, tokens: Sequence[int], pos: Sequence[int], seq_id: Sequence[int], logits: Sequence[int]) -> np.ndarray:
+        """Extension (whisper_amd_decode_batch): one decoder pass over a batch as whisper_full builds it; no cell is removed first.  Returns the logits
+        rows of the flagged tokens, [number of flagged rows][n_vocab], in batch order."""
+        n = len(tokens)
+        assert len(pos) == n and len(seq_id) == n and len(logits) == n
+        r = self.lib.whisper_amd_decode_batch(self.ctx.ptr, self.ptr, (C.c_int32 * n)(*tokens), (C.c_int32 * n)(*pos), (C.c_int32 * n)(*seq_id),
+                                              (C.c_int8 * n)(*[1 if f else 0 for f in logits]), n)
+        if r != 0:
+            raise WhisperError("UnableToCalculateEvaluation", r)
+        nv = self.ctx.n_vocab()
+        rows = np.ctypeslib.as_array(self.lib.whisper_get_logits_from_state(self.ptr), shape=(n, nv))
+        return rows[[i for i in range(n) if logits[i]]].copy()
+
+    def kv_op(self, op: int, a: int = 0, b: int = 0, p0: int = -1, p1: int = -1) -> int:
+        """Extension (whisper_amd_kv_op): 0 clear, 1 seq_rm(a, p0, p1), 2 seq_cp(a -> b, p0, p1), 3 a new cache of `a` cells, 4 / 5 / 6 the cache's
+        n / head / size."""
+        r = self.lib.whisper_amd_kv_op(self.ptr, op, a, b, p0, p1)
+        if r < 0:
+            raise WhisperError("KvOp(%d)" % op, r)
+        return r
 
     def dtw_path(self, qk: np.ndarray, n_audio_tokens: int, sot_len: int, medfilt_width: int = 7, where: int = 0, cap: int = None, fill: int = -1):
         """Extension (whisper_amd_dtw_path): the DTW alignment alone over a host cube qk [n_heads][n_tokens][n_ctx] F32.  where = 0: the host
