@@ -599,6 +599,42 @@ WHISPER_API void whisper_amd_dtw_timings(struct whisper_state * state, int64_t o
 WHISPER_API int64_t whisper_amd_arena_read(struct whisper_context * ctx, int64_t offset, void * dst, int64_t cap);
 WHISPER_API void    whisper_amd_load_stats(struct whisper_context * ctx, int64_t out[6]);
 
+/* Audio front end (wa_audio.cpp): a recording as it comes out of a WAV file - int16 or F32 samples, one or two interleaved
+ * channels, 8 .. 192 kHz - converted, down-mixed and resampled to the 16 kHz mono F32 that whisper_full* takes, by HIP kernels on the
+ * state's stream.  whisper-rs callers do the first two steps on the host (src/utilities.rs) and its examples refuse every rate but 16 kHz.
+ * At 16 kHz the result is bit-identical to those utilities: I16 mono (float) s / 32768.0f, F32 stereo (l + r) / 2.0f, I16 stereo
+ * ((float) l + (float) r) / 2.0f / 32768.0f.  Other rates R go through a polyphase Kaiser-windowed sinc (g = gcd(R, 16000), L = 16000 / g,
+ * M = R / g; accepted: 8000 <= R <= 192000 with L <= 640, which covers 8, 11.025, 12, 16, 22.05, 24, 32, 44.1, 48, 88.2, 96, 176.4 and
+ * 192 kHz): ceil(n_frames 16000 / R) samples, each one F32 fmaf chain over its K taps (csrc/wa_audio.h states the arithmetic; the kernels
+ * and the host restatement there agree bit for bit).
+ * Refused, with an error log, -1 (whisper_amd_audio_to_pcm: NULL) and nothing written: null data with n_frames > 0, n_frames < 0, channels
+ * other than 1 or 2, an unknown format, a rate outside the rule above.
+ * whisper_amd_audio_n_samples: the output length for n_frames at sample_rate.
+ * whisper_amd_audio_to_pcm: `data` is a host or a device pointer (detected as whisper_pcm_to_mel does).  Returns a DEVICE pointer to
+ *   *n_samples F32 samples in a buffer the state owns (grown when needed, freed with the state), filled on the state's stream and valid until
+ *   the next call on this state; hand it to whisper_full_with_state / whisper_pcm_to_mel_with_state of the same state without any
+ *   synchronisation.  Host input may be released on return.  n_frames == 0 gives 0 samples and a non-null pointer.  The filter table of a
+ *   rate is built once per context and kept.  A HIP failure on the way is logged and the call is served by the host restatement;
+ *   WHISPER_AMD_AUDIO_HOST=1 in the environment when a state is created sends every call on that state there.
+ * whisper_amd_full_audio: whisper_amd_audio_to_pcm, then whisper_full_with_state on its result; returns that call's code.
+ * whisper_amd_audio_copy: copies up to `cap` samples of the state's last result into `dst` (host) and returns their full count; -1: none yet.
+ * whisper_amd_audio_taps: the filter table of a rate, taps[L][K] phase-major (output n, t = n M: phase t mod L, first input frame
+ *   t / L - K/2 + 1); copies up to `cap` values, returns L K (0 at 16 kHz: no filter); no device needed.
+ * whisper_amd_audio_tile: outputs per workgroup of the resampling kernel (tests put lengths on either side of it).
+ * whisper_amd_audio_stats: out = { calls served by the kernels, calls served by the host restatement, kernel attempts that fell back to
+ *   it } since the state was created (calls with no output sample count nowhere). */
+#define WHISPER_AMD_PCM_I16 0
+#define WHISPER_AMD_PCM_F32 1
+WHISPER_API int64_t       whisper_amd_audio_n_samples(int64_t n_frames, int sample_rate);
+WHISPER_API const float * whisper_amd_audio_to_pcm(struct whisper_state * state, const void * data, int64_t n_frames, int channels,
+                                                   int sample_rate, int format, int64_t * n_samples);
+WHISPER_API int           whisper_amd_full_audio(struct whisper_context * ctx, struct whisper_state * state, struct whisper_full_params params,
+                                                 const void * data, int64_t n_frames, int channels, int sample_rate, int format);
+WHISPER_API int64_t       whisper_amd_audio_copy(struct whisper_state * state, float * dst, int64_t cap);
+WHISPER_API int64_t       whisper_amd_audio_taps(int sample_rate, float * dst, int64_t cap, int * L, int * M, int * K);
+WHISPER_API int           whisper_amd_audio_tile(void);
+WHISPER_API void          whisper_amd_audio_stats(struct whisper_state * state, long out[3]);
+
 #ifdef __cplusplus
 }
 #endif

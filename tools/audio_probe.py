@@ -1,0 +1,91 @@
+"""Time of the audio front end for 30 s of 48 kHz stereo int16, the device path beside the host restatement, in ONE process.
+
+  to_pcm     whisper_amd_audio_to_pcm on a recording that lies in device memory: DEVICE time between two HIP events on the state's stream
+             (the resampling kernel alone), and the same call's wall time with the recording in host memory (upload + kernel + wait).
+  host       the same call on a state created with WHISPER_AMD_AUDIO_HOST=1: wa_audio_ref on the host, then the upload.  Wall time.
+  full       whisper_amd_full_audio (small shape, greedy, temperature_inc 0) on the device state, beside audio_to_pcm on the host state
+             followed by full() on a host copy of its result - what a caller without the front end does.  Wall time.
+
+`--calls` calls each after one warm-up call, alternating, best and median, printed as one JSON line.
+usage: python tools/audio_probe.py [--calls 10] [--shape small] [--rate 48000]"""
+import argparse
+import ctypes as C
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tools")); sys.path.insert(0, os.path.join(ROOT, "whisper-rust_amd"))
+import numpy as np  # noqa: E402
+import wsynth, whisper_rs as W  # noqa: E402
+
+
+def summary(ms):
+    return {"best_ms": round(min(ms), 3), "median_ms": round(statistics.median(ms), 3), "calls": len(ms)}
+
+
+def recording(rate, seconds=30):
+    """a fixed stereo int16 rendering of the synthetic audio at `rate`"""
+    pcm = wsynth.synth_audio(16000 * seconds, 0)
+    n = rate * seconds
+    up = np.interp(np.arange(n) * (16000.0 / rate), np.arange(len(pcm)), pcm)
+    scale = 0.8 * 32767.0 / float(np.abs(up).max())
+    return np.stack([np.rint(up * scale), np.rint(up * scale * 0.7)], axis=1).astype(np.int16).reshape(-1)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--calls", type=int, default=10)
+    ap.add_argument("--shape", default="small")
+    ap.add_argument("--rate", type=int, default=48000)
+    a = ap.parse_args()
+    lib = W.load_library()
+    W.set_log_callback(lib, lambda lvl, txt: sys.stderr.write(txt) if lvl >= 3 else None)
+    hip = C.CDLL("libamdhip64.so")
+    lib.whisper_amd_state_stream.restype = C.c_void_p
+    lib.whisper_amd_state_stream.argtypes = [C.c_void_p]
+    ctx = W.WhisperContext.new_with_params(wsynth.model_path(a.shape), W.WhisperContextParameters(lib, gpu_device=0), lib=lib)
+    dev = ctx.create_state()
+    os.environ["WHISPER_AMD_AUDIO_HOST"] = "1"          # the switch is read when a state is created
+    host = ctx.create_state()
+    os.environ.pop("WHISPER_AMD_AUDIO_HOST")
+    x = recording(a.rate)
+    n_frames = len(x) // 2
+    d = C.c_void_p()
+    assert hip.hipMalloc(C.byref(d), C.c_size_t(x.nbytes)) == 0
+    assert hip.hipMemcpy(d, C.c_void_p(x.ctypes.data), C.c_size_t(x.nbytes), 1) == 0
+    e0, e1 = C.c_void_p(), C.c_void_p()
+    assert hip.hipEventCreate(C.byref(e0)) == 0 and hip.hipEventCreate(C.byref(e1)) == 0
+    stream = C.c_void_p(lib.whisper_amd_state_stream(dev.ptr))
+    fp = W.FullParams(lib, 0, best_of=1, temperature_inc=0.0)
+    t = {k: [] for k in ("to_pcm_device_time", "to_pcm_wall_host_input", "host_restatement_wall", "full_audio_wall", "host_restatement_then_full_wall")}
+    segs = {}
+    for it in range(a.calls + 1):
+        assert hip.hipEventRecord(e0, stream) == 0
+        dev.audio_to_pcm((d.value, n_frames), 2, a.rate, W.PCM_I16)
+        assert hip.hipEventRecord(e1, stream) == 0 and hip.hipEventSynchronize(e1) == 0
+        ms = C.c_float()
+        assert hip.hipEventElapsedTime(C.byref(ms), e0, e1) == 0
+        w0 = time.perf_counter(); dev.audio_to_pcm(x, 2, a.rate); w1 = time.perf_counter()
+        host.audio_to_pcm(x, 2, a.rate); w2 = time.perf_counter()
+        dev.full_audio(fp, x, 2, a.rate); w3 = time.perf_counter()
+        segs["device"] = [(s["t0"], s["t1"], s["ids"]) for s in dev.segments()]
+        w4 = time.perf_counter()
+        host.audio_to_pcm(x, 2, a.rate)
+        host.full(fp, host.audio_copy()); w5 = time.perf_counter()
+        segs["host"] = [(s["t0"], s["t1"], s["ids"]) for s in host.segments()]
+        if it > 0:
+            for k, v in zip(t, (ms.value, (w1 - w0) * 1e3, (w2 - w1) * 1e3, (w3 - w2) * 1e3, (w5 - w4) * 1e3)):
+                t[k].append(v)
+    out = {k: summary(v) for k, v in t.items()}
+    out.update(rate=a.rate, shape=a.shape, n_frames=n_frames, n_samples=int(lib.whisper_amd_audio_n_samples(n_frames, a.rate)),
+               same_result=segs["device"] == segs["host"], stats_device_state=dev.audio_stats(), stats_host_state=host.audio_stats())
+    hip.hipFree(d)
+    dev.free(); host.free(); ctx.free()
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()

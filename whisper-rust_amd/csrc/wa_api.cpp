@@ -340,6 +340,7 @@ void whisper_free(struct whisper_context * ctx) {
     if (!ctx) return;
     wa_batcher_free_all(*ctx);
     whisper_free_state(ctx->state);
+    wa_audio_free(*ctx);
     wa_model_free(*ctx);
     delete ctx;
 }

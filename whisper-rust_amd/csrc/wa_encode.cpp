@@ -103,6 +103,7 @@ bool wa_state_alloc(whisper_context & ctx, whisper_state & st) {
     if (!dev_alloc(st.d_dyn, 8)) return false;
     { const char * g = getenv("WHISPER_AMD_NO_GRAPH"); st.graphs_enabled = !(g && g[0] == '1'); }
     { const char * g = getenv("WHISPER_AMD_DTW_HOST"); st.dtw_host = g && g[0] == '1'; }
+    { const char * g = getenv("WHISPER_AMD_AUDIO_HOST"); st.audio_host = g && g[0] == '1'; }
     {   // one-launch decode step: needs one workgroup per CU with all of them resident, d_head 64, d <= 1280
         const char * g = getenv("WHISPER_AMD_NO_MEGA");
         const int dt = hp.n_text_state, Ht = hp.n_text_head;
@@ -176,6 +177,7 @@ void wa_state_release(whisper_state & st) {
     if (st.copy_stream) { (void) hipStreamDestroy(st.copy_stream); st.copy_stream = nullptr; }
     dev_free(st.d_dyn); dev_free(st.d_att_partial); dev_free(st.d_att_pleft); dev_free(st.d_im2col); dev_free(st.d_logits); dev_free(st.d_aheads_qk);
     st.aheads_qk_cap = 0; dev_free(st.d_dtw); st.d_dtw_cap = 0;
+    dev_free(st.d_audio); st.d_audio_cap = 0; dev_free(st.d_audio_in); st.d_audio_in_cap = 0; st.audio_n = -1;
     if (st.h_dtw) { (void) hipHostFree(st.h_dtw); st.h_dtw = nullptr; st.h_dtw_cap = 0; }
     if (st.h_stage_i32)     { (void) hipHostFree(st.h_stage_i32);     st.h_stage_i32 = nullptr; }
     if (st.h_stage_mask)    { (void) hipHostFree(st.h_stage_mask);    st.h_stage_mask = nullptr; }

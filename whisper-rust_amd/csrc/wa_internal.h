@@ -140,6 +140,8 @@ struct whisper_context {
     std::vector<void *> batcher_cache;    // idle lock-step batchers (wa_decode.cpp), kept between whisper_amd_full_batch / whisper_full_parallel calls
     std::shared_ptr<const wa_grammar_vocab> grammar_vocab;     // the vocabulary's code points, decoded by the first call that brings a grammar (wa_full.cpp)
     std::mutex grammar_vocab_m;
+    std::map<int, float *> audio_taps;                         // the audio front end's filter tables on this device by input rate: built by the first call at a rate, kept (wa_audio.cpp)
+    std::mutex audio_taps_m;
     long batch_steps = 0, batch_rows = 0, batch_one_launch = 0, batch_served = 0; // the last whisper_amd_full_batch / whisper_full_parallel call: lock-step passes formed, their token rows, passes that were one launch, passes that delivered their rows
 };
 
@@ -352,6 +354,14 @@ struct whisper_state {
     bool dtw_host = false;                                  // WHISPER_AMD_DTW_HOST=1 when the state was created: the host path only
     long n_dtw_device = 0, n_dtw_host = 0, n_dtw_fallback = 0;      // calls served by the device path / by the host path / device attempts that fell back
     int64_t t_dtw_post_us = 0; long n_dtw_post = 0;         // whisper_full's DTW calls: wall time from the end of the decoder pass to t_dtw placed
+
+    // audio front end (wa_audio.cpp / wa_audio.hip): the 16 kHz mono F32 result of the last whisper_amd_audio_to_pcm call and the
+    // staging area for input that arrives in host memory; both grow-only, freed with the state
+    float * d_audio = nullptr; size_t d_audio_cap = 0;      // floats
+    uint8_t * d_audio_in = nullptr; size_t d_audio_in_cap = 0;      // bytes
+    int64_t audio_n = -1;                                   // samples of the last result, -1: none yet
+    bool audio_host = false;                                // WHISPER_AMD_AUDIO_HOST=1 when the state was created: the host path only
+    long n_audio_device = 0, n_audio_host = 0, n_audio_fallback = 0;    // calls served by the kernels / by the host path / device attempts that fell back
 };
 // the form a state's single-token run-ahead window (wa_spec_*) runs on, is gated on and is charged with its time-outs
 inline wa_launch_form & wa_window_form(whisper_state & st) { return st.single_via_rows ? st.rows_form : st.mega_form; }
@@ -396,4 +406,5 @@ std::atomic<int> & wa_encoders_in_flight(int device);
 bool wa_rows_prepare(whisper_context & ctx, whisper_state & st);      // buffers of the several-rows one-launch step (wa_encode.cpp); false: not available
 
 std::vector<int> wa_tokenize(const wa_vocab & vocab, const std::string & text);       // wa_api.cpp
+void wa_audio_free(whisper_context & ctx);                                                 // wa_audio.cpp: the filter tables
 int  wa_full(whisper_context * ctx, whisper_state * st, whisper_full_params params, const float * samples, int n_samples); // wa_full.cpp

@@ -278,8 +278,52 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     if hasattr(lib, "whisper_amd_arena_read"):
         proto("whisper_amd_arena_read", C.c_int64, P, C.c_int64, P, C.c_int64)
         proto("whisper_amd_load_stats", None, P, C.POINTER(C.c_int64))
+    if hasattr(lib, "whisper_amd_audio_to_pcm"):
+        proto("whisper_amd_audio_n_samples", C.c_int64, C.c_int64, I)
+        proto("whisper_amd_audio_to_pcm", P, P, P, C.c_int64, I, I, I, C.POINTER(C.c_int64))
+        proto("whisper_amd_full_audio", I, P, P, whisper_full_params, P, C.c_int64, I, I, I)
+        proto("whisper_amd_audio_copy", C.c_int64, P, C.POINTER(F), C.c_int64)
+        proto("whisper_amd_audio_taps", C.c_int64, I, C.POINTER(F), C.c_int64, C.POINTER(I), C.POINTER(I), C.POINTER(I))
+        proto("whisper_amd_audio_tile", I)
+        proto("whisper_amd_audio_stats", None, P, C.POINTER(C.c_long))
     _LIBS[path] = lib
     return lib
+
+
+PCM_I16, PCM_F32 = 0, 1      # WHISPER_AMD_PCM_* (include/whisper_amd.h)
+
+
+# whisper-rs' audio utilities (src/utilities.rs) restated in numpy, every operation rounded to F32 on its own
+def convert_integer_to_float_audio(samples) -> np.ndarray:
+    """i16 -> f32: s as f32 / 32768.0"""
+    return np.asarray(samples, dtype=np.int16).astype(np.float32) / np.float32(32768.0)
+
+
+def convert_stereo_to_mono_audio(samples) -> np.ndarray:
+    """interleaved stereo f32 -> mono f32: (l + r) / 2.0; an odd number of samples is an error as in whisper-rs"""
+    samples = np.asarray(samples, dtype=np.float32)
+    if len(samples) % 2:
+        raise WhisperError("HalfSampleMissing")
+    return (samples[0::2] + samples[1::2]) / np.float32(2.0)
+
+
+def convert_stereo_i16_to_mono_f32(samples) -> np.ndarray:
+    """interleaved stereo i16 -> mono f32: (l as f32 + r as f32) / 2.0 / 32768.0"""
+    samples = np.asarray(samples, dtype=np.int16)
+    if len(samples) % 2:
+        raise WhisperError("HalfSampleMissing")
+    return (samples[0::2].astype(np.float32) + samples[1::2].astype(np.float32)) / np.float32(2.0) / np.float32(32768.0)
+
+
+def audio_taps(lib: C.CDLL, sample_rate: int):
+    """Extension (whisper_amd_audio_taps): (taps [L][K] F32, L, M, K) of the audio front end's filter for an input rate; None when the rate is refused."""
+    L, M, K = C.c_int(), C.c_int(), C.c_int()
+    n = lib.whisper_amd_audio_taps(sample_rate, None, 0, C.byref(L), C.byref(M), C.byref(K))
+    if n < 0:
+        return None
+    t = np.zeros(max(n, 1), np.float32)
+    lib.whisper_amd_audio_taps(sample_rate, t.ctypes.data_as(C.POINTER(C.c_float)), n, None, None, None)
+    return t[:n].reshape(L.value, K.value), L.value, M.value, K.value
 
 
 DTW_REFUSED, DTW_NOT_TAKEN, DTW_HIP_ERROR = -1, -2, -3      # whisper_amd_dtw_path's codes (include/whisper_amd.h)
@@ -585,6 +629,57 @@ class WhisperState:
         out = (C.c_int64 * 2)()
         self.lib.whisper_amd_dtw_timings(self.ptr, out)
         return int(out[0]), int(out[1])
+
+    # -- audio front end (whisper_amd_audio_*): int16 / F32, mono / stereo, 8 .. 192 kHz -> 16 kHz mono F32 on the device -------
+    def _audio_args(self, data, channels, fmt):
+        """`data`: a numpy array of interleaved int16 or float32 samples on the host, or (device pointer, n_frames) with `fmt` given"""
+        if isinstance(data, tuple):
+            return data[0], int(data[1]), fmt
+        if fmt is None:
+            fmt = PCM_I16 if np.asarray(data).dtype == np.int16 else PCM_F32
+        data = np.ascontiguousarray(data, dtype=np.int16 if fmt == PCM_I16 else np.float32).reshape(-1)
+        self._audio_keep = data
+        return (data.ctypes.data if len(data) else None), len(data) // max(channels, 1), fmt
+
+    def audio_to_pcm(self, data, channels: int, sample_rate: int, fmt: Optional[int] = None) -> tuple:
+        """Extension (whisper_amd_audio_to_pcm): returns (device pointer, n_samples) of the 16 kHz mono F32 audio, valid until the next call
+        on this state; pass the pair to full() or pcm_to_mel_device()."""
+        ptr, n_frames, fmt = self._audio_args(data, channels, fmt)
+        n = C.c_int64(-1)
+        r = self.lib.whisper_amd_audio_to_pcm(self.ptr, C.c_void_p(ptr), n_frames, channels, sample_rate, fmt, C.byref(n))
+        if not r:
+            raise WhisperError("AudioRefused", -1)
+        return r, int(n.value)
+
+    def full_audio(self, params: "FullParams", data, channels: int, sample_rate: int, fmt: Optional[int] = None) -> int:
+        """Extension (whisper_amd_full_audio): audio_to_pcm + full() without a host copy of the PCM."""
+        ptr, n_frames, fmt = self._audio_args(data, channels, fmt)
+        r = self.lib.whisper_amd_full_audio(self.ctx.ptr, self.ptr, params.c, C.c_void_p(ptr), n_frames, channels, sample_rate, fmt)
+        if r != 0:
+            raise WhisperError("GenericError(%d)" % r, r)
+        return r
+
+    def audio_copy(self) -> np.ndarray:
+        """Extension (whisper_amd_audio_copy): the last audio_to_pcm / full_audio result as a host array."""
+        n = self.lib.whisper_amd_audio_copy(self.ptr, None, 0)
+        if n < 0:
+            raise WhisperError("NoAudio", int(n))
+        out = np.zeros(max(n, 1), np.float32)
+        if self.lib.whisper_amd_audio_copy(self.ptr, out.ctypes.data_as(C.POINTER(C.c_float)), n) != n:
+            raise WhisperError("NoAudio", -1)
+        return out[:n]
+
+    def audio_stats(self) -> tuple:
+        """Extension: audio front end calls on this state (served by the kernels, served by the host restatement, kernel attempts that fell back)."""
+        out = (C.c_long * 3)()
+        self.lib.whisper_amd_audio_stats(self.ptr, out)
+        return int(out[0]), int(out[1]), int(out[2])
+
+    def pcm_to_mel_device(self, ptr: int, n: int, n_threads: int = 1):
+        """pcm_to_mel on PCM that lies in device memory (e.g. audio_to_pcm's result)"""
+        r = self.lib.whisper_pcm_to_mel_with_state(self.ctx.ptr, self.ptr, C.cast(C.c_void_p(ptr), C.POINTER(C.c_float)), n, n_threads)
+        if r != 0:
+            raise WhisperError("UnableToCalculateSpectrogram", r)
 
     def n_len(self) -> int:
         return self.lib.whisper_n_len_from_state(self.ptr)
