@@ -635,6 +635,71 @@ WHISPER_API int64_t       whisper_amd_audio_taps(int sample_rate, float * dst, i
 WHISPER_API int           whisper_amd_audio_tile(void);
 WHISPER_API void          whisper_amd_audio_stats(struct whisper_state * state, long out[3]);
 
+/* Long recordings (wa_long.cpp): a recording of any length cut at the silences the VAD found, the speech packed into chunks of
+ * at most max_chunk_ms, the chunks transcribed in lock-step waves, the times mapped back.  A chunk is whisper_full_with_state on that chunk's
+ * speech-only audio and nothing else, so every chunk's result is the one that call gives for it alone.
+ * whisper_vad_detect_speech (and every call built on it: whisper_vad_segments_from_samples, whisper_full* with vad = true) takes a host or a
+ *   device pointer, detected as whisper_pcm_to_mel does; device audio is read in place, on the VAD context's OWN stream, which is ordered
+ *   against no other: work that still writes the audio on another stream - whisper_amd_audio_to_pcm's on its state's stream, a caller's own
+ *   kernel - is the caller's to finish first (hipStreamSynchronize on that stream).  whisper_amd_full_long does that for ctx->state's stream.
+ * whisper_amd_full_long, on the context's own state (ctx->state):
+ *   - `samples` is a host or a device pointer.  Host PCM is uploaded once into a buffer the state owns; device PCM is read where it lies (work
+ *     on it that the caller queued on another stream than the state's is the caller's to finish first).
+ *   - max_chunk_ms <= 0 means 30000; n_parallel <= 0 means 8; n_parallel is clamped to 8 (the lock-step group's width).
+ *   - params.vad_model_path and params.vad_params are used; params.vad itself is not looked at.  The VAD context is the one
+ *     whisper_full(vad = true) keeps on the state.
+ *   - Chunks: greedy, in order, whole VAD segments.  A chunk takes the next segment while its packed length stays <= max_chunk_ms; a single
+ *     segment longer than that is a chunk of its own and whisper_full's 30 s window loop covers it.  Packed length, audio and time table of a
+ *     chunk are what whisper_full(vad = true) makes of that run of segments taken as the whole list, with the caller's n_samples: the
+ *     chunk's last segment gets no overlap extension and no trailing silence, the n_samples - 1 / n_samples clamps apply, 0.1 s of silence
+ *     stands between segments, the table's original times are the caller's.  A chunk shorter than 100 ms gives no segments, as whisper_full
+ *     on it would; nothing is padded.
+ *   - One launch of k_long_pack writes every chunk into one allocation of the state, each chunk on a 256-byte boundary, byte for byte what
+ *     the host function gives.  WHISPER_AMD_LONG_HOST=1 in the environment, read at each call, takes the host function instead; so does a
+ *     call whose HIP path fails (logged, counted).  VAD and pack are complete before the first wave starts.
+ *   - The chunks run in waves of up to n_parallel, as whisper_amd_full_batch runs its chunks: one state, host thread and stream per member,
+ *     single-token steps in lock step.  Member params follow whisper_full_parallel's members: new_segment and progress callbacks nulled,
+ *     print_* off.  encoder_begin_callback, abort_callback and logits_filter_callback stay set and are called CONCURRENTLY from up to
+ *     n_parallel threads, as whisper_full_parallel's members call them: what they touch must be safe for that.  The states beside ctx->state
+ *     are made for the call and released at its end.  Chunks are independent: no prompt is carried from one chunk to the next, whatever
+ *     no_context says and whatever the context transcribed before (no_context = false still carries the context from one 30 s window to the
+ *     next INSIDE a chunk longer than 30 s); initial_prompt applies to each.  whisper_amd_batch_stats then sums the call's waves.
+ *   - Results are appended to ctx->state in chunk order with t0 / t1 ALREADY mapped into the caller's audio through the chunk's table; a
+ *     segment lasts at least 10 cs (t1 >= t0 + 10, the getters' rule), then t0 = max(t0, previous segment's t1).  The state's own VAD table
+ *     is cleared, so the getters return the stored times.  Token t0 / t1 / t_dtw that are >= 0 are mapped the same way.
+ *     new_segment_callback fires on ctx->state once per appended segment; whisper_full_lang_id is the first chunk's.
+ *   - Returns 0 with no segments when the VAD finds no speech (earlier results are cleared, as whisper_full does); -1 with a log line for a
+ *     missing or refused VAD model, non-zero offset_ms / duration_ms (not supported here) and null arguments; otherwise the first non-zero
+ *     chunk code, with the results and the chunk list cleared.  No exception crosses the boundary.
+ * whisper_amd_full_long_audio: whisper_amd_audio_to_pcm on ctx->state, then whisper_amd_full_long on its device result.
+ * whisper_amd_long_n_chunks / _chunk_info: the last call's chunks; out = { first segment, segment count, packed samples, original start cs,
+ *   original end cs, result segments }; -1 for an index out of range.
+ * whisper_amd_long_chunk_copy: the packed PCM of chunk i, kept until the next call: copies up to `cap` samples, returns their full count.
+ * whisper_amd_long_stats: out = { pack path taken (0 host, 1 kernel), device packs that fell back since the state was created, chunks, waves,
+ *   us VAD, us plan + pack, us transcription (member states made and released, waves, mapping), bytes of the CALLER'S recording copied host -> device (0 for device
+ *   input; the pack's piece table and, on the host pack path, the packed chunks it uploads are not counted) } of the last whisper_amd_full_long
+ *   call; whisper_amd_long_pack sets the first, the third and the last for its own call.
+ * whisper_amd_long_plan: the planner alone, no device needed: segs_cs = n_segs pairs (start, end) in centiseconds; writes up to `cap` chunks,
+ *   returns their full count, -1 for refused arguments.
+ * whisper_amd_long_pack: the pack alone on a caller's segment list and runs (first[c], count[c]); where = 0 the host function, 1 the kernel
+ *   (no fallback); 0 on success.  The chunks are then read with whisper_amd_long_chunk_copy on the state's context when `state` is its own state.
+ * whisper_amd_long_tile: output samples per workgroup of k_long_pack (tests put piece boundaries on either side of it).
+ * whisper_amd_context_state: ctx->state, for the calls above that take a state. */
+WHISPER_API int     whisper_amd_full_long(struct whisper_context * ctx, struct whisper_full_params params, const float * samples, int n_samples,
+                                          int max_chunk_ms, int n_parallel);
+WHISPER_API int     whisper_amd_full_long_audio(struct whisper_context * ctx, struct whisper_full_params params, const void * data, int64_t n_frames,
+                                                int channels, int sample_rate, int format, int max_chunk_ms, int n_parallel);
+WHISPER_API int     whisper_amd_long_n_chunks(struct whisper_context * ctx);
+WHISPER_API int     whisper_amd_long_chunk_info(struct whisper_context * ctx, int i, int64_t out[6]);
+WHISPER_API int64_t whisper_amd_long_chunk_copy(struct whisper_context * ctx, int i, float * dst, int64_t cap);
+WHISPER_API void    whisper_amd_long_stats(struct whisper_context * ctx, int64_t out[8]);
+WHISPER_API int     whisper_amd_long_plan(const int64_t * segs_cs, int n_segs, int n_samples, float samples_overlap, int max_chunk_samples,
+                                          int32_t * first, int32_t * count, int64_t * packed, int cap);
+WHISPER_API int     whisper_amd_long_pack(struct whisper_state * state, const float * samples, int n_samples, const int64_t * segs_cs, int n_segs,
+                                          float samples_overlap, const int32_t * first, const int32_t * count, int n_chunks, int where);
+WHISPER_API int     whisper_amd_long_tile(void);
+WHISPER_API struct whisper_state * whisper_amd_context_state(struct whisper_context * ctx);
+
 #ifdef __cplusplus
 }
 #endif

@@ -335,7 +335,7 @@ struct whisper_state * whisper_init_state(struct whisper_context * ctx) {
     return st;
 }
 
-void whisper_free_state(struct whisper_state * st) { if (st) { whisper_vad_free(st->vad_context); wa_state_release(*st); delete st; } }
+void whisper_free_state(struct whisper_state * st) { if (st) { whisper_vad_free(st->vad_context); wa_long_free(*st); wa_state_release(*st); delete st; } }
 void whisper_free(struct whisper_context * ctx) {
     if (!ctx) return;
     wa_batcher_free_all(*ctx);
@@ -611,38 +611,6 @@ int whisper_full(struct whisper_context * ctx, struct whisper_full_params params
     }
     return whisper_full_with_state(ctx, ctx->state, params, samples, n_samples);
 }
-// Lock-step decode groups for chunks transcribed together on one device (whisper_amd_full_batch, whisper_full_parallel): groups of
-// WHISPER_AMD_BATCH_GROUP chunks share a decoder pass (wa_decode.cpp: wa_batcher).  Where the pass is ONE launch (wa_rows.hip; it owns the
-// device while it runs) the default is one group of up to 8 - every weight row read once for eight tokens.  Where only the launch
-// sequence is available (a pass is then a chain of short latency-bound launches) groups of 4 run side by side on their own streams:
-// two 4-row passes finish sooner than one 8-row pass after the other (round 2: 8 chunks 488x real time as one group, 589x as two).
-struct wa_batch_groups {
-    whisper_context * ctx;
-    std::vector<whisper_state *> members;
-    std::vector<wa_batcher *> bats;
-    wa_batch_groups(whisper_context * c, const std::vector<whisper_state *> & m) : ctx(c), members(m) {
-        static const bool off = getenv("WHISPER_AMD_NO_BATCHER") != nullptr;
-        int group = !members.empty() && members[0]->rows_form.enabled() ? WA_MAX_DECODERS : 4;
-        if (const char * g = getenv("WHISPER_AMD_BATCH_GROUP")) group = std::max(2, std::min(WA_MAX_DECODERS, atoi(g)));
-        for (size_t i0 = 0; i0 < members.size() && !off; i0 += group) {
-            const size_t n = std::min((size_t) group, members.size() - i0);
-            wa_batcher * b = wa_batcher_create(*ctx, (int) n);       // null for a group of one: that chunk decodes on its own (the members of a quantised group too, unless the one-launch form serves it)
-            bats.push_back(b);
-            for (size_t i = i0; i < i0 + n; ++i) members[i]->batcher = b;
-        }
-    }
-    ~wa_batch_groups() {
-        for (auto * st : members) st->batcher = nullptr;
-        ctx->batch_steps = ctx->batch_rows = ctx->batch_one_launch = ctx->batch_served = 0;
-        for (auto * b : bats) if (b) {
-            long st_ = 0, rw_ = 0, ol_ = 0, sv_ = 0;
-            wa_batcher_stats(b, &st_, &rw_, &ol_, &sv_);
-            ctx->batch_steps += st_; ctx->batch_rows += rw_; ctx->batch_one_launch += ol_; ctx->batch_served += sv_;
-            wa_batcher_destroy(b);
-        }
-    }
-};
-
 int whisper_full_parallel(struct whisper_context * ctx, struct whisper_full_params params, const float * samples, int n_samples, int n_processors) {
     // ref: whisper.cpp:7736-7864: the audio is cut into n_processors equal parts, each transcribed on a state of its own (here:
     // concurrently on this device, one HIP stream each), the segment lists appended with their time offsets.  As in the reference

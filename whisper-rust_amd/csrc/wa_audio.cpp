@@ -33,21 +33,6 @@ static const float * audio_taps_device(whisper_context & ctx, const wa_audio_pla
     return d;
 }
 
-template <typename T> static bool audio_reserve(T *& buf, size_t & cap, size_t need) {
-    if (need <= cap && buf) return true;
-    if (buf) { (void) hipFree(buf); buf = nullptr; cap = 0; }
-    if (!WA_HIP_OK(hipMalloc((void **) &buf, need * sizeof(T)))) { buf = nullptr; return false; }
-    cap = need;
-    return true;
-}
-
-static bool audio_is_device(const void * p) {
-    hipPointerAttribute_t attr;
-    if (p && hipPointerGetAttributes(&attr, p) == hipSuccess && attr.type == hipMemoryTypeDevice) return true;
-    (void) hipGetLastError();   // clear the "invalid value" left by a plain host pointer
-    return false;
-}
-
 // the kernels: input staged in HBM when it arrives in host memory, everything on the state's stream
 static bool audio_device_path(whisper_context & ctx, whisper_state & st, const void * data, bool on_device, int64_t n_frames, int channels, int format,
                               const wa_audio_plan & p, int64_t n_out) {
@@ -56,7 +41,7 @@ static bool audio_device_path(whisper_context & ctx, whisper_state & st, const v
     const void * d_in = data;
     if (!on_device) {
         const size_t bytes = (size_t) n_frames * channels * (format == WA_AUDIO_I16 ? 2 : 4);
-        if (!audio_reserve(st.d_audio_in, st.d_audio_in_cap, bytes)) return false;
+        if (!wa_dev_reserve(st.d_audio_in, st.d_audio_in_cap, bytes)) return false;
         if (!WA_HIP_OK(hipMemcpyAsync(st.d_audio_in, data, bytes, hipMemcpyHostToDevice, st.stream))) return false;
         d_in = st.d_audio_in;
     }
@@ -93,10 +78,10 @@ const float * whisper_amd_audio_to_pcm(struct whisper_state * st, const void * d
         wa_audio_plan_make(sample_rate, p);
         const int64_t n_out = wa_audio_n_out(n_frames, sample_rate);
         if (!WA_HIP_OK(hipSetDevice(ctx.device))) return nullptr;
-        if (!audio_reserve(st->d_audio, st->d_audio_cap, (size_t) std::max<int64_t>(n_out, 256))) return nullptr;
+        if (!wa_dev_reserve(st->d_audio, st->d_audio_cap, (size_t) std::max<int64_t>(n_out, 256))) return nullptr;
         st->audio_n = -1;
         if (n_out > 0) {
-            const bool on_device = audio_is_device(data);
+            const bool on_device = wa_is_device_ptr(data);
             bool served = false;
             if (!st->audio_host) {
                 served = audio_device_path(ctx, *st, data, on_device, n_frames, channels, format, p, n_out);

@@ -212,11 +212,9 @@ bool wa_mel_compute(whisper_context & ctx, whisper_state & st, const float * sam
 
     // the samples may already live in HBM (bench / chunk sharding) - then no copy at all
     const float * d_pcm = nullptr;
-    hipPointerAttribute_t attr;
-    if (hipPointerGetAttributes(&attr, samples) == hipSuccess && attr.type == hipMemoryTypeDevice) {
+    if (wa_is_device_ptr(samples)) {
         d_pcm = samples;
     } else {
-        (void) hipGetLastError();   // clear the "invalid value" left by a plain host pointer
         if ((size_t) n_samples > st.d_pcm_cap) {
             dev_free(st.d_pcm);
             st.d_pcm_cap = 0;

@@ -576,12 +576,11 @@ int runner::run(const float * samples, int n_samples) {
         if (n_samples > 0) {
             std::vector<float> host;
             const float * pcm = samples;
-            hipPointerAttribute_t attr;
-            if (hipPointerGetAttributes(&attr, samples) == hipSuccess && attr.type == hipMemoryTypeDevice) {    // PCM handed over in HBM
+            if (wa_is_device_ptr(samples)) {    // PCM handed over in HBM
                 host.resize(n_samples);
                 if (!WA_HIP_OK(hipMemcpy(host.data(), samples, (size_t) n_samples * sizeof(float), hipMemcpyDeviceToHost))) return -2;
                 pcm = host.data();
-            } else (void) hipGetLastError();
+            }
             st->energy = signal_energy(pcm, n_samples, 32);
         }
     }

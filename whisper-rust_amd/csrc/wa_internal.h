@@ -15,8 +15,10 @@
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdint>
 #include <cstdio>
+#include <cstdlib>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -44,6 +46,22 @@ int64_t wa_time_us();
 bool wa_hip_ok(hipError_t e, const char * what, const char * file, int line);
 
 static inline int wa_pad(int x, int n) { return ((x + n - 1) / n) * n; }
+
+// true where `p` lies in device memory: PCM handed over in HBM (whisper_pcm_to_mel*, whisper_full*, whisper_vad_detect_speech, the audio front end)
+static inline bool wa_is_device_ptr(const void * p) {
+    hipPointerAttribute_t attr;
+    if (p && hipPointerGetAttributes(&attr, p) == hipSuccess && attr.type == hipMemoryTypeDevice) return true;
+    (void) hipGetLastError();   // clear the "invalid value" left by a plain host pointer
+    return false;
+}
+// a grow-only device buffer of `need` elements: kept when it is large enough, else freed and allocated anew (contents lost); false: buf is null
+template <typename T> static inline bool wa_dev_reserve(T *& buf, size_t & cap, size_t need) {
+    if (need <= cap && buf) return true;
+    if (buf) { (void) hipFree(buf); buf = nullptr; cap = 0; }
+    if (!WA_HIP_OK(hipMalloc((void **) &buf, need * sizeof(T)))) { buf = nullptr; return false; }
+    cap = need;
+    return true;
+}
 
 // ---------------------------------------------------------------------------------------------
 // model
@@ -362,6 +380,10 @@ struct whisper_state {
     int64_t audio_n = -1;                                   // samples of the last result, -1: none yet
     bool audio_host = false;                                // WHISPER_AMD_AUDIO_HOST=1 when the state was created: the host path only
     long n_audio_device = 0, n_audio_host = 0, n_audio_fallback = 0;    // calls served by the kernels / by the host path / device attempts that fell back
+
+    // long recordings (wa_long.cpp): the uploaded PCM, the chunk buffer, the piece table and the last call's chunk list;
+    // made by the first whisper_amd_full_long / whisper_amd_long_pack call on this state, freed with it
+    struct wa_long_state * lng = nullptr;
 };
 // the form a state's single-token run-ahead window (wa_spec_*) runs on, is gated on and is charged with its time-outs
 inline wa_launch_form & wa_window_form(whisper_state & st) { return st.single_via_rows ? st.rows_form : st.mega_form; }
@@ -379,6 +401,8 @@ bool wa_decode     (whisper_context & ctx, whisper_state & st, const wa_batch & 
                     ggml_abort_callback cb, void * cb_data);                         // wa_decode.cpp
 // VAD (wa_vad.cpp)
 whisper_vad_context * wa_vad_create_from_file(const char * path, int n_threads, int device);
+bool wa_vad_segments_for(whisper_context * ctx, whisper_state * st, const whisper_full_params & params, const float * samples, int n_samples,
+                         std::vector<wa_vad_seg> & segs);      // `samples` host or device; false: failure; the state's table is cleared
 bool wa_vad_for_full(whisper_context * ctx, whisper_state * st, const whisper_full_params & params, const float * samples, int n_samples,
                      std::vector<float> & filtered);           // false: failure; `filtered` empty: no speech
 // host-overlapped greedy decoding on the one-launch step (wa_decode.cpp); launch k decodes position pos0 + k
@@ -396,6 +420,38 @@ void wa_batcher_destroy(wa_batcher * b);          // hands the batcher back to i
 void wa_batcher_release(wa_batcher * b);          // frees it
 void wa_batcher_free_all(whisper_context & ctx);  // whisper_free
 void wa_batcher_stats(const wa_batcher * b, long * steps, long * rows, long * one_launch = nullptr, long * served = nullptr);
+// Lock-step decode groups for chunks transcribed together on one device (whisper_amd_full_batch, whisper_full_parallel, whisper_amd_full_long):
+// groups of WHISPER_AMD_BATCH_GROUP chunks share a decoder pass (wa_decode.cpp: wa_batcher).  Where the pass is ONE launch (wa_rows.hip; it owns the
+// device while it runs) the default is one group of up to 8 - every weight row read once for eight tokens.  Where only the launch
+// sequence is available (a pass is then a chain of short latency-bound launches) groups of 4 run side by side on their own streams:
+// two 4-row passes finish sooner than one 8-row pass after the other (round 2: 8 chunks 488x real time as one group, 589x as two).
+struct wa_batch_groups {
+    whisper_context * ctx;
+    std::vector<whisper_state *> members;
+    std::vector<wa_batcher *> bats;
+    wa_batch_groups(whisper_context * c, const std::vector<whisper_state *> & m) : ctx(c), members(m) {
+        static const bool off = getenv("WHISPER_AMD_NO_BATCHER") != nullptr;
+        int group = !members.empty() && members[0]->rows_form.enabled() ? WA_MAX_DECODERS : 4;
+        if (const char * g = getenv("WHISPER_AMD_BATCH_GROUP")) group = std::max(2, std::min(WA_MAX_DECODERS, atoi(g)));
+        for (size_t i0 = 0; i0 < members.size() && !off; i0 += group) {
+            const size_t n = std::min((size_t) group, members.size() - i0);
+            wa_batcher * b = wa_batcher_create(*ctx, (int) n);       // null for a group of one: that chunk decodes on its own (the members of a quantised group too, unless the one-launch form serves it)
+            bats.push_back(b);
+            for (size_t i = i0; i < i0 + n; ++i) members[i]->batcher = b;
+        }
+    }
+    ~wa_batch_groups() {
+        for (auto * st : members) st->batcher = nullptr;
+        ctx->batch_steps = ctx->batch_rows = ctx->batch_one_launch = ctx->batch_served = 0;
+        for (auto * b : bats) if (b) {
+            long st_ = 0, rw_ = 0, ol_ = 0, sv_ = 0;
+            wa_batcher_stats(b, &st_, &rw_, &ol_, &sv_);
+            ctx->batch_steps += st_; ctx->batch_rows += rw_; ctx->batch_one_launch += ol_; ctx->batch_served += sv_;
+            wa_batcher_destroy(b);
+        }
+    }
+};
+void wa_long_free(whisper_state & st);            // wa_long.cpp: what whisper_amd_full_long / whisper_amd_long_pack keep on a state
 bool wa_state_alloc(whisper_context & ctx, whisper_state & st);
 void wa_state_release(whisper_state & st);
 bool wa_kv_self_realloc(whisper_context & ctx, whisper_state & st, int n_cells);

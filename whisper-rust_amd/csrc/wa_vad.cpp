@@ -115,12 +115,15 @@ static bool vad_run_slabs(whisper_vad_context & v, const float * samples, int n_
     if (n_chunks == 0) return true;
     if (!WA_HIP_OK(hipSetDevice(v.device))) return false;
     const int n_slabs = (n_chunks + v.slab - 1) / v.slab;
+    // audio that already lies in HBM (whisper_amd_audio_to_pcm's result, whisper_amd_full_long's buffer) is read in place: a slab starts at a
+    // multiple of 512 floats of it and the kernel reads nothing at or past n_valid
+    const bool on_device = wa_is_device_ptr(samples);
     auto enqueue = [&](int k) {
         const int b = k & 1, c0 = k * v.slab, nc = std::min(v.slab, n_chunks - c0);
         const int64_t s0 = (int64_t) c0 * WA_VAD_WINDOW;
         const int n_valid = (int) std::min<int64_t>((int64_t) nc * WA_VAD_WINDOW, (int64_t) n_samples - s0);
-        return WA_HIP_OK(hipMemcpyAsync(v.d_samples[b], samples + s0, (size_t) n_valid * sizeof(float), hipMemcpyHostToDevice, v.stream))
-            && wa_vad_front_launch(v.dev, v.d_samples[b], n_valid, nc, v.d_out[b], (void *) v.stream)
+        return (on_device || WA_HIP_OK(hipMemcpyAsync(v.d_samples[b], samples + s0, (size_t) n_valid * sizeof(float), hipMemcpyHostToDevice, v.stream)))
+            && wa_vad_front_launch(v.dev, on_device ? samples + s0 : v.d_samples[b], n_valid, nc, v.d_out[b], (void *) v.stream)
             && WA_HIP_OK(hipMemcpyAsync(v.h_out[b], v.d_out[b], (size_t) nc * WA_VAD_GATES * sizeof(float), hipMemcpyDeviceToHost, v.stream))
             && WA_HIP_OK(hipEventRecord(v.ev[b], v.stream));
     };
@@ -226,9 +229,10 @@ void whisper_amd_vad_timings(struct whisper_vad_context * vctx, int64_t out_us[3
 // -------------------------------------------------------------------------------------------------
 // whisper_full / whisper_full_parallel with vad = true (ref: whisper.cpp:6615-6793): the speech-only audio and the state's table
 // -------------------------------------------------------------------------------------------------
-bool wa_vad_for_full(whisper_context * ctx, whisper_state * st, const whisper_full_params & params, const float * samples, int n_samples,
-                     std::vector<float> & filtered) {
-    WA_INFO("%s: VAD is enabled, processing speech segments only\n", __func__);
+// the state's VAD context (made from params.vad_model_path by the first call) over `samples`, host or device: its segments
+bool wa_vad_segments_for(whisper_context * ctx, whisper_state * st, const whisper_full_params & params, const float * samples, int n_samples,
+                         std::vector<wa_vad_seg> & segs) {
+    segs.clear();
     st->vad_mapping_table.clear();
     st->has_vad_segments = false;
     if (!st->vad_context) {
@@ -236,8 +240,15 @@ bool wa_vad_for_full(whisper_context * ctx, whisper_state * st, const whisper_fu
         if (!st->vad_context) { WA_ERROR("%s: failed to initialize VAD context\n", __func__); return false; }
     }
     if (!whisper_vad_detect_speech(st->vad_context, samples, n_samples)) { WA_ERROR("%s: failed to detect speech\n", __func__); return false; }
-    const std::vector<wa_vad_seg> segs = wa_vad_segments_from_probs(st->vad_context->probs.data(), (int) st->vad_context->probs.size(),
-                                                                    st->vad_context->model.n_window, params.vad_params);
+    segs = wa_vad_segments_from_probs(st->vad_context->probs.data(), (int) st->vad_context->probs.size(), st->vad_context->model.n_window, params.vad_params);
+    return true;
+}
+
+bool wa_vad_for_full(whisper_context * ctx, whisper_state * st, const whisper_full_params & params, const float * samples, int n_samples,
+                     std::vector<float> & filtered) {
+    WA_INFO("%s: VAD is enabled, processing speech segments only\n", __func__);
+    std::vector<wa_vad_seg> segs;
+    if (!wa_vad_segments_for(ctx, st, params, samples, n_samples, segs)) return false;
     filtered.clear();
     if (!segs.empty()) {
         st->has_vad_segments = true;

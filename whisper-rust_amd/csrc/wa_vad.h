@@ -57,7 +57,8 @@ std::vector<wa_vad_seg> wa_vad_segments_from_probs(const float * probs, int n_pr
 
 struct wa_vad_map_point { int64_t processed_time, original_time; };    // centiseconds in the speech-only audio / in the caller's audio
 // the audio whisper_full transcribes when vad = true (speech segments, 0.1 s of silence between them) and its table;
-// `filtered` stays empty when there is no segment
+// `filtered` stays empty when there is no segment.  Lengths, pieces and table are wa_long_plan.h's wa_vad_layout_make, which the chunk planner and
+// the pack kernel of whisper_amd_full_long use too
 void wa_vad_filter_audio(const std::vector<wa_vad_seg> & segs, float samples_overlap, const float * samples, int n_samples,
                          std::vector<float> & filtered, std::vector<wa_vad_map_point> & table);
 int64_t wa_vad_map_time(int64_t processed_time, const std::vector<wa_vad_map_point> & table);

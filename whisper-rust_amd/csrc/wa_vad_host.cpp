@@ -2,6 +2,7 @@
 // Plain C++; every floating-point operation below is one the reference performs, in its order.  Built with -ffp-contract=off: the
 // only fused multiply-adds are the written ones (the W_hh h chains, which ggml_vec_dot_f32 forms with vfmadd on an AVX2 build).
 #include "wa_vad.h"
+#include "wa_long_plan.h"
 
 #include <immintrin.h>
 
@@ -201,8 +202,8 @@ float wa_vad_step(const wa_vad_model & m, wa_vad_lstm & st, const float * gate_i
 // -------------------------------------------------------------------------------------------------
 // speech segments (ref: whisper.cpp:5202-5436), integer for integer
 // -------------------------------------------------------------------------------------------------
-static int     cs_to_samples(int64_t cs)  { return (int) ((cs / 100.0) * WHISPER_SAMPLE_RATE + 0.5); }
-static int64_t samples_to_cs(int samples) { return (int64_t) ((samples / (double) WHISPER_SAMPLE_RATE) * 100.0 + 0.5); }
+static int     cs_to_samples(int64_t cs)  { return wa_vad_cs_to_samples(cs); }
+static int64_t samples_to_cs(int samples) { return wa_vad_samples_to_cs(samples); }
 
 std::vector<wa_vad_seg> wa_vad_segments_from_probs(const float * probs, int n_probs, int n_window, const whisper_vad_params & params) {
     const float threshold               = params.threshold;
@@ -320,67 +321,13 @@ void wa_vad_filter_audio(const std::vector<wa_vad_seg> & segs, float samples_ove
     filtered.clear();
     table.clear();
     if (segs.empty()) return;
-    const int n_seg = (int) segs.size();
-    const int overlap_samples = samples_overlap * WHISPER_SAMPLE_RATE;
-    int filtered_n_samples = 0;
-    for (int i = 0; i < n_seg; i++) {
-        const int segment_start_samples = cs_to_samples(segs[i].start);
-        int segment_end_samples = cs_to_samples(segs[i].end);
-        if (i < n_seg - 1) segment_end_samples += overlap_samples;
-        segment_end_samples = std::min(segment_end_samples, n_samples - 1);
-        filtered_n_samples += (segment_end_samples - segment_start_samples);
-    }
-    const int silence_samples = 0.1 * WHISPER_SAMPLE_RATE;
-    const int total_silence_samples = (n_seg > 1) ? (n_seg - 1) * silence_samples : 0;
-    const int total_samples_needed = filtered_n_samples + total_silence_samples;
-    // The length handed to the transcription is total_samples_needed (the first pass clamps a segment's end to n_samples - 1); the
-    // copy below clamps to n_samples, so a last segment that reaches the end of the audio copies one sample more than was counted:
-    // the reference writes it past its vector's size.  Here the buffer has room for it and the length stays the reference's.
-    std::vector<float> buf((size_t) std::max(total_samples_needed, 0) + (size_t) n_seg + 1, 0.0f);
-    table.reserve(segs.size() * 4);
-
-    int offset = 0;
-    for (int i = 0; i < n_seg; i++) {
-        int segment_start_samples = cs_to_samples(segs[i].start);
-        int segment_end_samples   = cs_to_samples(segs[i].end);
-        if (i < n_seg - 1) segment_end_samples += overlap_samples;
-        segment_start_samples = std::min(segment_start_samples, n_samples - 1);
-        segment_end_samples   = std::min(segment_end_samples, n_samples);
-        const int segment_length = segment_end_samples - segment_start_samples;
-        if (segment_length <= 0) continue;
-
-        const int64_t orig_start = segs[i].start, orig_end = segs[i].end;
-        const int64_t vad_start = samples_to_cs(offset), vad_end = samples_to_cs(offset + segment_length);
-        table.push_back({ vad_start, orig_start });
-        table.push_back({ vad_end, orig_end });
-
-        const int64_t min_segment_length = 100, point_interval = 20;     // a point every 200 ms inside segments longer than 1 s
-        if (vad_end - vad_start > min_segment_length) {
-            const int64_t segment_duration = vad_end - vad_start;
-            const int num_points = (int) (segment_duration / point_interval) - 1;
-            for (int j = 1; j <= num_points; j++) {
-                const int64_t vad_time = vad_start + j * point_interval;
-                if (vad_time >= vad_end) continue;
-                const int64_t vad_elapsed = vad_time - vad_start, vad_total = vad_end - vad_start, orig_total = orig_end - orig_start;
-                table.push_back({ vad_time, orig_start + (vad_elapsed * orig_total) / vad_total });
-            }
-        }
-        if ((size_t) offset + (size_t) segment_length > buf.size()) buf.resize((size_t) offset + (size_t) segment_length, 0.0f);
-        memcpy(buf.data() + offset, samples + segment_start_samples, (size_t) segment_length * sizeof(float));
-        offset += segment_length;
-
-        if (i < n_seg - 1) {
-            table.push_back({ samples_to_cs(offset), orig_end });
-            table.push_back({ samples_to_cs(offset + silence_samples), segs[i + 1].start });
-            if ((size_t) offset + (size_t) silence_samples > buf.size()) buf.resize((size_t) offset + (size_t) silence_samples, 0.0f);
-            memset(buf.data() + offset, 0, (size_t) silence_samples * sizeof(float));
-            offset += silence_samples;
-        }
-    }
-    std::sort(table.begin(), table.end(), [](const wa_vad_map_point & a, const wa_vad_map_point & b) { return a.processed_time < b.processed_time; });
-    table.erase(std::unique(table.begin(), table.end(), [](const wa_vad_map_point & a, const wa_vad_map_point & b) { return a.processed_time == b.processed_time; }), table.end());
-
-    buf.resize((size_t) std::max(total_samples_needed, 0));
+    // lengths, pieces and table: wa_long_plan.h states them once, for this copy and for the device's (wa_long.hip).  The length handed to the
+    // transcription is the reference's; the sample a last segment reaching the end of the audio would copy past it is cut off.
+    std::vector<wa_long_piece> pieces;
+    const int total = wa_vad_layout_make(segs.data(), (int) segs.size(), samples_overlap, n_samples, &pieces, &table);
+    std::vector<float> buf((size_t) total, 0.0f);
+    for (const wa_long_piece & p : pieces)
+        if (p.src >= 0) memcpy(buf.data() + p.dst, samples + p.src, (size_t) p.len * sizeof(float));
     filtered.swap(buf);
 }
 

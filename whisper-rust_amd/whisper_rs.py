@@ -286,6 +286,19 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         proto("whisper_amd_audio_taps", C.c_int64, I, C.POINTER(F), C.c_int64, C.POINTER(I), C.POINTER(I), C.POINTER(I))
         proto("whisper_amd_audio_tile", I)
         proto("whisper_amd_audio_stats", None, P, C.POINTER(C.c_long))
+    if hasattr(lib, "whisper_amd_full_long"):
+        I64P, I32P = C.POINTER(C.c_int64), C.POINTER(C.c_int32)
+        proto("whisper_amd_full_long", I, P, whisper_full_params, P, I, I, I)
+        proto("whisper_amd_full_long_audio", I, P, whisper_full_params, P, C.c_int64, I, I, I, I, I)
+        proto("whisper_amd_long_n_chunks", I, P)
+        proto("whisper_amd_long_chunk_info", I, P, I, I64P)
+        proto("whisper_amd_long_chunk_copy", C.c_int64, P, I, C.POINTER(F), C.c_int64)
+        proto("whisper_amd_long_stats", None, P, I64P)
+        proto("whisper_amd_long_plan", I, I64P, I, I, F, I, I32P, I32P, I64P, I)
+        proto("whisper_amd_long_pack", I, P, P, I, I64P, I, F, I32P, I32P, I, I)
+        proto("whisper_amd_long_tile", I)
+        proto("whisper_amd_context_state", P, P)
+        proto("whisper_amd_batch_stats", None, P, C.POINTER(C.c_long), C.POINTER(C.c_long))
     _LIBS[path] = lib
     return lib
 
@@ -899,7 +912,87 @@ class WhisperFullContext:
                             tok_t0=[t.t0 for t in toks], tok_t1=[t.t1 for t in toks]))
         return out
 
+    # -- long recordings (whisper_amd_full_long, whisper_amd_long_*) -------------------------------
+    def state_ptr(self) -> int:
+        """Extension (whisper_amd_context_state): the context's own state, for the calls that take one."""
+        return self.lib.whisper_amd_context_state(self.ptr)
+
+    def full_long(self, params: FullParams, pcm, max_chunk_ms: int = 0, n_parallel: int = 0) -> int:
+        """Extension (whisper_amd_full_long).  `pcm`: numpy f32 array on the host, or (device pointer, n)."""
+        if isinstance(pcm, tuple):
+            ptr, n = pcm
+        else:
+            self._pcm_keep = pcm = _f32(pcm)
+            ptr, n = pcm.ctypes.data, len(pcm)
+        return self.lib.whisper_amd_full_long(self.ptr, params.c, C.c_void_p(ptr), n, max_chunk_ms, n_parallel)
+
+    def full_long_audio(self, params: FullParams, data, channels: int, sample_rate: int, fmt: Optional[int] = None, max_chunk_ms: int = 0,
+                        n_parallel: int = 0) -> int:
+        """Extension (whisper_amd_full_long_audio): interleaved int16 or float32 samples at any supported rate."""
+        if fmt is None:
+            fmt = PCM_I16 if np.asarray(data).dtype == np.int16 else PCM_F32
+        self._audio_keep = data = np.ascontiguousarray(data, dtype=np.int16 if fmt == PCM_I16 else np.float32).reshape(-1)
+        return self.lib.whisper_amd_full_long_audio(self.ptr, params.c, C.c_void_p(data.ctypes.data), len(data) // max(channels, 1), channels,
+                                                    sample_rate, fmt, max_chunk_ms, n_parallel)
+
+    def long_chunks(self) -> list[dict]:
+        """Extension (whisper_amd_long_chunk_info): the last call's chunks."""
+        out, v = [], (C.c_int64 * 6)()
+        for i in range(self.lib.whisper_amd_long_n_chunks(self.ptr)):
+            if self.lib.whisper_amd_long_chunk_info(self.ptr, i, v) != 0:
+                raise WhisperError("GenericError", -1)
+            out.append(dict(first=int(v[0]), count=int(v[1]), packed=int(v[2]), t0=int(v[3]), t1=int(v[4]), n_result=int(v[5])))
+        return out
+
+    def long_chunk_copy(self, i: int) -> np.ndarray:
+        """Extension (whisper_amd_long_chunk_copy): the packed PCM of chunk i."""
+        n = self.lib.whisper_amd_long_chunk_copy(self.ptr, i, None, 0)
+        if n < 0:
+            raise WhisperError("NoChunk", int(n))
+        out = np.zeros(max(n, 1), np.float32)
+        if self.lib.whisper_amd_long_chunk_copy(self.ptr, i, out.ctypes.data_as(C.POINTER(C.c_float)), n) != n:
+            raise WhisperError("NoChunk", -1)
+        return out[:n]
+
+    def long_stats(self) -> dict:
+        """Extension (whisper_amd_long_stats) of the last whisper_amd_full_long call."""
+        v = (C.c_int64 * 8)()
+        self.lib.whisper_amd_long_stats(self.ptr, v)
+        return dict(zip(("path", "fallbacks", "chunks", "waves", "vad_us", "pack_us", "transcribe_us", "h2d_bytes"), (int(x) for x in v)))
+
+    def long_pack(self, pcm, segs, overlap: float, runs, where: int) -> int:
+        """Extension (whisper_amd_long_pack) on the context's state: `segs` [(start cs, end cs)], `runs` [(first, count)]; `pcm` as full_long."""
+        if isinstance(pcm, tuple):
+            ptr, n = pcm
+        else:
+            self._pcm_keep = pcm = _f32(pcm)
+            ptr, n = pcm.ctypes.data, len(pcm)
+        s = np.ascontiguousarray(segs, dtype=np.int64).reshape(-1)
+        first = np.ascontiguousarray([r[0] for r in runs], dtype=np.int32)
+        count = np.ascontiguousarray([r[1] for r in runs], dtype=np.int32)
+        return self.lib.whisper_amd_long_pack(self.state_ptr(), C.c_void_p(ptr), n, s.ctypes.data_as(C.POINTER(C.c_int64)), len(s) // 2, overlap,
+                                              first.ctypes.data_as(C.POINTER(C.c_int32)), count.ctypes.data_as(C.POINTER(C.c_int32)), len(runs), where)
+
+    def batch_stats(self) -> tuple:
+        """Extension (whisper_amd_batch_stats): lock-step passes of the last batch / parallel / long call and the rows they served."""
+        a, b = C.c_long(0), C.c_long(0)
+        self.lib.whisper_amd_batch_stats(self.ptr, C.byref(a), C.byref(b))
+        return int(a.value), int(b.value)
+
     def free(self):
         if self.ptr:
             self.lib.whisper_free(self.ptr)
             self.ptr = None
+
+
+def long_plan(lib: C.CDLL, segs, n_samples: int, overlap: float, max_chunk_samples: int) -> list[tuple]:
+    """Extension (whisper_amd_long_plan, no device): [(first, count, packed samples)] for `segs` [(start cs, end cs)]."""
+    s = np.ascontiguousarray(segs, dtype=np.int64).reshape(-1)
+    n = lib.whisper_amd_long_plan(s.ctypes.data_as(C.POINTER(C.c_int64)), len(s) // 2, n_samples, overlap, max_chunk_samples, None, None, None, 0)
+    if n < 0:
+        raise WhisperError("GenericError", int(n))
+    first, count, packed = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int64)
+    lib.whisper_amd_long_plan(s.ctypes.data_as(C.POINTER(C.c_int64)), len(s) // 2, n_samples, overlap, max_chunk_samples,
+                              first.ctypes.data_as(C.POINTER(C.c_int32)), count.ctypes.data_as(C.POINTER(C.c_int32)),
+                              packed.ctypes.data_as(C.POINTER(C.c_int64)), n)
+    return [(int(first[i]), int(count[i]), int(packed[i])) for i in range(n)]
