@@ -700,6 +700,59 @@ WHISPER_API int     whisper_amd_long_pack(struct whisper_state * state, const fl
 WHISPER_API int     whisper_amd_long_tile(void);
 WHISPER_API struct whisper_state * whisper_amd_context_state(struct whisper_context * ctx);
 
+/* Forced alignment (wa_align.cpp): the audio and the text are both known; when was each token said, and how well does the
+ * model agree with it?  One teacher-forced decoder pass over [sot, lang, not, tokens..., eot] - the pass whisper_full's DTW runs over its own
+ * result - whose logits rows stay on the device: k_align_score (wa_align.hip) turns each row into one record there.
+ * The scores are taken on the RAW logits of the model.  No suppression list, no blank or non-speech rule and no timestamp rule applies: this
+ * is the model's distribution over the vocabulary, not the choice of whisper_full's sampler (whose plog / p follow its own rules and its own
+ * F32 summation order).  For a row with logits x and target t (csrc/wa_align.h states it once more, with the host function):
+ *   mx = max x, best_id = the lowest index that attains it; lse = mx + log(sum_i exp((double) x_i - (double) mx)), sum and exp in F64;
+ *   plog = (float) (x_t - lse), p = (float) exp(x_t - lse); best_plog / best_p the same for best_id;
+ *   rank = #{ i : x_i > x_t or (x_i == x_t and i < t) } - 0 where the target is the model's own choice;
+ *   a -inf logit adds 0 to the sum; a -inf target gives plog = -inf, p = 0.
+ *   (Evaluated as (x_t - mx) - log1p(sum over i != best_id): the same value, precise also where the model is sure and plog approaches -0.)
+ * Layouts are ABI: whisper_amd_align_score 24 bytes (plog 0, p 4, best_id 8, best_plog 12, rank 16, best_p 20), whisper_amd_align_token
+ * 32 bytes (id 0, plog 4, p 8, best_id 12, best_plog 16, rank 20, t_dtw 24).
+ * whisper_amd_align: one window.  Log-mel of `samples` (a host or a device pointer, detected as whisper_pcm_to_mel does), the encoder at
+ *   params.offset_ms / 10, the sequence [sot, lang, not, tokens..., eot] - lang on multilingual models only: params.language, detected when
+ *   that is null, "" or "auto" -, one decoder pass, the scores with target = the next token, and - on a context created with
+ *   dtw_token_timestamps and a preset - the DTW alignment over the window's frames (to the end of the audio or of params.duration_ms, at
+ *   most 30 s).  out[i], i < n_tokens, belongs to tokens[i]; out[n_tokens] is the row of the closing eot (id = eot, t_dtw = -1).  t_dtw is
+ *   placed as whisper_full places it: the first time index of the token's run on the path x 2 + offset, in centiseconds; -1 for every token
+ *   on a context without alignment heads, and for the tokens that the path does not reach.
+ *   Returns 0, or - with an error log line, nothing written and the state as usable as before -
+ *     WHISPER_AMD_ALIGN_BAD_TOKEN   a token < 0 or >= eot (text tokens only: no timestamps, no specials)
+ *     WHISPER_AMD_ALIGN_NO_TOKENS   n_tokens <= 0, or a null pointer among the arguments
+ *     WHISPER_AMD_ALIGN_TOO_LONG    the sequence has more rows than the state's decoder holds (the text context; walk windows with offset_ms)
+ *     WHISPER_AMD_ALIGN_FLASH_ATTN  the context was created with flash_attn: only the exact path is scored
+ *     WHISPER_AMD_ALIGN_TOO_SHORT   less than 100 ms of audio after the offset
+ *   or whisper_full's codes for the stages they share: -2 mel, -3 language detection, -6 encode, -8 decode (and the scores' launch or copy).
+ *   The state's results (segments, tokens) are not touched; its self-attention cells are cleared, so that whisper_full afterwards behaves as
+ *   on a fresh state.  The pass's logits never reach the host and it does not write whisper_get_logits_from_state (language detection, where
+ *   the call has to do it, is whisper_lang_auto_detect_with_state at offset 0 as in whisper_full: one single-token pass that does).
+ * whisper_amd_align_score: the scores alone, for a caller's own logits - host [n_rows][n_vocab] F32, target[n_rows] in [0, n_vocab).
+ *   where = 0: the host function.  where = 1: uploaded into the state's buffer and scored by the launcher of the product path, on the state's
+ *   stream.  The two agree in best_id and rank; plog / p may differ in the last bit of an F64 exp.  0, WHISPER_AMD_ALIGN_NO_TOKENS for refused
+ *   arguments (nothing written), -8 for a HIP failure.
+ * whisper_amd_align_stats: out = { whisper_amd_align calls that returned 0, logits rows scored by the kernel, bytes of logits that stayed on
+ *   the device (rows x n_vocab x 4, whisper_amd_align's rows only) } since the state was created.
+ * whisper_amd_align_timings: out = { device time in us of the last k_align_score launch on this state, between two HIP events; wall time in
+ *   us of the last whisper_amd_align call } (tools/align_probe.py). */
+#define WHISPER_AMD_ALIGN_BAD_TOKEN  (-21)
+#define WHISPER_AMD_ALIGN_NO_TOKENS  (-22)
+#define WHISPER_AMD_ALIGN_TOO_LONG   (-23)
+#define WHISPER_AMD_ALIGN_FLASH_ATTN (-24)
+#define WHISPER_AMD_ALIGN_TOO_SHORT  (-25)
+struct whisper_amd_align_score { float plog; float p; int32_t best_id; float best_plog; int32_t rank; float best_p; };
+struct whisper_amd_align_token { whisper_token id; float plog; float p; whisper_token best_id; float best_plog; int32_t rank; int64_t t_dtw; };
+WHISPER_API int  whisper_amd_align(struct whisper_context * ctx, struct whisper_state * state, struct whisper_full_params params,
+                                   const float * samples, int n_samples, const whisper_token * tokens, int n_tokens,
+                                   struct whisper_amd_align_token * out);
+WHISPER_API int  whisper_amd_align_score(struct whisper_state * state, const float * logits, int n_rows, int n_vocab, const int32_t * target,
+                                         int where, struct whisper_amd_align_score * out);
+WHISPER_API void whisper_amd_align_stats(struct whisper_state * state, long out[3]);
+WHISPER_API void whisper_amd_align_timings(struct whisper_state * state, int64_t out[2]);
+
 #ifdef __cplusplus
 }
 #endif

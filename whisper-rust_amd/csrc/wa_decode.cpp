@@ -170,9 +170,12 @@ static void decode_launch(whisper_context & ctx, whisper_state & st, int n_token
     }
     // final LayerNorm + logits = token_embedding . x, for the flagged rows only (the reference computes all rows and
     // copies out the flagged ones, whisper.cpp:2835, 2965-2971)
-    if (n_rows) {
-        wa_epi e; e.out = st.d_logits; e.ldo = n_vocab;
-        wa_launch_ln_gemv_exact(s, WA_EPI_F32, st.d_dx, d, st.d_rows, m.d_ln.w, m.d_ln.b, hp.eps, m.d_te, d, n_rows, n_vocab, d, e);
+    // The product takes up to WA_MAX_DECODERS rows; the alignment pass (st.align_pass: every text row flagged, output in d_align_logits) runs
+    // it once per block of as many rows.
+    float * const logits_out = st.align_pass ? st.d_align_logits : st.d_logits;
+    for (int r0 = 0; r0 < n_rows; r0 += WA_MAX_DECODERS) {
+        wa_epi e; e.out = logits_out + (size_t) r0 * n_vocab; e.ldo = n_vocab;
+        wa_launch_ln_gemv_exact(s, WA_EPI_F32, st.d_dx, d, st.d_rows + r0, m.d_ln.w, m.d_ln.b, hp.eps, m.d_te, d, std::min(WA_MAX_DECODERS, n_rows - r0), n_vocab, d, e);
     }
 }
 
@@ -257,15 +260,20 @@ static void decode_launch_quant(whisper_context & ctx, whisper_state & st, int n
             qlin(WA_EPI_RESID, st.d_q32b, 4 * d, L.fc2, n_tokens, e2);
         }
     }
-    if (n_rows) {       // final LayerNorm of the flagged rows (packed), then the logits product over the quantised token embedding
+    // final LayerNorm of the flagged rows (packed), then the logits product over the quantised token embedding: up to WA_MAX_DECODERS rows at a
+    // time (the alignment pass, st.align_pass, flags every text row and has them in d_align_logits: one block of rows after the other through
+    // the same operand rows, in stream order)
+    float * const logits_out = st.align_pass ? st.d_align_logits : st.d_logits;
+    for (int r0 = 0; r0 < n_rows; r0 += WA_MAX_DECODERS) {
+        const int nr = std::min(WA_MAX_DECODERS, n_rows - r0);
         const int nb = d >> 5;
-        for (int i = 0; i < n_rows; ++i)
-            if (QK) wa_launch_layernorm_exact(s, st.d_dx + (size_t) h_rows[i] * d, d, 1, d, m.d_ln.w, m.d_ln.b, hp.eps, nullptr, 0, st.d_q32a + (size_t) i * d, d);
-            else wa_launch_layernorm_exact(s, st.d_dx + (size_t) h_rows[i] * d, d, 1, d, m.d_ln.w, m.d_ln.b, hp.eps, nullptr, 0, nullptr, 0,
+        for (int i = 0; i < nr; ++i)
+            if (QK) wa_launch_layernorm_exact(s, st.d_dx + (size_t) h_rows[r0 + i] * d, d, 1, d, m.d_ln.w, m.d_ln.b, hp.eps, nullptr, 0, st.d_q32a + (size_t) i * d, d);
+            else wa_launch_layernorm_exact(s, st.d_dx + (size_t) h_rows[r0 + i] * d, d, 1, d, m.d_ln.w, m.d_ln.b, hp.eps, nullptr, 0, nullptr, 0,
                                       st.d_q8 + (size_t) i * d, st.d_q8d + (size_t) i * nb, st.d_q8s ? st.d_q8s + (size_t) i * nb : nullptr);
-        if (QK) quant(st.d_q32a, d, n_rows, d);
-        wa_epi e; e.out = st.d_logits; e.ldo = n_vocab;
-        qmul(WA_EPI_F32, m.te_q, n_rows, e);
+        if (QK) quant(st.d_q32a, d, nr, d);
+        wa_epi e; e.out = logits_out + (size_t) r0 * n_vocab; e.ldo = n_vocab;
+        qmul(WA_EPI_F32, m.te_q, nr, e);
     }
 }
 
@@ -952,14 +960,16 @@ bool wa_decode(whisper_context & ctx, whisper_state & st, const wa_batch & batch
     {
         int n_rows_req = 0;
         for (int i = 0; i < n_tokens; ++i) n_rows_req += batch.logits[i] ? 1 : 0;
-        if (n_rows_req > WA_MAX_DECODERS) { WA_ERROR("%s: too many logits rows requested (%d)\n", __func__, n_rows_req); return false; }
+        if (n_rows_req > WA_MAX_DECODERS && !st.align_pass) { WA_ERROR("%s: too many logits rows requested (%d)\n", __func__, n_rows_req); return false; }
     }
     auto & kv = st.kv_self;
     if (!wa_kv_find_slot(kv, batch)) return false;
     kv.n = std::min(kv.size, (uint32_t) std::max(1, wa_kv_cell_max(kv)));     // padding = 1 (whisper.cpp:2892-2893)
     const int n_kv = kv.n, kv_head = kv.head;
 
-    st.logits.resize((size_t) n_tokens * n_vocab);
+    // (the alignment pass, st.align_pass: its rows stay on the device, in d_align_logits, and `logits` keeps what the last other pass left)
+    if (st.align_pass && (m.n_loaded == 0 || !st.d_align_logits)) return false;
+    if (!st.align_pass) st.logits.resize((size_t) n_tokens * n_vocab);
     if (m.n_loaded == 0) {          // header-only test model
         std::fill(st.logits.begin(), st.logits.end(), 0.0f);
         return !(abort_cb && abort_cb(abort_data));
@@ -996,7 +1006,7 @@ bool wa_decode(whisper_context & ctx, whisper_state & st, const wa_batch & batch
     }
     // (take_pass: a form paused after a time-out counts this pass down, which the launch sequence serves)
     if (!done && steady && st.mega_form.take_pass() && device_free) done = mega_step(ctx, st, h_tok[0], h_pos[0], n_kv, kv_head) == 1;
-    if (!done && !steady && n_tokens <= WA_ROWS_MAX && n_rows >= 1 && !save_aheads && st.rows_form.enabled() && n_kv <= WA_ROWS_MAXKV && device_free) {
+    if (!done && !steady && !st.align_pass && n_tokens <= WA_ROWS_MAX && n_rows >= 1 && !save_aheads && st.rows_form.enabled() && n_kv <= WA_ROWS_MAXKV && device_free) {
         // one token per live decoder (beam search, best_of, the bench's small batches): all rows in ONE launch (wa_rows.hip)
         if (need_mask) (void) hipMemcpyAsync(st.d_mask, h_mask, (size_t) n_tokens * n_kv, hipMemcpyHostToDevice, s);
         wa_rows_row rr[WA_MAX_DECODERS];
@@ -1041,11 +1051,11 @@ bool wa_decode(whisper_context & ctx, whisper_state & st, const wa_batch & batch
     } else {
         decode_launch(ctx, st, n_tokens, n_kv, kv_head, need_mask ? st.d_mask : nullptr, n_rows, save_aheads);
     }
-    if (n_rows) (void) hipMemcpyAsync(st.h_logits_pinned, st.d_logits, (size_t) n_rows * n_vocab * sizeof(float), hipMemcpyDeviceToHost, s);
+    if (n_rows && !st.align_pass) (void) hipMemcpyAsync(st.h_logits_pinned, st.d_logits, (size_t) n_rows * n_vocab * sizeof(float), hipMemcpyDeviceToHost, s);
     if (!WA_HIP_OK(hipStreamSynchronize(s))) return false;
     }
     st.staged_n = 0;
-    if (!from_batcher) {     // (the batcher delivered its row straight into st.logits)
+    if (!from_batcher && !st.align_pass) {     // (the batcher delivered its row straight into st.logits)
         if (st.defer_rows && n_rows > 1) { st.staged_n = n_rows; st.staged_of.assign(h_rows, h_rows + n_rows); }      // the caller's per-decoder threads fetch them
         else for (int r = 0; r < n_rows; ++r)
             memcpy(st.logits.data() + (size_t) h_rows[r] * n_vocab, st.h_logits_pinned + (size_t) r * n_vocab, n_vocab * sizeof(float));

@@ -64,12 +64,81 @@ static int dtw_device_path(whisper_state & st, const float * d_x, const long lon
     return (int) path.size();
 }
 
+int wa_dtw_pass(whisper_context * ctx, whisper_state * st, const std::vector<whisper_token> & tokens, int sot_len_, int n_frames, int medfilt_width,
+                bool score_rows, wa_dtw_path_t & path, int64_t & t_pass_end) {
+    const auto & hp = ctx->model.hp;
+    const int n_audio_ctx = st->exp_n_audio_ctx > 0 ? st->exp_n_audio_ctx : hp.n_audio_ctx;
+    const int H = hp.n_text_head;
+    const bool want_dtw = !(st->aheads_n <= 0 || n_frames > 2 * n_audio_ctx || medfilt_width % 2 == 0);
+    if (!want_dtw && !score_rows) return -1;
+    if (!WA_HIP_OK(hipSetDevice(ctx->device))) return -1;
+    const size_t sot_len = (size_t) sot_len_;
+    const int n_tokens = (int) tokens.size();
+    if (n_tokens > st->dec_mpad) { WA_WARN("%s: too many tokens for DTW (%d)\n", __func__, n_tokens); return -1; }
+
+    // capture buffer: [layer slot][token][head][n_audio_ctx] F32 for the layers that own alignment heads; sized for a multiple of 64 tokens
+    // so that a longer window seldom replaces it
+    std::vector<int> slot(hp.n_text_layer, -1);
+    int n_slots = 0;
+    if (want_dtw) for (int il = 0; il < hp.n_text_layer; ++il) if (!st->aheads[il].empty()) slot[il] = n_slots++;
+    const size_t per_layer = (size_t) n_tokens * H * n_audio_ctx;
+    if (want_dtw && !dtw_reserve_capture(*st, (size_t) std::min(st->dec_mpad, wa_pad(n_tokens, 64)) * H * n_audio_ctx * n_slots)) return -1;
+
+    // the decoder pass (whisper.cpp:8823-8829)
+    wa_kv_clear(st->kv_self);
+    auto & b = st->batch;
+    b.n_tokens = n_tokens;
+    b.token.assign(tokens.begin(), tokens.end());
+    b.pos.resize(n_tokens); b.seq_id.assign(n_tokens, 0); b.logits.assign(n_tokens, 0);
+    for (int i = 0; i < n_tokens; ++i) b.pos[i] = i;
+    if (score_rows) for (int i = sot_len_; i < n_tokens - 1; ++i) b.logits[i] = 1;      // row i predicts token i + 1
+    else b.logits[n_tokens - 1] = 1;
+    wa_kv_seq_rm(st->kv_self, 0, 0, -1);
+    // wa_decode indexes the capture buffer by layer; give it a slot table through aheads_slot
+    if (want_dtw) st->aheads_slot = slot;
+    const bool ok = wa_decode(*ctx, *st, b, want_dtw, nullptr, nullptr);
+    if (!ok) { WA_ERROR("%s: decoder pass failed\n", __func__); return -1; }
+    t_pass_end = wa_time_us();
+    if (!want_dtw) return 0;
+
+    // the alignment heads in the capture buffer, head k at (slot, head): x(k, t, j) = d_aheads_qk[head_off[k] + t * H * n_audio_ctx + j]
+    const int n_heads = st->aheads_n;
+    const int n_audio_tokens = n_frames / 2;
+    if (n_audio_tokens <= 0) return 0;
+    std::vector<long long> head_off;
+    for (int il = 0; il < hp.n_text_layer; ++il)
+        for (int h : st->aheads[il]) head_off.push_back((long long) ((size_t) slot[il] * per_layer + (size_t) h * n_audio_ctx));
+    const long long tok_stride = (long long) H * n_audio_ctx;
+    if (medfilt_width >= n_audio_tokens) { WA_WARN("%s: too few audio frames for the median filter\n", __func__); return 0; }
+    if (!wa_dtw_args_ok(n_heads, n_tokens, n_audio_ctx, n_audio_tokens, (int) sot_len, medfilt_width)) return 0;      // (N <= 0)
+
+    bool served = false;
+    if (!st->dtw_host && dtw_device_takes(*st, n_tokens, n_audio_tokens, (int) sot_len, medfilt_width)) {
+        served = dtw_device_path(*st, st->d_aheads_qk, head_off.data(), tok_stride, n_heads, n_tokens, n_audio_tokens, (int) sot_len, path) >= 0;
+        if (served) st->n_dtw_device++; else { st->n_dtw_fallback++; WA_WARN("%s: the device path failed, taking the host path\n", __func__); }
+    }
+    if (!served) {
+        // copy back the alignment heads only, the frames in use: cube[k][t][j]
+        const int M_ = n_audio_tokens;
+        std::vector<float> cube((size_t) n_heads * n_tokens * M_);
+        std::vector<long long> off_h(n_heads);
+        for (int k = 0; k < n_heads; ++k) {
+            off_h[k] = (long long) k * n_tokens * M_;
+            if (!WA_HIP_OK(hipMemcpy2D(cube.data() + off_h[k], (size_t) M_ * sizeof(float), st->d_aheads_qk + head_off[k], (size_t) tok_stride * sizeof(float),
+                                       (size_t) M_ * sizeof(float), n_tokens, hipMemcpyDeviceToHost))) return 0;
+        }
+        const wa_dtw_view v = { cube.data(), off_h.data(), n_heads, (long long) M_, n_tokens, M_ };
+        if (wa_dtw_host_path(v, M_, (int) sot_len, medfilt_width, path) < 0) return 0;
+        st->n_dtw_host++;
+    }
+    return 1;
+}
+
 void wa_dtw_timestamps(whisper_context * ctx, whisper_state * st, const whisper_full_params & params, int i_segment, size_t n_segments,
                        int seek, int n_frames, int medfilt_width) {
     const auto & hp = ctx->model.hp;
     const auto & vocab = ctx->vocab;
     const int n_audio_ctx = st->exp_n_audio_ctx > 0 ? st->exp_n_audio_ctx : hp.n_audio_ctx;
-    const int H = hp.n_text_head;
     if (st->aheads_n <= 0 || n_frames > 2 * n_audio_ctx || medfilt_width % 2 == 0) return;
     if (!WA_HIP_OK(hipSetDevice(ctx->device))) return;
 
@@ -85,63 +154,10 @@ void wa_dtw_timestamps(whisper_context * ctx, whisper_state * st, const whisper_
     for (size_t i = i_segment; i < i_segment + n_segments; ++i)
         for (const auto & t : st->result_all[i].tokens) if (t.id < vocab.token_eot) tokens.push_back(t.id);
     tokens.push_back(vocab.token_eot);
-    const int n_tokens = (int) tokens.size();
-    if (n_tokens > st->dec_mpad) { WA_WARN("%s: too many tokens for DTW (%d)\n", __func__, n_tokens); return; }
-
-    // capture buffer: [layer slot][token][head][n_audio_ctx] F32 for the layers that own alignment heads; sized for a multiple of 64 tokens
-    // so that a longer window seldom replaces it
-    std::vector<int> slot(hp.n_text_layer, -1);
-    int n_slots = 0;
-    for (int il = 0; il < hp.n_text_layer; ++il) if (!st->aheads[il].empty()) slot[il] = n_slots++;
-    const size_t per_layer = (size_t) n_tokens * H * n_audio_ctx;
-    if (!dtw_reserve_capture(*st, (size_t) std::min(st->dec_mpad, wa_pad(n_tokens, 64)) * H * n_audio_ctx * n_slots)) return;
-
-    // the decoder pass (whisper.cpp:8823-8829)
-    wa_kv_clear(st->kv_self);
-    auto & b = st->batch;
-    b.n_tokens = n_tokens;
-    b.token.assign(tokens.begin(), tokens.end());
-    b.pos.resize(n_tokens); b.seq_id.assign(n_tokens, 0); b.logits.assign(n_tokens, 0);
-    for (int i = 0; i < n_tokens; ++i) b.pos[i] = i;
-    b.logits[n_tokens - 1] = 1;
-    wa_kv_seq_rm(st->kv_self, 0, 0, -1);
-    // wa_decode indexes the capture buffer by layer; give it a slot table through aheads_slot
-    st->aheads_slot = slot;
-    const bool ok = wa_decode(*ctx, *st, b, true, nullptr, nullptr);
-    if (!ok) { WA_ERROR("%s: decoder pass failed\n", __func__); return; }
-    const int64_t t_post = wa_time_us();
-
-    // the alignment heads in the capture buffer, head k at (slot, head): x(k, t, j) = d_aheads_qk[head_off[k] + t * H * n_audio_ctx + j]
-    const int n_heads = st->aheads_n;
-    const int n_audio_tokens = n_frames / 2;
-    if (n_audio_tokens <= 0) return;
-    std::vector<long long> head_off;
-    for (int il = 0; il < hp.n_text_layer; ++il)
-        for (int h : st->aheads[il]) head_off.push_back((long long) ((size_t) slot[il] * per_layer + (size_t) h * n_audio_ctx));
-    const long long tok_stride = (long long) H * n_audio_ctx;
-    if (medfilt_width >= n_audio_tokens) { WA_WARN("%s: too few audio frames for the median filter\n", __func__); return; }
-    if (!wa_dtw_args_ok(n_heads, n_tokens, n_audio_ctx, n_audio_tokens, (int) sot_len, medfilt_width)) return;      // (N <= 0)
 
     wa_dtw_path_t path;                                   // (token index, time index)
-    bool served = false;
-    if (!st->dtw_host && dtw_device_takes(*st, n_tokens, n_audio_tokens, (int) sot_len, medfilt_width)) {
-        served = dtw_device_path(*st, st->d_aheads_qk, head_off.data(), tok_stride, n_heads, n_tokens, n_audio_tokens, (int) sot_len, path) >= 0;
-        if (served) st->n_dtw_device++; else { st->n_dtw_fallback++; WA_WARN("%s: the device path failed, taking the host path\n", __func__); }
-    }
-    if (!served) {
-        // copy back the alignment heads only, the frames in use: cube[k][t][j]
-        const int M_ = n_audio_tokens;
-        std::vector<float> cube((size_t) n_heads * n_tokens * M_);
-        std::vector<long long> off_h(n_heads);
-        for (int k = 0; k < n_heads; ++k) {
-            off_h[k] = (long long) k * n_tokens * M_;
-            if (!WA_HIP_OK(hipMemcpy2D(cube.data() + off_h[k], (size_t) M_ * sizeof(float), st->d_aheads_qk + head_off[k], (size_t) tok_stride * sizeof(float),
-                                       (size_t) M_ * sizeof(float), n_tokens, hipMemcpyDeviceToHost))) return;
-        }
-        const wa_dtw_view v = { cube.data(), off_h.data(), n_heads, (long long) M_, n_tokens, M_ };
-        if (wa_dtw_host_path(v, M_, (int) sot_len, medfilt_width, path) < 0) return;
-        st->n_dtw_host++;
-    }
+    int64_t t_post = 0;
+    if (wa_dtw_pass(ctx, st, tokens, (int) sot_len, n_frames, medfilt_width, false, path, t_post) != 1) return;
 
     // place the timestamps on the text tokens of the new segments (whisper.cpp:8894-8920)
     int32_t last_v = 0;

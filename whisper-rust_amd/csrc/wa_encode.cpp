@@ -177,6 +177,7 @@ void wa_state_release(whisper_state & st) {
     if (st.copy_stream) { (void) hipStreamDestroy(st.copy_stream); st.copy_stream = nullptr; }
     dev_free(st.d_dyn); dev_free(st.d_att_partial); dev_free(st.d_att_pleft); dev_free(st.d_im2col); dev_free(st.d_logits); dev_free(st.d_aheads_qk);
     st.aheads_qk_cap = 0; dev_free(st.d_dtw); st.d_dtw_cap = 0;
+    wa_align_free(st);
     dev_free(st.d_audio); st.d_audio_cap = 0; dev_free(st.d_audio_in); st.d_audio_in_cap = 0; st.audio_n = -1;
     if (st.h_dtw) { (void) hipHostFree(st.h_dtw); st.h_dtw = nullptr; st.h_dtw_cap = 0; }
     if (st.h_stage_i32)     { (void) hipHostFree(st.h_stage_i32);     st.h_stage_i32 = nullptr; }

@@ -373,6 +373,17 @@ struct whisper_state {
     long n_dtw_device = 0, n_dtw_host = 0, n_dtw_fallback = 0;      // calls served by the device path / by the host path / device attempts that fell back
     int64_t t_dtw_post_us = 0; long n_dtw_post = 0;         // whisper_full's DTW calls: wall time from the end of the decoder pass to t_dtw placed
 
+    // forced alignment (wa_align.cpp / wa_align.hip).  While `align_pass` is set, wa_decode takes any number of flagged rows,
+    // points the vocabulary product at d_align_logits [rows padded to 64][n_vocab] instead of d_logits, copies no logits to the host and
+    // leaves `logits` alone.  The buffers are grow-only, made by the first call that needs them and freed with the state.
+    bool align_pass = false;
+    float * d_align_logits = nullptr; size_t align_logits_cap = 0;      // floats
+    uint8_t * d_align_io = nullptr; size_t d_align_io_cap = 0;          // targets | records
+    uint8_t * h_align_io = nullptr; size_t h_align_io_cap = 0;          // pinned: targets (up) | records (down)
+    hipEvent_t ev_align[2] = { nullptr, nullptr };                      // around k_align_score (whisper_amd_align_timings)
+    long n_align_calls = 0, n_align_rows = 0; long long align_bytes_kept = 0;
+    int64_t t_align_kernel_us = 0, t_align_call_us = 0;
+
     // audio front end (wa_audio.cpp / wa_audio.hip): the 16 kHz mono F32 result of the last whisper_amd_audio_to_pcm call and the
     // staging area for input that arrives in host memory; both grow-only, freed with the state
     float * d_audio = nullptr; size_t d_audio_cap = 0;      // floats
@@ -452,6 +463,16 @@ struct wa_batch_groups {
     }
 };
 void wa_long_free(whisper_state & st);            // wa_long.cpp: what whisper_amd_full_long / whisper_amd_long_pack keep on a state
+void wa_align_free(whisper_state & st);           // wa_align.cpp: what whisper_amd_align / whisper_amd_align_score keep on a state
+// wa_dtw.cpp: the middle of the DTW token timestamps for any token sequence [sot.., not, text.., eot] with sot_len tokens in front of `not`: one
+// decoder pass over it with the alignment heads captured, then the device or the host DTW over n_frames / 2 audio positions.
+// score_rows = false (whisper_full): logits for the last row only; nothing is run where no DTW can follow.
+// score_rows = true (whisper_amd_align, which sets st->align_pass around the call): rows sot_len .. n - 2 are flagged, and the pass runs - without
+// capture - even where no DTW can follow (no alignment heads).
+// Returns 1 with `path` (token index, time index) filled, 0 when the pass ran and there is no path, -1 when the pass did not run or failed.
+// `t_pass_end` receives the time at which the decoder pass returned.
+int wa_dtw_pass(whisper_context * ctx, whisper_state * st, const std::vector<whisper_token> & tokens, int sot_len, int n_frames, int medfilt_width,
+                bool score_rows, std::vector<std::pair<int32_t, int32_t>> & path, int64_t & t_pass_end);
 bool wa_state_alloc(whisper_context & ctx, whisper_state & st);
 void wa_state_release(whisper_state & st);
 bool wa_kv_self_realloc(whisper_context & ctx, whisper_state & st, int n_cells);

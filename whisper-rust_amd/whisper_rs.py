@@ -85,6 +85,20 @@ class whisper_vad_params(C.Structure):
     ]
 
 
+class whisper_amd_align_score(C.Structure):      # 24 bytes (include/whisper_amd.h)
+    _fields_ = [("plog", C.c_float), ("p", C.c_float), ("best_id", C.c_int32), ("best_plog", C.c_float), ("rank", C.c_int32), ("best_p", C.c_float)]
+
+
+class whisper_amd_align_token(C.Structure):      # 32 bytes
+    _fields_ = [("id", C.c_int32), ("plog", C.c_float), ("p", C.c_float), ("best_id", C.c_int32), ("best_plog", C.c_float), ("rank", C.c_int32),
+                ("t_dtw", C.c_int64)]
+
+
+# whisper_amd_align's refusal codes (include/whisper_amd.h)
+ALIGN_BAD_TOKEN, ALIGN_NO_TOKENS, ALIGN_TOO_LONG, ALIGN_FLASH_ATTN, ALIGN_TOO_SHORT = -21, -22, -23, -24, -25
+ALIGN_SCORE_DTYPE = np.dtype([("plog", "<f4"), ("p", "<f4"), ("best_id", "<i4"), ("best_plog", "<f4"), ("rank", "<i4"), ("best_p", "<f4")])
+
+
 class whisper_vad_context_params(C.Structure):
     _fields_ = [("n_threads", C.c_int), ("use_gpu", C.c_bool), ("gpu_device", C.c_int)]
 
@@ -299,6 +313,11 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         proto("whisper_amd_long_tile", I)
         proto("whisper_amd_context_state", P, P)
         proto("whisper_amd_batch_stats", None, P, C.POINTER(C.c_long), C.POINTER(C.c_long))
+    if hasattr(lib, "whisper_amd_align"):
+        proto("whisper_amd_align", I, P, P, whisper_full_params, P, I, C.POINTER(C.c_int32), I, C.POINTER(whisper_amd_align_token))
+        proto("whisper_amd_align_score", I, P, C.POINTER(F), I, I, C.POINTER(C.c_int32), I, C.POINTER(whisper_amd_align_score))
+        proto("whisper_amd_align_stats", None, P, C.POINTER(C.c_long))
+        proto("whisper_amd_align_timings", None, P, C.POINTER(C.c_int64))
     _LIBS[path] = lib
     return lib
 
@@ -641,6 +660,53 @@ class WhisperState:
         """Extension: (wall time in us of full()'s DTW post-processing on this state - decoder pass done to t_dtw placed -, number of such calls)."""
         out = (C.c_int64 * 2)()
         self.lib.whisper_amd_dtw_timings(self.ptr, out)
+        return int(out[0]), int(out[1])
+
+    # -- forced alignment (whisper_amd_align*): times and log-probabilities of a known transcript --------------------------------
+    def align(self, params: "FullParams", pcm, ids: Sequence[int]) -> list[dict]:
+        """Extension (whisper_amd_align): one window of `pcm` (numpy f32 array on the host, or (device pointer, n)) against the text tokens `ids`.
+        Returns len(ids) + 1 dicts {id, plog, p, best_id, best_plog, rank, t_dtw}; the last one is the closing eot's.  Scores are the model's
+        own (raw logits, no sampler rules); t_dtw is -1 without alignment heads.  Raises WhisperError with the C code on refusal."""
+        if isinstance(pcm, tuple):
+            ptr, n = pcm
+        else:
+            self._pcm_keep = pcm = np.ascontiguousarray(pcm, dtype=np.float32)
+            ptr, n = (pcm.ctypes.data if len(pcm) else None), len(pcm)
+        n_tok = len(ids)
+        out = (whisper_amd_align_token * (n_tok + 1))()
+        r = self.lib.whisper_amd_align(self.ctx.ptr, self.ptr, params.c, C.c_void_p(ptr), n, (C.c_int32 * max(n_tok, 1))(*ids), n_tok, out)
+        if r != 0:
+            raise WhisperError("AlignError(%d)" % r, r)
+        return [dict(id=o.id, plog=o.plog, p=o.p, best_id=o.best_id, best_plog=o.best_plog, rank=o.rank, t_dtw=o.t_dtw) for o in out]
+
+    def align_text(self, params: "FullParams", pcm, text: str) -> list[dict]:
+        """align() on the tokens whisper_tokenize gives for `text`"""
+        return self.align(params, pcm, self.ctx.tokenize(text))
+
+    def align_score(self, logits: np.ndarray, target: Sequence[int], where: int = 1) -> np.ndarray:
+        """Extension (whisper_amd_align_score): the scores alone over host logits [n_rows][n_vocab].  where = 0: the host function, 1: the kernel on
+        this state's stream.  Returns a structured array with fields plog, p, best_id, best_plog, rank, best_p."""
+        logits = np.ascontiguousarray(logits, dtype=np.float32)
+        n_rows, n_vocab = logits.shape
+        tgt = np.ascontiguousarray(target, dtype=np.int32)
+        assert len(tgt) == n_rows
+        out = (whisper_amd_align_score * n_rows)()
+        r = self.lib.whisper_amd_align_score(self.ptr, logits.ctypes.data_as(C.POINTER(C.c_float)), n_rows, n_vocab, tgt.ctypes.data_as(C.POINTER(C.c_int32)),
+                                             where, out)
+        if r != 0:
+            raise WhisperError("AlignError(%d)" % r, r)
+        return np.frombuffer(out, dtype=ALIGN_SCORE_DTYPE).copy()
+
+    def align_stats(self) -> tuple:
+        """Extension: (align() calls that succeeded, logits rows scored on the device, bytes of logits that stayed on the device) since the state was created."""
+        out = (C.c_long * 3)()
+        self.lib.whisper_amd_align_stats(self.ptr, out)
+        return int(out[0]), int(out[1]), int(out[2])
+
+    def align_timings(self) -> tuple:
+        """Extension: (device time in us of the last score kernel launch between two HIP events, wall time in us of the last align() call)."""
+        out = (C.c_int64 * 2)()
+        self.lib.whisper_amd_align_timings(self.ptr, out)
         return int(out[0]), int(out[1])
 
     # -- audio front end (whisper_amd_audio_*): int16 / F32, mono / stereo, 8 .. 192 kHz -> 16 kHz mono F32 on the device -------
