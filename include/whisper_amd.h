@@ -753,6 +753,84 @@ WHISPER_API int  whisper_amd_align_score(struct whisper_state * state, const flo
 WHISPER_API void whisper_amd_align_stats(struct whisper_state * state, long out[3]);
 WHISPER_API void whisper_amd_align_timings(struct whisper_state * state, int64_t out[2]);
 
+/* Live streaming sessions (wa_stream.cpp): audio transcribed while it arrives, in the sliding windows of the reference's
+ * examples/stream/stream.cpp (its step mode).  A session owns a state, a 16 kHz ring in device memory and the resampler's carry; the caller
+ * pushes packets of any size in the session's rate, channel count and format (what whisper_amd_audio_to_pcm takes) and runs the windows that
+ * became due.  Every struct travels by pointer.  One thread at a time per session.  No exception crosses the boundary.
+ * Sizes: keep_ms = min(keep_ms, step_ms), length_ms = max(length_ms, step_ms); n_step, n_len, n_keep = (int) ((1e-3 ms) * 16000) samples;
+ *   n_new_line = max(1, length_ms / step_ms - 1).
+ * Window k consumes exactly n_step new samples: take = min(old, max(0, n_keep + n_len - n_step)); the window is the last `take` samples of the
+ *   previous window followed by the new ones; old becomes the window's length.  After the window's whisper_full the iteration count goes up by
+ *   one; when it is a multiple of n_new_line the line is COMMITTED: old becomes the window's last n_keep samples and, with carry_prompt, the
+ *   prompt of the following windows becomes every token id of every segment of this window's result (until the next commit it stays what it
+ *   was).  Without drops window k is the range [e - len, e) of the session's 16 kHz sample axis, e = (k + 1) n_step, len <= n_keep + n_len.
+ *   stream.cpp's VAD mode (step_ms <= 0, vad_simple) is not offered.
+ * The 16 kHz axis of a session is whisper_amd_audio_to_pcm's of the whole input, bit for bit, however the input is cut into packets: sample n
+ *   becomes final - is written to the ring - with the packet that brings the last frame its filter reads (floor(n M / L) + K/2), and
+ *   whisper_amd_stream_flush releases the rest, the frames behind the end of input read as zero.
+ * whisper_amd_stream_open: refused (NULL, an error log line, nothing made) for null arguments, a rate, channel count or format that
+ *   whisper_amd_audio_to_pcm refuses, step_ms <= 0, and keep_ms + length_ms > 30000 after the clamps.  A flash_attn context is served.  The
+ *   ring holds n_keep + n_len + backlog samples, backlog = backlog_ms x 16 (at least 2 n_step + 1).  WHISPER_AMD_STREAM_HOST=1 in the
+ *   environment when the session opens keeps ring and carry on the host and serves every feed and gather by the host restatement
+ *   (csrc/wa_stream.h); a session whose HIP path fails moves there for good (logged; whisper_amd_stream_info counts the feeds each way).
+ * whisper_amd_stream_feed: `data` is a host or a device pointer (detected as whisper_pcm_to_mel does) to n_frames frames.  One kernel launch on
+ *   the state's stream; host input may be released on return, device input stays stream-ordered.  Returns the number of windows now due, or
+ *   WHISPER_AMD_STREAM_FULL with NOTHING changed when the packet's samples do not fit the backlog beside those still unconsumed (drop_late = 1:
+ *   the unconsumed samples are discarded and counted first, as a late step would; FULL only for a packet larger than the backlog itself),
+ *   WHISPER_AMD_STREAM_ENDED after a flush, WHISPER_AMD_STREAM_BAD_ARGS for null or negative arguments.
+ * whisper_amd_stream_flush: the end of input.  Releases the filter's tail; what is left behind the last whole step becomes one last, shorter
+ *   window.  Returns the windows due.  Feeds are refused until whisper_amd_stream_reset.
+ * whisper_amd_stream_pending: the windows due.
+ * whisper_amd_stream_step: runs ONE due window: one gather launch into the state's PCM buffer, then whisper_full_with_state on it with *params
+ *   as the caller gave them, but for prompt_tokens / prompt_n_tokens, which are the session's when carry_prompt is set.  stream.cpp's own
+ *   settings are the recommended ones: single_segment = true, no_timestamps = true, an audio_ctx that fits the window.  The result is, bit for
+ *   bit, what whisper_full_with_state gives on that state for those samples and that prompt; read it with whisper_full_*_from_state on
+ *   whisper_amd_stream_state.  Returns 1, 0 when no window is due, whisper_full's negative code when it fails (the window's audio counts as
+ *   consumed), or a WHISPER_AMD_STREAM_* code.  drop_late = 1 is stream.cpp's rule: when more than 2 n_step new samples are pending at a step,
+ *   all of them are discarded and counted and NO window runs (0); the next window is then the old tail followed by fresh audio.
+ * whisper_amd_stream_step_many: one due window of every session of `ss` that has one.  All sessions belong to one context
+ *   (WHISPER_AMD_STREAM_MIXED otherwise, and for n > 64).  Groups of up to 8: ONE gather launch for the group, then its members run as
+ *   whisper_amd_full_batch runs its chunks - a host thread, state and stream per member, single-token steps in lock step - each with its own
+ *   params copy.  Callbacks follow whisper_amd_full_long's rule: new_segment and progress callbacks nulled, print_* off; encoder_begin, abort
+ *   and logits_filter callbacks stay set and are called concurrently.  Every session's result is the one whisper_amd_stream_step gives it
+ *   alone.  Returns the number of windows that ran, or the first failure's code.  whisper_amd_batch_stats then describes the call's groups.
+ * whisper_amd_stream_info: out = { windows run, the last window's start on the absolute 16 kHz axis, its length, its take, whether it committed
+ *   (0 / 1), the prompt tokens it ran with, samples dropped, windows due, feeds served by the kernels, feeds served by the host restatement }.
+ * whisper_amd_stream_window_copy / _prompt_copy: the last window's PCM / the prompt it ran with: copies up to `cap`, returns the full count.
+ * whisper_amd_stream_reset: forget everything fed; the next window equals a fresh session's first.
+ * whisper_amd_stream_tile: outputs per workgroup of the two kernels (tests put packet and window sizes on either side of it). */
+#define WHISPER_AMD_STREAM_BAD_ARGS (-31)
+#define WHISPER_AMD_STREAM_FULL     (-32)
+#define WHISPER_AMD_STREAM_ENDED    (-33)
+#define WHISPER_AMD_STREAM_MIXED    (-34)
+#define WHISPER_AMD_STREAM_FAILED   (-35)
+struct whisper_amd_stream;
+struct whisper_amd_stream_params {
+    int32_t step_ms;        /* 3000  */
+    int32_t length_ms;      /* 10000 */
+    int32_t keep_ms;        /* 200   */
+    int32_t sample_rate;    /* 16000 */
+    int32_t channels;       /* 1     */
+    int32_t format;         /* WHISPER_AMD_PCM_F32 */
+    int32_t backlog_ms;     /* 30000: unconsumed audio the ring holds beside one window */
+    int32_t carry_prompt;   /* 1: stream.cpp without --no-context */
+    int32_t drop_late;      /* 0 */
+};
+WHISPER_API void    whisper_amd_stream_default_params(struct whisper_amd_stream_params * p);
+WHISPER_API struct whisper_amd_stream * whisper_amd_stream_open(struct whisper_context * ctx, const struct whisper_amd_stream_params * p);
+WHISPER_API void    whisper_amd_stream_close(struct whisper_amd_stream * s);
+WHISPER_API int     whisper_amd_stream_feed(struct whisper_amd_stream * s, const void * data, int64_t n_frames);
+WHISPER_API int     whisper_amd_stream_flush(struct whisper_amd_stream * s);
+WHISPER_API int     whisper_amd_stream_pending(struct whisper_amd_stream * s);
+WHISPER_API int     whisper_amd_stream_step(struct whisper_amd_stream * s, const struct whisper_full_params * params);
+WHISPER_API int     whisper_amd_stream_step_many(struct whisper_amd_stream ** ss, int n, const struct whisper_full_params * params);
+WHISPER_API struct whisper_state * whisper_amd_stream_state(struct whisper_amd_stream * s);
+WHISPER_API int     whisper_amd_stream_info(struct whisper_amd_stream * s, int64_t out[10]);
+WHISPER_API int64_t whisper_amd_stream_window_copy(struct whisper_amd_stream * s, float * dst, int64_t cap);
+WHISPER_API int     whisper_amd_stream_prompt_copy(struct whisper_amd_stream * s, whisper_token * dst, int cap);
+WHISPER_API void    whisper_amd_stream_reset(struct whisper_amd_stream * s);
+WHISPER_API int     whisper_amd_stream_tile(void);
+
 #ifdef __cplusplus
 }
 #endif

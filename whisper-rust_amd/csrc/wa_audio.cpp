@@ -20,7 +20,7 @@ void wa_audio_free(whisper_context & ctx) {
 }
 
 // the device copy of a rate's table: built and uploaded by the first call at that rate on this context, kept until whisper_free
-static const float * audio_taps_device(whisper_context & ctx, const wa_audio_plan & p) {
+const float * wa_audio_taps_device(whisper_context & ctx, const wa_audio_plan & p) {
     std::lock_guard<std::mutex> lock(ctx.audio_taps_m);
     auto it = ctx.audio_taps.find(p.rate);
     if (it != ctx.audio_taps.end()) return it->second;
@@ -37,7 +37,7 @@ static const float * audio_taps_device(whisper_context & ctx, const wa_audio_pla
 static bool audio_device_path(whisper_context & ctx, whisper_state & st, const void * data, bool on_device, int64_t n_frames, int channels, int format,
                               const wa_audio_plan & p, int64_t n_out) {
     const float * d_taps = nullptr;
-    if (p.K && !(d_taps = audio_taps_device(ctx, p))) return false;
+    if (p.K && !(d_taps = wa_audio_taps_device(ctx, p))) return false;
     const void * d_in = data;
     if (!on_device) {
         const size_t bytes = (size_t) n_frames * channels * (format == WA_AUDIO_I16 ? 2 : 4);

@@ -484,4 +484,6 @@ bool wa_rows_prepare(whisper_context & ctx, whisper_state & st);      // buffers
 
 std::vector<int> wa_tokenize(const wa_vocab & vocab, const std::string & text);       // wa_api.cpp
 void wa_audio_free(whisper_context & ctx);                                                 // wa_audio.cpp: the filter tables
+struct wa_audio_plan;
+const float * wa_audio_taps_device(whisper_context & ctx, const wa_audio_plan & p);        // wa_audio.cpp: a rate's table on the device, kept until whisper_free; null: failed
 int  wa_full(whisper_context * ctx, whisper_state * st, whisper_full_params params, const float * samples, int n_samples); // wa_full.cpp

@@ -1,0 +1,415 @@
+// wa_stream.cpp - live streaming sessions: the whisper_amd_stream_* entry points of include/whisper_amd.h.
+//
+// A session owns a state, a 16 kHz ring in HBM and the resampler's carry.  A feed is one launch of k_stream_push (wa_stream.hip) on the state's
+// stream: the packet is converted and resampled behind the carry and every output that became final goes into the ring.  A step is one launch
+// of k_stream_window - the ring pieces of the window that is due, copied into the state's PCM buffer - and whisper_full_with_state on that
+// buffer, read in place, with the session's prompt.  step_many gathers the due windows of up to 8 sessions in ONE launch and runs them through
+// the lock-step groups of whisper_amd_full_batch.  The plan - which samples, how many, when a line is committed - is wa_stream.h's, a restatement
+// of the reference's examples/stream/stream.cpp; wa_stream_ref there, the same push and gather on the host, serves WHISPER_AMD_STREAM_HOST=1
+// (read when a session opens) and every session after a HIP call of its own failed: ring and carry are copied down once and stay on the host.
+#include "wa_internal.h"
+#include "wa_stream.h"
+
+#include <climits>
+#include <cstring>
+#include <thread>
+
+struct whisper_amd_stream {
+    whisper_context * ctx = nullptr;
+    whisper_state * st = nullptr;
+    whisper_amd_stream_params prm;
+    wa_stream_plan plan;
+    wa_audio_plan ap;
+    const float * d_taps = nullptr;
+    int64_t cap = 0, backlog = 0;
+    float * d_ring = nullptr;
+    float * d_carry[2] = { nullptr, nullptr };      // [cur] holds the carry, the push writes the other
+    int cur = 0;
+    uint8_t * d_zero = nullptr;                     // K/2 zero frames: the flush packet
+    int64_t T = 0, n_out = 0;                       // frames fed, outputs final
+    bool ended = false, host = false;
+    wa_stream_ref ref;                              // host == true: the carry and the ring live here
+    std::vector<whisper_token> prompt, prompt_run;  // for the following windows / the one the last window ran with
+    wa_stream_step last;                            // the last window
+    int64_t windows = 0, feeds_device = 0, feeds_host = 0;
+};
+
+static int frame_bytes(const whisper_amd_stream & S) { return S.prm.channels * (S.prm.format == WA_AUDIO_I16 ? 2 : 4); }
+
+// a HIP call of this session failed: its carry and ring move to the host for good
+static bool stream_to_host(whisper_amd_stream & S) {
+    (void) hipGetLastError();
+    if (!S.ref.init(S.prm.sample_rate, S.prm.channels, S.prm.format, S.cap)) return false;
+    if (S.d_ring) {
+        if (!WA_HIP_OK(hipStreamSynchronize(S.st->stream)) ||
+            !WA_HIP_OK(hipMemcpy(S.ref.ring.data(), S.d_ring, (size_t) S.cap * sizeof(float), hipMemcpyDeviceToHost))) return false;
+        if (!S.ref.carry.empty() &&
+            !WA_HIP_OK(hipMemcpy(S.ref.carry.data(), S.d_carry[S.cur], S.ref.carry.size() * sizeof(float), hipMemcpyDeviceToHost))) return false;
+    }
+    S.host = true;
+    return true;
+}
+
+static bool push_device(whisper_amd_stream & S, const void * data, bool on_device, int64_t n_frames, int64_t n_new) {
+    whisper_state & st = *S.st;
+    const void * d_in = data;
+    if (!on_device) {
+        const size_t bytes = (size_t) n_frames * frame_bytes(S);
+        if (!wa_dev_reserve(st.d_audio_in, st.d_audio_in_cap, bytes)) return false;
+        if (!WA_HIP_OK(hipMemcpyAsync(st.d_audio_in, data, bytes, hipMemcpyHostToDevice, st.stream))) return false;
+        d_in = st.d_audio_in;
+    }
+    if (!wa_stream_push_launch(st.stream, d_in, n_frames, S.prm.channels, S.prm.format, S.ap, S.d_taps, S.T, S.d_carry[S.cur], S.d_carry[S.cur ^ 1], S.n_out,
+                               n_new, S.d_ring, S.cap, S.plan.r_w)) return false;
+    // the caller may release a host buffer on return; device input stays stream-ordered
+    if (!on_device && !WA_HIP_OK(hipStreamSynchronize(st.stream))) return false;
+    if (S.ap.K) S.cur ^= 1;
+    return true;
+}
+
+static bool push_host(whisper_amd_stream & S, const void * data, bool on_device, int64_t n_frames, int64_t n_new) {
+    std::vector<uint8_t> in;
+    if (on_device) {
+        in.resize((size_t) n_frames * frame_bytes(S));
+        if (!WA_HIP_OK(hipStreamSynchronize(S.st->stream)) || !WA_HIP_OK(hipMemcpy(in.data(), data, in.size(), hipMemcpyDeviceToHost))) return false;
+        data = in.data();
+    }
+    std::vector<float> out((size_t) std::max<int64_t>(n_new, 1));
+    S.ref.T = S.T; S.ref.n_out = S.n_out;
+    if (S.ref.push(data, n_frames, out.data()) != n_new) return false;
+    S.ref.ring_write(S.plan.r_w, out.data(), n_new);
+    return true;
+}
+
+// a packet, or (flush) the K/2 zero frames behind the end of input
+static int stream_push(whisper_amd_stream & S, const void * data, int64_t n_frames, bool flush) {
+    const int64_t n_new = wa_stream_final(S.ap, S.T + n_frames) - S.n_out;
+    if (S.plan.pending() + n_new > S.backlog) {
+        if (!S.prm.drop_late || n_new > S.backlog) {
+            WA_ERROR("%s: refused: %lld new samples beside %lld pending do not fit a backlog of %lld\n", __func__, (long long) n_new,
+                     (long long) S.plan.pending(), (long long) S.backlog);
+            return WHISPER_AMD_STREAM_FULL;
+        }
+        WA_WARN("%s: cannot process audio fast enough, dropping %lld samples\n", __func__, (long long) S.plan.pending());
+        S.plan.drop_pending();
+    }
+    if (!WA_HIP_OK(hipSetDevice(S.ctx->device))) return WHISPER_AMD_STREAM_FAILED;
+    const bool on_device = wa_is_device_ptr(data);
+    bool served = false;
+    if (!S.host) {
+        served = push_device(S, data, on_device, n_frames, n_new);
+        if (served) S.feeds_device++;
+        else {
+            WA_WARN("%s: the device path failed, this session continues on the host\n", __func__);
+            if (!stream_to_host(S)) { WA_ERROR("%s: the ring could not be copied to the host\n", __func__); return WHISPER_AMD_STREAM_FAILED; }
+        }
+    }
+    if (!served) {
+        if (!push_host(S, data, on_device, n_frames, n_new)) { WA_ERROR("%s: the host path failed\n", __func__); return WHISPER_AMD_STREAM_FAILED; }
+        S.feeds_host++;
+    }
+    if (!flush) S.T += n_frames;
+    S.n_out += n_new;
+    S.plan.r_w += n_new;
+    return (int) S.plan.due(S.ended || flush);
+}
+
+// the window's ring pieces as a row of the gather kernel's table
+static wa_stream_window window_row(const whisper_amd_stream & S, const wa_stream_step & step) {
+    wa_stream_window w;
+    memset(&w, 0, sizeof(w));
+    w.ring = S.d_ring; w.dst = S.st->d_audio; w.len = step.len;
+    w.n_pieces = wa_stream_ring_pieces(step.r0, step.len, S.cap, w.slot, w.plen);
+    return w;
+}
+
+static bool gather_host(whisper_amd_stream & S, const wa_stream_step & step) {
+    std::vector<float> win((size_t) step.len);
+    int32_t slot[2], plen[2];
+    const int n = wa_stream_ring_pieces(step.r0, step.len, S.cap, slot, plen);
+    S.ref.gather(n, slot, plen, win.data());
+    return WA_HIP_OK(hipMemcpyAsync(S.st->d_audio, win.data(), win.size() * sizeof(float), hipMemcpyHostToDevice, S.st->stream)) &&
+           WA_HIP_OK(hipStreamSynchronize(S.st->stream));
+}
+
+// the windows of `due` (at most WA_STREAM_SESSIONS) into their states' PCM buffers: one launch for those whose ring is on the device
+static bool gather(const std::vector<whisper_amd_stream *> & due, const std::vector<wa_stream_step> & steps) {
+    wa_stream_windows tab;
+    memset(&tab, 0, sizeof(tab));
+    int n = 0;
+    whisper_amd_stream * first = nullptr;
+    for (size_t i = 0; i < due.size(); ++i) if (!due[i]->host) {
+        // pushes of device input are not synchronised: the joint launch runs on ONE member's stream
+        if (due.size() > 1 && !WA_HIP_OK(hipStreamSynchronize(due[i]->st->stream))) return false;
+        if (!first) first = due[i];
+        tab.w[n++] = window_row(*due[i], steps[i]);
+    }
+    if (n > 0) {
+        bool ok = wa_stream_window_launch(first->st->stream, tab, n);
+        // complete before a lock-step group starts: a foreign kernel beside the one-launch passes costs hand-off time-outs
+        if (ok && due.size() > 1) ok = WA_HIP_OK(hipStreamSynchronize(first->st->stream));
+        if (!ok) {
+            for (size_t i = 0; i < due.size(); ++i) if (!due[i]->host) {
+                WA_WARN("%s: the device gather failed, session %d continues on the host\n", __func__, (int) i);
+                if (!stream_to_host(*due[i])) return false;
+            }
+        }
+    }
+    for (size_t i = 0; i < due.size(); ++i) if (due[i]->host && !gather_host(*due[i], steps[i])) return false;
+    return true;
+}
+
+static whisper_full_params window_params(whisper_amd_stream & S, const whisper_full_params & params) {
+    whisper_full_params pc = params;
+    S.prompt_run = S.prompt;
+    if (S.prm.carry_prompt) { pc.prompt_tokens = S.prompt_run.empty() ? nullptr : S.prompt_run.data(); pc.prompt_n_tokens = (int) S.prompt_run.size(); }
+    else {
+        S.prompt_run.clear();
+        if (params.prompt_tokens && params.prompt_n_tokens > 0) S.prompt_run.assign(params.prompt_tokens, params.prompt_tokens + params.prompt_n_tokens);
+    }
+    return pc;
+}
+
+static void window_done(whisper_amd_stream & S, const wa_stream_step & step, int rc) {
+    S.last = step;
+    S.windows++;
+    if (rc == 0 && step.commit && S.prm.carry_prompt) {
+        S.prompt.clear();
+        for (const wa_segment & seg : S.st->result_all) for (const whisper_token_data & t : seg.tokens) S.prompt.push_back(t.id);
+    }
+}
+
+static int step_many(whisper_amd_stream ** ss, int n, const whisper_full_params & params) {
+    whisper_context * ctx = ss[0]->ctx;
+    if (!WA_HIP_OK(hipSetDevice(ctx->device))) return WHISPER_AMD_STREAM_FAILED;
+    std::vector<whisper_amd_stream *> due;
+    std::vector<wa_stream_step> steps;
+    for (int i = 0; i < n; ++i) {
+        wa_stream_step s;
+        if (wa_stream_next(ss[i]->plan, ss[i]->ended, s)) { due.push_back(ss[i]); steps.push_back(s); }
+        else if (s.dropped > 0) WA_WARN("%s: cannot process audio fast enough, dropped %lld samples\n", __func__, (long long) s.dropped);
+    }
+    int ran = 0, bad = 0;
+    long b_steps = 0, b_rows = 0, b_one = 0, b_served = 0;
+    for (size_t g0 = 0; g0 < due.size(); g0 += WA_STREAM_SESSIONS) {
+        const size_t gn = std::min<size_t>(WA_STREAM_SESSIONS, due.size() - g0);
+        const std::vector<whisper_amd_stream *> grp(due.begin() + g0, due.begin() + g0 + gn);
+        const std::vector<wa_stream_step> gst(steps.begin() + g0, steps.begin() + g0 + gn);
+        std::vector<int> rcs(gn, WHISPER_AMD_STREAM_FAILED);
+        if (gather(grp, gst)) {
+            std::vector<whisper_state *> members;
+            std::vector<whisper_full_params> pcs;
+            for (whisper_amd_stream * S : grp) {
+                members.push_back(S->st);
+                whisper_full_params pc = window_params(*S, params);        // a copy per member: the prompts differ
+                pc.print_progress = false; pc.print_realtime = false; pc.print_timestamps = false; pc.print_special = false;
+                pc.new_segment_callback = nullptr; pc.new_segment_callback_user_data = nullptr;
+                pc.progress_callback = nullptr; pc.progress_callback_user_data = nullptr;
+                pcs.push_back(pc);
+            }
+            {
+                std::vector<std::thread> workers;
+                wa_batch_groups groups(ctx, members);       // ends after the joins
+                auto run = [&](size_t i) {
+                    rcs[i] = whisper_full_with_state(ctx, members[i], pcs[i], members[i]->d_audio, gst[i].len);
+                    wa_batcher_leave(members[i]->batcher);
+                };
+                for (size_t i = 1; i < gn; ++i) workers.emplace_back(run, i);
+                run(0);
+                for (auto & w : workers) w.join();
+            }
+            b_steps += ctx->batch_steps; b_rows += ctx->batch_rows; b_one += ctx->batch_one_launch; b_served += ctx->batch_served;
+        } else WA_ERROR("%s: the window gather failed\n", __func__);
+        for (size_t i = 0; i < gn; ++i) {
+            window_done(*grp[i], gst[i], rcs[i]);
+            if (rcs[i] == 0) ++ran; else if (!bad) bad = rcs[i] < 0 ? rcs[i] : WHISPER_AMD_STREAM_FAILED;
+        }
+    }
+    if (due.size() > 1) { ctx->batch_steps = b_steps; ctx->batch_rows = b_rows; ctx->batch_one_launch = b_one; ctx->batch_served = b_served; }
+    return bad ? bad : ran;
+}
+
+static void stream_free(whisper_amd_stream * s) {
+    if (!s) return;
+    if (s->ctx) (void) hipSetDevice(s->ctx->device);
+    if (s->st && s->st->stream) (void) hipStreamSynchronize(s->st->stream);
+    if (s->d_ring) (void) hipFree(s->d_ring);
+    if (s->d_carry[0]) (void) hipFree(s->d_carry[0]);
+    if (s->d_carry[1]) (void) hipFree(s->d_carry[1]);
+    if (s->d_zero) (void) hipFree(s->d_zero);
+    if (s->st) whisper_free_state(s->st);
+    delete s;
+}
+
+static bool stream_clear(whisper_amd_stream & S) {
+    S.plan.reset();
+    S.T = 0; S.n_out = 0; S.ended = false; S.cur = 0;
+    S.prompt.clear(); S.prompt_run.clear();
+    S.last = wa_stream_step(); S.windows = 0;
+    if (S.host) { S.ref.reset(); return true; }
+    const size_t C = (size_t) std::max(wa_stream_carry_len(S.ap), 1);
+    return WA_HIP_OK(hipMemsetAsync(S.d_carry[0], 0, C * sizeof(float), S.st->stream)) &&
+           WA_HIP_OK(hipMemsetAsync(S.d_carry[1], 0, C * sizeof(float), S.st->stream));
+}
+
+extern "C" {
+
+void whisper_amd_stream_default_params(struct whisper_amd_stream_params * p) {
+    if (!p) return;
+    p->step_ms = 3000; p->length_ms = 10000; p->keep_ms = 200; p->sample_rate = WA_AUDIO_RATE; p->channels = 1; p->format = WHISPER_AMD_PCM_F32;
+    p->backlog_ms = 30000; p->carry_prompt = 1; p->drop_late = 0;
+}
+
+struct whisper_amd_stream * whisper_amd_stream_open(struct whisper_context * ctx, const struct whisper_amd_stream_params * p) {
+    if (!ctx || !p) { WA_ERROR("%s: refused: null context or params\n", __func__); return nullptr; }
+    wa_stream_sizes z;
+    if (!wa_audio_args_ok(nullptr, 0, p->channels, p->sample_rate, p->format)) {
+        WA_ERROR("%s: refused: %d channels, %d Hz, format %d\n", __func__, p->channels, p->sample_rate, p->format);
+        return nullptr;
+    }
+    if (!wa_stream_sizes_make(p->step_ms, p->length_ms, p->keep_ms, z) || p->backlog_ms < 0) {
+        WA_ERROR("%s: refused: step %d ms, length %d ms, keep %d ms, backlog %d ms (step > 0, keep + length <= %d after the clamps)\n", __func__, p->step_ms,
+                 p->length_ms, p->keep_ms, p->backlog_ms, WA_STREAM_MAX_WINDOW_MS);
+        return nullptr;
+    }
+    whisper_amd_stream * s = nullptr;
+    try {
+        s = new whisper_amd_stream;
+        s->ctx = ctx; s->prm = *p; s->plan.z = z; s->plan.drop_late = p->drop_late != 0;
+        wa_audio_plan_make(p->sample_rate, s->ap);
+        s->backlog = std::max<int64_t>((int64_t) p->backlog_ms * (WA_AUDIO_RATE / 1000), 2 * (int64_t) z.n_step + 1);   // the drop rule needs to see 2 n_step + 1
+        s->cap = (int64_t) z.n_keep + z.n_len + s->backlog;
+        const char * env = getenv("WHISPER_AMD_STREAM_HOST");
+        if (!WA_HIP_OK(hipSetDevice(ctx->device)) || !(s->st = whisper_init_state(ctx))) { stream_free(s); return nullptr; }
+        if (!wa_dev_reserve(s->st->d_audio, s->st->d_audio_cap, (size_t) std::max(z.n_keep + z.n_len, 256))) { stream_free(s); return nullptr; }
+        if (env && atoi(env) != 0) {
+            if (!stream_to_host(*s)) { stream_free(s); return nullptr; }
+            return s;
+        }
+        const size_t C = (size_t) std::max(wa_stream_carry_len(s->ap), 1), zb = (size_t) std::max(wa_stream_flush_frames(s->ap), 1) * frame_bytes(*s);
+        bool ok = (!s->ap.K || (s->d_taps = wa_audio_taps_device(*ctx, s->ap)))
+               && WA_HIP_OK(hipMalloc((void **) &s->d_ring, (size_t) s->cap * sizeof(float)))
+               && WA_HIP_OK(hipMalloc((void **) &s->d_carry[0], C * sizeof(float))) && WA_HIP_OK(hipMalloc((void **) &s->d_carry[1], C * sizeof(float)))
+               && WA_HIP_OK(hipMalloc((void **) &s->d_zero, zb)) && WA_HIP_OK(hipMemsetAsync(s->d_zero, 0, zb, s->st->stream))
+               && WA_HIP_OK(hipMemsetAsync(s->d_ring, 0, (size_t) s->cap * sizeof(float), s->st->stream)) && stream_clear(*s);
+        if (!ok) {          // no device ring: the session lives on the host from the start
+            WA_WARN("%s: the device buffers could not be made, this session runs on the host\n", __func__);
+            if (s->d_ring) { (void) hipFree(s->d_ring); s->d_ring = nullptr; }
+            if (!stream_to_host(*s)) { stream_free(s); return nullptr; }
+        }
+        return s;
+    } catch (const std::exception & e) { WA_ERROR("%s: exception: %s\n", __func__, e.what()); }
+    catch (...) { WA_ERROR("%s: unknown exception\n", __func__); }
+    stream_free(s);
+    return nullptr;
+}
+
+void whisper_amd_stream_close(struct whisper_amd_stream * s) { try { stream_free(s); } catch (...) { } }
+
+int whisper_amd_stream_feed(struct whisper_amd_stream * s, const void * data, int64_t n_frames) {
+    if (!s || n_frames < 0 || (!data && n_frames > 0) || n_frames > INT64_MAX / WA_AUDIO_MAX_L / 2) {
+        WA_ERROR("%s: refused: null session or data, or a bad frame count\n", __func__);
+        return WHISPER_AMD_STREAM_BAD_ARGS;
+    }
+    if (s->ended) { WA_ERROR("%s: refused: the session was flushed; reset it first\n", __func__); return WHISPER_AMD_STREAM_ENDED; }
+    try { return n_frames == 0 ? (int) s->plan.due(false) : stream_push(*s, data, n_frames, false); }
+    catch (const std::exception & e) { WA_ERROR("%s: exception: %s\n", __func__, e.what()); }
+    catch (...) { WA_ERROR("%s: unknown exception\n", __func__); }
+    return WHISPER_AMD_STREAM_FAILED;
+}
+
+int whisper_amd_stream_flush(struct whisper_amd_stream * s) {
+    if (!s) { WA_ERROR("%s: refused: null session\n", __func__); return WHISPER_AMD_STREAM_BAD_ARGS; }
+    try {
+        if (!s->ended) {
+            const int Z = wa_stream_flush_frames(s->ap);
+            if (Z > 0) {
+                const std::vector<uint8_t> zeros((size_t) Z * frame_bytes(*s), 0);
+                const int rc = stream_push(*s, s->host ? (const void *) zeros.data() : (const void *) s->d_zero, Z, true);
+                if (rc < 0) return rc;
+            }
+            s->ended = true;
+        }
+        return (int) s->plan.due(true);
+    } catch (const std::exception & e) { WA_ERROR("%s: exception: %s\n", __func__, e.what()); }
+    catch (...) { WA_ERROR("%s: unknown exception\n", __func__); }
+    return WHISPER_AMD_STREAM_FAILED;
+}
+
+int whisper_amd_stream_pending(struct whisper_amd_stream * s) { return s ? (int) s->plan.due(s->ended) : WHISPER_AMD_STREAM_BAD_ARGS; }
+
+int whisper_amd_stream_step_many(struct whisper_amd_stream ** ss, int n, const struct whisper_full_params * params) {
+    if (!ss || !params || n <= 0) { WA_ERROR("%s: refused: null or empty arguments\n", __func__); return WHISPER_AMD_STREAM_BAD_ARGS; }
+    if (n > 64) { WA_ERROR("%s: refused: %d sessions are more than 64\n", __func__, n); return WHISPER_AMD_STREAM_MIXED; }
+    for (int i = 0; i < n; ++i) {
+        if (!ss[i]) { WA_ERROR("%s: refused: session %d is null\n", __func__, i); return WHISPER_AMD_STREAM_BAD_ARGS; }
+        if (ss[i]->ctx != ss[0]->ctx) { WA_ERROR("%s: refused: session %d belongs to another context\n", __func__, i); return WHISPER_AMD_STREAM_MIXED; }
+        for (int j = 0; j < i; ++j) if (ss[j] == ss[i]) { WA_ERROR("%s: refused: session %d is listed twice\n", __func__, i); return WHISPER_AMD_STREAM_BAD_ARGS; }
+    }
+    try { return step_many(ss, n, *params); }
+    catch (const std::exception & e) { WA_ERROR("%s: exception: %s\n", __func__, e.what()); }
+    catch (...) { WA_ERROR("%s: unknown exception\n", __func__); }
+    return WHISPER_AMD_STREAM_FAILED;
+}
+
+int whisper_amd_stream_step(struct whisper_amd_stream * s, const struct whisper_full_params * params) {
+    if (!s || !params) { WA_ERROR("%s: refused: null session or params\n", __func__); return WHISPER_AMD_STREAM_BAD_ARGS; }
+    try {
+        if (!WA_HIP_OK(hipSetDevice(s->ctx->device))) return WHISPER_AMD_STREAM_FAILED;
+        wa_stream_step step;
+        if (!wa_stream_next(s->plan, s->ended, step)) {
+            if (step.dropped > 0) WA_WARN("%s: cannot process audio fast enough, dropped %lld samples\n", __func__, (long long) step.dropped);
+            return 0;
+        }
+        int rc = WHISPER_AMD_STREAM_FAILED;
+        if (gather({ s }, { step })) {
+            const whisper_full_params pc = window_params(*s, *params);      // the caller's, but for the prompt
+            rc = whisper_full_with_state(s->ctx, s->st, pc, s->st->d_audio, step.len);
+        } else WA_ERROR("%s: the window gather failed\n", __func__);
+        window_done(*s, step, rc);
+        return rc == 0 ? 1 : rc < 0 ? rc : WHISPER_AMD_STREAM_FAILED;
+    } catch (const std::exception & e) { WA_ERROR("%s: exception: %s\n", __func__, e.what()); }
+    catch (...) { WA_ERROR("%s: unknown exception\n", __func__); }
+    return WHISPER_AMD_STREAM_FAILED;
+}
+
+struct whisper_state * whisper_amd_stream_state(struct whisper_amd_stream * s) { return s ? s->st : nullptr; }
+
+int whisper_amd_stream_info(struct whisper_amd_stream * s, int64_t out[10]) {
+    if (!s || !out) return WHISPER_AMD_STREAM_BAD_ARGS;
+    out[0] = s->windows;
+    out[1] = s->last.ranges.empty() ? 0 : s->last.ranges[0].start;
+    out[2] = s->last.len; out[3] = s->last.take; out[4] = s->last.commit ? 1 : 0;
+    out[5] = (int64_t) s->prompt_run.size();
+    out[6] = s->plan.dropped; out[7] = s->plan.due(s->ended); out[8] = s->feeds_device; out[9] = s->feeds_host;
+    return 0;
+}
+
+int64_t whisper_amd_stream_window_copy(struct whisper_amd_stream * s, float * dst, int64_t cap) {
+    if (!s || cap < 0 || (cap > 0 && !dst)) return WHISPER_AMD_STREAM_BAD_ARGS;
+    const int64_t n = std::min<int64_t>(cap, s->last.len);
+    if (!WA_HIP_OK(hipSetDevice(s->ctx->device)) || !WA_HIP_OK(hipStreamSynchronize(s->st->stream))) return WHISPER_AMD_STREAM_FAILED;
+    if (n > 0 && !WA_HIP_OK(hipMemcpy(dst, s->st->d_audio, (size_t) n * sizeof(float), hipMemcpyDeviceToHost))) return WHISPER_AMD_STREAM_FAILED;
+    return s->last.len;
+}
+
+int whisper_amd_stream_prompt_copy(struct whisper_amd_stream * s, whisper_token * dst, int cap) {
+    if (!s || cap < 0 || (cap > 0 && !dst)) return WHISPER_AMD_STREAM_BAD_ARGS;
+    const int n = std::min(cap, (int) s->prompt_run.size());
+    if (n > 0) memcpy(dst, s->prompt_run.data(), (size_t) n * sizeof(whisper_token));
+    return (int) s->prompt_run.size();
+}
+
+void whisper_amd_stream_reset(struct whisper_amd_stream * s) {
+    if (!s) return;
+    try {
+        (void) hipSetDevice(s->ctx->device);
+        if (!stream_clear(*s)) WA_ERROR("%s: the carry could not be cleared\n", __func__);
+        s->st->result_all.clear();
+        s->st->prompt_past.clear();
+    } catch (...) { }
+}
+
+int whisper_amd_stream_tile(void) { return WA_STREAM_TILE; }
+
+} // extern "C"

@@ -99,6 +99,10 @@ ALIGN_BAD_TOKEN, ALIGN_NO_TOKENS, ALIGN_TOO_LONG, ALIGN_FLASH_ATTN, ALIGN_TOO_SH
 ALIGN_SCORE_DTYPE = np.dtype([("plog", "<f4"), ("p", "<f4"), ("best_id", "<i4"), ("best_plog", "<f4"), ("rank", "<i4"), ("best_p", "<f4")])
 
 
+class whisper_amd_stream_params(C.Structure):    # 36 bytes, passed by pointer (include/whisper_amd.h)
+    _fields_ = [(n, C.c_int32) for n in ("step_ms", "length_ms", "keep_ms", "sample_rate", "channels", "format", "backlog_ms", "carry_prompt", "drop_late")]
+
+
 class whisper_vad_context_params(C.Structure):
     _fields_ = [("n_threads", C.c_int), ("use_gpu", C.c_bool), ("gpu_device", C.c_int)]
 
@@ -318,6 +322,22 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         proto("whisper_amd_align_score", I, P, C.POINTER(F), I, I, C.POINTER(C.c_int32), I, C.POINTER(whisper_amd_align_score))
         proto("whisper_amd_align_stats", None, P, C.POINTER(C.c_long))
         proto("whisper_amd_align_timings", None, P, C.POINTER(C.c_int64))
+    if hasattr(lib, "whisper_amd_stream_open"):
+        SP, FP = C.POINTER(whisper_amd_stream_params), C.POINTER(whisper_full_params)
+        proto("whisper_amd_stream_default_params", None, SP)
+        proto("whisper_amd_stream_open", P, P, SP)
+        proto("whisper_amd_stream_close", None, P)
+        proto("whisper_amd_stream_feed", I, P, P, C.c_int64)
+        proto("whisper_amd_stream_flush", I, P)
+        proto("whisper_amd_stream_pending", I, P)
+        proto("whisper_amd_stream_step", I, P, FP)
+        proto("whisper_amd_stream_step_many", I, C.POINTER(C.c_void_p), I, FP)
+        proto("whisper_amd_stream_state", P, P)
+        proto("whisper_amd_stream_info", I, P, C.POINTER(C.c_int64))
+        proto("whisper_amd_stream_window_copy", C.c_int64, P, C.POINTER(F), C.c_int64)
+        proto("whisper_amd_stream_prompt_copy", I, P, C.POINTER(C.c_int32), I)
+        proto("whisper_amd_stream_reset", None, P)
+        proto("whisper_amd_stream_tile", I)
     _LIBS[path] = lib
     return lib
 
@@ -1062,3 +1082,99 @@ def long_plan(lib: C.CDLL, segs, n_samples: int, overlap: float, max_chunk_sampl
                               first.ctypes.data_as(C.POINTER(C.c_int32)), count.ctypes.data_as(C.POINTER(C.c_int32)),
                               packed.ctypes.data_as(C.POINTER(C.c_int64)), n)
     return [(int(first[i]), int(count[i]), int(packed[i])) for i in range(n)]
+
+
+# ---------------------------------------------------------------------------------------------------
+# live streaming sessions (whisper_amd_stream_*): sliding windows on a device ring
+# ---------------------------------------------------------------------------------------------------
+STREAM_BAD_ARGS, STREAM_FULL, STREAM_ENDED, STREAM_MIXED, STREAM_FAILED = -31, -32, -33, -34, -35    # WHISPER_AMD_STREAM_*
+STREAM_INFO = ("windows", "start", "length", "take", "committed", "prompt_tokens", "dropped", "pending", "feeds_device", "feeds_host")
+
+
+def stream_params(lib: C.CDLL, **kw) -> whisper_amd_stream_params:
+    """`whisper_amd_stream_default_params()` with the given fields replaced."""
+    p = whisper_amd_stream_params()
+    lib.whisper_amd_stream_default_params(C.byref(p))
+    for k, v in kw.items():
+        if not hasattr(p, k):
+            raise AttributeError(k)
+        setattr(p, k, v)
+    return p
+
+
+class WhisperStream:
+    """A live session (whisper_amd_stream_open): feed packets, step the windows that are due, read the results from `state`."""
+
+    def __init__(self, ctx: WhisperContext, **kw):
+        self.ctx, self.lib = ctx, ctx.lib
+        self.params = stream_params(self.lib, **kw)
+        self.ptr = self.lib.whisper_amd_stream_open(ctx.ptr, C.byref(self.params))
+        if not self.ptr:
+            raise WhisperError("StreamOpenRefused")
+        self.state = WhisperState(ctx, self.lib.whisper_amd_stream_state(self.ptr))       # owned by the session: never free()d through this object
+
+    def feed(self, data) -> int:
+        """`data`: a numpy array of the session's format (interleaved where it has two channels), or a (device pointer, n_frames) tuple.
+        Returns the windows now due or a negative STREAM_* code."""
+        if isinstance(data, tuple):
+            return self.lib.whisper_amd_stream_feed(self.ptr, C.c_void_p(data[0]), data[1])
+        a = np.ascontiguousarray(data, dtype=np.int16 if self.params.format == PCM_I16 else np.float32).reshape(-1)
+        return self.lib.whisper_amd_stream_feed(self.ptr, C.c_void_p(a.ctypes.data), len(a) // self.params.channels)
+
+    def flush(self) -> int:
+        return self.lib.whisper_amd_stream_flush(self.ptr)
+
+    def pending(self) -> int:
+        return self.lib.whisper_amd_stream_pending(self.ptr)
+
+    def step(self, params: FullParams) -> int:
+        return self.lib.whisper_amd_stream_step(self.ptr, C.byref(params.c))
+
+    def info(self) -> dict:
+        out = (C.c_int64 * 10)()
+        if self.lib.whisper_amd_stream_info(self.ptr, out) != 0:
+            raise WhisperError("StreamInfo")
+        return dict(zip(STREAM_INFO, [int(v) for v in out]))
+
+    def window(self) -> np.ndarray:
+        """The last window's PCM."""
+        n = self.lib.whisper_amd_stream_window_copy(self.ptr, None, 0)
+        if n < 0:
+            raise WhisperError("StreamWindowCopy", int(n))
+        out = np.zeros(max(n, 1), np.float32)
+        if self.lib.whisper_amd_stream_window_copy(self.ptr, out.ctypes.data_as(C.POINTER(C.c_float)), n) != n:
+            raise WhisperError("StreamWindowCopy")
+        return out[:n]
+
+    def prompt(self) -> list:
+        """The prompt the last window ran with."""
+        n = self.lib.whisper_amd_stream_prompt_copy(self.ptr, None, 0)
+        out = (C.c_int32 * max(n, 1))()
+        self.lib.whisper_amd_stream_prompt_copy(self.ptr, out, n)
+        return list(out[:n])
+
+    def segments(self) -> list:
+        return self.state.segments()
+
+    def reset(self):
+        self.lib.whisper_amd_stream_reset(self.ptr)
+
+    def close(self):
+        if self.ptr:
+            self.lib.whisper_amd_stream_close(self.ptr)
+            self.ptr = None
+            self.state.ptr = None
+
+
+def stream_step_many(streams: Sequence["WhisperStream"], params: FullParams) -> int:
+    """Extension (whisper_amd_stream_step_many): one due window of every session that has one; the windows that ran or a negative code."""
+    n = len(streams)
+    sp = (C.c_void_p * max(n, 1))(*[s.ptr for s in streams])
+    return streams[0].lib.whisper_amd_stream_step_many(sp, n, C.byref(params.c))
+
+
+def batch_stats(ctx) -> tuple:
+    """Extension (whisper_amd_batch_stats): lock-step passes of the context's last batch call and the rows they served."""
+    a, b = C.c_long(0), C.c_long(0)
+    ctx.lib.whisper_amd_batch_stats(ctx.ptr, C.byref(a), C.byref(b))
+    return int(a.value), int(b.value)
