@@ -764,7 +764,7 @@ WHISPER_API void whisper_amd_align_timings(struct whisper_state * state, int64_t
  *   one; when it is a multiple of n_new_line the line is COMMITTED: old becomes the window's last n_keep samples and, with carry_prompt, the
  *   prompt of the following windows becomes every token id of every segment of this window's result (until the next commit it stays what it
  *   was).  Without drops window k is the range [e - len, e) of the session's 16 kHz sample axis, e = (k + 1) n_step, len <= n_keep + n_len.
- *   stream.cpp's VAD mode (step_ms <= 0, vad_simple) is not offered.
+ *   stream.cpp's VAD mode (step_ms <= 0) is whisper_amd_stream_open_vad below: utterances cut at pauses by the Silero VAD, not by vad_simple.
  * The 16 kHz axis of a session is whisper_amd_audio_to_pcm's of the whole input, bit for bit, however the input is cut into packets: sample n
  *   becomes final - is written to the ring - with the packet that brings the last frame its filter reads (floor(n M / L) + K/2), and
  *   whisper_amd_stream_flush releases the rest, the frames behind the end of input read as zero.
@@ -830,6 +830,62 @@ WHISPER_API int64_t whisper_amd_stream_window_copy(struct whisper_amd_stream * s
 WHISPER_API int     whisper_amd_stream_prompt_copy(struct whisper_amd_stream * s, whisper_token * dst, int cap);
 WHISPER_API void    whisper_amd_stream_reset(struct whisper_amd_stream * s);
 WHISPER_API int     whisper_amd_stream_tile(void);
+
+/* Live sessions that cut at pauses (wa_stream.cpp, csrc/wa_stream_vad.h): nothing runs while the line is silent, and each
+ * utterance is transcribed once, when the speaker pauses.  The yardstick is stated offline.  Let x[0..T) be the session's 16 kHz axis (above), P
+ * the probabilities whisper_vad_detect_speech gives on x, S the segments whisper_vad_segments_from_probs gives for params->vad.  Utterance j is
+ * the contiguous range [cs_to_samples(S[j].start), min(cs_to_samples(S[j].end), T)) - none of vad = true's overlap or inserted silence.  A VAD
+ * session delivers exactly these utterances, in order, however the input was cut into packets, each one as soon as later audio can no longer
+ * change it, the rest at the flush; its probabilities so far are the first windows of P, bit for bit (the session carries the LSTM state from
+ * one 512-sample window to the next; the last partial window exists only at the flush, zero-filled).
+ * When an utterance is due: its last speech ended at sample e (a multiple of 512) and the window that ends at or beyond e + 3200 has been
+ *   processed with no speech candidate open - the reference merges neighbours less than 3200 samples apart, so a candidate that opened inside
+ *   that gap is waited for until the rules have kept or discarded it.  Delay bound, in samples fed beyond e, when nothing reaches the threshold
+ *   behind e: max(ceil512(min_silence_samples) + 512, 3584) plus what the resampler holds back (K/2 input frames) and, with vad_on_feed = 0, the
+ *   time to the next poll.  A candidate behind e is decided at most max_speech_duration_s later.
+ * The length cap: an utterance holds at most max_utterance_ms (<= 30000: the state's PCM buffer; vad.max_speech_duration_s may not exceed it).
+ *   The reference's merge pass can re-join what max_speech split; a merge whose result would exceed the cap is NOT made: the earlier part is
+ *   delivered as it stands, flagged `split`, and the rest follows as the next utterance.  This is the one departure from S; for inputs whose S
+ *   has no segment over the cap the utterances ARE S.  (csrc/wa_stream_vad.h states the rule; tools/stream_vad_ref.py restates it.)
+ * Prompt: carry_prompt = 0 (stream.cpp's VAD mode never fills prompt_tokens): every utterance runs with the caller's prompt.  1: utterance j + 1
+ *   runs with every token id of utterance j's result.
+ * whisper_amd_stream_open_vad: `vctx` is the caller's whisper_vad_context on the context's device; sessions share it read-only (it must outlive
+ *   them; whisper_vad_detect_speech on it stays the caller's to use), each owns its LSTM state and probabilities.  The ring holds max_utterance +
+ *   backlog samples, backlog = backlog_ms x 16, raised to 16000 x max_speech_duration_s + 8192: an open speech and a candidate behind it always
+ *   fit.  Refused (NULL, an error log line, nothing made) for null arguments, what whisper_amd_audio_to_pcm refuses, speech_pad_ms outside
+ *   [0, 100], max_utterance_ms outside (0, 30000], max_speech_duration_s above the cap (or below one window and its pads: the reference then
+ *   drops the bound), negative durations, a vctx of another device.  whisper_amd_stream_open keeps refusing step_ms <= 0.
+ * The calls above on a VAD session: _feed is the same single k_stream_push launch; with vad_on_feed = 1 it also runs the front end on the
+ *   session's new whole windows (one k_stream_vad_front launch straight from the ring), the recurrence and the segmenter on the calling thread,
+ *   and returns the utterances due.  FULL, with nothing changed, when the packet would overwrite an utterance that is due or still open, or a
+ *   window not yet processed.  _flush processes the last partial window and closes an open speech.  _pending: the utterances due.  _step /
+ *   _step_many run ONE due utterance per session - one k_stream_window gather (per group of 8), then whisper_full_with_state, alone or in the
+ *   lock-step group, exactly as for windows; segment times are relative to the utterance.  _info: windows run counts utterances, take is 0,
+ *   committed 1.  _window_copy / _prompt_copy: the last utterance's PCM and prompt.  _reset: a fresh session's state, LSTM included.
+ * whisper_amd_stream_vad_poll_many: for servers that set vad_on_feed = 0: the new whole windows of all `ss` (VAD sessions of one context and
+ *   one vctx; at most 64; MIXED otherwise) through ONE k_stream_vad_front launch per group of up to 8 sessions, then recurrences and segmenters
+ *   on the calling thread.  Returns the utterances due in total.  Nothing is done for windows already processed.
+ * whisper_amd_stream_utterance_info: out = { utterances run, the last one's start on the absolute 16 kHz axis, its length, its start_cs, its
+ *   end_cs, whether it was split at the cap (0 / 1), front-end launches so far, windows processed so far }.
+ * whisper_amd_stream_vad_probs_copy: the probabilities so far: copies up to `cap`, returns the full count.
+ * WHISPER_AMD_STREAM_HOST=1 (or a HIP failure): the session stages its new windows linearly and uses the whole-recording front-end launch; the
+ *   bits are the same. */
+struct whisper_amd_stream_vad_params {
+    int32_t sample_rate;        /* 16000 */
+    int32_t channels;           /* 1     */
+    int32_t format;             /* WHISPER_AMD_PCM_F32 */
+    int32_t backlog_ms;         /* 40000 */
+    int32_t carry_prompt;       /* 0     */
+    int32_t max_utterance_ms;   /* 30000 */
+    int32_t vad_on_feed;        /* 1     */
+    struct whisper_vad_params vad;      /* whisper_vad_default_params() with max_speech_duration_s = 30 */
+};
+WHISPER_API void    whisper_amd_stream_vad_default_params(struct whisper_amd_stream_vad_params * p);
+WHISPER_API struct whisper_amd_stream * whisper_amd_stream_open_vad(struct whisper_context * ctx, struct whisper_vad_context * vctx,
+                                                                     const struct whisper_amd_stream_vad_params * p);
+WHISPER_API int     whisper_amd_stream_vad_poll_many(struct whisper_amd_stream ** ss, int n);
+WHISPER_API int     whisper_amd_stream_utterance_info(struct whisper_amd_stream * s, int64_t out[8]);
+WHISPER_API int64_t whisper_amd_stream_vad_probs_copy(struct whisper_amd_stream * s, float * dst, int64_t cap);
 
 #ifdef __cplusplus
 }

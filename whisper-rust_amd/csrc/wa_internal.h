@@ -416,6 +416,10 @@ bool wa_vad_segments_for(whisper_context * ctx, whisper_state * st, const whispe
                          std::vector<wa_vad_seg> & segs);      // `samples` host or device; false: failure; the state's table is cleared
 bool wa_vad_for_full(whisper_context * ctx, whisper_state * st, const whisper_full_params & params, const float * samples, int n_samples,
                      std::vector<float> & filtered);           // false: failure; `filtered` empty: no speech
+// what a live VAD session (wa_stream.cpp) reads of the caller's context: shared, never written
+int                  wa_vad_ctx_device(const whisper_vad_context * v);
+const wa_vad_model & wa_vad_ctx_model (const whisper_vad_context * v);
+const wa_vad_dev &   wa_vad_ctx_dev   (const whisper_vad_context * v);
 // host-overlapped greedy decoding on the one-launch step (wa_decode.cpp); launch k decodes position pos0 + k
 struct wa_spec_state { int last, penult, seek_delta, has_ts; };
 bool wa_spec_begin (whisper_context & ctx, whisper_state & st, const std::vector<uint32_t> & suppress_bits);

@@ -226,6 +226,10 @@ void whisper_amd_vad_timings(struct whisper_vad_context * vctx, int64_t out_us[3
     out_us[0] = vctx->t_vad_us; out_us[1] = vctx->t_front_wait_us; out_us[2] = vctx->t_host_us;
 }
 
+int                  wa_vad_ctx_device(const whisper_vad_context * v) { return v->device; }
+const wa_vad_model & wa_vad_ctx_model (const whisper_vad_context * v) { return v->model; }
+const wa_vad_dev &   wa_vad_ctx_dev   (const whisper_vad_context * v) { return v->dev; }
+
 // -------------------------------------------------------------------------------------------------
 // whisper_full / whisper_full_parallel with vad = true (ref: whisper.cpp:6615-6793): the speech-only audio and the state's table
 // -------------------------------------------------------------------------------------------------

@@ -75,3 +75,22 @@ struct wa_vad_dev {            // device pointers; F16 rows of K halfs (layer 0:
 };
 // out[c][512] = W_ih x_c + b_ih for windows c < n_chunks of d_samples; samples at and past n_valid count as zero
 bool wa_vad_front_launch(const wa_vad_dev & w, const float * d_samples, int n_valid, int n_chunks, float * d_out, void * stream);
+
+// The same front end on the ring windows of several live sessions in ONE launch (k_stream_vad_front; wa_stream_vad.cpp).
+// Session i contributes first[i + 1] - first[i] consecutive windows: sample q of them lies in ring slot (slot + q) mod cap and counts as zero at
+// and past n_valid (the partial window of a flush).  Window k's 512 gate inputs go to out + 512 k, memory the device can write (the session's
+// pinned host buffer).  The table travels as a kernel argument.
+#define WA_SVAD_SESSIONS     8        // sessions per launch
+#define WA_SVAD_MAX_WINDOWS  1024     // windows of one session per launch (32 s of audio)
+struct wa_svad_session {
+    const float * ring;
+    float * out;
+    int32_t cap, slot, n_valid, pad_;
+};
+struct wa_svad_table {
+    wa_svad_session s[WA_SVAD_SESSIONS];
+    int32_t first[WA_SVAD_SESSIONS + 1];      // prefix counts of the flat (session, window) list; first[0] = 0
+    int32_t n_sessions;
+};
+// false: the table is refused (nothing was launched) or the launch failed.  The caller has made sure the ring holds the samples.
+bool wa_svad_front_launch(const wa_vad_dev & w, const wa_svad_table & t, void * stream);

@@ -131,14 +131,11 @@ __device__ __forceinline__ void vad_scatter(wa_f16 * I, int ld, int c, int lout,
 }
 __device__ __forceinline__ float vad_bias_relu(float v, float b) { const float y = v + b; return y > 0.f ? y : 0.f; }
 
-struct vad_front_args {
-    wa_vad_dev w;
-    const float * samples;
-    int n_valid, n_chunks;
-    float * out;
-};
-
-__global__ __launch_bounds__(256, 2) void k_vad_front(vad_front_args A) {
+// The front end of one workgroup: VT windows from load(c, s) - sample s (0 .. 511) of the workgroup's window c, 0.0f where there is none -
+// through every layer; store(c, j, lo, hi) receives gate inputs j and j + 256 of window c (b_ih added).  k_vad_front and k_stream_vad_front
+// are this body with their own load and store: the layers, their order of operations and the LDS layout are stated once.
+template <class Load, class Store>
+__device__ __forceinline__ void vad_front_body(const wa_vad_dev & W, Load load, Store store) {
     __shared__ __attribute__((aligned(16))) wa_f16 P[VT * V_PS];              // padded windows, F16 (the STFT's im2col rounds them)
     __shared__ __attribute__((aligned(16))) wa_f16 I0[VT * 4 * V_LD01];       // im2col rows of layer 0: (window, t) x 129 * 3
     __shared__ __attribute__((aligned(16))) wa_f16 I1[VT * 2 * V_LD01];       // layer 1: (window, t) x 128 * 3
@@ -146,15 +143,12 @@ __global__ __launch_bounds__(256, 2) void k_vad_front(vad_front_args A) {
     __shared__ __attribute__((aligned(16))) wa_f16 I3[VT * V_LD23];           // layer 3: window x 64 * 3
     __shared__ __attribute__((aligned(16))) float  X[VT * V_LDX];             // LSTM input: window x 128
     const int tid = threadIdx.x;
-    const int chunk0 = blockIdx.x * VT;
 
     // windows: zero-filled past the end of the audio, then reflect-padded by 64 (ops.cpp:6784-6790: left[-i] = left[i], right[i] = right[-i])
     for (int idx = tid; idx < VT * (WA_VAD_WINDOW + 2 * WA_VAD_PAD); idx += 256) {
         const int c = idx / (WA_VAD_WINDOW + 2 * WA_VAD_PAD), j = idx - c * (WA_VAD_WINDOW + 2 * WA_VAD_PAD);
         const int s = j < WA_VAD_PAD ? WA_VAD_PAD - j : j < WA_VAD_PAD + WA_VAD_WINDOW ? j - WA_VAD_PAD : 2 * WA_VAD_WINDOW + WA_VAD_PAD - 2 - j;
-        const long long g = (long long) (chunk0 + c) * WA_VAD_WINDOW + s;
-        const float v = (chunk0 + c < A.n_chunks && g < (long long) A.n_valid) ? A.samples[g] : 0.0f;
-        P[c * V_PS + j] = f2h(v);
+        P[c * V_PS + j] = f2h(load(c, s));
     }
     for (int i = tid; i < VT * 4 * V_LD01; i += 256) I0[i] = 0;
     for (int i = tid; i < VT * 2 * V_LD01; i += 256) I1[i] = 0;
@@ -162,38 +156,38 @@ __global__ __launch_bounds__(256, 2) void k_vad_front(vad_front_args A) {
     __syncthreads();
 
     // STFT (K = 256, stride 128: 4 frames per window) + magnitude sqrtf(re re + im im) -> layer 0's rows (stride 1, 4 steps)
-    vad_layer_f16<WA_VAD_NFFT>(VT * 4, 2 * WA_VAD_BINS, [&](int r) { return &P[(r >> 2) * V_PS + (r & 3) * WA_VAD_HOP]; }, A.w.stft, WA_VAD_NFFT,
+    vad_layer_f16<WA_VAD_NFFT>(VT * 4, 2 * WA_VAD_BINS, [&](int r) { return &P[(r >> 2) * V_PS + (r & 3) * WA_VAD_HOP]; }, W.stft, WA_VAD_NFFT,
         [&](int r, int j, float re, float im) {
             const float r2 = re * re, i2 = im * im;
             vad_scatter(I0, V_LD01, r >> 2, 4, 1, r & 3, j, f2h(sqrtf(r2 + i2)));
         });
     __syncthreads();
     // layer 0: 129 -> 128, stride 1, 4 steps -> layer 1's rows (stride 2, 2 steps)
-    vad_layer_f16<387>(VT * 4, 128, [&](int r) { return &I0[r * V_LD01]; }, A.w.enc_w[0], WA_VAD_LD0,
+    vad_layer_f16<387>(VT * 4, 128, [&](int r) { return &I0[r * V_LD01]; }, W.enc_w[0], WA_VAD_LD0,
         [&](int r, int j, float lo, float hi) {
-            vad_scatter(I1, V_LD01, r >> 2, 2, 2, r & 3, j,      f2h(vad_bias_relu(lo, A.w.enc_b[0][j])));
-            vad_scatter(I1, V_LD01, r >> 2, 2, 2, r & 3, j + 64, f2h(vad_bias_relu(hi, A.w.enc_b[0][j + 64])));
+            vad_scatter(I1, V_LD01, r >> 2, 2, 2, r & 3, j,      f2h(vad_bias_relu(lo, W.enc_b[0][j])));
+            vad_scatter(I1, V_LD01, r >> 2, 2, 2, r & 3, j + 64, f2h(vad_bias_relu(hi, W.enc_b[0][j + 64])));
         });
     __syncthreads();
     // layer 1: 128 -> 64, stride 2, 2 steps -> layer 2's rows (stride 2, 1 step)
-    vad_layer_f16<384>(VT * 2, 64, [&](int r) { return &I1[r * V_LD01]; }, A.w.enc_w[1], 384,
+    vad_layer_f16<384>(VT * 2, 64, [&](int r) { return &I1[r * V_LD01]; }, W.enc_w[1], 384,
         [&](int r, int j, float lo, float hi) {
-            vad_scatter(I2, V_LD23, r >> 1, 1, 2, r & 1, j,      f2h(vad_bias_relu(lo, A.w.enc_b[1][j])));
-            vad_scatter(I2, V_LD23, r >> 1, 1, 2, r & 1, j + 32, f2h(vad_bias_relu(hi, A.w.enc_b[1][j + 32])));
+            vad_scatter(I2, V_LD23, r >> 1, 1, 2, r & 1, j,      f2h(vad_bias_relu(lo, W.enc_b[1][j])));
+            vad_scatter(I2, V_LD23, r >> 1, 1, 2, r & 1, j + 32, f2h(vad_bias_relu(hi, W.enc_b[1][j + 32])));
         });
     __syncthreads();
     // layer 2: 64 -> 64, stride 2, 1 step -> layer 3's rows (stride 1, 1 step)
-    vad_layer_f16<192>(VT, 64, [&](int r) { return &I2[r * V_LD23]; }, A.w.enc_w[2], 192,
+    vad_layer_f16<192>(VT, 64, [&](int r) { return &I2[r * V_LD23]; }, W.enc_w[2], 192,
         [&](int r, int j, float lo, float hi) {
-            vad_scatter(I3, V_LD23, r, 1, 1, 0, j,      f2h(vad_bias_relu(lo, A.w.enc_b[2][j])));
-            vad_scatter(I3, V_LD23, r, 1, 1, 0, j + 32, f2h(vad_bias_relu(hi, A.w.enc_b[2][j + 32])));
+            vad_scatter(I3, V_LD23, r, 1, 1, 0, j,      f2h(vad_bias_relu(lo, W.enc_b[2][j])));
+            vad_scatter(I3, V_LD23, r, 1, 1, 0, j + 32, f2h(vad_bias_relu(hi, W.enc_b[2][j + 32])));
         });
     __syncthreads();
     // layer 3: 64 -> 128, stride 1, 1 step: its time step 0 is the LSTM's input, in F32
-    vad_layer_f16<192>(VT, 128, [&](int r) { return &I3[r * V_LD23]; }, A.w.enc_w[3], 192,
+    vad_layer_f16<192>(VT, 128, [&](int r) { return &I3[r * V_LD23]; }, W.enc_w[3], 192,
         [&](int r, int j, float lo, float hi) {
-            X[r * V_LDX + j]      = vad_bias_relu(lo, A.w.enc_b[3][j]);
-            X[r * V_LDX + j + 64] = vad_bias_relu(hi, A.w.enc_b[3][j + 64]);
+            X[r * V_LDX + j]      = vad_bias_relu(lo, W.enc_b[3][j]);
+            X[r * V_LDX + j + 64] = vad_bias_relu(hi, W.enc_b[3][j + 64]);
         });
     __syncthreads();
     // W_ih x + b_ih (F32 weights, K = 128)
@@ -202,17 +196,33 @@ __global__ __launch_bounds__(256, 2) void k_vad_front(vad_front_args A) {
         for (int p = tid; p < total; p += 256) {
             const int rp = p / np, j = p - rp * np;
             float r[2][2];
-            vad_patch_f32<WA_VAD_HID>(&X[(2 * rp) * V_LDX], &X[(2 * rp + 1) * V_LDX], A.w.w_ih + (size_t) j * WA_VAD_HID, A.w.w_ih + (size_t) (j + np) * WA_VAD_HID, r);
-#pragma unroll
-            for (int q = 0; q < 2; ++q) {
-                const int c = chunk0 + 2 * rp + q;
-                if (c < A.n_chunks) {
-                    A.out[(size_t) c * WA_VAD_GATES + j]      = r[q][0] + A.w.b_ih[j];
-                    A.out[(size_t) c * WA_VAD_GATES + j + np] = r[q][1] + A.w.b_ih[j + np];
-                }
-            }
+            vad_patch_f32<WA_VAD_HID>(&X[(2 * rp) * V_LDX], &X[(2 * rp + 1) * V_LDX], W.w_ih + (size_t) j * WA_VAD_HID, W.w_ih + (size_t) (j + np) * WA_VAD_HID, r);
+            store(2 * rp,     j, r[0][0] + W.b_ih[j], r[0][1] + W.b_ih[j + np]);
+            store(2 * rp + 1, j, r[1][0] + W.b_ih[j], r[1][1] + W.b_ih[j + np]);
         }
     }
+}
+
+struct vad_front_args {
+    wa_vad_dev w;
+    const float * samples;
+    int n_valid, n_chunks;
+    float * out;
+};
+
+__global__ __launch_bounds__(256, 2) void k_vad_front(vad_front_args A) {
+    const int chunk0 = blockIdx.x * VT;
+    vad_front_body(A.w,
+        [&](int c, int s) {
+            const long long g = (long long) (chunk0 + c) * WA_VAD_WINDOW + s;
+            return (chunk0 + c < A.n_chunks && g < (long long) A.n_valid) ? A.samples[g] : 0.0f;
+        },
+        [&](int c, int j, float lo, float hi) {
+            if (chunk0 + c < A.n_chunks) {
+                A.out[(size_t) (chunk0 + c) * WA_VAD_GATES + j]                    = lo;
+                A.out[(size_t) (chunk0 + c) * WA_VAD_GATES + j + WA_VAD_GATES / 2] = hi;
+            }
+        });
 }
 
 bool wa_vad_front_launch(const wa_vad_dev & w, const float * d_samples, int n_valid, int n_chunks, float * d_out, void * stream) {
@@ -220,5 +230,62 @@ bool wa_vad_front_launch(const wa_vad_dev & w, const float * d_samples, int n_va
     vad_front_args a;
     a.w = w; a.samples = d_samples; a.n_valid = n_valid; a.n_chunks = n_chunks; a.out = d_out;
     hipLaunchKernelGGL(k_vad_front, dim3((n_chunks + VT - 1) / VT), dim3(256), 0, (hipStream_t) stream, a);
+    return hipGetLastError() == hipSuccess;
+}
+
+// k_stream_vad_front: the same front end on the ring windows of up to WA_SVAD_SESSIONS live sessions (wa_stream_vad.cpp).
+// The (session, window) pairs of a launch form one flat list - session 0's new windows, then session 1's, ... - that travels as its prefix
+// counts; workgroup b takes flat rows 8 b .. 8 b + 7 whatever sessions they belong to.  Sample s of a session's window k is ring slot
+// (slot + 512 k + s) mod cap, zero at and past n_valid (a flush's partial window): the loads go straight into the LDS tile above, so a window
+// may wrap inside the ring and start at any slot.  Row k's 512 gate inputs go to out + 512 k, the session's pinned host buffer.
+struct svad_front_args {
+    wa_vad_dev w;
+    wa_svad_table t;
+};
+
+__global__ __launch_bounds__(256, 2) void k_stream_vad_front(svad_front_args A) {
+    __shared__ int row_s[VT], row_k[VT];            // the session and the window of each tile row; session -1: no row
+    if (threadIdx.x < VT) {
+        const int f = blockIdx.x * VT + threadIdx.x;
+        int s = -1, k = 0;
+        if (f < A.t.first[A.t.n_sessions]) {
+            s = 0;
+            while (s + 1 < A.t.n_sessions && f >= A.t.first[s + 1]) ++s;
+            k = f - A.t.first[s];
+        }
+        row_s[threadIdx.x] = s; row_k[threadIdx.x] = k;
+    }
+    __syncthreads();
+    vad_front_body(A.w,
+        [&](int c, int s) {
+            const int i = row_s[c];
+            if (i < 0) return 0.0f;
+            const wa_svad_session & z = A.t.s[i];
+            const int off = row_k[c] * WA_VAD_WINDOW + s;
+            return off < z.n_valid ? z.ring[(int) (((long long) z.slot + off) % z.cap)] : 0.0f;
+        },
+        [&](int c, int j, float lo, float hi) {
+            const int i = row_s[c];
+            if (i >= 0) {
+                float * o = A.t.s[i].out + (size_t) row_k[c] * WA_VAD_GATES;
+                o[j] = lo; o[j + WA_VAD_GATES / 2] = hi;
+            }
+        });
+}
+
+bool wa_svad_front_launch(const wa_vad_dev & w, const wa_svad_table & t, void * stream) {
+    if (t.n_sessions <= 0 || t.n_sessions > WA_SVAD_SESSIONS || t.first[0] != 0) return false;
+    for (int i = 0; i < t.n_sessions; ++i) {
+        const wa_svad_session & z = t.s[i];
+        const int n = t.first[i + 1] - t.first[i];
+        if (n < 0 || n > WA_SVAD_MAX_WINDOWS) return false;
+        if (n > 0 && (!z.ring || !z.out || z.cap <= 0 || z.slot < 0 || z.slot >= z.cap || z.n_valid <= (n - 1) * WA_VAD_WINDOW || z.n_valid > n * WA_VAD_WINDOW ||
+                      z.n_valid > z.cap)) return false;
+    }
+    const int total = t.first[t.n_sessions];
+    if (total == 0) return true;
+    svad_front_args a;
+    a.w = w; a.t = t;
+    hipLaunchKernelGGL(k_stream_vad_front, dim3((total + VT - 1) / VT), dim3(256), 0, (hipStream_t) stream, a);
     return hipGetLastError() == hipSuccess;
 }

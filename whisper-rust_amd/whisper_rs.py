@@ -103,6 +103,11 @@ class whisper_amd_stream_params(C.Structure):    # 36 bytes, passed by pointer (
     _fields_ = [(n, C.c_int32) for n in ("step_ms", "length_ms", "keep_ms", "sample_rate", "channels", "format", "backlog_ms", "carry_prompt", "drop_late")]
 
 
+class whisper_amd_stream_vad_params(C.Structure):    # passed by pointer (include/whisper_amd.h)
+    _fields_ = [(n, C.c_int32) for n in ("sample_rate", "channels", "format", "backlog_ms", "carry_prompt", "max_utterance_ms", "vad_on_feed")] + \
+               [("vad", whisper_vad_params)]
+
+
 class whisper_vad_context_params(C.Structure):
     _fields_ = [("n_threads", C.c_int), ("use_gpu", C.c_bool), ("gpu_device", C.c_int)]
 
@@ -338,6 +343,13 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         proto("whisper_amd_stream_prompt_copy", I, P, C.POINTER(C.c_int32), I)
         proto("whisper_amd_stream_reset", None, P)
         proto("whisper_amd_stream_tile", I)
+    if hasattr(lib, "whisper_amd_stream_open_vad"):
+        VP = C.POINTER(whisper_amd_stream_vad_params)
+        proto("whisper_amd_stream_vad_default_params", None, VP)
+        proto("whisper_amd_stream_open_vad", P, P, P, VP)
+        proto("whisper_amd_stream_vad_poll_many", I, C.POINTER(C.c_void_p), I)
+        proto("whisper_amd_stream_utterance_info", I, P, C.POINTER(C.c_int64))
+        proto("whisper_amd_stream_vad_probs_copy", C.c_int64, P, C.POINTER(F), C.c_int64)
     _LIBS[path] = lib
     return lib
 
@@ -1164,6 +1176,58 @@ class WhisperStream:
             self.lib.whisper_amd_stream_close(self.ptr)
             self.ptr = None
             self.state.ptr = None
+
+
+UTTERANCE_INFO = ("utterances", "start", "length", "start_cs", "end_cs", "split", "front_launches", "windows")
+
+
+def stream_vad_params(lib: C.CDLL, vad=None, **kw) -> whisper_amd_stream_vad_params:
+    """`whisper_amd_stream_vad_default_params()` with the given fields replaced; `vad`: a dict of whisper_vad_params fields."""
+    p = whisper_amd_stream_vad_params()
+    lib.whisper_amd_stream_vad_default_params(C.byref(p))
+    for k, v in kw.items():
+        if not hasattr(p, k):
+            raise AttributeError(k)
+        setattr(p, k, v)
+    for k, v in (vad or {}).items():
+        if not hasattr(p.vad, k):
+            raise AttributeError(k)
+        setattr(p.vad, k, v)
+    return p
+
+
+class WhisperVadStream(WhisperStream):
+    """A live session that cuts at pauses (whisper_amd_stream_open_vad): feed packets, step the utterances that are due.  `vctx` is a
+    WhisperVadContext the caller keeps alive; sessions share it."""
+
+    def __init__(self, ctx: WhisperContext, vctx: "WhisperVadContext", vad=None, **kw):
+        self.ctx, self.lib, self.vctx = ctx, ctx.lib, vctx
+        self.params = stream_vad_params(self.lib, vad, **kw)
+        self.ptr = self.lib.whisper_amd_stream_open_vad(ctx.ptr, vctx.ptr if vctx is not None else None, C.byref(self.params))
+        if not self.ptr:
+            raise WhisperError("StreamOpenRefused")
+        self.state = WhisperState(ctx, self.lib.whisper_amd_stream_state(self.ptr))
+
+    def utterance_info(self) -> dict:
+        out = (C.c_int64 * 8)()
+        if self.lib.whisper_amd_stream_utterance_info(self.ptr, out) != 0:
+            raise WhisperError("StreamUtteranceInfo")
+        return dict(zip(UTTERANCE_INFO, [int(v) for v in out]))
+
+    def probs(self) -> np.ndarray:
+        n = self.lib.whisper_amd_stream_vad_probs_copy(self.ptr, None, 0)
+        if n < 0:
+            raise WhisperError("StreamVadProbsCopy", int(n))
+        out = np.zeros(max(n, 1), np.float32)
+        self.lib.whisper_amd_stream_vad_probs_copy(self.ptr, out.ctypes.data_as(C.POINTER(C.c_float)), n)
+        return out[:n]
+
+
+def stream_vad_poll_many(streams: Sequence["WhisperVadStream"]) -> int:
+    """Extension (whisper_amd_stream_vad_poll_many): the front end on the new windows of all sessions; the utterances due in total."""
+    n = len(streams)
+    sp = (C.c_void_p * max(n, 1))(*[s.ptr for s in streams])
+    return streams[0].lib.whisper_amd_stream_vad_poll_many(sp, n)
 
 
 def stream_step_many(streams: Sequence["WhisperStream"], params: FullParams) -> int:
