@@ -700,6 +700,86 @@ WHISPER_API int     whisper_amd_long_pack(struct whisper_state * state, const fl
 WHISPER_API int     whisper_amd_long_tile(void);
 WHISPER_API struct whisper_state * whisper_amd_context_state(struct whisper_context * ctx);
 
+/* Two-channel recordings (wa_channels.cpp): a stereo call recording carries one speaker per channel.  The audio front end
+ * above can only average the two; the calls here keep them apart: both channels as two planes of 16 kHz F32 from ONE launch, the energy of
+ * spans of either plane, the reference cli's --diarize rule, and whisper_amd_full_long for both channels in one call, whose chunks share
+ * the lock-step waves.  csrc/wa_channels.h states every piece of arithmetic once; the kernels and the host functions there agree bit for bit.
+ * whisper_amd_audio_split: `data` is a host or a device pointer (detected as whisper_pcm_to_mel does) to n_frames interleaved STEREO frames,
+ *   int16 or F32, at any rate whisper_amd_audio_to_pcm accepts.  Returns a DEVICE pointer to a planar buffer the state owns: channel c lies
+ *   at ptr + c * *stride, *n_samples F32 samples each, *stride = *n_samples rounded up to 64 floats (the floats between a plane's end and
+ *   the stride are undefined).  Plane c is, bit for bit, what whisper_amd_audio_to_pcm gives for channel c presented as a mono recording of
+ *   the same rate and format, with the context's filter table for that rate.  The buffer is an allocation of its own - not
+ *   whisper_amd_audio_to_pcm's - filled on the state's stream, kept until the next split on this state and freed with the state.  Host input
+ *   may be released on return.  n_frames == 0 gives 0 samples and a non-null pointer.  Refused as whisper_amd_audio_to_pcm refuses (NULL, an
+ *   error log line, nothing written), also for a null n_samples or stride.  A HIP failure on the way is logged, counted and served by the host
+ *   restatement; WHISPER_AMD_CHANNELS_HOST=1 in the environment, read at each call, sends split and energy to the host functions.
+ * whisper_amd_audio_split_copy: copies up to `cap` samples of plane `channel` of the state's last split into `dst` (host) and returns their
+ *   full count; -1: no split yet, or a channel other than 0 / 1.
+ * whisper_amd_channel_energy: energy[2 i + c] = the sum of |x_c[j]| over j in [is0[i], is1[i]) of the state's last split, in F64, spans
+ *   clamped to [0, n_samples], 0.0 for an empty span; ONE launch serves all spans of both channels, without atomics, in the fixed order of
+ *   csrc/wa_channels.h (lane l of whisper_amd_channels_energy_lanes() takes the samples whose index is l modulo that count, ascending, then a
+ *   stated tree), which does not depend on launch geometry.  where: 0 the host function, 1 the kernel (no fallback), any other value the
+ *   kernel with the host function behind it (and WHISPER_AMD_CHANNELS_HOST honoured).  0 on success, -1 refused or failed.
+ * whisper_amd_channel_speakers: the reference cli's --diarize rule (examples/cli/cli.cpp) on caller-given times in centiseconds: sample
+ *   = clamp((int) (t * 16000 / 100), 0, n_samples - 1) (kept in 64 bits: beyond the 37 h at which the cli's int cast stops being defined it is
+ *   n_samples - 1), energies over [sample(t0), sample(t1)), then in F64 e0 > ratio * e1 -> 0, else
+ *   e1 > ratio * e0 -> 1, else -1 (undecided: the cli prints "?"); ratio <= 0 means the cli's 1.1.  `energy` ([n][2]) may be null.  With
+ *   whisper_amd_full_long_audio (the down-mix) followed by whisper_amd_audio_split and this call on the segment times a caller gets what
+ *   cli --diarize prints.  The cli sums sequentially; the fixed order here differs from that by at most n 2^-53 relative, so the labels
+ *   agree wherever the energies are not within that of the threshold.
+ * whisper_amd_full_long_channels, on the context's own state: whisper_amd_full_long for both channels of one recording in one call.
+ *   - One whisper_amd_audio_split: the recording crosses PCIe once (host input) or never (device input).
+ *   - The VAD runs per plane, where it lies, on the state's VAD context, channel 0 then channel 1.
+ *   - crosstalk_ratio = g > 0: ONE energy launch covers every VAD segment of both channels over its own span [cs_to_samples(start),
+ *     min(cs_to_samples(end), n_samples)); a segment of channel c is dropped when E_c < g * E_other (the other speaker bleeding through).
+ *     g = 0 launches nothing and drops nothing; g < 0 is refused.
+ *   - The chunk planner runs per channel over that channel's kept segments (max_chunk_ms <= 0 means 30000); ONE launch of k_long_pack packs
+ *     the chunks of both channels (WHISPER_AMD_LONG_HOST=1 keeps meaning the host pack).
+ *   - All chunks form one list ordered by (original start, channel) and run in waves of n_parallel (<= 0 means 8, clamped to 8) exactly as
+ *     whisper_amd_full_long's: C0 + C1 chunks take ceil((C0 + C1) / n_parallel) waves.  Member params, callbacks and prompt rules are those
+ *     of whisper_amd_full_long.
+ *   - Results: per channel, times mapped and clamped as whisper_amd_full_long does - at least 10 cs, t0 = max(t0, t1 of the previous segment
+ *     OF THE SAME CHANNEL): overlapping speech on the two channels stays overlapping - then both channels' segments are merged into
+ *     ctx->state's list by (t0, channel); a channel's segments always keep their own order (csrc/wa_channels.h: wa_ch_merge).  new_segment_callback fires once per merged segment, in merged order;
+ *     whisper_full_lang_id is the first chunk's in wave order; the state's VAD table is cleared.  whisper_amd_long_n_chunks / _chunk_info /
+ *     _chunk_copy describe the chunks in wave order (segment indices count within the chunk's channel, after the gate).
+ *   - With crosstalk_ratio = 0 the segments of channel c in the merged list are exactly what whisper_amd_full_long gives on
+ *     whisper_amd_audio_to_pcm of channel c extracted on the host: texts, token ids, p / plog bit patterns, t0 / t1 and token times.
+ *   - Returns 0 with no segments when neither channel has speech, 0 with one channel's segments when only one has; -1 with a log line for
+ *     null arguments, what the split refuses, n_frames == 0, more than INT_MAX samples, non-zero offset_ms / duration_ms, a negative
+ *     crosstalk_ratio (all of these before anything of the state is touched) and for a missing or refused VAD model; otherwise the first
+ *     non-zero chunk code; results and chunk list are then cleared.  No exception crosses the boundary.
+ * whisper_amd_long_segment_channel / whisper_amd_long_chunk_channel: the channel (0 / 1) of result segment / chunk i of the last call;
+ *   -1: out of range, or the last long call had no channels.
+ * whisper_amd_channels_stats: out = { split path taken (0 host, 1 kernel), split attempts on the device that fell back since the state was
+ *   created, energy launches, pack launches, VAD segments found on channel 0, on channel 1, segments dropped by the gate, chunks, waves,
+ *   bytes of the CALLER'S recording copied host -> device (0 for device input), energy launches whose result did not arrive and that the host
+ *   function served instead since the state was created (a launch that took place counts as a launch too) } of the last
+ *   whisper_amd_full_long_channels call;
+ *   whisper_amd_long_stats then holds its times: us in the two VAD passes, us gate + plan + pack, us transcription.
+ * whisper_amd_channels_tile: outputs per channel and workgroup of the split kernel (tests put lengths on either side of it). */
+struct whisper_amd_channels_params {
+    int32_t max_chunk_ms;        /* 30000 */
+    int32_t n_parallel;          /* 8 */
+    double  crosstalk_ratio;     /* 0.0: the gate is off */
+};
+WHISPER_API const float * whisper_amd_audio_split(struct whisper_state * state, const void * data, int64_t n_frames, int sample_rate, int format,
+                                                  int64_t * n_samples, int64_t * stride);
+WHISPER_API int64_t       whisper_amd_audio_split_copy(struct whisper_state * state, int channel, float * dst, int64_t cap);
+WHISPER_API int           whisper_amd_channel_energy(struct whisper_state * state, const int64_t * is0, const int64_t * is1, int n_spans, int where,
+                                                     double * energy);
+WHISPER_API int           whisper_amd_channel_speakers(struct whisper_state * state, const int64_t * t0_cs, const int64_t * t1_cs, int n, double ratio,
+                                                       double * energy, int8_t * speaker);
+WHISPER_API void          whisper_amd_channels_default_params(struct whisper_amd_channels_params * p);
+WHISPER_API int           whisper_amd_full_long_channels(struct whisper_context * ctx, struct whisper_full_params params,
+                                                         const struct whisper_amd_channels_params * cp, const void * data, int64_t n_frames,
+                                                         int sample_rate, int format);
+WHISPER_API int           whisper_amd_long_segment_channel(struct whisper_context * ctx, int i_segment);
+WHISPER_API int           whisper_amd_long_chunk_channel(struct whisper_context * ctx, int i_chunk);
+WHISPER_API void          whisper_amd_channels_stats(struct whisper_context * ctx, int64_t out[11]);
+WHISPER_API int           whisper_amd_channels_tile(void);
+WHISPER_API int           whisper_amd_channels_energy_lanes(void);
+
 /* Forced alignment (wa_align.cpp): the audio and the text are both known; when was each token said, and how well does the
  * model agree with it?  One teacher-forced decoder pass over [sot, lang, not, tokens..., eot] - the pass whisper_full's DTW runs over its own
  * result - whose logits rows stay on the device: k_align_score (wa_align.hip) turns each row into one record there.

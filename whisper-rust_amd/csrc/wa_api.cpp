@@ -335,7 +335,7 @@ struct whisper_state * whisper_init_state(struct whisper_context * ctx) {
     return st;
 }
 
-void whisper_free_state(struct whisper_state * st) { if (st) { whisper_vad_free(st->vad_context); wa_long_free(*st); wa_state_release(*st); delete st; } }
+void whisper_free_state(struct whisper_state * st) { if (st) { whisper_vad_free(st->vad_context); wa_long_free(*st); wa_channels_free(*st); wa_state_release(*st); delete st; } }
 void whisper_free(struct whisper_context * ctx) {
     if (!ctx) return;
     wa_batcher_free_all(*ctx);

@@ -395,6 +395,10 @@ struct whisper_state {
     // long recordings (wa_long.cpp): the uploaded PCM, the chunk buffer, the piece table and the last call's chunk list;
     // made by the first whisper_amd_full_long / whisper_amd_long_pack call on this state, freed with it
     struct wa_long_state * lng = nullptr;
+
+    // two-channel recordings (wa_channels.cpp): the planar buffer of the last whisper_amd_audio_split, the span and energy tables
+    // and the counters; made by the first call on this state, freed with it
+    struct wa_channels_state * chn = nullptr;
 };
 // the form a state's single-token run-ahead window (wa_spec_*) runs on, is gated on and is charged with its time-outs
 inline wa_launch_form & wa_window_form(whisper_state & st) { return st.single_via_rows ? st.rows_form : st.mega_form; }
@@ -467,6 +471,7 @@ struct wa_batch_groups {
     }
 };
 void wa_long_free(whisper_state & st);            // wa_long.cpp: what whisper_amd_full_long / whisper_amd_long_pack keep on a state
+void wa_channels_free(whisper_state & st);        // wa_channels.cpp: what whisper_amd_audio_split / whisper_amd_channel_energy keep on a state
 void wa_align_free(whisper_state & st);           // wa_align.cpp: what whisper_amd_align / whisper_amd_align_score keep on a state
 // wa_dtw.cpp: the middle of the DTW token timestamps for any token sequence [sot.., not, text.., eot] with sot_len tokens in front of `not`: one
 // decoder pass over it with the alignment heads captured, then the device or the host DTW over n_frames / 2 audio positions.

@@ -8,30 +8,13 @@
 // stream synchronise - before the first wave starts: a foreign kernel beside the one-launch passes costs hand-off time-outs.
 // wa_vad_filter_audio, the host function, is the yardstick and the fallback: WHISPER_AMD_LONG_HOST=1, read at each call, takes it, and so
 // does a call whose HIP path fails (logged and counted).
-#include "wa_internal.h"
-#include "wa_long.h"
+#include "wa_long_host.h"
 
 #include <climits>
 #include <cstring>
 #include <thread>
 
-struct wa_long_rec {
-    int first = 0, count = 0, packed = 0;      // segments [first, first + count), samples of speech-only audio
-    int64_t off = 0;                           // its first float in d_chunks (a multiple of WA_LONG_ALIGN)
-    int64_t t0 = 0, t1 = 0;                    // the caller's centiseconds: start of the first segment, end of the last
-    int n_result = 0;                          // result segments it gave
-    std::vector<wa_vad_map_point> table;
-};
-
-struct wa_long_state {
-    float * d_pcm = nullptr; size_t d_pcm_cap = 0;                  // host PCM, uploaded once
-    float * d_chunks = nullptr; size_t d_chunks_cap = 0;            // every chunk of the last call
-    wa_long_piece * d_pieces = nullptr; size_t d_pieces_cap = 0;    // the pack kernel's table
-    std::vector<wa_long_rec> chunks;                                // the last call's
-    int64_t stats[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };                  // whisper_amd_long_stats; [1] counts since the state was created
-};
-
-static wa_long_state & long_of(whisper_state & st) {
+wa_long_state & wa_long_of(whisper_state & st) {
     if (!st.lng) st.lng = new wa_long_state;
     return *st.lng;
 }
@@ -49,7 +32,7 @@ void wa_long_free(whisper_state & st) {
 
 // host PCM into the state's buffer, once
 static const float * long_upload(whisper_state & st, const float * h_samples, int n_samples) {
-    wa_long_state & L = long_of(st);
+    wa_long_state & L = wa_long_of(st);
     if (!wa_dev_reserve(L.d_pcm, L.d_pcm_cap, (size_t) std::max(n_samples, WA_LONG_ALIGN))) return nullptr;
     if (!WA_HIP_OK(hipMemcpyAsync(L.d_pcm, h_samples, (size_t) n_samples * sizeof(float), hipMemcpyHostToDevice, st.stream)) ||
         !WA_HIP_OK(hipStreamSynchronize(st.stream))) return nullptr;
@@ -57,29 +40,33 @@ static const float * long_upload(whisper_state & st, const float * h_samples, in
     return L.d_pcm;
 }
 
-// Every chunk of `plan` into the state's chunk buffer and chunk list.  One of h_samples / d_samples may be null: the kernel path (where = 1)
-// uploads host audio first, the host path (where = 0) copies device audio down.  Complete - synchronised - on return.
-static bool long_pack(whisper_state & st, const float * h_samples, const float * d_samples, int n_samples, const wa_vad_seg * segs, float samples_overlap,
-                      const std::vector<wa_long_chunk> & plan, int where) {
-    wa_long_state & L = long_of(st);
+bool wa_long_pack(whisper_state & st, const float * h_samples, const float * d_samples, const std::vector<wa_long_src> & srcs,
+                  const std::vector<wa_long_pick> & order, float samples_overlap, int where) {
+    wa_long_state & L = wa_long_of(st);
     L.chunks.clear();
+    if (srcs.empty() || (h_samples && (srcs.size() != 1 || srcs[0].src_off != 0))) return false;
     std::vector<wa_long_piece> all, pieces;
+    std::vector<int> src_of;
     int64_t off = 0;
-    for (const wa_long_chunk & c : plan) {
+    for (const wa_long_pick & pk : order) {
+        if (pk.src < 0 || (size_t) pk.src >= srcs.size() || pk.chunk < 0 || (size_t) pk.chunk >= srcs[(size_t) pk.src].plan->size()) return false;
+        const wa_long_src & S = srcs[(size_t) pk.src];
+        const wa_long_chunk & c = (*S.plan)[(size_t) pk.chunk];
         wa_long_rec r;
-        r.first = c.first; r.count = c.count; r.off = off;
-        r.packed = wa_vad_layout_make(segs + c.first, c.count, samples_overlap, n_samples, &pieces, &r.table);
-        r.t0 = segs[c.first].start; r.t1 = segs[c.first + c.count - 1].end;
+        r.first = c.first; r.count = c.count; r.off = off; r.channel = S.channel;
+        r.packed = wa_vad_layout_make(S.segs + c.first, c.count, samples_overlap, S.n_samples, &pieces, &r.table);
+        r.t0 = S.segs[c.first].start; r.t1 = S.segs[c.first + c.count - 1].end;
         int64_t cur = off;
         for (const wa_long_piece & p : pieces) {        // contiguous from the chunk's start; the kernel trusts what is checked here
-            if (p.dst + off != cur || p.len <= 0 || p.src < -1 || (p.src >= 0 && p.src + p.len > (int64_t) n_samples) || cur + p.len > off + r.packed) return false;
-            all.push_back({ cur, p.src, p.len });
+            if (p.dst + off != cur || p.len <= 0 || p.src < -1 || (p.src >= 0 && p.src + p.len > (int64_t) S.n_samples) || cur + p.len > off + r.packed) return false;
+            all.push_back({ cur, p.src >= 0 ? p.src + S.src_off : -1, p.len });
             cur += p.len;
         }
         const int64_t next = (off + r.packed + WA_LONG_ALIGN - 1) / WA_LONG_ALIGN * WA_LONG_ALIGN;
         if (next > cur) all.push_back({ cur, -1, next - cur });     // what no piece covers is zero; so is the gap in front of the next chunk
         off = next;
         L.chunks.push_back(std::move(r));
+        src_of.push_back(pk.src);
     }
     const int64_t n_out = off;
     if (all.size() > (size_t) INT_MAX) return false;
@@ -87,31 +74,61 @@ static bool long_pack(whisper_state & st, const float * h_samples, const float *
     L.stats[0] = where;
     if (n_out == 0) return true;
     if (where == 1) {
-        const float * src = d_samples ? d_samples : long_upload(st, h_samples, n_samples);
+        const float * src = d_samples ? d_samples : long_upload(st, h_samples, srcs[0].n_samples);
         if (!src) return false;
-        return wa_dev_reserve(L.d_pieces, L.d_pieces_cap, all.size())
+        if (!(wa_dev_reserve(L.d_pieces, L.d_pieces_cap, all.size())
             && WA_HIP_OK(hipMemcpyAsync(L.d_pieces, all.data(), all.size() * sizeof(wa_long_piece), hipMemcpyHostToDevice, st.stream))
-            && wa_long_pack_launch((void *) st.stream, src, L.d_pieces, (int) all.size(), n_out, L.d_chunks)
-            && WA_HIP_OK(hipStreamSynchronize(st.stream));
+            && wa_long_pack_launch((void *) st.stream, src, L.d_pieces, (int) all.size(), n_out, L.d_chunks))) return false;
+        L.n_pack_launches++;
+        return WA_HIP_OK(hipStreamSynchronize(st.stream));
     }
-    std::vector<float> down;
-    const float * src = h_samples;
-    if (!src) {
-        down.resize((size_t) n_samples);
-        if (!WA_HIP_OK(hipStreamSynchronize(st.stream)) ||
-            !WA_HIP_OK(hipMemcpy(down.data(), d_samples, (size_t) n_samples * sizeof(float), hipMemcpyDeviceToHost))) return false;
-        src = down.data();
+    std::vector<std::vector<float>> down(srcs.size());
+    std::vector<const float *> host(srcs.size(), h_samples);
+    if (!h_samples) {
+        if (!WA_HIP_OK(hipStreamSynchronize(st.stream))) return false;
+        for (size_t k = 0; k < srcs.size(); ++k) {
+            down[k].resize((size_t) srcs[k].n_samples);
+            if (!WA_HIP_OK(hipMemcpy(down[k].data(), d_samples + srcs[k].src_off, down[k].size() * sizeof(float), hipMemcpyDeviceToHost))) return false;
+            host[k] = down[k].data();
+        }
     }
     std::vector<float> img((size_t) n_out, 0.0f), filtered;
     std::vector<wa_vad_map_point> table;
-    for (const wa_long_rec & r : L.chunks) {
-        const std::vector<wa_vad_seg> sub(segs + r.first, segs + r.first + r.count);
-        wa_vad_filter_audio(sub, samples_overlap, src, n_samples, filtered, table);
+    for (size_t c = 0; c < L.chunks.size(); ++c) {
+        const wa_long_rec & r = L.chunks[c];
+        const wa_long_src & S = srcs[(size_t) src_of[c]];
+        const std::vector<wa_vad_seg> sub(S.segs + r.first, S.segs + r.first + r.count);
+        wa_vad_filter_audio(sub, samples_overlap, host[(size_t) src_of[c]], S.n_samples, filtered, table);
         if ((int) filtered.size() != r.packed) return false;
         if (r.packed > 0) memcpy(img.data() + r.off, filtered.data(), (size_t) r.packed * sizeof(float));
     }
     return WA_HIP_OK(hipMemcpyAsync(L.d_chunks, img.data(), img.size() * sizeof(float), hipMemcpyHostToDevice, st.stream))
         && WA_HIP_OK(hipStreamSynchronize(st.stream));
+}
+
+bool wa_long_pack_any(whisper_state & st, const float * h_samples, const float * d_samples, const std::vector<wa_long_src> & srcs,
+                      const std::vector<wa_long_pick> & order, float samples_overlap, const char * who) {
+    wa_long_state & L = wa_long_of(st);
+    const char * env = getenv("WHISPER_AMD_LONG_HOST");
+    bool packed = false;
+    if (!(env && atoi(env) != 0)) {
+        packed = wa_long_pack(st, h_samples, d_samples, srcs, order, samples_overlap, 1);
+        if (!packed) { L.stats[1]++; (void) hipGetLastError(); WA_WARN("%s: the device pack failed, taking the host path\n", who); }
+    }
+    if (!packed && !wa_long_pack(st, h_samples, d_samples, srcs, order, samples_overlap, 0)) {
+        WA_ERROR("%s: the host pack failed\n", who);
+        L.chunks.clear();
+        return false;
+    }
+    return true;
+}
+
+// one segment list over one buffer, every chunk of its plan in order
+static void single_source(const wa_vad_seg * segs, int n_samples, const std::vector<wa_long_chunk> & plan, std::vector<wa_long_src> & srcs,
+                          std::vector<wa_long_pick> & order) {
+    srcs = { { segs, n_samples, 0, -1, &plan } };
+    order.clear();
+    for (size_t c = 0; c < plan.size(); ++c) order.push_back({ 0, (int) c });
 }
 
 static std::vector<wa_vad_seg> long_segs(const int64_t * segs_cs, int n_segs) {
@@ -139,11 +156,71 @@ static void long_wave(whisper_context * ctx, const std::vector<whisper_state *> 
     for (auto & w : workers) w.join();
 }
 
+int wa_long_waves(whisper_context * ctx, const whisper_full_params & params, int n_parallel, std::vector<std::vector<wa_segment>> & results) {
+    whisper_state * st = ctx->state;
+    wa_long_state & L = wa_long_of(*st);
+    const int64_t t = wa_time_us();
+    const size_t n_chunks = L.chunks.size();
+    std::vector<whisper_state *> states = { st };         // the context's state and, as whisper_full_parallel, states of this call
+    auto release = [&]() { for (size_t i = 1; i < states.size(); ++i) whisper_free_state(states[i]); states.resize(1); };
+    for (size_t i = 1; i < std::min(n_chunks, (size_t) n_parallel); ++i) {
+        whisper_state * s = whisper_init_state(ctx);
+        if (!s) { release(); L.chunks.clear(); return -1; }
+        states.push_back(s);
+    }
+    whisper_full_params pc = params;
+    pc.vad = false; pc.offset_ms = 0; pc.duration_ms = 0;
+    pc.print_progress = false; pc.print_realtime = false; pc.print_timestamps = false; pc.print_special = false;
+    pc.new_segment_callback = nullptr; pc.new_segment_callback_user_data = nullptr;
+    pc.progress_callback = nullptr; pc.progress_callback_user_data = nullptr;
+
+    std::vector<int> rcs(n_chunks, 0);
+    results.assign(n_chunks, std::vector<wa_segment>());
+    long steps = 0, rows = 0, one_launch = 0, served = 0;
+    int lang_id = st->lang_id;
+    for (size_t c0 = 0; c0 < n_chunks; c0 += states.size()) {
+        const std::vector<whisper_state *> members(states.begin(), states.begin() + std::min(states.size(), n_chunks - c0));
+        long_wave(ctx, members, pc, L.d_chunks, L.chunks, c0, rcs);
+        steps += ctx->batch_steps; rows += ctx->batch_rows; one_launch += ctx->batch_one_launch; served += ctx->batch_served;
+        for (size_t i = 0; i < members.size(); ++i) { results[c0 + i] = std::move(members[i]->result_all); members[i]->result_all.clear(); }
+        if (c0 == 0) lang_id = st->lang_id;
+        L.stats[3]++;
+    }
+    ctx->batch_steps = steps; ctx->batch_rows = rows; ctx->batch_one_launch = one_launch; ctx->batch_served = served;
+    for (size_t i = 1; i < states.size(); ++i) {
+        whisper_state * s = states[i];
+        st->t_mel_us += s->t_mel_us; st->t_sample_us += s->t_sample_us; st->t_encode_us += s->t_encode_us; st->t_decode_us += s->t_decode_us;
+        st->t_batchd_us += s->t_batchd_us; st->t_prompt_us += s->t_prompt_us;
+        st->n_sample += s->n_sample; st->n_encode += s->n_encode; st->n_decode += s->n_decode; st->n_batchd += s->n_batchd; st->n_prompt += s->n_prompt;
+    }
+    release();
+    st->lang_id = lang_id;
+    st->vad_mapping_table.clear();                  // the times are stored mapped: the getters return them as they are
+    st->has_vad_segments = false;
+    L.stats[6] = wa_time_us() - t;                  // states and waves; a caller that maps the times afterwards sets it again, mapping included
+    for (int rc : rcs) if (rc != 0) { L.chunks.clear(); return rc; }       // a failed call describes no chunks
+    return 0;
+}
+
+void wa_long_map_segment(wa_segment & seg, const std::vector<wa_vad_map_point> & table) {
+    const int64_t t0 = wa_vad_map_time(seg.t0, table);
+    int64_t t1 = wa_vad_map_time(seg.t1, table);
+    if (t1 - t0 < 10) t1 = t0 + 10;
+    seg.t0 = t0;
+    seg.t1 = t1;
+    for (whisper_token_data & tok : seg.tokens) {
+        if (tok.t0 >= 0) tok.t0 = wa_vad_map_time(tok.t0, table);
+        if (tok.t1 >= 0) tok.t1 = wa_vad_map_time(tok.t1, table);
+        if (tok.t_dtw >= 0) tok.t_dtw = wa_vad_map_time(tok.t_dtw, table);
+    }
+}
+
 static int long_full(whisper_context * ctx, whisper_full_params params, const float * samples, int n_samples, int max_chunk_ms, int n_parallel) {
     whisper_state * st = ctx->state;
-    wa_long_state & L = long_of(*st);
+    wa_long_state & L = wa_long_of(*st);
     st->result_all.clear();
     L.chunks.clear();
+    L.seg_channel.clear();
     for (int k : { 0, 2, 3, 4, 5, 6, 7 }) L.stats[k] = 0;
     if (max_chunk_ms <= 0) max_chunk_ms = 30000;
     if (n_parallel <= 0) n_parallel = 8;
@@ -165,82 +242,32 @@ static int long_full(whisper_context * ctx, whisper_full_params params, const fl
 
     t = wa_time_us();
     const std::vector<wa_long_chunk> plan = wa_long_plan(segs.data(), (int) segs.size(), n_samples, params.vad_params.samples_overlap, max_chunk_samples);
-    const char * env = getenv("WHISPER_AMD_LONG_HOST");
-    bool packed = false;
-    if (!(env && atoi(env) != 0)) {
-        packed = long_pack(*st, on_device ? nullptr : samples, d_samples, n_samples, segs.data(), params.vad_params.samples_overlap, plan, 1);
-        if (!packed) { L.stats[1]++; (void) hipGetLastError(); WA_WARN("%s: the device pack failed, taking the host path\n", __func__); }
-    }
-    if (!packed && !long_pack(*st, on_device ? nullptr : samples, d_samples, n_samples, segs.data(), params.vad_params.samples_overlap, plan, 0)) {
-        WA_ERROR("%s: the host pack failed\n", __func__);
-        L.chunks.clear();
-        return -1;
-    }
+    std::vector<wa_long_src> srcs;
+    std::vector<wa_long_pick> order;
+    single_source(segs.data(), n_samples, plan, srcs, order);
+    if (!wa_long_pack_any(*st, on_device ? nullptr : samples, d_samples, srcs, order, params.vad_params.samples_overlap, __func__)) return -1;
     L.stats[5] = wa_time_us() - t;
     L.stats[2] = (int64_t) L.chunks.size();
     WA_INFO("%s: %d speech segments in %d chunks of at most %d ms\n", __func__, (int) segs.size(), (int) L.chunks.size(), max_chunk_ms);
 
     t = wa_time_us();
-    const size_t n_chunks = L.chunks.size();
-    std::vector<whisper_state *> states = { st };         // the context's state and, as whisper_full_parallel, states of this call
-    auto release = [&]() { for (size_t i = 1; i < states.size(); ++i) whisper_free_state(states[i]); states.resize(1); };
-    for (size_t i = 1; i < std::min(n_chunks, (size_t) n_parallel); ++i) {
-        whisper_state * s = whisper_init_state(ctx);
-        if (!s) { release(); L.chunks.clear(); return -1; }
-        states.push_back(s);
-    }
-    whisper_full_params pc = params;
-    pc.vad = false; pc.offset_ms = 0; pc.duration_ms = 0;
-    pc.print_progress = false; pc.print_realtime = false; pc.print_timestamps = false; pc.print_special = false;
-    pc.new_segment_callback = nullptr; pc.new_segment_callback_user_data = nullptr;
-    pc.progress_callback = nullptr; pc.progress_callback_user_data = nullptr;
-
-    std::vector<int> rcs(n_chunks, 0);
-    std::vector<std::vector<wa_segment>> results(n_chunks);
-    long steps = 0, rows = 0, one_launch = 0, served = 0;
-    int lang_id = st->lang_id;
-    for (size_t c0 = 0; c0 < n_chunks; c0 += states.size()) {
-        const std::vector<whisper_state *> members(states.begin(), states.begin() + std::min(states.size(), n_chunks - c0));
-        long_wave(ctx, members, pc, L.d_chunks, L.chunks, c0, rcs);
-        steps += ctx->batch_steps; rows += ctx->batch_rows; one_launch += ctx->batch_one_launch; served += ctx->batch_served;
-        for (size_t i = 0; i < members.size(); ++i) { results[c0 + i] = std::move(members[i]->result_all); members[i]->result_all.clear(); }
-        if (c0 == 0) lang_id = st->lang_id;
-        L.stats[3]++;
-    }
-    ctx->batch_steps = steps; ctx->batch_rows = rows; ctx->batch_one_launch = one_launch; ctx->batch_served = served;
-    for (size_t i = 1; i < states.size(); ++i) {
-        whisper_state * s = states[i];
-        st->t_mel_us += s->t_mel_us; st->t_sample_us += s->t_sample_us; st->t_encode_us += s->t_encode_us; st->t_decode_us += s->t_decode_us;
-        st->t_batchd_us += s->t_batchd_us; st->t_prompt_us += s->t_prompt_us;
-        st->n_sample += s->n_sample; st->n_encode += s->n_encode; st->n_decode += s->n_decode; st->n_batchd += s->n_batchd; st->n_prompt += s->n_prompt;
-    }
-    release();
-    st->lang_id = lang_id;
-    st->vad_mapping_table.clear();                  // the times below are stored mapped: the getters return them as they are
-    st->has_vad_segments = false;
-    for (int rc : rcs) if (rc != 0) { L.stats[6] = wa_time_us() - t; L.chunks.clear(); return rc; }       // a failed call describes no chunks
+    std::vector<std::vector<wa_segment>> results;
+    const int rc = wa_long_waves(ctx, params, n_parallel, results);
+    if (rc != 0) return rc;
 
     // the chunks' segments in chunk order, their times mapped into the caller's audio through the chunk's own table: a segment lasts
     // at least 10 cs (the getters' rule) and does not start before the previous one ended
-    for (size_t c = 0; c < n_chunks; ++c) {
+    for (size_t c = 0; c < L.chunks.size(); ++c) {
         wa_long_rec & r = L.chunks[c];
         r.n_result = (int) results[c].size();
         for (wa_segment & seg : results[c]) {
-            const int64_t t0 = wa_vad_map_time(seg.t0, r.table);
-            int64_t t1 = wa_vad_map_time(seg.t1, r.table);
-            if (t1 - t0 < 10) t1 = t0 + 10;
-            seg.t0 = st->result_all.empty() ? t0 : std::max(t0, st->result_all.back().t1);
-            seg.t1 = t1;
-            for (whisper_token_data & tok : seg.tokens) {
-                if (tok.t0 >= 0) tok.t0 = wa_vad_map_time(tok.t0, r.table);
-                if (tok.t1 >= 0) tok.t1 = wa_vad_map_time(tok.t1, r.table);
-                if (tok.t_dtw >= 0) tok.t_dtw = wa_vad_map_time(tok.t_dtw, r.table);
-            }
+            wa_long_map_segment(seg, r.table);
+            if (!st->result_all.empty()) seg.t0 = std::max(seg.t0, st->result_all.back().t1);
             st->result_all.push_back(std::move(seg));
             if (params.new_segment_callback) params.new_segment_callback(ctx, st, 1, params.new_segment_callback_user_data);
         }
     }
-    L.stats[6] = wa_time_us() - t;
+    L.stats[6] = wa_time_us() - t;                  // as before the waves became wa_long_waves: member states, waves and mapping
     return 0;
 }
 
@@ -319,12 +346,15 @@ int whisper_amd_long_pack(struct whisper_state * st, const float * samples, int 
         }
         if (!WA_HIP_OK(hipSetDevice(st->ctx->device))) return -1;
         const bool on_device = wa_is_device_ptr(samples);
-        long_of(*st).stats[7] = 0;
-        if (!long_pack(*st, on_device ? nullptr : samples, on_device ? samples : nullptr, n_samples, segs.data(), samples_overlap, plan, where)) {
-            long_of(*st).chunks.clear();
+        wa_long_of(*st).stats[7] = 0;
+        std::vector<wa_long_src> srcs;
+        std::vector<wa_long_pick> order;
+        single_source(segs.data(), n_samples, plan, srcs, order);
+        if (!wa_long_pack(*st, on_device ? nullptr : samples, on_device ? samples : nullptr, srcs, order, samples_overlap, where)) {
+            wa_long_of(*st).chunks.clear();
             return -1;
         }
-        long_of(*st).stats[2] = n_chunks;
+        wa_long_of(*st).stats[2] = n_chunks;
         return 0;
     } catch (const std::exception & e) { WA_ERROR("%s: exception: %s\n", __func__, e.what()); return -1; }
 }

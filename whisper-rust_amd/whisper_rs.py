@@ -99,6 +99,10 @@ ALIGN_BAD_TOKEN, ALIGN_NO_TOKENS, ALIGN_TOO_LONG, ALIGN_FLASH_ATTN, ALIGN_TOO_SH
 ALIGN_SCORE_DTYPE = np.dtype([("plog", "<f4"), ("p", "<f4"), ("best_id", "<i4"), ("best_plog", "<f4"), ("rank", "<i4"), ("best_p", "<f4")])
 
 
+class whisper_amd_channels_params(C.Structure):  # 16 bytes, passed by pointer (include/whisper_amd.h)
+    _fields_ = [("max_chunk_ms", C.c_int32), ("n_parallel", C.c_int32), ("crosstalk_ratio", C.c_double)]
+
+
 class whisper_amd_stream_params(C.Structure):    # 36 bytes, passed by pointer (include/whisper_amd.h)
     _fields_ = [(n, C.c_int32) for n in ("step_ms", "length_ms", "keep_ms", "sample_rate", "channels", "format", "backlog_ms", "carry_prompt", "drop_late")]
 
@@ -322,6 +326,19 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         proto("whisper_amd_long_tile", I)
         proto("whisper_amd_context_state", P, P)
         proto("whisper_amd_batch_stats", None, P, C.POINTER(C.c_long), C.POINTER(C.c_long))
+    if hasattr(lib, "whisper_amd_audio_split"):
+        I64P = C.POINTER(C.c_int64)
+        proto("whisper_amd_audio_split", P, P, P, C.c_int64, I, I, I64P, I64P)
+        proto("whisper_amd_audio_split_copy", C.c_int64, P, I, C.POINTER(F), C.c_int64)
+        proto("whisper_amd_channel_energy", I, P, I64P, I64P, I, I, C.POINTER(C.c_double))
+        proto("whisper_amd_channel_speakers", I, P, I64P, I64P, I, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_int8))
+        proto("whisper_amd_channels_default_params", None, C.POINTER(whisper_amd_channels_params))
+        proto("whisper_amd_full_long_channels", I, P, whisper_full_params, C.POINTER(whisper_amd_channels_params), P, C.c_int64, I, I)
+        proto("whisper_amd_long_segment_channel", I, P, I)
+        proto("whisper_amd_long_chunk_channel", I, P, I)
+        proto("whisper_amd_channels_stats", None, P, I64P)
+        proto("whisper_amd_channels_tile", I)
+        proto("whisper_amd_channels_energy_lanes", I)
     if hasattr(lib, "whisper_amd_align"):
         proto("whisper_amd_align", I, P, P, whisper_full_params, P, I, C.POINTER(C.c_int32), I, C.POINTER(whisper_amd_align_token))
         proto("whisper_amd_align_score", I, P, C.POINTER(F), I, I, C.POINTER(C.c_int32), I, C.POINTER(whisper_amd_align_score))
@@ -780,6 +797,50 @@ class WhisperState:
             raise WhisperError("NoAudio", -1)
         return out[:n]
 
+    # -- two-channel recordings (whisper_amd_audio_split, whisper_amd_channel_*) ------------------
+    def audio_split(self, data, sample_rate: int, fmt: Optional[int] = None) -> tuple:
+        """Extension (whisper_amd_audio_split): `data` interleaved stereo as _audio_args takes it.  Returns (device pointer, n_samples, stride):
+        channel c lies at pointer + 4 * c * stride bytes, valid until the next split on this state."""
+        ptr, n_frames, fmt = self._audio_args(data, 2, fmt)
+        n, stride = C.c_int64(-1), C.c_int64(-1)
+        r = self.lib.whisper_amd_audio_split(self.ptr, C.c_void_p(ptr), n_frames, sample_rate, fmt, C.byref(n), C.byref(stride))
+        if not r:
+            raise WhisperError("AudioRefused", -1)
+        return r, int(n.value), int(stride.value)
+
+    def audio_split_copy(self, channel: int) -> np.ndarray:
+        """Extension (whisper_amd_audio_split_copy): plane `channel` of the last audio_split as a host array."""
+        n = self.lib.whisper_amd_audio_split_copy(self.ptr, channel, None, 0)
+        if n < 0:
+            raise WhisperError("NoAudio", int(n))
+        out = np.zeros(max(n, 1), np.float32)
+        if self.lib.whisper_amd_audio_split_copy(self.ptr, channel, out.ctypes.data_as(C.POINTER(C.c_float)), n) != n:
+            raise WhisperError("NoAudio", -1)
+        return out[:n]
+
+    def channel_energy(self, spans, where: int = -1) -> np.ndarray:
+        """Extension (whisper_amd_channel_energy): `spans` [(first sample, end sample)] -> float64 [n][2]; where 0 host, 1 kernel, else either."""
+        a = np.ascontiguousarray([s[0] for s in spans], dtype=np.int64)
+        b = np.ascontiguousarray([s[1] for s in spans], dtype=np.int64)
+        e = np.full((max(len(spans), 1), 2), np.nan, np.float64)
+        I64P = C.POINTER(C.c_int64)
+        if self.lib.whisper_amd_channel_energy(self.ptr, a.ctypes.data_as(I64P), b.ctypes.data_as(I64P), len(spans), where,
+                                               e.ctypes.data_as(C.POINTER(C.c_double))) != 0:
+            raise WhisperError("GenericError", -1)
+        return e[:len(spans)]
+
+    def channel_speakers(self, times_cs, ratio: float = 0.0) -> tuple:
+        """Extension (whisper_amd_channel_speakers): `times_cs` [(t0, t1)] in centiseconds -> (labels int8 [n]: 0, 1, -1 = undecided; energies [n][2])."""
+        a = np.ascontiguousarray([t[0] for t in times_cs], dtype=np.int64)
+        b = np.ascontiguousarray([t[1] for t in times_cs], dtype=np.int64)
+        e = np.full((max(len(times_cs), 1), 2), np.nan, np.float64)
+        lab = np.full(max(len(times_cs), 1), -2, np.int8)
+        I64P = C.POINTER(C.c_int64)
+        if self.lib.whisper_amd_channel_speakers(self.ptr, a.ctypes.data_as(I64P), b.ctypes.data_as(I64P), len(times_cs), ratio,
+                                                 e.ctypes.data_as(C.POINTER(C.c_double)), lab.ctypes.data_as(C.POINTER(C.c_int8))) != 0:
+            raise WhisperError("GenericError", -1)
+        return lab[:len(times_cs)], e[:len(times_cs)]
+
     def audio_stats(self) -> tuple:
         """Extension: audio front end calls on this state (served by the kernels, served by the host restatement, kernel attempts that fell back)."""
         out = (C.c_long * 3)()
@@ -1070,6 +1131,37 @@ class WhisperFullContext:
         count = np.ascontiguousarray([r[1] for r in runs], dtype=np.int32)
         return self.lib.whisper_amd_long_pack(self.state_ptr(), C.c_void_p(ptr), n, s.ctypes.data_as(C.POINTER(C.c_int64)), len(s) // 2, overlap,
                                               first.ctypes.data_as(C.POINTER(C.c_int32)), count.ctypes.data_as(C.POINTER(C.c_int32)), len(runs), where)
+
+    # -- two-channel recordings (whisper_amd_full_long_channels) ----------------------------------
+    def full_long_channels(self, params: FullParams, data, sample_rate: int, fmt: Optional[int] = None, max_chunk_ms: int = 0, n_parallel: int = 0,
+                           crosstalk_ratio: float = 0.0) -> int:
+        """Extension (whisper_amd_full_long_channels).  `data`: interleaved stereo int16 / float32 on the host, or (device pointer, n_frames) with `fmt`."""
+        if isinstance(data, tuple):
+            ptr, n_frames = data
+        else:
+            if fmt is None:
+                fmt = PCM_I16 if np.asarray(data).dtype == np.int16 else PCM_F32
+            self._audio_keep = data = np.ascontiguousarray(data, dtype=np.int16 if fmt == PCM_I16 else np.float32).reshape(-1)
+            ptr, n_frames = (data.ctypes.data if len(data) else None), len(data) // 2
+        cp = whisper_amd_channels_params()
+        self.lib.whisper_amd_channels_default_params(C.byref(cp))
+        cp.max_chunk_ms, cp.n_parallel, cp.crosstalk_ratio = max_chunk_ms, n_parallel, crosstalk_ratio
+        return self.lib.whisper_amd_full_long_channels(self.ptr, params.c, C.byref(cp), C.c_void_p(ptr), n_frames, sample_rate, fmt)
+
+    def segment_channels(self) -> list[int]:
+        """Extension (whisper_amd_long_segment_channel): the channel of every result segment; -1 where the last long call had no channels."""
+        return [self.lib.whisper_amd_long_segment_channel(self.ptr, i) for i in range(self.lib.whisper_full_n_segments(self.ptr))]
+
+    def chunk_channels(self) -> list[int]:
+        """Extension (whisper_amd_long_chunk_channel): the channel of every chunk of the last call, in wave order."""
+        return [self.lib.whisper_amd_long_chunk_channel(self.ptr, i) for i in range(self.lib.whisper_amd_long_n_chunks(self.ptr))]
+
+    def channels_stats(self) -> dict:
+        """Extension (whisper_amd_channels_stats) of the last whisper_amd_full_long_channels call."""
+        v = (C.c_int64 * 11)()
+        self.lib.whisper_amd_channels_stats(self.ptr, v)
+        return dict(zip(("split_path", "split_fallbacks", "energy_launches", "pack_launches", "segments_0", "segments_1", "dropped", "chunks", "waves",
+                         "h2d_bytes", "energy_fallbacks"), (int(x) for x in v)))
 
     def batch_stats(self) -> tuple:
         """Extension (whisper_amd_batch_stats): lock-step passes of the last batch / parallel / long call and the rows they served."""
