@@ -1,7 +1,7 @@
 // wa_api.cpp - the C ABI (include/whisper_amd.h): constructors, stage API, getters, language table,
 // tokenizer, logging, default parameters.  Everything here is host-side glue; the compute lives in
 // wa_encode.cpp / wa_decode.cpp / wa_kernels.hip and the decode loop in wa_full.cpp.
-#include "wa_internal.h"
+#include "wa_wave.h"
 
 #include <algorithm>
 #include <chrono>
@@ -172,8 +172,7 @@ whisper_context * init_common(whisper_model_loader * loader, whisper_context_par
     ctx->params = params;
     ctx->device = params.gpu_device;
     ctx->exact = !params.flash_attn;   // flash_attn trades the reference's summation order for MFMA speed, as it does in the reference
-    bool ok = false;
-    try { ok = wa_model_load(loader, *ctx); } catch (const std::exception & e) { WA_ERROR("%s: exception: %s\n", __func__, e.what()); ok = false; }
+    const bool ok = wa_guard(__func__, false, [&] { return wa_model_load(loader, *ctx); });
     loader->close(loader->context);
     if (!ok) {
         WA_ERROR("%s: failed to load model\n", __func__);
@@ -329,9 +328,7 @@ static bool aheads_init(const whisper_context & ctx, whisper_state & st) {
 struct whisper_state * whisper_init_state(struct whisper_context * ctx) {
     if (!ctx) return nullptr;
     whisper_state * st = new whisper_state;
-    bool ok = false;
-    try { ok = wa_state_alloc(*ctx, *st) && aheads_init(*ctx, *st); } catch (...) { ok = false; }
-    if (!ok) { WA_ERROR("%s: failed to allocate state\n", __func__); whisper_free_state(st); return nullptr; }
+    if (!wa_guard(__func__, false, [&] { return wa_state_alloc(*ctx, *st) && aheads_init(*ctx, *st); })) { WA_ERROR("%s: failed to allocate state\n", __func__); whisper_free_state(st); return nullptr; }
     return st;
 }
 
@@ -397,7 +394,7 @@ float * whisper_get_logits(struct whisper_context * ctx) { return ctx->state->lo
 // -------------------------------------------------------------------------------------------------
 int whisper_tokenize(struct whisper_context * ctx, const char * text, whisper_token * tokens, int n_max_tokens) {
     std::vector<int> res;
-    try { res = wa_tokenize(ctx->vocab, text); } catch (...) { return -1; }
+    if (!wa_guard(__func__, false, [&] { res = wa_tokenize(ctx->vocab, text); return true; })) return -1;
     if (n_max_tokens < (int) res.size()) {
         WA_ERROR("%s: too many resulting tokens: %d (max %d)\n", __func__, (int) res.size(), n_max_tokens);
         return -(int) res.size();
@@ -589,27 +586,25 @@ struct whisper_full_params * whisper_full_default_params_by_ref(enum whisper_sam
 // -------------------------------------------------------------------------------------------------
 int whisper_full_with_state(struct whisper_context * ctx, struct whisper_state * st, struct whisper_full_params params, const float * samples, int n_samples) {
     if (!ctx || !st) return -1;
-    try { return wa_full(ctx, st, params, samples, n_samples); }
-    catch (const std::exception & e) { WA_ERROR("%s: exception: %s\n", __func__, e.what()); return -1; }
-    catch (...) { WA_ERROR("%s: unknown exception\n", __func__); return -1; }
+    return wa_guard(__func__, -1, [&] { return wa_full(ctx, st, params, samples, n_samples); });
 }
 // vad = true: the speech-only audio of whisper_full / whisper_full_parallel, computed on ctx->state (whose table the getters then use)
 static int vad_prepare(whisper_context * ctx, const whisper_full_params & params, const float * samples, int n_samples, std::vector<float> & vad_samples) {
-    try {
-        if (wa_vad_for_full(ctx, ctx->state, params, samples, n_samples, vad_samples)) return 0;
-        WA_ERROR("%s: failed to compute VAD\n", __func__);
-    } catch (const std::exception & e) { WA_ERROR("%s: exception: %s\n", __func__, e.what()); }
+    if (wa_vad_for_full(ctx, ctx->state, params, samples, n_samples, vad_samples)) return 0;
+    WA_ERROR("%s: failed to compute VAD\n", __func__);
     return -1;
 }
 int whisper_full(struct whisper_context * ctx, struct whisper_full_params params, const float * samples, int n_samples) {
     if (!ctx || !ctx->state) return -1;
-    std::vector<float> vad_samples;
-    if (params.vad) {            // ref: whisper.cpp:7719-7732
-        if (vad_prepare(ctx, params, samples, n_samples, vad_samples) < 0) return -1;
-        if (vad_samples.empty()) { ctx->state->result_all.clear(); return 0; }
-        samples = vad_samples.data(); n_samples = (int) vad_samples.size();
-    }
-    return whisper_full_with_state(ctx, ctx->state, params, samples, n_samples);
+    return wa_guard(__func__, -1, [&] {
+        std::vector<float> vad_samples;
+        if (params.vad) {            // ref: whisper.cpp:7719-7732
+            if (vad_prepare(ctx, params, samples, n_samples, vad_samples) < 0) return -1;
+            if (vad_samples.empty()) { ctx->state->result_all.clear(); return 0; }
+            samples = vad_samples.data(); n_samples = (int) vad_samples.size();
+        }
+        return whisper_full_with_state(ctx, ctx->state, params, samples, n_samples);
+    });
 }
 int whisper_full_parallel(struct whisper_context * ctx, struct whisper_full_params params, const float * samples, int n_samples, int n_processors) {
     // ref: whisper.cpp:7736-7864: the audio is cut into n_processors equal parts, each transcribed on a state of its own (here:
@@ -617,62 +612,50 @@ int whisper_full_parallel(struct whisper_context * ctx, struct whisper_full_para
     // the transcription may be degraded near the cuts.
     if (!ctx || !ctx->state) return -1;
     if (n_processors <= 1) return whisper_full(ctx, params, samples, n_samples);
-    std::vector<float> vad_samples;
-    if (params.vad) {            // ref: whisper.cpp:7747-7759 (no speech: 0, and unlike whisper_full the earlier results stay)
-        if (vad_prepare(ctx, params, samples, n_samples, vad_samples) < 0) return -1;
-        if (vad_samples.empty()) return 0;
-        samples = vad_samples.data(); n_samples = (int) vad_samples.size();
-    }
-    const int offset_samples = (WHISPER_SAMPLE_RATE * params.offset_ms) / 1000;
-    const int n_per = (n_samples - offset_samples) / n_processors;
-    std::vector<whisper_state *> states;
-    std::vector<std::thread> workers;
-    std::vector<int> rcs(n_processors, 0);
-    for (int i = 0; i < n_processors - 1; ++i) {
-        whisper_state * st = whisper_init_state(ctx);
-        if (!st) { for (auto * s2 : states) whisper_free_state(s2); return -1; }
-        states.push_back(st);
-    }
-    std::vector<whisper_state *> members = { ctx->state };
-    members.insert(members.end(), states.begin(), states.end());
-    {
-    wa_batch_groups groups(ctx, members);           // the parts' single-token steps in lock step (as whisper_amd_full_batch); ends with the joins
-    for (int i = 0; i < n_processors - 1; ++i) {
-        whisper_state * st = states[i];
-        const int start = offset_samples + (i + 1) * n_per;
-        const int n_cur = (i == n_processors - 2) ? n_samples - start : n_per;
-        whisper_full_params pc = params;
-        pc.offset_ms = 0; pc.print_progress = false; pc.print_realtime = false;
-        pc.new_segment_callback = nullptr; pc.new_segment_callback_user_data = nullptr;
-        pc.progress_callback = nullptr; pc.progress_callback_user_data = nullptr;
-        workers.emplace_back([=, &rcs]() { rcs[i + 1] = whisper_full_with_state(ctx, st, pc, samples + start, n_cur); wa_batcher_leave(st->batcher); });
-    }
-    {
-        whisper_full_params pc = params;
-        pc.print_realtime = false;
-        rcs[0] = whisper_full_with_state(ctx, ctx->state, pc, samples, offset_samples + n_per);
-        wa_batcher_leave(ctx->state->batcher);
-    }
-    for (auto & w : workers) w.join();
-    }
+    std::vector<whisper_state *> states;            // the parts' own states: freed below whatever happens behind the guard
+    const int rc = wa_guard(__func__, -1, [&] {
+        std::vector<float> vad_samples;
+        if (params.vad) {            // ref: whisper.cpp:7747-7759 (no speech: 0, and unlike whisper_full the earlier results stay)
+            if (vad_prepare(ctx, params, samples, n_samples, vad_samples) < 0) return -1;
+            if (vad_samples.empty()) return 0;
+            samples = vad_samples.data(); n_samples = (int) vad_samples.size();
+        }
+        const int offset_samples = (WHISPER_SAMPLE_RATE * params.offset_ms) / 1000;
+        const int n_per = (n_samples - offset_samples) / n_processors;
+        std::vector<whisper_state *> members = { ctx->state };
+        for (int i = 1; i < n_processors; ++i) {
+            whisper_state * st = whisper_init_state(ctx);
+            if (!st) return -1;
+            states.push_back(st);
+            members.push_back(st);
+        }
+        // the parts' single-token steps in lock step (as whisper_amd_full_batch): part 0 with the caller's params but for print_realtime, the others silent
+        whisper_full_params p0 = params, pc = params;
+        p0.print_realtime = false;
+        wa_params_silent(pc);
+        pc.offset_ms = 0;
+        const std::vector<int> rcs = wa_wave_run(ctx, members, [&](size_t i) {
+            if (i == 0) return whisper_full_with_state(ctx, members[0], p0, samples, offset_samples + n_per);
+            const int start = offset_samples + (int) i * n_per;
+            return whisper_full_with_state(ctx, members[i], pc, samples + start, (int) i == n_processors - 1 ? n_samples - start : n_per);
+    });
     const int64_t offset_t = (int64_t) params.offset_ms / 10.0;
-    for (int i = 0; i < n_processors - 1; ++i) {
-        for (auto & r : states[i]->result_all) {
-            r.t0 += 100 * ((i + 1) * n_per) / WHISPER_SAMPLE_RATE + offset_t;
-            r.t1 += 100 * ((i + 1) * n_per) / WHISPER_SAMPLE_RATE + offset_t;
+    for (int i = 1; i < n_processors; ++i) {
+        for (auto & r : members[i]->result_all) {
+            r.t0 += 100 * (i * n_per) / WHISPER_SAMPLE_RATE + offset_t;
+            r.t1 += 100 * (i * n_per) / WHISPER_SAMPLE_RATE + offset_t;
             if (!ctx->state->result_all.empty()) r.t0 = std::max(r.t0, ctx->state->result_all.back().t1);    // no overlapping segments
             ctx->state->result_all.push_back(std::move(r));
             if (params.new_segment_callback) params.new_segment_callback(ctx, ctx->state, 1, params.new_segment_callback_user_data);
         }
-        ctx->state->t_mel_us += states[i]->t_mel_us; ctx->state->t_sample_us += states[i]->t_sample_us; ctx->state->t_encode_us += states[i]->t_encode_us;
-        ctx->state->t_decode_us += states[i]->t_decode_us; ctx->state->t_batchd_us += states[i]->t_batchd_us; ctx->state->t_prompt_us += states[i]->t_prompt_us;
-        ctx->state->n_sample += states[i]->n_sample; ctx->state->n_encode += states[i]->n_encode; ctx->state->n_decode += states[i]->n_decode;
-        ctx->state->n_batchd += states[i]->n_batchd; ctx->state->n_prompt += states[i]->n_prompt;
-        whisper_free_state(states[i]);
+        wa_state_add_counters(*ctx->state, *members[i]);
     }
     ctx->state->t_mel_us /= n_processors; ctx->state->t_sample_us /= n_processors; ctx->state->t_encode_us /= n_processors; ctx->state->t_decode_us /= n_processors;
-    WA_WARN("%s: the audio has been split into %d chunks; the transcription quality may be degraded near the boundaries\n", __func__, n_processors);
-    return rcs[0];
+    WA_WARN("whisper_full_parallel: the audio has been split into %d chunks; the transcription quality may be degraded near the boundaries\n", n_processors);
+    return rcs[0];          // as the reference: the other parts' codes are not reported
+    });
+    for (whisper_state * st : states) whisper_free_state(st);
+    return rc;
 }
 
 // -------------------------------------------------------------------------------------------------
@@ -771,26 +754,18 @@ int whisper_amd_decoder_info(struct whisper_state * st, int j, double out[8], in
 int whisper_amd_full_batch(struct whisper_context * ctx, struct whisper_state ** states, int n_chunks, struct whisper_full_params params,
                            const float * const * samples, const int * n_samples) {
     // Chunks are independent: each runs the ordinary whisper_full_with_state loop on its own state and HIP
-    // stream from its own host thread.  A single decode step is latency-bound and occupies a fraction of the 256 CUs, so the
+    // stream from a host thread of its own (chunk 0: the calling thread; wa_wave.h).  A single decode step is latency-bound and occupies a fraction of the 256 CUs, so the
     // streams overlap on the device; the weights are shared and read-only.  Callbacks, if any, fire concurrently.
     if (!ctx || !states || n_chunks <= 0) return -1;
-    std::vector<int> rc(n_chunks, 0);
-    std::vector<std::thread> th;
-    th.reserve(n_chunks);
     // The one-launch steps own the device while they run (one slot per device, wa_decode.cpp).  Members of a lock-step group do not open
     // host-overlap windows (wa_full.cpp); a chunk that decodes alone - the last one of its group - takes the slot step by step.
     // ... and where the chunks' loops ask for a plain single-token step at the same time, ONE decoder pass serves a group of them
-    {
-        wa_batch_groups groups(ctx, std::vector<whisper_state *>(states, states + n_chunks));
-        for (int i = 0; i < n_chunks; ++i)
-            th.emplace_back([&, i]() {
-                rc[i] = whisper_full_with_state(ctx, states[i], params, samples[i], n_samples[i]);
-                wa_batcher_leave(states[i]->batcher);
-            });
-        for (auto & t : th) t.join();
-    }
-    for (int r : rc) if (r != 0) return r;
-    return 0;
+    return wa_guard(__func__, -1, [&] {
+        const std::vector<whisper_state *> members(states, states + n_chunks);
+        for (int r : wa_wave_run(ctx, members, [&](size_t i) { return whisper_full_with_state(ctx, states[i], params, samples[i], n_samples[i]); }))
+            if (r != 0) return r;
+        return 0;
+    });
 }
 
 } // extern "C"

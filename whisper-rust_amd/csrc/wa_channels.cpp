@@ -262,8 +262,8 @@ const float * whisper_amd_audio_split(struct whisper_state * st, const void * da
                  !st || !n_samples || !stride ? " (null state, n_samples or stride)" : !data && n_frames > 0 ? " (null data)" : "");
         return nullptr;
     }
-    try { return channels_split(st, data, n_frames, sample_rate, format, n_samples, stride, __func__); }
-    catch (const std::exception & e) { WA_ERROR("%s: exception: %s\n", __func__, e.what()); return nullptr; }
+    const char * who = __func__;
+    return wa_guard(who, (const float *) nullptr, [&] { return channels_split(st, data, n_frames, sample_rate, format, n_samples, stride, who); });
 }
 
 int64_t whisper_amd_audio_split_copy(struct whisper_state * st, int channel, float * dst, int64_t cap) {
@@ -280,11 +280,11 @@ int whisper_amd_channel_energy(struct whisper_state * st, const int64_t * is0, c
         WA_ERROR("%s: refused: null arguments, or no whisper_amd_audio_split on this state yet\n", __func__);
         return -1;
     }
-    try {
+    return wa_guard(__func__, -1, [&] {
         std::vector<long long> spans((size_t) n_spans * 2);
         for (int i = 0; i < n_spans; ++i) { spans[2 * (size_t) i] = is0[i]; spans[2 * (size_t) i + 1] = is1[i]; }
         return channels_energy(*st, spans, where, energy) ? 0 : -1;
-    } catch (const std::exception & e) { WA_ERROR("%s: exception: %s\n", __func__, e.what()); return -1; }
+    });
 }
 
 int whisper_amd_channel_speakers(struct whisper_state * st, const int64_t * t0_cs, const int64_t * t1_cs, int n, double ratio, double * energy,
@@ -293,7 +293,7 @@ int whisper_amd_channel_speakers(struct whisper_state * st, const int64_t * t0_c
         WA_ERROR("%s: refused: null arguments, or no whisper_amd_audio_split on this state yet\n", __func__);
         return -1;
     }
-    try {
+    return wa_guard(__func__, -1, [&] {
         const int64_t n_samples = st->chn->n;
         std::vector<long long> spans((size_t) n * 2);
         for (int i = 0; i < n; ++i) {
@@ -305,7 +305,7 @@ int whisper_amd_channel_speakers(struct whisper_state * st, const int64_t * t0_c
         for (int i = 0; i < n; ++i) speaker[i] = (int8_t) wa_ch_label(e[2 * (size_t) i], e[2 * (size_t) i + 1], ratio);
         if (energy && n > 0) memcpy(energy, e.data(), e.size() * sizeof(double));
         return 0;
-    } catch (const std::exception & e) { WA_ERROR("%s: exception: %s\n", __func__, e.what()); return -1; }
+    });
 }
 
 void whisper_amd_channels_default_params(struct whisper_amd_channels_params * p) {
@@ -326,10 +326,7 @@ int whisper_amd_full_long_channels(struct whisper_context * ctx, struct whisper_
         WA_ERROR("%s: refused: %lld samples at 16 kHz are more than whisper_full takes\n", __func__, (long long) wa_audio_n_out(n_frames, sample_rate));
         return -1;
     }
-    int rc = -1;
-    try { rc = channels_full(ctx, params, *cp, data, n_frames, sample_rate, format); }
-    catch (const std::exception & e) { WA_ERROR("%s: exception: %s\n", __func__, e.what()); rc = -1; }
-    catch (...) { WA_ERROR("%s: unknown exception\n", __func__); rc = -1; }
+    const int rc = wa_guard(__func__, -1, [&] { return channels_full(ctx, params, *cp, data, n_frames, sample_rate, format); });
     if (rc != 0) {
         ctx->state->result_all.clear();
         if (ctx->state->lng) { ctx->state->lng->seg_channel.clear(); ctx->state->lng->chunks.clear(); }

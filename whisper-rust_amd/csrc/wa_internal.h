@@ -19,6 +19,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <exception>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -44,6 +45,14 @@ int64_t wa_time_us();
 
 #define WA_HIP_OK(expr) wa_hip_ok((expr), #expr, __FILE__, __LINE__)
 bool wa_hip_ok(hipError_t e, const char * what, const char * file, int line);
+
+// The exception guard of the C entry points: what `body` returns, or `fail` after logging whatever it threw.  Nothing crosses the C boundary.
+template <typename R, typename F> static inline R wa_guard(const char * who, R fail, F && body) {
+    try { return body(); }
+    catch (const std::exception & e) { WA_ERROR("%s: exception: %s\n", who, e.what()); }
+    catch (...) { WA_ERROR("%s: unknown exception\n", who); }
+    return fail;
+}
 
 static inline int wa_pad(int x, int n) { return ((x + n - 1) / n) * n; }
 
@@ -431,7 +440,7 @@ bool wa_spec_launch(whisper_context & ctx, whisper_state & st, int k, int pos, i
 int  wa_spec_wait  (whisper_context & ctx, whisper_state & st, int k, int * token_used);   // 0 ok (logits in st.logits row 0), 1 redo, -1 gave up
 void wa_spec_drain (whisper_context & ctx, whisper_state & st);
 void wa_spec_end   (whisper_context & ctx, whisper_state & st);
-// lock-step batched decode of the chunks of one whisper_amd_full_batch call (wa_decode.cpp)
+// lock-step batched decode of the members of one wave (wa_decode.cpp); groups are formed, run and ended by wa_wave_run (wa_wave.h) alone
 struct wa_batcher;
 wa_batcher * wa_batcher_create(whisper_context & ctx, int n_members);      // null: not applicable (quantised model, one chunk)
 void wa_batcher_leave(wa_batcher * b);
@@ -439,37 +448,6 @@ void wa_batcher_destroy(wa_batcher * b);          // hands the batcher back to i
 void wa_batcher_release(wa_batcher * b);          // frees it
 void wa_batcher_free_all(whisper_context & ctx);  // whisper_free
 void wa_batcher_stats(const wa_batcher * b, long * steps, long * rows, long * one_launch = nullptr, long * served = nullptr);
-// Lock-step decode groups for chunks transcribed together on one device (whisper_amd_full_batch, whisper_full_parallel, whisper_amd_full_long):
-// groups of WHISPER_AMD_BATCH_GROUP chunks share a decoder pass (wa_decode.cpp: wa_batcher).  Where the pass is ONE launch (wa_rows.hip; it owns the
-// device while it runs) the default is one group of up to 8 - every weight row read once for eight tokens.  Where only the launch
-// sequence is available (a pass is then a chain of short latency-bound launches) groups of 4 run side by side on their own streams:
-// two 4-row passes finish sooner than one 8-row pass after the other (round 2: 8 chunks 488x real time as one group, 589x as two).
-struct wa_batch_groups {
-    whisper_context * ctx;
-    std::vector<whisper_state *> members;
-    std::vector<wa_batcher *> bats;
-    wa_batch_groups(whisper_context * c, const std::vector<whisper_state *> & m) : ctx(c), members(m) {
-        static const bool off = getenv("WHISPER_AMD_NO_BATCHER") != nullptr;
-        int group = !members.empty() && members[0]->rows_form.enabled() ? WA_MAX_DECODERS : 4;
-        if (const char * g = getenv("WHISPER_AMD_BATCH_GROUP")) group = std::max(2, std::min(WA_MAX_DECODERS, atoi(g)));
-        for (size_t i0 = 0; i0 < members.size() && !off; i0 += group) {
-            const size_t n = std::min((size_t) group, members.size() - i0);
-            wa_batcher * b = wa_batcher_create(*ctx, (int) n);       // null for a group of one: that chunk decodes on its own (the members of a quantised group too, unless the one-launch form serves it)
-            bats.push_back(b);
-            for (size_t i = i0; i < i0 + n; ++i) members[i]->batcher = b;
-        }
-    }
-    ~wa_batch_groups() {
-        for (auto * st : members) st->batcher = nullptr;
-        ctx->batch_steps = ctx->batch_rows = ctx->batch_one_launch = ctx->batch_served = 0;
-        for (auto * b : bats) if (b) {
-            long st_ = 0, rw_ = 0, ol_ = 0, sv_ = 0;
-            wa_batcher_stats(b, &st_, &rw_, &ol_, &sv_);
-            ctx->batch_steps += st_; ctx->batch_rows += rw_; ctx->batch_one_launch += ol_; ctx->batch_served += sv_;
-            wa_batcher_destroy(b);
-        }
-    }
-};
 void wa_long_free(whisper_state & st);            // wa_long.cpp: what whisper_amd_full_long / whisper_amd_long_pack keep on a state
 void wa_channels_free(whisper_state & st);        // wa_channels.cpp: what whisper_amd_audio_split / whisper_amd_channel_energy keep on a state
 void wa_align_free(whisper_state & st);           // wa_align.cpp: what whisper_amd_align / whisper_amd_align_score keep on a state

@@ -2,17 +2,17 @@
 //
 // A recording of any length is cut at the silences the VAD found (wa_long_plan.h: chunks of whole segments, at most max_chunk_ms of
 // speech-only audio each), every chunk's speech-only audio is written by ONE launch of k_long_pack (wa_long.hip) into a buffer of the
-// context's state, and the chunks run in waves of n_parallel through the lock-step groups of whisper_amd_full_batch: a chunk is
+// context's state, and the chunks run in waves of n_parallel through wa_wave_run (wa_wave.h), as whisper_amd_full_batch's do: a chunk is
 // whisper_full_with_state on its audio, nothing else.  The PCM crosses PCIe once (host input) or never (device input): the VAD reads it in
 // place (wa_vad.cpp), the pack kernel reads it in place, the members read the packed chunks in place.  VAD and pack have completed - a
 // stream synchronise - before the first wave starts: a foreign kernel beside the one-launch passes costs hand-off time-outs.
 // wa_vad_filter_audio, the host function, is the yardstick and the fallback: WHISPER_AMD_LONG_HOST=1, read at each call, takes it, and so
 // does a call whose HIP path fails (logged and counted).
 #include "wa_long_host.h"
+#include "wa_wave.h"
 
 #include <climits>
 #include <cstring>
-#include <thread>
 
 wa_long_state & wa_long_of(whisper_state & st) {
     if (!st.lng) st.lng = new wa_long_state;
@@ -137,25 +137,7 @@ static std::vector<wa_vad_seg> long_segs(const int64_t * segs_cs, int n_segs) {
     return segs;
 }
 
-// the waves: chunks [c0, c0 + members) of the list, chunk c0 + i on states[i], in lock step where a group forms
-static void long_wave(whisper_context * ctx, const std::vector<whisper_state *> & members, const whisper_full_params & pc, const float * d_chunks,
-                      const std::vector<wa_long_rec> & chunks, size_t c0, std::vector<int> & rcs) {
-    std::vector<std::thread> workers;
-    wa_batch_groups groups(ctx, members);           // ends after the joins
-    auto run = [&, ctx](size_t i) {
-        const wa_long_rec & r = chunks[c0 + i];
-        // chunks are independent: nothing of the state's earlier text - an earlier call's on the context's state, the previous wave's chunk on
-        // any member - prompts this one, whatever no_context says; inside the chunk whisper_full's windows carry their context as they always do
-        members[i]->prompt_past.clear();
-        if (r.packed > 0) rcs[c0 + i] = whisper_full_with_state(ctx, members[i], pc, d_chunks + r.off, r.packed);
-        else members[i]->result_all.clear();        // every segment clamped away: no audio, no result
-        wa_batcher_leave(members[i]->batcher);
-    };
-    for (size_t i = 1; i < members.size(); ++i) workers.emplace_back(run, i);
-    run(0);
-    for (auto & w : workers) w.join();
-}
-
+// the waves (wa_wave.h): chunks [c0, c0 + members) of the list, chunk c0 + i on states[i], in lock step where a group forms
 int wa_long_waves(whisper_context * ctx, const whisper_full_params & params, int n_parallel, std::vector<std::vector<wa_segment>> & results) {
     whisper_state * st = ctx->state;
     wa_long_state & L = wa_long_of(*st);
@@ -169,30 +151,33 @@ int wa_long_waves(whisper_context * ctx, const whisper_full_params & params, int
         states.push_back(s);
     }
     whisper_full_params pc = params;
+    wa_params_silent(pc);
     pc.vad = false; pc.offset_ms = 0; pc.duration_ms = 0;
-    pc.print_progress = false; pc.print_realtime = false; pc.print_timestamps = false; pc.print_special = false;
-    pc.new_segment_callback = nullptr; pc.new_segment_callback_user_data = nullptr;
-    pc.progress_callback = nullptr; pc.progress_callback_user_data = nullptr;
+    pc.print_timestamps = false; pc.print_special = false;      // print_special: no special tokens in a chunk's text (wa_full.cpp)
 
-    std::vector<int> rcs(n_chunks, 0);
+    std::vector<int> rcs;
     results.assign(n_chunks, std::vector<wa_segment>());
-    long steps = 0, rows = 0, one_launch = 0, served = 0;
+    wa_wave_totals totals;
     int lang_id = st->lang_id;
     for (size_t c0 = 0; c0 < n_chunks; c0 += states.size()) {
         const std::vector<whisper_state *> members(states.begin(), states.begin() + std::min(states.size(), n_chunks - c0));
-        long_wave(ctx, members, pc, L.d_chunks, L.chunks, c0, rcs);
-        steps += ctx->batch_steps; rows += ctx->batch_rows; one_launch += ctx->batch_one_launch; served += ctx->batch_served;
+        const std::vector<int> wave = wa_wave_run(ctx, members, [&](size_t i) {
+            const wa_long_rec & r = L.chunks[c0 + i];
+            // chunks are independent: nothing of the state's earlier text - an earlier call's on the context's state, the previous wave's chunk on
+            // any member - prompts this one, whatever no_context says; inside the chunk whisper_full's windows carry their context as they always do
+            members[i]->prompt_past.clear();
+            if (r.packed > 0) return whisper_full_with_state(ctx, members[i], pc, L.d_chunks + r.off, r.packed);
+            members[i]->result_all.clear();         // every segment clamped away: no audio, no result
+            return 0;
+        });
+        rcs.insert(rcs.end(), wave.begin(), wave.end());
+        totals.add(ctx);
         for (size_t i = 0; i < members.size(); ++i) { results[c0 + i] = std::move(members[i]->result_all); members[i]->result_all.clear(); }
         if (c0 == 0) lang_id = st->lang_id;
         L.stats[3]++;
     }
-    ctx->batch_steps = steps; ctx->batch_rows = rows; ctx->batch_one_launch = one_launch; ctx->batch_served = served;
-    for (size_t i = 1; i < states.size(); ++i) {
-        whisper_state * s = states[i];
-        st->t_mel_us += s->t_mel_us; st->t_sample_us += s->t_sample_us; st->t_encode_us += s->t_encode_us; st->t_decode_us += s->t_decode_us;
-        st->t_batchd_us += s->t_batchd_us; st->t_prompt_us += s->t_prompt_us;
-        st->n_sample += s->n_sample; st->n_encode += s->n_encode; st->n_decode += s->n_decode; st->n_batchd += s->n_batchd; st->n_prompt += s->n_prompt;
-    }
+    totals.publish(ctx);
+    for (size_t i = 1; i < states.size(); ++i) wa_state_add_counters(*st, *states[i]);
     release();
     st->lang_id = lang_id;
     st->vad_mapping_table.clear();                  // the times are stored mapped: the getters return them as they are
@@ -277,10 +262,7 @@ int whisper_amd_full_long(struct whisper_context * ctx, struct whisper_full_para
                           int n_parallel) {
     if (!ctx || !ctx->state || !samples || n_samples <= 0) { WA_ERROR("%s: refused: null context, state or samples\n", __func__); return -1; }
     if (params.offset_ms != 0 || params.duration_ms != 0) { WA_ERROR("%s: refused: offset_ms / duration_ms are not supported here\n", __func__); return -1; }
-    int rc = -1;
-    try { rc = long_full(ctx, params, samples, n_samples, max_chunk_ms, n_parallel); }
-    catch (const std::exception & e) { WA_ERROR("%s: exception: %s\n", __func__, e.what()); rc = -1; }
-    catch (...) { WA_ERROR("%s: unknown exception\n", __func__); rc = -1; }
+    const int rc = wa_guard(__func__, -1, [&] { return long_full(ctx, params, samples, n_samples, max_chunk_ms, n_parallel); });
     if (rc != 0) ctx->state->result_all.clear();
     return rc;
 }
@@ -322,7 +304,7 @@ void whisper_amd_long_stats(struct whisper_context * ctx, int64_t out[8]) {
 int whisper_amd_long_plan(const int64_t * segs_cs, int n_segs, int n_samples, float samples_overlap, int max_chunk_samples, int32_t * first,
                           int32_t * count, int64_t * packed, int cap) {
     if (n_segs < 0 || (n_segs > 0 && !segs_cs) || n_samples < 0 || cap < 0) return -1;
-    try {
+    return wa_guard(__func__, -1, [&] {
         const std::vector<wa_vad_seg> segs = long_segs(segs_cs, n_segs);
         const std::vector<wa_long_chunk> plan = wa_long_plan(segs.data(), n_segs, n_samples, samples_overlap, max_chunk_samples);
         for (size_t c = 0; c < plan.size() && c < (size_t) cap; ++c) {
@@ -331,13 +313,13 @@ int whisper_amd_long_plan(const int64_t * segs_cs, int n_segs, int n_samples, fl
             if (packed) packed[c] = plan[c].packed;
         }
         return (int) plan.size();
-    } catch (...) { return -1; }
+    });
 }
 
 int whisper_amd_long_pack(struct whisper_state * st, const float * samples, int n_samples, const int64_t * segs_cs, int n_segs, float samples_overlap,
                           const int32_t * first, const int32_t * count, int n_chunks, int where) {
     if (!st || !st->ctx || !samples || n_samples <= 0 || !segs_cs || n_segs <= 0 || !first || !count || n_chunks <= 0 || (where != 0 && where != 1)) return -1;
-    try {
+    return wa_guard(__func__, -1, [&] {
         const std::vector<wa_vad_seg> segs = long_segs(segs_cs, n_segs);
         std::vector<wa_long_chunk> plan;
         for (int c = 0; c < n_chunks; ++c) {
@@ -356,7 +338,7 @@ int whisper_amd_long_pack(struct whisper_state * st, const float * samples, int 
         }
         wa_long_of(*st).stats[2] = n_chunks;
         return 0;
-    } catch (const std::exception & e) { WA_ERROR("%s: exception: %s\n", __func__, e.what()); return -1; }
+    });
 }
 
 int whisper_amd_long_tile(void) { return WA_LONG_TILE; }

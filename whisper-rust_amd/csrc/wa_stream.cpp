@@ -3,9 +3,9 @@
 // A session owns a state, a 16 kHz ring in HBM and the resampler's carry.  A feed is one launch of k_stream_push (wa_stream.hip) on the state's
 // stream: the packet is converted and resampled behind the carry and every output that became final goes into the ring.  A step is one launch
 // of k_stream_window - the ring pieces of the window that is due, copied into the state's PCM buffer - and whisper_full_with_state on that
-// buffer, read in place, with the session's prompt.  step_many gathers the due windows of up to 8 sessions in ONE launch and runs them through
-// the lock-step groups of whisper_amd_full_batch.  The plan - which samples, how many, when a line is committed - is wa_stream.h's, a restatement
-// of the reference's examples/stream/stream.cpp; wa_stream_ref there, the same push and gather on the host, serves WHISPER_AMD_STREAM_HOST=1
+// buffer, read in place, with the session's prompt.  step_many gathers the due windows of up to 8 sessions in ONE launch and runs them as
+// one wave (wa_wave_run, wa_wave.h), as whisper_amd_full_batch runs its chunks.  The plan - which samples, how many, when a line is committed -
+// is wa_stream.h's, a restatement of the reference's examples/stream/stream.cpp; wa_stream_ref there, the same push and gather on the host, serves WHISPER_AMD_STREAM_HOST=1
 // (read when a session opens) and every session after a HIP call of its own failed: ring and carry are copied down once and stay on the host.
 //
 // A VAD session (whisper_amd_stream_open_vad) is the same object with another plan: no steps, but the utterances the Silero VAD
@@ -13,14 +13,13 @@
 // k_stream_vad_front (wa_vad.hip), which reads them where they lie in the rings and writes their gate inputs into the sessions' pinned buffers;
 // the calling thread then walks each session's LSTM (wa_vad_step) and its incremental segmenter (wa_stream_vad.h).  An utterance that became
 // final is queued; a step gathers it - the same k_stream_window launch - and runs whisper_full_with_state on it, as for a window.
-#include "wa_internal.h"
+#include "wa_wave.h"
 #include "wa_stream.h"
 #include "wa_stream_vad.h"
 
 #include <climits>
 #include <cstring>
 #include <deque>
-#include <thread>
 
 struct whisper_amd_stream {
     whisper_context * ctx = nullptr;
@@ -361,7 +360,7 @@ static int step_many(whisper_amd_stream ** ss, int n, const whisper_full_params 
         else if (s.dropped > 0) WA_WARN("%s: cannot process audio fast enough, dropped %lld samples\n", __func__, (long long) s.dropped);
     }
     int ran = 0, bad = 0;
-    long b_steps = 0, b_rows = 0, b_one = 0, b_served = 0;
+    wa_wave_totals totals;
     for (size_t g0 = 0; g0 < due.size(); g0 += WA_STREAM_SESSIONS) {
         const size_t gn = std::min<size_t>(WA_STREAM_SESSIONS, due.size() - g0);
         const std::vector<whisper_amd_stream *> grp(due.begin() + g0, due.begin() + g0 + gn);
@@ -373,30 +372,19 @@ static int step_many(whisper_amd_stream ** ss, int n, const whisper_full_params 
             for (whisper_amd_stream * S : grp) {
                 members.push_back(S->st);
                 whisper_full_params pc = window_params(*S, params);        // a copy per member: the prompts differ
-                pc.print_progress = false; pc.print_realtime = false; pc.print_timestamps = false; pc.print_special = false;
-                pc.new_segment_callback = nullptr; pc.new_segment_callback_user_data = nullptr;
-                pc.progress_callback = nullptr; pc.progress_callback_user_data = nullptr;
+                wa_params_silent(pc);
+                pc.print_timestamps = false; pc.print_special = false;     // print_special: no special tokens in a window's text (wa_full.cpp)
                 pcs.push_back(pc);
             }
-            {
-                std::vector<std::thread> workers;
-                wa_batch_groups groups(ctx, members);       // ends after the joins
-                auto run = [&](size_t i) {
-                    rcs[i] = whisper_full_with_state(ctx, members[i], pcs[i], members[i]->d_audio, gst[i].len);
-                    wa_batcher_leave(members[i]->batcher);
-                };
-                for (size_t i = 1; i < gn; ++i) workers.emplace_back(run, i);
-                run(0);
-                for (auto & w : workers) w.join();
-            }
-            b_steps += ctx->batch_steps; b_rows += ctx->batch_rows; b_one += ctx->batch_one_launch; b_served += ctx->batch_served;
+            rcs = wa_wave_run(ctx, members, [&](size_t i) { return whisper_full_with_state(ctx, members[i], pcs[i], members[i]->d_audio, gst[i].len); });
+            totals.add(ctx);
         } else WA_ERROR("%s: the window gather failed\n", __func__);
         for (size_t i = 0; i < gn; ++i) {
             window_done(*grp[i], gst[i], rcs[i]);
             if (rcs[i] == 0) ++ran; else if (!bad) bad = rcs[i] < 0 ? rcs[i] : WHISPER_AMD_STREAM_FAILED;
         }
     }
-    if (due.size() > 1) { ctx->batch_steps = b_steps; ctx->batch_rows = b_rows; ctx->batch_one_launch = b_one; ctx->batch_served = b_served; }
+    totals.publish(ctx);
     return bad ? bad : ran;
 }
 
@@ -475,20 +463,21 @@ struct whisper_amd_stream * whisper_amd_stream_open(struct whisper_context * ctx
         return nullptr;
     }
     whisper_amd_stream * s = nullptr;
-    try {
+    const bool ok = wa_guard(__func__, false, [&] {
         s = new whisper_amd_stream;
         s->ctx = ctx; s->prm = *p; s->plan.z = z; s->plan.drop_late = p->drop_late != 0;
         wa_audio_plan_make(p->sample_rate, s->ap);
         s->backlog = std::max<int64_t>((int64_t) p->backlog_ms * (WA_AUDIO_RATE / 1000), 2 * (int64_t) z.n_step + 1);   // the drop rule needs to see 2 n_step + 1
         s->cap = (int64_t) z.n_keep + z.n_len + s->backlog;
-        return stream_make(s, (size_t) std::max(z.n_keep + z.n_len, 256));
-    } catch (const std::exception & e) { WA_ERROR("%s: exception: %s\n", __func__, e.what()); }
-    catch (...) { WA_ERROR("%s: unknown exception\n", __func__); }
+        s = stream_make(s, (size_t) std::max(z.n_keep + z.n_len, 256));
+        return true;
+    });
+    if (ok) return s;           // null where stream_make failed: it has freed the session
     stream_free(s);
     return nullptr;
 }
 
-void whisper_amd_stream_close(struct whisper_amd_stream * s) { try { stream_free(s); } catch (...) { } }
+void whisper_amd_stream_close(struct whisper_amd_stream * s) { (void) wa_guard(__func__, 0, [&] { stream_free(s); return 0; }); }
 
 int whisper_amd_stream_feed(struct whisper_amd_stream * s, const void * data, int64_t n_frames) {
     if (!s || n_frames < 0 || (!data && n_frames > 0) || n_frames > INT64_MAX / WA_AUDIO_MAX_L / 2) {
@@ -496,15 +485,14 @@ int whisper_amd_stream_feed(struct whisper_amd_stream * s, const void * data, in
         return WHISPER_AMD_STREAM_BAD_ARGS;
     }
     if (s->ended) { WA_ERROR("%s: refused: the session was flushed; reset it first\n", __func__); return WHISPER_AMD_STREAM_ENDED; }
-    try { return n_frames == 0 ? (int) (s->vad ? stream_due(*s) : s->plan.due(false)) : stream_push(*s, data, n_frames, false); }
-    catch (const std::exception & e) { WA_ERROR("%s: exception: %s\n", __func__, e.what()); }
-    catch (...) { WA_ERROR("%s: unknown exception\n", __func__); }
-    return WHISPER_AMD_STREAM_FAILED;
+    return wa_guard(__func__, WHISPER_AMD_STREAM_FAILED, [&] {
+        return n_frames == 0 ? (int) (s->vad ? stream_due(*s) : s->plan.due(false)) : stream_push(*s, data, n_frames, false);
+    });
 }
 
 int whisper_amd_stream_flush(struct whisper_amd_stream * s) {
     if (!s) { WA_ERROR("%s: refused: null session\n", __func__); return WHISPER_AMD_STREAM_BAD_ARGS; }
-    try {
+    return wa_guard(__func__, WHISPER_AMD_STREAM_FAILED, [&]() -> int {
         if (!s->ended) {
             const int Z = wa_stream_flush_frames(s->ap);
             if (Z > 0) {
@@ -516,9 +504,7 @@ int whisper_amd_stream_flush(struct whisper_amd_stream * s) {
             if (s->vad && s->vprm.vad_on_feed && !vad_process(&s, 1)) return WHISPER_AMD_STREAM_FAILED;
         }
         return (int) (s->vad ? stream_due(*s) : s->plan.due(true));
-    } catch (const std::exception & e) { WA_ERROR("%s: exception: %s\n", __func__, e.what()); }
-    catch (...) { WA_ERROR("%s: unknown exception\n", __func__); }
-    return WHISPER_AMD_STREAM_FAILED;
+    });
 }
 
 int whisper_amd_stream_pending(struct whisper_amd_stream * s) { return s ? (int) stream_due(*s) : WHISPER_AMD_STREAM_BAD_ARGS; }
@@ -531,31 +517,27 @@ int whisper_amd_stream_step_many(struct whisper_amd_stream ** ss, int n, const s
         if (ss[i]->ctx != ss[0]->ctx) { WA_ERROR("%s: refused: session %d belongs to another context\n", __func__, i); return WHISPER_AMD_STREAM_MIXED; }
         for (int j = 0; j < i; ++j) if (ss[j] == ss[i]) { WA_ERROR("%s: refused: session %d is listed twice\n", __func__, i); return WHISPER_AMD_STREAM_BAD_ARGS; }
     }
-    try { return step_many(ss, n, *params); }
-    catch (const std::exception & e) { WA_ERROR("%s: exception: %s\n", __func__, e.what()); }
-    catch (...) { WA_ERROR("%s: unknown exception\n", __func__); }
-    return WHISPER_AMD_STREAM_FAILED;
+    return wa_guard(__func__, WHISPER_AMD_STREAM_FAILED, [&] { return step_many(ss, n, *params); });
 }
 
 int whisper_amd_stream_step(struct whisper_amd_stream * s, const struct whisper_full_params * params) {
     if (!s || !params) { WA_ERROR("%s: refused: null session or params\n", __func__); return WHISPER_AMD_STREAM_BAD_ARGS; }
-    try {
+    const char * const who = __func__;
+    return wa_guard(who, WHISPER_AMD_STREAM_FAILED, [&]() -> int {
         if (!WA_HIP_OK(hipSetDevice(s->ctx->device))) return WHISPER_AMD_STREAM_FAILED;
         wa_stream_step step;
         if (!stream_next(*s, step)) {
-            if (step.dropped > 0) WA_WARN("%s: cannot process audio fast enough, dropped %lld samples\n", __func__, (long long) step.dropped);
+            if (step.dropped > 0) WA_WARN("%s: cannot process audio fast enough, dropped %lld samples\n", who, (long long) step.dropped);
             return 0;
         }
         int rc = WHISPER_AMD_STREAM_FAILED;
         if (gather({ s }, { step })) {
             const whisper_full_params pc = window_params(*s, *params);      // the caller's, but for the prompt
             rc = whisper_full_with_state(s->ctx, s->st, pc, s->st->d_audio, step.len);
-        } else WA_ERROR("%s: the window gather failed\n", __func__);
+        } else WA_ERROR("%s: the window gather failed\n", who);
         window_done(*s, step, rc);
         return rc == 0 ? 1 : rc < 0 ? rc : WHISPER_AMD_STREAM_FAILED;
-    } catch (const std::exception & e) { WA_ERROR("%s: exception: %s\n", __func__, e.what()); }
-    catch (...) { WA_ERROR("%s: unknown exception\n", __func__); }
-    return WHISPER_AMD_STREAM_FAILED;
+    });
 }
 
 struct whisper_state * whisper_amd_stream_state(struct whisper_amd_stream * s) { return s ? s->st : nullptr; }
@@ -587,12 +569,13 @@ int whisper_amd_stream_prompt_copy(struct whisper_amd_stream * s, whisper_token 
 
 void whisper_amd_stream_reset(struct whisper_amd_stream * s) {
     if (!s) return;
-    try {
+    (void) wa_guard(__func__, 0, [&] {
         (void) hipSetDevice(s->ctx->device);
-        if (!stream_clear(*s)) WA_ERROR("%s: the carry could not be cleared\n", __func__);
+        if (!stream_clear(*s)) WA_ERROR("whisper_amd_stream_reset: the carry could not be cleared\n");
         s->st->result_all.clear();
         s->st->prompt_past.clear();
-    } catch (...) { }
+        return 0;
+    });
 }
 
 int whisper_amd_stream_tile(void) { return WA_STREAM_TILE; }
@@ -621,7 +604,7 @@ struct whisper_amd_stream * whisper_amd_stream_open_vad(struct whisper_context *
         return nullptr;
     }
     whisper_amd_stream * s = nullptr;
-    try {
+    const bool ok = wa_guard(__func__, false, [&] {
         s = new whisper_amd_stream;
         s->ctx = ctx; s->vad = true; s->vprm = *p; s->vctx = vctx;
         whisper_amd_stream_default_params(&s->prm);
@@ -633,9 +616,10 @@ struct whisper_amd_stream * whisper_amd_stream_open_vad(struct whisper_context *
         // an open speech of the cap's length and a candidate behind it, up to max_speech long, must fit beside one another
         s->backlog = std::max<int64_t>((int64_t) p->backlog_ms * (WA_AUDIO_RATE / 1000), (int64_t) WA_AUDIO_RATE * (int64_t) p->vad.max_speech_duration_s + 8192);
         s->cap = s->seg.cap_samples + s->backlog;
-        return stream_make(s, (size_t) std::max<int64_t>(s->seg.cap_samples, 256));
-    } catch (const std::exception & e) { WA_ERROR("%s: exception: %s\n", __func__, e.what()); }
-    catch (...) { WA_ERROR("%s: unknown exception\n", __func__); }
+        s = stream_make(s, (size_t) std::max<int64_t>(s->seg.cap_samples, 256));
+        return true;
+    });
+    if (ok) return s;           // null where stream_make failed: it has freed the session
     stream_free(s);
     return nullptr;
 }
@@ -651,14 +635,13 @@ int whisper_amd_stream_vad_poll_many(struct whisper_amd_stream ** ss, int n) {
         }
         for (int j = 0; j < i; ++j) if (ss[j] == ss[i]) { WA_ERROR("%s: refused: session %d is listed twice\n", __func__, i); return WHISPER_AMD_STREAM_BAD_ARGS; }
     }
-    try {
-        if (!vad_process(ss, n)) { WA_ERROR("%s: the front end failed\n", __func__); return WHISPER_AMD_STREAM_FAILED; }
+    const char * const who = __func__;
+    return wa_guard(who, WHISPER_AMD_STREAM_FAILED, [&]() -> int {
+        if (!vad_process(ss, n)) { WA_ERROR("%s: the front end failed\n", who); return WHISPER_AMD_STREAM_FAILED; }
         int64_t due = 0;
         for (int i = 0; i < n; ++i) due += (int64_t) ss[i]->due.size();
         return (int) std::min<int64_t>(due, INT_MAX);
-    } catch (const std::exception & e) { WA_ERROR("%s: exception: %s\n", __func__, e.what()); }
-    catch (...) { WA_ERROR("%s: unknown exception\n", __func__); }
-    return WHISPER_AMD_STREAM_FAILED;
+    });
 }
 
 int whisper_amd_stream_utterance_info(struct whisper_amd_stream * s, int64_t out[8]) {
