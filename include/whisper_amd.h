@@ -599,8 +599,8 @@ WHISPER_API void whisper_amd_dtw_timings(struct whisper_state * state, int64_t o
 WHISPER_API int64_t whisper_amd_arena_read(struct whisper_context * ctx, int64_t offset, void * dst, int64_t cap);
 WHISPER_API void    whisper_amd_load_stats(struct whisper_context * ctx, int64_t out[6]);
 
-/* Audio front end (wa_audio.cpp): a recording as it comes out of a WAV file - int16 or F32 samples, one or two interleaved
- * channels, 8 .. 192 kHz - converted, down-mixed and resampled to the 16 kHz mono F32 that whisper_full* takes, by HIP kernels on the
+/* Audio front end (wa_audio.cpp): a recording as it comes out of a WAV file (whisper_amd_wav_parse reads the header) - 8-, 16-, 24- or
+ * 32-bit PCM, F32, F64 or G.711 mu-law / A-law samples, one or two interleaved channels, 8 .. 192 kHz - converted, down-mixed and resampled to the 16 kHz mono F32 that whisper_full* takes, by HIP kernels on the
  * state's stream.  whisper-rs callers do the first two steps on the host (src/utilities.rs) and its examples refuse every rate but 16 kHz.
  * At 16 kHz the result is bit-identical to those utilities: I16 mono (float) s / 32768.0f, F32 stereo (l + r) / 2.0f, I16 stereo
  * ((float) l + (float) r) / 2.0f / 32768.0f.  Other rates R go through a polyphase Kaiser-windowed sinc (g = gcd(R, 16000), L = 16000 / g,
@@ -622,9 +622,37 @@ WHISPER_API void    whisper_amd_load_stats(struct whisper_context * ctx, int64_t
  *   t / L - K/2 + 1); copies up to `cap` values, returns L K (0 at 16 kHz: no filter); no device needed.
  * whisper_amd_audio_tile: outputs per workgroup of the resampling kernel (tests put lengths on either side of it).
  * whisper_amd_audio_stats: out = { calls served by the kernels, calls served by the host restatement, kernel attempts that fell back to
- *   it } since the state was created (calls with no output sample count nowhere). */
-#define WHISPER_AMD_PCM_I16 0
-#define WHISPER_AMD_PCM_F32 1
+ *   it } since the state was created (calls with no output sample count nowhere).
+ *
+ * Sample formats.  Every entry that takes a `format` (here, whisper_amd_full_long_audio, whisper_amd_audio_split,
+ * whisper_amd_full_long_channels, and whisper_amd_stream_open / _open_vad through their params) takes every code below; 2, anything above 8
+ * and every negative code are refused.  A sample becomes a value v in F32 and is divided by the format's scale S, every operation rounded
+ * on its own: U8 v = (float) ((int) u - 128), S = 128; S24 (3 bytes little-endian, packed) v = (float) s, S = 8388608; S32 v = (float) s
+ * rounded to nearest even, S = 2147483648; F64 v = (float) x rounded to nearest even, no scale, NaN and Inf passing through as F32's do;
+ * ULAW / ALAW v = (float) e with e the G.711 expansion to int16 (csrc/wa_audio.h: wa_audio_ulaw, wa_audio_alaw), S = 32768.  Mono v / S,
+ * stereo ((vl + vr) / 2.0f) / S.  So G.711 input gives, bit for bit, what I16 input holding the expanded samples gives, and U8 / S24 / S32 /
+ * F64 input what F32 input holding the per-sample v / S gives.
+ * Alignment: a HOST pointer may have any alignment in every format (the samples of a WAV image lie where its header ends).  A DEVICE pointer
+ * may be any byte address for U8, ULAW, ALAW and S24, and must be naturally aligned (2, 4, 4, 8 bytes) for I16, S32, F32 and F64.
+ *
+ * whisper_amd_wav_parse: walks the header of a RIFF/WAVE image in host memory (`size` bytes) and fills `out`: data_offset - the byte offset of
+ *   the first sample -, n_frames, channels, sample_rate, format (a code below) and bits, ready to hand `(char *) image + data_offset` and the
+ *   rest to any entry above.  PCM of 8 / 16 / 24 / 32 bits (tag 1), IEEE float of 32 / 64 bits (tag 3), A-law (6) and mu-law (7), plain or
+ *   in the extensible form (tag 0xFFFE with the standard sub-format GUID, valid bits equal to container bits); nBlockAlign must be
+ *   channels * bits / 8.  The data length is the smaller of the declared one and what the image holds; a declared 0 or 0xFFFFFFFF means "to
+ *   the end"; n_frames rounds down.  Channels and rate are reported as found.  Returns 0, or -1 null or short arguments, -2 not RIFF ... WAVE
+ *   (RF64 and RIFX included), -3 a malformed chunk list or no "fmt " chunk before "data", -4 an unsupported encoding or an nBlockAlign that
+ *   does not fit it, -5 no "data" chunk; on failure *out is untouched.  No device needed. */
+#define WHISPER_AMD_PCM_I16  0
+#define WHISPER_AMD_PCM_F32  1
+#define WHISPER_AMD_PCM_U8   3   /* unsigned 8-bit PCM */
+#define WHISPER_AMD_PCM_S24  4   /* signed 24-bit PCM, 3 bytes little-endian, packed */
+#define WHISPER_AMD_PCM_S32  5   /* signed 32-bit PCM */
+#define WHISPER_AMD_PCM_F64  6   /* IEEE double */
+#define WHISPER_AMD_PCM_ULAW 7   /* G.711 mu-law */
+#define WHISPER_AMD_PCM_ALAW 8   /* G.711 A-law */
+struct whisper_amd_wav_info { int64_t data_offset, n_frames; int32_t channels, sample_rate, format, bits; };
+WHISPER_API int           whisper_amd_wav_parse(const void * image, int64_t size, struct whisper_amd_wav_info * out);
 WHISPER_API int64_t       whisper_amd_audio_n_samples(int64_t n_frames, int sample_rate);
 WHISPER_API const float * whisper_amd_audio_to_pcm(struct whisper_state * state, const void * data, int64_t n_frames, int channels,
                                                    int sample_rate, int format, int64_t * n_samples);

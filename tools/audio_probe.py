@@ -7,7 +7,11 @@
              followed by full() on a host copy of its result - what a caller without the front end does.  Wall time.
 
 `--calls` calls each after one warm-up call, alternating, best and median, printed as one JSON line.
-usage: python tools/audio_probe.py [--calls 10] [--shape small] [--rate 48000]"""
+
+`--format i16,f32,u8,s24,s32,f64,ulaw,alaw` (any of them) measures the sample formats instead: the same recording (`--seconds`, `--channels`, `--rate`)
+rendered in each format, lying in device memory, through whisper_amd_audio_to_pcm - DEVICE time between two HIP events, the formats taken in
+turn within every round after one warm-up round - with the bytes a caller uploads for it, as one JSON line.
+usage: python tools/audio_probe.py [--calls 10] [--shape small] [--rate 48000] [--format LIST [--seconds 60] [--channels 1]]"""
 import argparse
 import ctypes as C
 import json
@@ -35,12 +39,69 @@ def recording(rate, seconds=30):
     return np.stack([np.rint(up * scale), np.rint(up * scale * 0.7)], axis=1).astype(np.int16).reshape(-1)
 
 
+FORMATS = {"i16": W.PCM_I16, "f32": W.PCM_F32, "u8": W.PCM_U8, "s24": W.PCM_S24, "s32": W.PCM_S32, "f64": W.PCM_F64, "ulaw": W.PCM_ULAW, "alaw": W.PCM_ALAW}
+
+
+def rendered(x, name):
+    """the int16 samples `x` in format `name`, as the array the entry reads"""
+    s = x.astype(np.int32)
+    return {"i16": lambda: x, "f32": lambda: (s / 32768.0).astype(np.float32), "u8": lambda: ((s >> 8) + 128).astype(np.uint8), "s24": lambda: W.pack_s24(s << 8),
+            "s32": lambda: (s << 16).astype(np.int32), "f64": lambda: s / 32768.0, "ulaw": lambda: W.linear_to_ulaw(x), "alaw": lambda: W.linear_to_alaw(x)}[name]()
+
+
+def probe_formats(a):
+    names = a.format.split(",")
+    assert all(n in FORMATS for n in names), "--format takes a list of %s" % ", ".join(FORMATS)
+    lib = W.load_library()
+    W.set_log_callback(lib, lambda lvl, txt: sys.stderr.write(txt) if lvl >= 3 else None)
+    hip = C.CDLL("libamdhip64.so")
+    lib.whisper_amd_state_stream.restype = C.c_void_p
+    lib.whisper_amd_state_stream.argtypes = [C.c_void_p]
+    ctx = W.WhisperContext.new_with_params(wsynth.model_path(a.shape), W.WhisperContextParameters(lib, gpu_device=0), lib=lib)
+    st = ctx.create_state()
+    x = recording(a.rate, a.seconds)
+    if a.channels == 1:
+        x = np.ascontiguousarray(x[0::2])
+    n_frames = len(x) // a.channels
+    bufs = {}
+    for n in names:
+        r = np.ascontiguousarray(rendered(x, n)).reshape(-1)
+        d = C.c_void_p()
+        assert hip.hipMalloc(C.byref(d), C.c_size_t(r.nbytes)) == 0 and hip.hipMemcpy(d, C.c_void_p(r.ctypes.data), C.c_size_t(r.nbytes), 1) == 0
+        bufs[n] = (d, r.nbytes)
+    e0, e1 = C.c_void_p(), C.c_void_p()
+    assert hip.hipEventCreate(C.byref(e0)) == 0 and hip.hipEventCreate(C.byref(e1)) == 0
+    stream = C.c_void_p(lib.whisper_amd_state_stream(st.ptr))
+    t = {n: [] for n in names}
+    for it in range(a.calls + 1):
+        for n in names:
+            assert hip.hipEventRecord(e0, stream) == 0
+            st.audio_to_pcm((bufs[n][0].value, n_frames), a.channels, a.rate, FORMATS[n])
+            assert hip.hipEventRecord(e1, stream) == 0 and hip.hipEventSynchronize(e1) == 0
+            ms = C.c_float()
+            assert hip.hipEventElapsedTime(C.byref(ms), e0, e1) == 0
+            if it > 0:
+                t[n].append(ms.value)
+    out = {"rate": a.rate, "channels": a.channels, "seconds": a.seconds, "n_frames": n_frames, "n_samples": int(lib.whisper_amd_audio_n_samples(n_frames, a.rate)),
+           "stats": st.audio_stats(),
+           "formats": {n: dict(summary(t[n]), worst_ms=round(max(t[n]), 3), upload_bytes=bufs[n][1]) for n in names}}
+    for d, _ in bufs.values():
+        hip.hipFree(d)
+    st.free(); ctx.free()
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--calls", type=int, default=10)
     ap.add_argument("--shape", default="small")
     ap.add_argument("--rate", type=int, default=48000)
+    ap.add_argument("--format", default=None)
+    ap.add_argument("--seconds", type=int, default=60)
+    ap.add_argument("--channels", type=int, default=1, choices=(1, 2))
     a = ap.parse_args()
+    if a.format:
+        return probe_formats(a)
     lib = W.load_library()
     W.set_log_callback(lib, lambda lvl, txt: sys.stderr.write(txt) if lvl >= 3 else None)
     hip = C.CDLL("libamdhip64.so")

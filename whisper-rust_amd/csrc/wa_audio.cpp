@@ -2,16 +2,24 @@
 //
 // whisper-rs callers turn a recording into 16 kHz mono F32 on the host before whisper_full (src/utilities.rs: convert_integer_to_float_audio,
 // convert_stereo_to_mono_audio) and the examples refuse any other rate.  Here int16 or F32 input with one or two channels at 8 .. 192 kHz
-// is converted, down-mixed and resampled by the kernels of wa_audio.hip on the state's stream, into a buffer of the state that
+// (and, in the kernels of wa_audio_fmt.hip, 8-, 24- and 32-bit PCM, F64 and G.711) is converted, down-mixed and resampled by the kernels of wa_audio.hip on the state's stream, into a buffer of the state that
 // whisper_full_with_state reads in place.  The arithmetic is wa_audio.h's; wa_audio_ref, the same arithmetic on the host, serves
 // WHISPER_AMD_AUDIO_HOST=1 (read when the state is created) and any call whose HIP path fails: the failure is logged and the call succeeds.
 #include "wa_internal.h"
 #include "wa_audio.h"
+#include "wa_wav.h"
 
 #include <climits>
+#include <cstddef>
 #include <cstring>
 
 static_assert(WA_AUDIO_I16 == WHISPER_AMD_PCM_I16 && WA_AUDIO_F32 == WHISPER_AMD_PCM_F32, "the format codes of wa_audio.h are the header's");
+static_assert(WA_AUDIO_U8 == WHISPER_AMD_PCM_U8 && WA_AUDIO_S24 == WHISPER_AMD_PCM_S24 && WA_AUDIO_S32 == WHISPER_AMD_PCM_S32 &&
+              WA_AUDIO_F64 == WHISPER_AMD_PCM_F64 && WA_AUDIO_ULAW == WHISPER_AMD_PCM_ULAW && WA_AUDIO_ALAW == WHISPER_AMD_PCM_ALAW,
+              "the format codes of wa_audio.h are the header's");
+static_assert(sizeof(wa_wav_info) == sizeof(whisper_amd_wav_info) && offsetof(wa_wav_info, n_frames) == offsetof(whisper_amd_wav_info, n_frames) &&
+              offsetof(wa_wav_info, channels) == offsetof(whisper_amd_wav_info, channels) && offsetof(wa_wav_info, bits) == offsetof(whisper_amd_wav_info, bits),
+              "wa_wav.h's record is the header's");
 
 void wa_audio_free(whisper_context & ctx) {
     std::lock_guard<std::mutex> lock(ctx.audio_taps_m);
@@ -40,12 +48,13 @@ static bool audio_device_path(whisper_context & ctx, whisper_state & st, const v
     if (p.K && !(d_taps = wa_audio_taps_device(ctx, p))) return false;
     const void * d_in = data;
     if (!on_device) {
-        const size_t bytes = (size_t) n_frames * channels * (format == WA_AUDIO_I16 ? 2 : 4);
+        const size_t bytes = (size_t) n_frames * wa_audio_frame_bytes(format, channels);
         if (!wa_dev_reserve(st.d_audio_in, st.d_audio_in_cap, bytes)) return false;
         if (!WA_HIP_OK(hipMemcpyAsync(st.d_audio_in, data, bytes, hipMemcpyHostToDevice, st.stream))) return false;
         d_in = st.d_audio_in;
     }
-    if (!wa_audio_launch(st.stream, d_in, n_frames, channels, format, p, d_taps, n_out, st.d_audio)) return false;
+    if (!(wa_audio_format_base(format) ? wa_audio_launch(st.stream, d_in, n_frames, channels, format, p, d_taps, n_out, st.d_audio)
+                                       : wa_audio_fmt_launch(st.stream, d_in, n_frames, channels, format, p, d_taps, n_out, st.d_audio))) return false;
     // the caller may release a host buffer on return; device input stays stream-ordered
     return on_device || WA_HIP_OK(hipStreamSynchronize(st.stream));
 }
@@ -53,7 +62,7 @@ static bool audio_device_path(whisper_context & ctx, whisper_state & st, const v
 static bool audio_host_path(whisper_state & st, const void * data, bool on_device, int64_t n_frames, int channels, int rate, int format, int64_t n_out) {
     std::vector<uint8_t> in;
     if (on_device) {
-        in.resize((size_t) n_frames * channels * (format == WA_AUDIO_I16 ? 2 : 4));
+        in.resize((size_t) n_frames * wa_audio_frame_bytes(format, channels));
         if (!WA_HIP_OK(hipStreamSynchronize(st.stream)) || !WA_HIP_OK(hipMemcpy(in.data(), data, in.size(), hipMemcpyDeviceToHost))) return false;
         data = in.data();
     }
@@ -139,6 +148,18 @@ int64_t whisper_amd_audio_taps(int sample_rate, float * dst, int64_t cap, int * 
 }
 
 int whisper_amd_audio_tile(void) { return WA_AUDIO_TILE; }
+
+int whisper_amd_wav_parse(const void * image, int64_t size, struct whisper_amd_wav_info * out) {
+    return wa_guard(__func__, -1, [&] {
+        wa_wav_info w;
+        const int rc = wa_wav_parse(image, size, out ? &w : nullptr);
+        if (rc == 0) {
+            out->data_offset = w.data_offset; out->n_frames = w.n_frames; out->channels = w.channels; out->sample_rate = w.sample_rate;
+            out->format = w.format; out->bits = w.bits;
+        }
+        return rc;
+    });
+}
 
 void whisper_amd_audio_stats(struct whisper_state * st, long out[3]) {
     if (!out) return;

@@ -45,7 +45,7 @@ static bool channels_host_only() {
     return env && atoi(env) != 0;
 }
 
-static size_t frame_bytes(int format) { return format == WA_AUDIO_I16 ? 4 : 8; }
+static size_t frame_bytes(int format) { return wa_audio_frame_bytes(format, 2); }
 
 // the kernels: input staged in HBM when it arrives in host memory, everything on the state's stream
 static bool split_device_path(whisper_context & ctx, whisper_state & st, wa_channels_state & C, const void * data, bool on_device, int64_t n_frames, int format,
@@ -60,7 +60,8 @@ static bool split_device_path(whisper_context & ctx, whisper_state & st, wa_chan
         C.split_h2d = (int64_t) bytes;
         d_in = st.d_audio_in;
     }
-    if (!wa_ch_split_launch(st.stream, d_in, n_frames, format, p, d_taps, n_out, stride, C.d_planes)) return false;
+    if (!(wa_audio_format_base(format) ? wa_ch_split_launch(st.stream, d_in, n_frames, format, p, d_taps, n_out, stride, C.d_planes)
+                                       : wa_ch_split_fmt_launch(st.stream, d_in, n_frames, format, p, d_taps, n_out, stride, C.d_planes))) return false;
     // the caller may release a host buffer on return; device input stays stream-ordered
     return on_device || WA_HIP_OK(hipStreamSynchronize(st.stream));
 }

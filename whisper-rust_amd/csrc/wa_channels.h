@@ -5,7 +5,7 @@
 // restatement the kernels of wa_channels.hip are held to bit for bit, and serves a call whose HIP path fails (wa_channels.cpp).
 //
 // Split.  Plane c of a recording is wa_audio.h's result for channel c taken as a MONO recording of the same rate and format: sample
-// conversion (float) s[2 i + c] / 32768.0f or f[2 i + c], then - at rates other than 16 kHz - the same F32 fmaf chain over the same taps
+// conversion (float) s[2 i + c] / 32768.0f or f[2 i + c] (the other formats: v / S of sample 2 i + c, wa_audio.h's table), then - at rates other than 16 kHz - the same F32 fmaf chain over the same taps
 // (wa_audio_taps), k ascending from 0.0f, x zero outside the input.  Plane c lies at out + c * stride, stride = wa_ch_stride(n_out).
 //
 // Energy.  E_c[a, b) = sum over j in [a, b) of |x_c[j]| in F64, a and b clamped to [0, n], 0.0 where a >= b, in ONE order that depends on
@@ -51,8 +51,9 @@ inline int wa_ch_span(const wa_audio_plan & p) { return (int) (((int64_t) (WA_CH
 
 // channel c of frame i as F32
 inline float wa_ch_frame(const void * data, int64_t i, int c, int format) {
-    if (format == WA_AUDIO_I16) return (float) ((const int16_t *) data)[2 * i + c] / 32768.0f;
-    return ((const float *) data)[2 * i + c];
+    if (format == WA_AUDIO_I16) return wa_audio_load_i16(data, 2 * i + c) / 32768.0f;
+    if (format != WA_AUDIO_F32) return wa_audio_channel_fmt(data, i, c, format);
+    return wa_audio_load_f32(data, 2 * i + c);
 }
 
 // Both planes on the host: out[c * stride + n], n < wa_audio_n_out(n_frames, rate); returns that count, -1 on refused arguments.
@@ -160,5 +161,8 @@ inline std::vector<wa_ch_item> wa_ch_merge(std::vector<wa_ch_item> items[2]) {
 // wa_audio_taps' table (unused at 16 kHz).  false: the launch failed or the shape is not served (nothing was launched).
 bool wa_ch_split_launch(void * stream, const void * d_data, long long n_frames, int format, const wa_audio_plan & p, const float * d_taps, long long n_out,
                         long long stride, float * d_out);
+// the same for the formats that are not wa_audio_format_base (wa_audio_fmt.hip)
+bool wa_ch_split_fmt_launch(void * stream, const void * d_data, long long n_frames, int format, const wa_audio_plan & p, const float * d_taps, long long n_out,
+                            long long stride, float * d_out);
 // d_energy[2 * i + c] = E_c[d_spans[2 * i], d_spans[2 * i + 1]) for i < n_spans over the planes d_planes + c * stride of n samples each, in ONE launch
 bool wa_ch_energy_launch(void * stream, const float * d_planes, long long n, long long stride, const long long * d_spans, int n_spans, double * d_energy);

@@ -58,7 +58,9 @@ struct whisper_amd_stream {
 
 static int64_t stream_due(const whisper_amd_stream & S) { return S.vad ? (int64_t) S.due.size() : S.plan.due(S.ended); }
 
-static int frame_bytes(const whisper_amd_stream & S) { return S.prm.channels * (S.prm.format == WA_AUDIO_I16 ? 2 : 4); }
+// of a packet, or (flush) of the zero frames behind the end of input, which travel in wa_audio_silence_format
+static int packet_format(const whisper_amd_stream & S, bool flush) { return flush ? wa_audio_silence_format(S.prm.format) : S.prm.format; }
+static size_t frame_bytes(const whisper_amd_stream & S, bool flush) { return wa_audio_frame_bytes(packet_format(S, flush), S.prm.channels); }
 
 // a HIP call of this session failed: its carry and ring move to the host for good
 static bool stream_to_host(whisper_amd_stream & S) {
@@ -74,33 +76,38 @@ static bool stream_to_host(whisper_amd_stream & S) {
     return true;
 }
 
-static bool push_device(whisper_amd_stream & S, const void * data, bool on_device, int64_t n_frames, int64_t n_new) {
+static bool push_device(whisper_amd_stream & S, const void * data, bool on_device, int64_t n_frames, int64_t n_new, bool flush) {
     whisper_state & st = *S.st;
     const void * d_in = data;
     if (!on_device) {
-        const size_t bytes = (size_t) n_frames * frame_bytes(S);
+        const size_t bytes = (size_t) n_frames * frame_bytes(S, flush);
         if (!wa_dev_reserve(st.d_audio_in, st.d_audio_in_cap, bytes)) return false;
         if (!WA_HIP_OK(hipMemcpyAsync(st.d_audio_in, data, bytes, hipMemcpyHostToDevice, st.stream))) return false;
         d_in = st.d_audio_in;
     }
-    if (!wa_stream_push_launch(st.stream, d_in, n_frames, S.prm.channels, S.prm.format, S.ap, S.d_taps, S.T, S.d_carry[S.cur], S.d_carry[S.cur ^ 1], S.n_out,
-                               n_new, S.d_ring, S.cap, S.plan.r_w)) return false;
+    const int format = packet_format(S, flush);
+    if (!(wa_audio_format_base(format) ? wa_stream_push_launch : wa_stream_push_fmt_launch)(st.stream, d_in, n_frames, S.prm.channels, format, S.ap, S.d_taps, S.T,
+                                                                                            S.d_carry[S.cur], S.d_carry[S.cur ^ 1], S.n_out, n_new, S.d_ring,
+                                                                                            S.cap, S.plan.r_w)) return false;
     // the caller may release a host buffer on return; device input stays stream-ordered
     if (!on_device && !WA_HIP_OK(hipStreamSynchronize(st.stream))) return false;
     if (S.ap.K) S.cur ^= 1;
     return true;
 }
 
-static bool push_host(whisper_amd_stream & S, const void * data, bool on_device, int64_t n_frames, int64_t n_new) {
+static bool push_host(whisper_amd_stream & S, const void * data, bool on_device, int64_t n_frames, int64_t n_new, bool flush) {
     std::vector<uint8_t> in;
     if (on_device) {
-        in.resize((size_t) n_frames * frame_bytes(S));
+        in.resize((size_t) n_frames * frame_bytes(S, flush));
         if (!WA_HIP_OK(hipStreamSynchronize(S.st->stream)) || !WA_HIP_OK(hipMemcpy(in.data(), data, in.size(), hipMemcpyDeviceToHost))) return false;
         data = in.data();
     }
     std::vector<float> out((size_t) std::max<int64_t>(n_new, 1));
     S.ref.T = S.T; S.ref.n_out = S.n_out;
-    if (S.ref.push(data, n_frames, out.data()) != n_new) return false;
+    S.ref.format = packet_format(S, flush);
+    const bool pushed = S.ref.push(data, n_frames, out.data()) == n_new;
+    S.ref.format = S.prm.format;
+    if (!pushed) return false;
     S.ref.ring_write(S.plan.r_w, out.data(), n_new);
     return true;
 }
@@ -260,7 +267,7 @@ static int stream_push(whisper_amd_stream & S, const void * data, int64_t n_fram
     const bool on_device = wa_is_device_ptr(data);
     bool served = false;
     if (!S.host) {
-        served = push_device(S, data, on_device, n_frames, n_new);
+        served = push_device(S, data, on_device, n_frames, n_new, flush);
         if (served) S.feeds_device++;
         else {
             WA_WARN("%s: the device path failed, this session continues on the host\n", __func__);
@@ -268,7 +275,7 @@ static int stream_push(whisper_amd_stream & S, const void * data, int64_t n_fram
         }
     }
     if (!served) {
-        if (!push_host(S, data, on_device, n_frames, n_new)) { WA_ERROR("%s: the host path failed\n", __func__); return WHISPER_AMD_STREAM_FAILED; }
+        if (!push_host(S, data, on_device, n_frames, n_new, flush)) { WA_ERROR("%s: the host path failed\n", __func__); return WHISPER_AMD_STREAM_FAILED; }
         S.feeds_host++;
     }
     if (!flush) S.T += n_frames;
@@ -428,7 +435,7 @@ static whisper_amd_stream * stream_make(whisper_amd_stream * s, size_t pcm_float
         if (!stream_to_host(*s)) { stream_free(s); return nullptr; }
         return s;
     }
-    const size_t C = (size_t) std::max(wa_stream_carry_len(s->ap), 1), zb = (size_t) std::max(wa_stream_flush_frames(s->ap), 1) * frame_bytes(*s);
+    const size_t C = (size_t) std::max(wa_stream_carry_len(s->ap), 1), zb = (size_t) std::max(wa_stream_flush_frames(s->ap), 1) * frame_bytes(*s, true);
     bool ok = (!s->ap.K || (s->d_taps = wa_audio_taps_device(*ctx, s->ap)))
            && WA_HIP_OK(hipMalloc((void **) &s->d_ring, (size_t) s->cap * sizeof(float)))
            && WA_HIP_OK(hipMalloc((void **) &s->d_carry[0], C * sizeof(float))) && WA_HIP_OK(hipMalloc((void **) &s->d_carry[1], C * sizeof(float)))
@@ -496,7 +503,7 @@ int whisper_amd_stream_flush(struct whisper_amd_stream * s) {
         if (!s->ended) {
             const int Z = wa_stream_flush_frames(s->ap);
             if (Z > 0) {
-                const std::vector<uint8_t> zeros((size_t) Z * frame_bytes(*s), 0);
+                const std::vector<uint8_t> zeros((size_t) Z * frame_bytes(*s, true), 0);
                 const int rc = stream_push(*s, s->host ? (const void *) zeros.data() : (const void *) s->d_zero, Z, true);
                 if (rc < 0) return rc;
             }

@@ -190,8 +190,11 @@ struct wa_stream_ref {
     int64_t flush(float * out) {
         const int64_t Z = wa_stream_flush_frames(ap);
         if (Z == 0) return 0;
-        const std::vector<uint8_t> zeros((size_t) Z * channels * (format == WA_AUDIO_I16 ? 2 : 4), 0);
+        const int fmt = format;
+        format = wa_audio_silence_format(fmt);     // zero bytes are silence in I16 and F32 only: the other formats' zero frames travel as F32
+        const std::vector<uint8_t> zeros((size_t) Z * wa_audio_frame_bytes(format, channels), 0);
         const int64_t T0 = T, made = push(zeros.data(), Z, out);
+        format = fmt;
         T = T0;                                    // the zero frames are no input: T keeps counting the caller's
         return made;
     }
@@ -213,6 +216,10 @@ struct wa_stream_ref {
 bool wa_stream_push_launch(void * stream, const void * d_data, long long n_frames, int channels, int format, const wa_audio_plan & p, const float * d_taps,
                            long long T, const float * d_carry_in, float * d_carry_out, long long n_first, long long n_new, float * d_ring, long long cap,
                            long long r_w);
+// the same for the formats that are not wa_audio_format_base (wa_audio_fmt.hip)
+bool wa_stream_push_fmt_launch(void * stream, const void * d_data, long long n_frames, int channels, int format, const wa_audio_plan & p, const float * d_taps,
+                               long long T, const float * d_carry_in, float * d_carry_out, long long n_first, long long n_new, float * d_ring, long long cap,
+                               long long r_w);
 
 // the windows of up to WA_STREAM_SESSIONS sessions in one launch: per session the ring, its pieces in window order and the destination
 struct wa_stream_window {

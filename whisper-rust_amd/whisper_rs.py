@@ -312,6 +312,8 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         proto("whisper_amd_audio_copy", C.c_int64, P, C.POINTER(F), C.c_int64)
         proto("whisper_amd_audio_taps", C.c_int64, I, C.POINTER(F), C.c_int64, C.POINTER(I), C.POINTER(I), C.POINTER(I))
         proto("whisper_amd_audio_tile", I)
+        if hasattr(lib, "whisper_amd_wav_parse"):
+            proto("whisper_amd_wav_parse", I, P, C.c_int64, P)
         proto("whisper_amd_audio_stats", None, P, C.POINTER(C.c_long))
     if hasattr(lib, "whisper_amd_full_long"):
         I64P, I32P = C.POINTER(C.c_int64), C.POINTER(C.c_int32)
@@ -372,6 +374,87 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
 
 
 PCM_I16, PCM_F32 = 0, 1      # WHISPER_AMD_PCM_* (include/whisper_amd.h)
+PCM_U8, PCM_S24, PCM_S32, PCM_F64, PCM_ULAW, PCM_ALAW = 3, 4, 5, 6, 7, 8
+PCM_SAMPLE_BYTES = {PCM_I16: 2, PCM_F32: 4, PCM_U8: 1, PCM_S24: 3, PCM_S32: 4, PCM_F64: 8, PCM_ULAW: 1, PCM_ALAW: 1}
+# what a host array of a format holds: S24 travels as its packed bytes (pack_s24)
+PCM_DTYPE = {PCM_I16: np.int16, PCM_F32: np.float32, PCM_U8: np.uint8, PCM_S24: np.uint8, PCM_S32: np.int32, PCM_F64: np.float64,
+             PCM_ULAW: np.uint8, PCM_ALAW: np.uint8}
+WAV_BAD_ARGS, WAV_NOT_WAVE, WAV_MALFORMED, WAV_UNSUPPORTED, WAV_NO_DATA = -1, -2, -3, -4, -5      # whisper_amd_wav_parse's codes
+
+
+def pcm_format_of(data, fmt: Optional[int]) -> int:
+    """the format of a host array when none is given: int16 is I16, everything else is taken as F32 (the other formats are named)"""
+    if fmt is None:
+        return PCM_I16 if np.asarray(data).dtype == np.int16 else PCM_F32
+    return fmt
+
+
+def pcm_array(data, fmt: int) -> np.ndarray:
+    """`data` as the flat contiguous array of format `fmt` that the C entries read"""
+    return np.ascontiguousarray(data, dtype=PCM_DTYPE.get(fmt, np.float32)).reshape(-1)
+
+
+def pcm_frames(a: np.ndarray, channels: int, fmt: int) -> int:
+    """frames in a flat array of format `fmt`: its bytes over the bytes of one frame"""
+    return a.nbytes // (PCM_SAMPLE_BYTES.get(fmt, 4) * max(channels, 1))
+
+
+def pack_s24(samples) -> np.ndarray:
+    """integers in [-2^23, 2^23) as packed 3-byte little-endian samples (uint8)"""
+    s = np.asarray(samples, dtype=np.int32).reshape(-1)
+    return np.ascontiguousarray(s.astype("<i4").view(np.uint8).reshape(-1, 4)[:, :3]).reshape(-1)
+
+
+def ulaw_to_linear(codes) -> np.ndarray:
+    """G.711 mu-law expansion to int16, the arithmetic of csrc/wa_audio.h (wa_audio_ulaw)"""
+    u = ~np.asarray(codes, dtype=np.uint8).astype(np.int32) & 0xFF
+    t = ((((u & 15) << 3) + 0x84) << ((u >> 4) & 7)) - 0x84
+    return np.where(u & 0x80, -t, t).astype(np.int16)
+
+
+def alaw_to_linear(codes) -> np.ndarray:
+    """G.711 A-law expansion to int16 (wa_audio_alaw)"""
+    a = np.asarray(codes, dtype=np.uint8).astype(np.int32) ^ 0x55
+    x = (a >> 4) & 7
+    t = ((a & 15) << 4) + 8
+    t = np.where(x > 0, (t + 0x100) << np.maximum(x - 1, 0), t)
+    return np.where(a & 0x80, t, -t).astype(np.int16)
+
+
+def linear_to_ulaw(samples) -> np.ndarray:
+    """G.711 mu-law compression of int16 samples (bias 0x84, clip 32635): the code whose expansion lies nearest below in magnitude"""
+    s = np.asarray(samples, dtype=np.int16).astype(np.int32)
+    sign = np.where(s < 0, 0x80, 0)
+    m = np.minimum(np.abs(s), 32635) + 0x84
+    seg = np.frexp(m.astype(np.float64))[1].astype(np.int32) - 8       # floor(log2 m) - 7; m in [0x84, 0x7fff]: segments 0 .. 7
+    return (~(sign | (seg << 4) | ((m >> (seg + 3)) & 15)) & 0xFF).astype(np.uint8)
+
+
+def linear_to_alaw(samples) -> np.ndarray:
+    """G.711 A-law compression of int16 samples: the code whose expansion lies nearest (the lower code where two are as near)"""
+    table = alaw_to_linear(np.arange(256, dtype=np.uint8)).astype(np.int32)
+    order = np.argsort(table, kind="stable")
+    levels = table[order]
+    s = np.asarray(samples, dtype=np.int16).astype(np.int32)
+    hi = np.clip(np.searchsorted(levels, s), 1, 255)
+    pick = np.where(s - levels[hi - 1] <= levels[hi] - s, hi - 1, hi)
+    return order[pick].astype(np.uint8)
+
+
+class whisper_amd_wav_info(C.Structure):
+    _fields_ = [("data_offset", C.c_int64), ("n_frames", C.c_int64), ("channels", C.c_int32), ("sample_rate", C.c_int32), ("format", C.c_int32),
+                ("bits", C.c_int32)]
+
+
+def wav_parse(lib: C.CDLL, image) -> dict:
+    """Extension (whisper_amd_wav_parse): the header of a RIFF/WAVE image (bytes or a uint8 array) as a dict of data_offset, n_frames, channels,
+    sample_rate, format and bits; raises WhisperError with the entry's code where it refuses."""
+    buf = np.frombuffer(bytes(image), np.uint8) if isinstance(image, (bytes, bytearray, memoryview)) else np.ascontiguousarray(image, dtype=np.uint8)
+    w = whisper_amd_wav_info()
+    rc = lib.whisper_amd_wav_parse(C.c_void_p(buf.ctypes.data if len(buf) else None), len(buf), C.byref(w))
+    if rc != 0:
+        raise WhisperError("WavRefused(%d)" % rc, rc)
+    return {k: int(getattr(w, k)) for k, _ in whisper_amd_wav_info._fields_}
 
 
 # whisper-rs' audio utilities (src/utilities.rs) restated in numpy, every operation rounded to F32 on its own
@@ -760,14 +843,14 @@ class WhisperState:
 
     # -- audio front end (whisper_amd_audio_*): int16 / F32, mono / stereo, 8 .. 192 kHz -> 16 kHz mono F32 on the device -------
     def _audio_args(self, data, channels, fmt):
-        """`data`: a numpy array of interleaved int16 or float32 samples on the host, or (device pointer, n_frames) with `fmt` given"""
+        """`data`: a numpy array of interleaved samples on the host - int16 or float32, or what PCM_DTYPE names for a `fmt` given (S24: packed
+        bytes) -, or (device pointer, n_frames) with `fmt` given"""
         if isinstance(data, tuple):
             return data[0], int(data[1]), fmt
-        if fmt is None:
-            fmt = PCM_I16 if np.asarray(data).dtype == np.int16 else PCM_F32
-        data = np.ascontiguousarray(data, dtype=np.int16 if fmt == PCM_I16 else np.float32).reshape(-1)
+        fmt = pcm_format_of(data, fmt)
+        data = pcm_array(data, fmt)
         self._audio_keep = data
-        return (data.ctypes.data if len(data) else None), len(data) // max(channels, 1), fmt
+        return (data.ctypes.data if len(data) else None), pcm_frames(data, channels, fmt), fmt
 
     def audio_to_pcm(self, data, channels: int, sample_rate: int, fmt: Optional[int] = None) -> tuple:
         """Extension (whisper_amd_audio_to_pcm): returns (device pointer, n_samples) of the 16 kHz mono F32 audio, valid until the next call
@@ -1087,11 +1170,10 @@ class WhisperFullContext:
 
     def full_long_audio(self, params: FullParams, data, channels: int, sample_rate: int, fmt: Optional[int] = None, max_chunk_ms: int = 0,
                         n_parallel: int = 0) -> int:
-        """Extension (whisper_amd_full_long_audio): interleaved int16 or float32 samples at any supported rate."""
-        if fmt is None:
-            fmt = PCM_I16 if np.asarray(data).dtype == np.int16 else PCM_F32
-        self._audio_keep = data = np.ascontiguousarray(data, dtype=np.int16 if fmt == PCM_I16 else np.float32).reshape(-1)
-        return self.lib.whisper_amd_full_long_audio(self.ptr, params.c, C.c_void_p(data.ctypes.data), len(data) // max(channels, 1), channels,
+        """Extension (whisper_amd_full_long_audio): interleaved samples of any format (int16 or float32 where `fmt` is not given) at any supported rate."""
+        fmt = pcm_format_of(data, fmt)
+        self._audio_keep = data = pcm_array(data, fmt)
+        return self.lib.whisper_amd_full_long_audio(self.ptr, params.c, C.c_void_p(data.ctypes.data), pcm_frames(data, channels, fmt), channels,
                                                     sample_rate, fmt, max_chunk_ms, n_parallel)
 
     def long_chunks(self) -> list[dict]:
@@ -1139,10 +1221,9 @@ class WhisperFullContext:
         if isinstance(data, tuple):
             ptr, n_frames = data
         else:
-            if fmt is None:
-                fmt = PCM_I16 if np.asarray(data).dtype == np.int16 else PCM_F32
-            self._audio_keep = data = np.ascontiguousarray(data, dtype=np.int16 if fmt == PCM_I16 else np.float32).reshape(-1)
-            ptr, n_frames = (data.ctypes.data if len(data) else None), len(data) // 2
+            fmt = pcm_format_of(data, fmt)
+            self._audio_keep = data = pcm_array(data, fmt)
+            ptr, n_frames = (data.ctypes.data if len(data) else None), pcm_frames(data, 2, fmt)
         cp = whisper_amd_channels_params()
         self.lib.whisper_amd_channels_default_params(C.byref(cp))
         cp.max_chunk_ms, cp.n_parallel, cp.crosstalk_ratio = max_chunk_ms, n_parallel, crosstalk_ratio
@@ -1222,8 +1303,8 @@ class WhisperStream:
         Returns the windows now due or a negative STREAM_* code."""
         if isinstance(data, tuple):
             return self.lib.whisper_amd_stream_feed(self.ptr, C.c_void_p(data[0]), data[1])
-        a = np.ascontiguousarray(data, dtype=np.int16 if self.params.format == PCM_I16 else np.float32).reshape(-1)
-        return self.lib.whisper_amd_stream_feed(self.ptr, C.c_void_p(a.ctypes.data), len(a) // self.params.channels)
+        a = pcm_array(data, self.params.format)
+        return self.lib.whisper_amd_stream_feed(self.ptr, C.c_void_p(a.ctypes.data), pcm_frames(a, self.params.channels, self.params.format))
 
     def flush(self) -> int:
         return self.lib.whisper_amd_stream_flush(self.ptr)
