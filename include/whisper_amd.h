@@ -69,7 +69,7 @@ WHISPER_API void ggml_backend_load_all(void);
 struct whisper_context;      /* read-only model: weights resident in HBM, vocab, filters          */
 struct whisper_state;        /* per-stream mutable state: mel, activations, KV caches, results    */
 struct whisper_full_params;
-struct whisper_vad_context;  /* Silero VAD: front end on the device, LSTM recurrence on the host ("VAD") */
+struct whisper_vad_context;  /* Silero VAD: front end and LSTM recurrence on the device ("VAD") */
 struct whisper_vad_segments;
 
 typedef int32_t whisper_pos;
@@ -458,6 +458,21 @@ WHISPER_API int64_t whisper_amd_vad_front  (struct whisper_vad_context * vctx, c
 WHISPER_API int     whisper_amd_vad_tile   (void);
 WHISPER_API void    whisper_amd_vad_timings(struct whisper_vad_context * vctx, int64_t out_us[3]);
 
+/* The VAD's LSTM recurrence on the device (k_vad_lstm): one launch walks up to 8 independent sequences, a workgroup each, and
+ * gives the bits of the host recurrence.  A context takes the device path unless, when it is created, WHISPER_AMD_VAD_LSTM_HOST=1 is set or
+ * this process's expf / tanhf differ from the restated ones on a fixed probe set (one warning); a failed HIP call of the path ends it for the
+ * context's lifetime.  Either path gives the same probabilities.
+ * whisper_amd_vad_lstm_path: 1 device, 0 host.
+ * whisper_amd_vad_recur: the kernel alone on the caller's data, all host pointers, staged by the call: sequence b < B (1..8) has n_windows[b]
+ *   rows of gate inputs gates[b][n][512], its state h[b], c[b] [128] (read, advanced, written back) and probs[b][n]; n_windows[b] = 0 leaves
+ *   sequence b untouched.  Returns 0, or -1 where the device path is off, the arguments are refused or a HIP call failed.
+ * whisper_amd_vad_lstm_stats: out = { k_vad_lstm launches, windows they walked, their device time in us (events around each launch) } since the
+ *   context was created; live sessions opened on the context count here too. */
+WHISPER_API int     whisper_amd_vad_lstm_path (struct whisper_vad_context * vctx);
+WHISPER_API int     whisper_amd_vad_recur     (struct whisper_vad_context * vctx, const float * const * gates, const int * n_windows, int B,
+                                               float * const * h, float * const * c, float * const * probs);
+WHISPER_API void    whisper_amd_vad_lstm_stats(struct whisper_vad_context * vctx, int64_t out[3]);
+
 /* Per-state stage timers in microseconds + call counts (the reference keeps them per state but
  * only prints ctx->state's, whisper.cpp:868-881,4274-4296):
  * out = { t_sample, t_encode, t_decode, t_batchd, t_prompt, t_mel, n_sample, n_encode, n_decode,
@@ -757,7 +772,8 @@ WHISPER_API struct whisper_state * whisper_amd_context_state(struct whisper_cont
  *   agree wherever the energies are not within that of the threshold.
  * whisper_amd_full_long_channels, on the context's own state: whisper_amd_full_long for both channels of one recording in one call.
  *   - One whisper_amd_audio_split: the recording crosses PCIe once (host input) or never (device input).
- *   - The VAD runs per plane, where it lies, on the state's VAD context, channel 0 then channel 1.
+ *   - The VAD runs per plane, where it lies, on the state's VAD context: both planes' front ends, then both recurrences in one launch per slab
+ *     (channel 0 then channel 1 where the context keeps the host recurrence).
  *   - crosstalk_ratio = g > 0: ONE energy launch covers every VAD segment of both channels over its own span [cs_to_samples(start),
  *     min(cs_to_samples(end), n_samples)); a segment of channel c is dropped when E_c < g * E_other (the other speaker bleeding through).
  *     g = 0 launches nothing and drops nothing; g < 0 is refused.
@@ -957,21 +973,26 @@ WHISPER_API int     whisper_amd_stream_tile(void);
  *   has no segment over the cap the utterances ARE S.  (csrc/wa_stream_vad.h states the rule; tools/stream_vad_ref.py restates it.)
  * Prompt: carry_prompt = 0 (stream.cpp's VAD mode never fills prompt_tokens): every utterance runs with the caller's prompt.  1: utterance j + 1
  *   runs with every token id of utterance j's result.
- * whisper_amd_stream_open_vad: `vctx` is the caller's whisper_vad_context on the context's device; sessions share it read-only (it must outlive
- *   them; whisper_vad_detect_speech on it stays the caller's to use), each owns its LSTM state and probabilities.  The ring holds max_utterance +
+ * whisper_amd_stream_open_vad: `vctx` is the caller's whisper_vad_context on the context's device; sessions share its weights read-only (it must
+ *   outlive them; whisper_vad_detect_speech on it stays the caller's to use, also while sessions run on other threads), each owns its LSTM state,
+ *   probabilities and the timing events of its launches.  All a session writes to the vctx are the whisper_amd_vad_lstm_stats counters and, after a
+ *   failed HIP call of the device recurrence, the flag behind whisper_amd_vad_lstm_path: atomics, so sessions of one vctx may run on threads of
+ *   their own (one thread at a time per session, as before).  The ring holds max_utterance +
  *   backlog samples, backlog = backlog_ms x 16, raised to 16000 x max_speech_duration_s + 8192: an open speech and a candidate behind it always
  *   fit.  Refused (NULL, an error log line, nothing made) for null arguments, what whisper_amd_audio_to_pcm refuses, speech_pad_ms outside
  *   [0, 100], max_utterance_ms outside (0, 30000], max_speech_duration_s above the cap (or below one window and its pads: the reference then
  *   drops the bound), negative durations, a vctx of another device.  whisper_amd_stream_open keeps refusing step_ms <= 0.
  * The calls above on a VAD session: _feed is the same single k_stream_push launch; with vad_on_feed = 1 it also runs the front end on the
- *   session's new whole windows (one k_stream_vad_front launch straight from the ring), the recurrence and the segmenter on the calling thread,
- *   and returns the utterances due.  FULL, with nothing changed, when the packet would overwrite an utterance that is due or still open, or a
+ *   session's new whole windows (one k_stream_vad_front launch straight from the ring), the recurrence behind it (one k_vad_lstm launch, the
+ *   session's LSTM state resident in device memory; on the calling thread where the VAD context keeps the host recurrence, see
+ *   whisper_amd_vad_lstm_path) and the segmenter on the calling thread, and returns the utterances due.  FULL, with nothing changed, when the packet would overwrite an utterance that is due or still open, or a
  *   window not yet processed.  _flush processes the last partial window and closes an open speech.  _pending: the utterances due.  _step /
  *   _step_many run ONE due utterance per session - one k_stream_window gather (per group of 8), then whisper_full_with_state, alone or in the
  *   lock-step group, exactly as for windows; segment times are relative to the utterance.  _info: windows run counts utterances, take is 0,
  *   committed 1.  _window_copy / _prompt_copy: the last utterance's PCM and prompt.  _reset: a fresh session's state, LSTM included.
  * whisper_amd_stream_vad_poll_many: for servers that set vad_on_feed = 0: the new whole windows of all `ss` (VAD sessions of one context and
- *   one vctx; at most 64; MIXED otherwise) through ONE k_stream_vad_front launch per group of up to 8 sessions, then recurrences and segmenters
+ *   one vctx; at most 64; MIXED otherwise) through ONE k_stream_vad_front launch per group of up to 8 sessions and ONE k_vad_lstm launch behind
+ *   it that walks every session's recurrence, a workgroup per session (whisper_amd_vad_lstm_stats of the vctx counts it); then the segmenters
  *   on the calling thread.  Returns the utterances due in total.  Nothing is done for windows already processed.
  * whisper_amd_stream_utterance_info: out = { utterances run, the last one's start on the absolute 16 kHz axis, its length, its start_cs, its
  *   end_cs, whether it was split at the cap (0 / 1), front-end launches so far, windows processed so far }.

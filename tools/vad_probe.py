@@ -3,7 +3,12 @@
 for VAD) on the synthetic VAD model: the 14 s test audio (438 windows) and 30 minutes of it repeated (56 250 windows).  Prints one JSON
 line; the product's split between waiting for the device and the host recurrence comes from whisper_amd_vad_timings.
 
-  python tools/vad_probe.py [--no-ref] [--reps 3]
+"recurrence": the device recurrence alone (k_vad_lstm through whisper_amd_vad_recur, device time from the events around each launch) over
+B = 1, 2, 8 sequences of 8192 windows each, in us per window of a sequence, and - with --parent, the library of the parent commit, whose
+recurrence is the host's - that library's whisper_vad_detect_speech on the same audio in the same session, the two alternating: its host
+recurrence per window (whisper_amd_vad_timings) and its wall time beside the product's.
+
+  python tools/vad_probe.py [--no-ref] [--reps 3] [--parent path/to/parent/libwhisper.so]
 """
 import argparse
 import ctypes as C
@@ -28,10 +33,56 @@ def timings(lib, v):
     return [int(x) for x in out]
 
 
+def recurrence(a, lib, v, mp, pcm, long_pcm, n_seq=8192):
+    out = dict(lstm_path=v.lstm_path(), windows_per_sequence=n_seq)
+    parent = pv = None
+    if a.parent:
+        parent = W.load_library(a.parent)
+        W.set_log_callback(parent, None)
+        pv = W.WhisperVadContext.new(mp, lib=parent)
+        pv.detect_speech(pcm)
+    gates = v.front(long_pcm[:n_seq * 512]) if out["lstm_path"] else None
+    z = np.zeros((8, 128), np.float32)
+    runs = {"B1": [], "B2": [], "B8": [], "parent_host_us_per_window": [], "parent_30_min_wall_ms": [], "product_30_min_wall_ms": [],
+            "parent_438_windows_wall_ms": [], "product_438_windows_wall_ms": []}
+    for rep in range(a.reps + 1):                            # the first round warms every shape up and is dropped
+        for B in (1, 2, 8):
+            if gates is None:
+                continue
+            s0 = v.lstm_stats()
+            v.recur([gates] * B, z[:B], z[:B])
+            s1 = v.lstm_stats()
+            assert s1[0] - s0[0] == 1 and s1[1] - s0[1] == B * n_seq
+            runs["B%d" % B].append((s1[2] - s0[2]) / n_seq)
+        for tag, ctx in (("product", v), ("parent", pv)):    # the 14 s audio, 20 calls each
+            if ctx is not None:
+                w0 = time.perf_counter()
+                for _ in range(20):
+                    ctx.detect_speech(pcm)
+                runs[tag + "_438_windows_wall_ms"].append((time.perf_counter() - w0) * 1e3 / 20)
+        w0 = time.perf_counter()
+        p_new = v.detect_speech(long_pcm)
+        runs["product_30_min_wall_ms"].append((time.perf_counter() - w0) * 1e3)
+        if pv is not None:
+            t0 = timings(parent, pv)
+            w0 = time.perf_counter()
+            p_old = pv.detect_speech(long_pcm)
+            runs["parent_30_min_wall_ms"].append((time.perf_counter() - w0) * 1e3)
+            runs["parent_host_us_per_window"].append((timings(parent, pv)[2] - t0[2]) / len(p_old))
+            out["same_bits_as_parent"] = bool(np.array_equal(p_new.view(np.uint32), p_old.view(np.uint32)))
+    if pv is not None:
+        pv.free()
+    for k, r in runs.items():
+        if len(r) > 1:
+            out[k] = dict(median=float(np.median(r[1:])), runs=[round(x, 3) for x in r[1:]])
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--no-ref", action="store_true")
     ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--parent", default=None)
     a = ap.parse_args()
     mp, pcm = V.model_path(), V.synth_audio()
     long_pcm = np.tile(pcm, -(-30 * 60 * 16000 // len(pcm)))[:30 * 60 * 16000]
@@ -58,6 +109,7 @@ def main():
         v.front(x)
         res[tag]["product_front_only_ms"] = (time.perf_counter() - w0) * 1e3
         res[tag]["bits_head"] = [int(b) for b in p[:4].view(np.uint32)]
+    res["recurrence"] = recurrence(a, lib, v, mp, pcm, long_pcm)
     v.free()
 
     ref_path = os.path.join(ROOT, "oracle", "_ref", "libwhisper_ref.so")

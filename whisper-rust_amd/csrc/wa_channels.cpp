@@ -172,10 +172,9 @@ static int channels_full(whisper_context * ctx, whisper_full_params params, cons
     // 2. the VAD per plane, where it lies
     int64_t t = wa_time_us();
     std::vector<wa_vad_seg> found[2], kept[2];
-    for (int c = 0; c < 2; ++c) {
-        if (!wa_vad_segments_for(ctx, st, params, planes + c * stride, n, found[c])) { WA_ERROR("%s: failed to compute VAD\n", __func__); return -1; }
-        C.stats[4 + c] = (int64_t) found[c].size();
-    }
+    const float * const plane[2] = { planes, planes + stride };
+    if (!wa_vad_segments_for2(ctx, st, params, plane, n, found)) { WA_ERROR("%s: failed to compute VAD\n", __func__); return -1; }
+    for (int c = 0; c < 2; ++c) C.stats[4 + c] = (int64_t) found[c].size();
     L.stats[4] = wa_time_us() - t;
     if (found[0].empty() && found[1].empty()) return 0;
 

@@ -427,12 +427,31 @@ bool wa_decode     (whisper_context & ctx, whisper_state & st, const wa_batch & 
 whisper_vad_context * wa_vad_create_from_file(const char * path, int n_threads, int device);
 bool wa_vad_segments_for(whisper_context * ctx, whisper_state * st, const whisper_full_params & params, const float * samples, int n_samples,
                          std::vector<wa_vad_seg> & segs);      // `samples` host or device; false: failure; the state's table is cleared
+bool wa_vad_segments_for2(whisper_context * ctx, whisper_state * st, const whisper_full_params & params, const float * const * planes, int n_samples,
+                          std::vector<wa_vad_seg> * segs);     // both planes of a two-channel recording (segs[2]): one recurrence launch per slab for the two
 bool wa_vad_for_full(whisper_context * ctx, whisper_state * st, const whisper_full_params & params, const float * samples, int n_samples,
                      std::vector<float> & filtered);           // false: failure; `filtered` empty: no speech
 // what a live VAD session (wa_stream.cpp) reads of the caller's context: shared, never written
 int                  wa_vad_ctx_device(const whisper_vad_context * v);
 const wa_vad_model & wa_vad_ctx_model (const whisper_vad_context * v);
 const wa_vad_dev &   wa_vad_ctx_dev   (const whisper_vad_context * v);
+// The device recurrence of that context (k_vad_lstm), for the sessions too.  Sessions of one context may run on threads of their own beside one
+// another and beside whisper_vad_detect_speech on it, so all they share with it is: the weights (never written), the path flag and the three
+// counters (atomics).  The timing events of a launch belong to whoever launches: a wa_vlstm_span of the caller's own.
+bool wa_vad_ctx_lstm_on (const whisper_vad_context * v);
+void wa_vad_ctx_lstm_off(whisper_vad_context * v, const char * who);       // after a HIP failure: host recurrence from then on (logged once)
+void wa_vad_ctx_lstm_add(whisper_vad_context * v, int64_t launches, int64_t windows, double device_us);
+// k_vad_lstm launches on one stream between timing events, at most WA_VLSTM_SPAN in flight; `publish`, after the stream was synchronised,
+// adds them to the context's counters.  A full span synchronises the stream itself and publishes before it goes on.  One owner, one thread.
+#define WA_VLSTM_SPAN 8
+struct wa_vlstm_span {
+    hipEvent_t ev[2 * WA_VLSTM_SPAN] = { nullptr };
+    int used = 0;
+    int64_t launches = 0, windows = 0;
+    bool launch(whisper_vad_context * v, const wa_vlstm_table & t, hipStream_t stream);
+    void publish(whisper_vad_context * v);
+    void release();
+};
 // host-overlapped greedy decoding on the one-launch step (wa_decode.cpp); launch k decodes position pos0 + k
 struct wa_spec_state { int last, penult, seek_delta, has_ts; };
 bool wa_spec_begin (whisper_context & ctx, whisper_state & st, const std::vector<uint32_t> & suppress_bits);

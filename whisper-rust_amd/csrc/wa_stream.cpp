@@ -10,8 +10,11 @@
 //
 // A VAD session (whisper_amd_stream_open_vad) is the same object with another plan: no steps, but the utterances the Silero VAD
 // cuts.  Its ring axis IS the absolute axis (nothing is dropped).  The new whole 512-sample windows of up to 8 sessions go through ONE launch of
-// k_stream_vad_front (wa_vad.hip), which reads them where they lie in the rings and writes their gate inputs into the sessions' pinned buffers;
-// the calling thread then walks each session's LSTM (wa_vad_step) and its incremental segmenter (wa_stream_vad.h).  An utterance that became
+// k_stream_vad_front (wa_vad.hip), which reads them where they lie in the rings and writes their gate inputs into the sessions' buffers in HBM;
+// ONE launch of k_vad_lstm (wa_vad_lstm.hip) behind it walks every session's LSTM over them, a workgroup per session, with the sessions' h and c
+// resident in HBM; probabilities and the new state come back in one small copy per session and the calling thread runs the incremental
+// segmenters (wa_stream_vad.h).  A VAD context that keeps the host recurrence (wa_vad.cpp) gets the gate inputs in pinned buffers and the
+// calling thread walks the LSTMs (wa_vad_step), as does every session after a HIP call of its own failed.  An utterance that became
 // final is queued; a step gathers it - the same k_stream_window launch - and runs whisper_full_with_state on it, as for a window.
 #include "wa_wave.h"
 #include "wa_stream.h"
@@ -49,7 +52,11 @@ struct whisper_amd_stream {
     std::deque<wa_svad_out> due;                    // utterances that are final and have not run
     int64_t win_done = 0;                           // windows processed: the front end stands at sample 512 win_done
     bool tail_done = false;                         // the end of input has been processed: partial window and the segmenter's flush
-    float * h_gates = nullptr; size_t h_gates_cap = 0;          // pinned, [windows][512]: k_stream_vad_front writes it
+    float * h_gates = nullptr; size_t h_gates_cap = 0;          // pinned, [windows][512]: k_stream_vad_front writes it (host recurrence)
+    float * d_gates = nullptr; size_t d_gates_cap = 0;          // the same in HBM (device recurrence)
+    float * d_lstm = nullptr;                                   // [h 128 | c 128 | probabilities of a tick, WA_SVAD_MAX_WINDOWS]: the state lives here;
+    std::vector<float> h_lstm;                                  //  its copy after each tick, which keeps `lstm` below current for a fall-back
+    wa_vlstm_span span;                                         // the timing events of the recurrence launches this session leads
     float * d_stage = nullptr; size_t d_stage_cap = 0;          // host ring only: the new windows laid out linearly, and their gate inputs
     float * d_stage_out = nullptr; size_t d_stage_out_cap = 0;
     wa_svad_out last_utt;
@@ -133,12 +140,13 @@ static int vad_new_windows(const whisper_amd_stream & S, int & n_valid) {
     return (int) n;
 }
 
-// gate inputs of n windows -> probabilities -> segmenter; then, at the end of input, the segmenter's flush
-static void vad_consume(whisper_amd_stream & S, const float * gates, int n) {
+// n windows' probabilities - the device's (`probs`), or the host recurrence over their gate inputs - -> segmenter; then, at the end of input,
+// the segmenter's flush
+static void vad_consume(whisper_amd_stream & S, const float * gates, int n, const float * probs = nullptr) {
     const wa_vad_model & m = wa_vad_ctx_model(S.vctx);
     std::vector<wa_svad_out> out;
     for (int k = 0; k < n; ++k) {
-        const float p = wa_vad_step(m, S.lstm, gates + (size_t) k * WA_VAD_GATES);
+        const float p = probs ? probs[k] : wa_vad_step(m, S.lstm, gates + (size_t) k * WA_VAD_GATES);
         S.probs.push_back(p);
         S.seg.push(p, out);
     }
@@ -174,6 +182,7 @@ static bool vad_process(whisper_amd_stream ** ss, int n) {
             memset(&tab, 0, sizeof(tab));
             whisper_amd_stream * row[WA_SVAD_SESSIONS];
             int cnt[WA_SVAD_SESSIONS], nr = 0;
+            const bool lstm_dev = wa_vad_ctx_lstm_on(ss[0]->vctx);      // for the whole group: one recurrence launch, or none
             for (int i = 0; i < gn; ++i) {
                 whisper_amd_stream & S = *ss[g0 + i];
                 int n_valid = 0;
@@ -183,7 +192,18 @@ static bool vad_process(whisper_amd_stream ** ss, int n) {
                     continue;
                 }
                 if (nw == WA_SVAD_MAX_WINDOWS) again = true;
-                if (!S.host) {
+                if (!S.host && lstm_dev) {
+                    const size_t hc = 2 * WA_VAD_HID;
+                    bool made = wa_dev_reserve(S.d_gates, S.d_gates_cap, std::max<size_t>((size_t) nw, 64) * WA_VAD_GATES);
+                    if (made && !S.d_lstm) {        // the state moves to the device as it stands
+                        S.h_lstm.assign(hc + WA_SVAD_MAX_WINDOWS, 0.0f);
+                        memcpy(S.h_lstm.data(), S.lstm.h, sizeof(S.lstm.h)); memcpy(S.h_lstm.data() + WA_VAD_HID, S.lstm.c, sizeof(S.lstm.c));
+                        made = WA_HIP_OK(hipMalloc((void **) &S.d_lstm, S.h_lstm.size() * sizeof(float)))
+                            && WA_HIP_OK(hipMemcpy(S.d_lstm, S.h_lstm.data(), hc * sizeof(float), hipMemcpyHostToDevice));
+                        if (!made && S.d_lstm) { (void) hipFree(S.d_lstm); S.d_lstm = nullptr; }
+                    }
+                    if (!made) { WA_WARN("%s: no device buffers for the recurrence, session %d continues on the host\n", __func__, g0 + i); if (!stream_to_host(S)) return false; }
+                } else if (!S.host) {
                     if (S.h_gates_cap < (size_t) nw * WA_VAD_GATES) {
                         if (S.h_gates) { (void) hipHostFree(S.h_gates); S.h_gates = nullptr; S.h_gates_cap = 0; }
                         const size_t want = std::max<size_t>((size_t) nw, 64) * WA_VAD_GATES;
@@ -193,7 +213,7 @@ static bool vad_process(whisper_amd_stream ** ss, int n) {
                 }
                 if (S.host) { if (!vad_front_host(S, nw, n_valid)) return false; continue; }
                 wa_svad_session & z = tab.s[nr];
-                z.ring = S.d_ring; z.out = S.h_gates; z.cap = (int32_t) S.cap; z.slot = (int32_t) ((S.win_done * WA_VAD_WINDOW) % S.cap); z.n_valid = n_valid;
+                z.ring = S.d_ring; z.out = lstm_dev ? S.d_gates : S.h_gates; z.cap = (int32_t) S.cap; z.slot = (int32_t) ((S.win_done * WA_VAD_WINDOW) % S.cap); z.n_valid = n_valid;
                 tab.first[nr + 1] = tab.first[nr] + nw;
                 row[nr] = &S; cnt[nr] = nw; ++nr;
             }
@@ -203,11 +223,47 @@ static bool vad_process(whisper_amd_stream ** ss, int n) {
             bool ok = true;
             // the pushes that wrote the rings ran on their own states' streams: the joint launch runs on ONE member's
             for (int i = 1; i < nr && ok; ++i) ok = WA_HIP_OK(hipStreamSynchronize(row[i]->st->stream));
-            ok = ok && wa_svad_front_launch(wa_vad_ctx_dev(row[0]->vctx), tab, (void *) q) && WA_HIP_OK(hipStreamSynchronize(q));
+            ok = ok && wa_svad_front_launch(wa_vad_ctx_dev(row[0]->vctx), tab, (void *) q);
+            if (ok && lstm_dev) {
+                // the recurrences of all of them in one launch behind the front end; probabilities and the new state in one copy per session
+                const size_t hc = 2 * WA_VAD_HID;
+                wa_vlstm_table lt;
+                memset(&lt, 0, sizeof(lt));
+                lt.n_seqs = nr;
+                for (int i = 0; i < nr; ++i) {
+                    wa_vlstm_seq & u = lt.s[i];
+                    u.gates = row[i]->d_gates; u.n = cnt[i];
+                    u.h = row[i]->d_lstm; u.c = u.h + WA_VAD_HID; u.probs = u.h + hc;
+                }
+                bool walked = row[0]->span.launch(row[0]->vctx, lt, q);
+                for (int i = 0; i < nr && walked; ++i)
+                    walked = WA_HIP_OK(hipMemcpyAsync(row[i]->h_lstm.data(), row[i]->d_lstm, (hc + (size_t) cnt[i]) * sizeof(float), hipMemcpyDeviceToHost, q));
+                walked = WA_HIP_OK(hipStreamSynchronize(q)) && walked;
+                row[0]->span.publish(row[0]->vctx);
+                if (!walked) {
+                    // only the recurrence failed: the context turns to the host recurrence, the sessions keep their rings; this tick's gate
+                    // inputs come down from HBM and the calling thread walks them from each session's last state
+                    wa_vad_ctx_lstm_off(row[0]->vctx, __func__);
+                    for (int i = 0; i < nr && ok; ++i) {
+                        std::vector<float> g((size_t) cnt[i] * WA_VAD_GATES);
+                        ok = WA_HIP_OK(hipMemcpy(g.data(), row[i]->d_gates, g.size() * sizeof(float), hipMemcpyDeviceToHost));
+                        if (ok) { row[i]->fe_launches++; vad_consume(*row[i], g.data(), cnt[i]); cnt[i] = 0; }
+                    }
+                    if (ok) continue;
+                }
+            } else ok = ok && WA_HIP_OK(hipStreamSynchronize(q));
             if (ok) {
-                for (int i = 0; i < nr; ++i) { row[i]->fe_launches++; vad_consume(*row[i], row[i]->h_gates, cnt[i]); }
+                for (int i = 0; i < nr; ++i) {
+                    whisper_amd_stream & S = *row[i];
+                    S.fe_launches++;
+                    if (lstm_dev) {
+                        memcpy(S.lstm.h, S.h_lstm.data(), sizeof(S.lstm.h)); memcpy(S.lstm.c, S.h_lstm.data() + WA_VAD_HID, sizeof(S.lstm.c));
+                        vad_consume(S, nullptr, cnt[i], S.h_lstm.data() + 2 * WA_VAD_HID);
+                    } else vad_consume(S, S.h_gates, cnt[i]);
+                }
             } else {
                 for (int i = 0; i < nr; ++i) {
+                    if (cnt[i] == 0) continue;          // served above
                     WA_WARN("%s: the device front end failed, session continues on the host\n", __func__);
                     int n_valid = 0;
                     if (!stream_to_host(*row[i])) return false;
@@ -404,6 +460,9 @@ static void stream_free(whisper_amd_stream * s) {
     if (s->d_carry[1]) (void) hipFree(s->d_carry[1]);
     if (s->d_zero) (void) hipFree(s->d_zero);
     if (s->h_gates) (void) hipHostFree(s->h_gates);
+    if (s->d_gates) (void) hipFree(s->d_gates);
+    if (s->d_lstm) (void) hipFree(s->d_lstm);
+    s->span.release();
     if (s->d_stage) (void) hipFree(s->d_stage);
     if (s->d_stage_out) (void) hipFree(s->d_stage_out);
     if (s->st) whisper_free_state(s->st);
@@ -418,6 +477,7 @@ static bool stream_clear(whisper_amd_stream & S) {
     if (S.vad) {
         S.seg.reset(); S.lstm.reset(); S.probs.clear(); S.due.clear();
         S.win_done = 0; S.tail_done = false; S.last_utt = wa_svad_out(); S.fe_launches = 0;
+        if (S.d_lstm && !WA_HIP_OK(hipMemsetAsync(S.d_lstm, 0, 2 * WA_VAD_HID * sizeof(float), S.st->stream))) return false;
     }
     if (S.host) { S.ref.reset(); return true; }
     const size_t C = (size_t) std::max(wa_stream_carry_len(S.ap), 1);

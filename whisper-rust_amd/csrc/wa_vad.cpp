@@ -1,13 +1,20 @@
-// wa_vad.cpp - whisper_vad_context and the whisper_vad_* API: device weights, the slab pipeline around k_vad_front (wa_vad.hip) and
-// the host recurrence (wa_vad_host.cpp); the VAD step of whisper_full / whisper_full_parallel (ref: whisper.cpp:6615-6793).
+// wa_vad.cpp - whisper_vad_context and the whisper_vad_* API: device weights, the slab pipeline around k_vad_front (wa_vad.hip), the
+// recurrence on the device (k_vad_lstm, wa_vad_lstm.hip) or on the host (wa_vad_host.cpp); the VAD step of whisper_full /
+// whisper_full_parallel (ref: whisper.cpp:6615-6793).
 //
 // whisper_vad_detect_speech cuts the audio into slabs of `slab` windows (4096; WHISPER_AMD_VAD_SLAB overrides it when the context is
-// created).  Slab k + 1's samples go to the device and its front end runs on the context's stream while the calling thread walks the
-// LSTM over slab k's gate inputs in a pinned buffer: two buffers of each kind, one event each.
+// created).  Device recurrence: each slab's front end and, behind it on the same stream, one k_vad_lstm launch over its gate
+// inputs where they lie in HBM; the state travels in HBM from slab to slab, the probabilities come back in one copy at the end, and the
+// calling thread waits once.  Two recordings of one call (the planes of whisper_amd_full_long_channels) share every recurrence launch.
+// Host recurrence - a context whose libm is not the one wa_libm.h restates (checked when it is created), WHISPER_AMD_VAD_LSTM_HOST=1, or
+// after a HIP call of the device path failed: slab k + 1's samples go to the device and its front end runs on the context's stream while the
+// calling thread walks the LSTM over slab k's gate inputs in a pinned buffer: two buffers of each kind, one event each.
 #include "wa_internal.h"
 #include "wa_vad.h"
+#include "wa_libm.h"
 
 #include <algorithm>
+#include <atomic>
 #include <cstdlib>
 #include <cstring>
 
@@ -26,6 +33,15 @@ struct whisper_vad_context {
     float * d_samples[2] = { nullptr, nullptr }, * d_out[2] = { nullptr, nullptr }, * h_out[2] = { nullptr, nullptr };
     hipEvent_t ev[2] = { nullptr, nullptr };
     std::vector<float> probs;
+    // the device recurrence
+    // the path of this context's lifetime; a failed HIP call of it turns it off for good.  This flag and the counters are all that live
+    // sessions on other threads write here (wa_internal.h); everything else below belongs to whisper_vad_detect_speech / _vad_recur
+    std::atomic<bool> lstm_dev{ false };
+    float * d_state = nullptr;             // [WA_VLSTM_SEQS][h 128 | c 128]
+    float * d_probs = nullptr; size_t d_probs_cap = 0;
+    float * d_rgates = nullptr; size_t d_rgates_cap = 0;       // whisper_amd_vad_recur's staged gate inputs
+    wa_vlstm_span span;
+    std::atomic<int64_t> lstm_launches{ 0 }, lstm_windows{ 0 }, lstm_dev_ns{ 0 };
 };
 
 // -------------------------------------------------------------------------------------------------
@@ -44,6 +60,7 @@ static bool vad_upload(whisper_vad_context & v) {
     for (int i = 1; i < 4; ++i) o_w[i] = put(m.enc_w[i].data(), m.enc_w[i].size() * 2);
     for (int i = 0; i < 4; ++i) o_b[i] = put(m.enc_b[i].data(), m.enc_b[i].size() * 4);
     const size_t o_wih = put(m.w_ih.data(), m.w_ih.size() * 4), o_bih = put(m.b_ih.data(), m.b_ih.size() * 4);
+    const size_t o_whh = put(m.w_hh.data(), m.w_hh.size() * 4), o_bhh = put(m.b_hh.data(), m.b_hh.size() * 4), o_wf = put(m.w_f.data(), m.w_f.size() * 2);
     img.resize(img.size() + 256);          // the kernel's look-ahead load never leaves a row, the slack is for good measure
     if (!WA_HIP_OK(hipMalloc(&v.d_weights, img.size()))) return false;
     if (!WA_HIP_OK(hipMemcpy(v.d_weights, img.data(), img.size(), hipMemcpyHostToDevice))) return false;
@@ -52,7 +69,19 @@ static bool vad_upload(whisper_vad_context & v) {
     for (int i = 0; i < 4; ++i) { v.dev.enc_w[i] = (const uint16_t *) (base + o_w[i]); v.dev.enc_b[i] = (const float *) (base + o_b[i]); }
     v.dev.w_ih = (const float *) (base + o_wih);
     v.dev.b_ih = (const float *) (base + o_bih);
+    v.dev.w_hh = (const float *) (base + o_whh);
+    v.dev.b_hh = (const float *) (base + o_bhh);
+    v.dev.w_f  = (const uint16_t *) (base + o_wf);
+    v.dev.b_f  = m.b_f;
     return true;
+}
+
+// once per process: wa_libm.h's expf and tanhf against this process's, on the fixed probe set
+static bool vad_libm_same(uint32_t & bad) {
+    static uint32_t first_bad = 0;
+    static const bool same = wa_libm_matches_host(&first_bad);
+    bad = first_bad;
+    return same;
 }
 
 whisper_vad_context * wa_vad_create(whisper_model_loader * loader, int n_threads, int device) {
@@ -78,6 +107,16 @@ whisper_vad_context * wa_vad_create(whisper_model_loader * loader, int n_threads
           && WA_HIP_OK(hipEventCreateWithFlags(&v->ev[i], hipEventDisableTiming));
     }
     if (!ok) { whisper_vad_free(v); return nullptr; }
+    // the recurrence's path, for this context's lifetime
+    const char * force = getenv("WHISPER_AMD_VAD_LSTM_HOST");
+    uint32_t bad = 0;
+    if (force && atoi(force) != 0) WA_INFO("%s: WHISPER_AMD_VAD_LSTM_HOST: the recurrence runs on the host\n", __func__);
+    else if (!vad_libm_same(bad))
+        WA_WARN("%s: this process's expf / tanhf differ from the restated ones (first at bits 0x%08x): the recurrence runs on the host\n", __func__, bad);
+    else if (!WA_HIP_OK(hipMalloc((void **) &v->d_state, (size_t) WA_VLSTM_SEQS * 2 * WA_VAD_HID * sizeof(float)))) {
+        (void) hipGetLastError();
+        WA_WARN("%s: no device state, the recurrence runs on the host\n", __func__);
+    } else v->lstm_dev = true;
     return v;
 }
 
@@ -140,6 +179,91 @@ static bool vad_run_slabs(whisper_vad_context & v, const float * samples, int n_
 }
 
 // -------------------------------------------------------------------------------------------------
+// the device recurrence
+// -------------------------------------------------------------------------------------------------
+bool wa_vad_ctx_lstm_on(const whisper_vad_context * v) { return v->lstm_dev.load(); }
+
+void wa_vad_ctx_lstm_off(whisper_vad_context * v, const char * who) {
+    (void) hipGetLastError();
+    if (v->lstm_dev.exchange(false)) WA_WARN("%s: the device recurrence failed, this VAD context continues with the host recurrence\n", who);
+}
+void wa_vad_ctx_lstm_add(whisper_vad_context * v, int64_t launches, int64_t windows, double device_us) {
+    v->lstm_launches += launches; v->lstm_windows += windows; v->lstm_dev_ns += (int64_t) (1e3 * device_us + 0.5);
+}
+
+bool wa_vlstm_span::launch(whisper_vad_context * v, const wa_vlstm_table & t, hipStream_t stream) {
+    int64_t n = 0;
+    for (int i = 0; i < t.n_seqs; ++i) n += t.s[i].n;
+    if (n == 0) return true;
+    if (used == WA_VLSTM_SPAN) {                         // every pair is in flight: drain them (a long recording, every 8 slabs)
+        if (!WA_HIP_OK(hipStreamSynchronize(stream))) return false;
+        publish(v);
+    }
+    hipEvent_t & e0 = ev[2 * used], & e1 = ev[2 * used + 1];
+    if ((!e0 && !WA_HIP_OK(hipEventCreate(&e0))) || (!e1 && !WA_HIP_OK(hipEventCreate(&e1)))) return false;
+    if (!WA_HIP_OK(hipEventRecord(e0, stream)) || !wa_vlstm_launch(wa_vad_ctx_dev(v), t, (void *) stream) || !WA_HIP_OK(hipEventRecord(e1, stream))) return false;
+    ++used; ++launches; windows += n;
+    return true;
+}
+void wa_vlstm_span::publish(whisper_vad_context * v) {
+    double us = 0.0;
+    for (int i = 0; i < used; ++i) {
+        float ms = 0.0f;
+        if (hipEventElapsedTime(&ms, ev[2 * i], ev[2 * i + 1]) == hipSuccess) us += 1e3 * (double) ms;
+        else (void) hipGetLastError();
+    }
+    wa_vad_ctx_lstm_add(v, launches, windows, us);
+    used = 0; launches = 0; windows = 0;
+}
+void wa_vlstm_span::release() {
+    for (hipEvent_t & e : ev) if (e) { (void) hipEventDestroy(e); e = nullptr; }
+}
+
+// B <= 2 recordings (host or device samples) through the slab loop with the recurrence on the device: probs[b] gets recording b's
+static bool vad_detect_device(whisper_vad_context & v, const float * const * samples, const int * n_samples, int B, std::vector<float> * probs) {
+    if (B < 1 || B > 2 || !WA_HIP_OK(hipSetDevice(v.device))) return false;
+    int n_chunks[2] = { 0, 0 }, n_slabs = 0;
+    size_t off[3] = { 0, 0, 0 };
+    for (int b = 0; b < B; ++b) {
+        n_chunks[b] = wa_vad_n_chunks(n_samples[b]);
+        off[b + 1] = off[b] + (size_t) n_chunks[b];
+        n_slabs = std::max(n_slabs, (n_chunks[b] + v.slab - 1) / v.slab);
+        probs[b].assign((size_t) n_chunks[b], 0.0f);
+    }
+    if (off[B] == 0) return true;
+    if (!wa_dev_reserve(v.d_probs, v.d_probs_cap, off[B])) return false;
+    // the LSTM state is zero at the start of every call
+    bool ok = WA_HIP_OK(hipMemsetAsync(v.d_state, 0, (size_t) B * 2 * WA_VAD_HID * sizeof(float), v.stream));
+    for (int k = 0; k < n_slabs && ok; ++k) {
+        wa_vlstm_table tab;
+        memset(&tab, 0, sizeof(tab));
+        tab.n_seqs = B;
+        for (int b = 0; b < B && ok; ++b) {
+            const int c0 = k * v.slab, nc = std::min(v.slab, n_chunks[b] - c0);
+            if (nc <= 0) continue;
+            const bool on_device = wa_is_device_ptr(samples[b]);
+            const int64_t s0 = (int64_t) c0 * WA_VAD_WINDOW;
+            const int n_valid = (int) std::min<int64_t>((int64_t) nc * WA_VAD_WINDOW, (int64_t) n_samples[b] - s0);
+            ok = (on_device || WA_HIP_OK(hipMemcpyAsync(v.d_samples[b], samples[b] + s0, (size_t) n_valid * sizeof(float), hipMemcpyHostToDevice, v.stream)))
+              && wa_vad_front_launch(v.dev, on_device ? samples[b] + s0 : v.d_samples[b], n_valid, nc, v.d_out[b], (void *) v.stream);
+            wa_vlstm_seq & q = tab.s[b];
+            q.gates = v.d_out[b]; q.n = nc;
+            q.h = v.d_state + (size_t) b * 2 * WA_VAD_HID; q.c = q.h + WA_VAD_HID;
+            q.probs = v.d_probs + off[b] + c0;
+        }
+        ok = ok && v.span.launch(&v, tab, v.stream);
+    }
+    std::vector<float> all(off[B]);
+    ok = ok && WA_HIP_OK(hipMemcpyAsync(all.data(), v.d_probs, off[B] * sizeof(float), hipMemcpyDeviceToHost, v.stream));
+    const int64_t t0 = wa_time_us();
+    ok = WA_HIP_OK(hipStreamSynchronize(v.stream)) && ok;         // nothing of this call may still be running, whatever failed
+    v.t_front_wait_us += wa_time_us() - t0;
+    v.span.publish(&v);
+    if (ok) for (int b = 0; b < B; ++b) std::copy(all.begin() + off[b], all.begin() + off[b + 1], probs[b].begin());
+    return ok;
+}
+
+// -------------------------------------------------------------------------------------------------
 // C API (ref: whisper.cpp:4445-4452, 4731-4773, 5100-5200, 5438-5475)
 // -------------------------------------------------------------------------------------------------
 struct whisper_vad_context_params whisper_vad_default_context_params(void) {
@@ -160,9 +284,18 @@ bool whisper_vad_detect_speech(struct whisper_vad_context * vctx, const float * 
     if (!vctx || n_samples < 0 || (n_samples > 0 && !samples)) return false;
     const int n_chunks = wa_vad_n_chunks(n_samples);
     WA_INFO("%s: detecting speech in %d samples, %d windows\n", __func__, n_samples, n_chunks);
+    const int64_t t_start = wa_time_us();
+    if (vctx->lstm_dev) {
+        const bool done = vad_detect_device(*vctx, &samples, &n_samples, 1, &vctx->probs);
+        if (done) {
+            vctx->t_vad_us += wa_time_us() - t_start;
+            WA_INFO("%s: vad time = %.2f ms processing %d samples\n", __func__, 1e-3f * vctx->t_vad_us, n_samples);
+            return true;
+        }
+        wa_vad_ctx_lstm_off(vctx, __func__);             // and this call starts over on the host path
+    }
     vctx->probs.assign((size_t) n_chunks, 0.0f);
     wa_vad_lstm st; st.reset();                         // the LSTM state is zero at the start of every call
-    const int64_t t_start = wa_time_us();
     const bool ok = vad_run_slabs(*vctx, samples, n_samples, [&](int c0, int nc, const float * gates) {
         const int64_t t0 = wa_time_us();
         for (int i = 0; i < nc; ++i) vctx->probs[(size_t) c0 + i] = wa_vad_step(vctx->model, st, gates + (size_t) i * WA_VAD_GATES);
@@ -201,6 +334,10 @@ void whisper_vad_free(struct whisper_vad_context * v) {
         if (v->ev[i]) (void) hipEventDestroy(v->ev[i]);
     }
     if (v->d_weights) (void) hipFree(v->d_weights);
+    if (v->d_state) (void) hipFree(v->d_state);
+    if (v->d_probs) (void) hipFree(v->d_probs);
+    if (v->d_rgates) (void) hipFree(v->d_rgates);
+    v->span.release();
     if (v->stream) (void) hipStreamDestroy(v->stream);
     delete v;
 }
@@ -226,6 +363,54 @@ void whisper_amd_vad_timings(struct whisper_vad_context * vctx, int64_t out_us[3
     out_us[0] = vctx->t_vad_us; out_us[1] = vctx->t_front_wait_us; out_us[2] = vctx->t_host_us;
 }
 
+int whisper_amd_vad_lstm_path(struct whisper_vad_context * vctx) { return vctx && vctx->lstm_dev ? 1 : 0; }
+void whisper_amd_vad_lstm_stats(struct whisper_vad_context * vctx, int64_t out[3]) {
+    if (!vctx || !out) return;
+    out[0] = vctx->lstm_launches.load(); out[1] = vctx->lstm_windows.load(); out[2] = (vctx->lstm_dev_ns.load() + 500) / 1000;
+}
+
+int whisper_amd_vad_recur(struct whisper_vad_context * vctx, const float * const * gates, const int * n_windows, int B, float * const * h, float * const * c,
+                          float * const * probs) {
+    if (!vctx || !vctx->lstm_dev || !gates || !n_windows || !h || !c || !probs || B < 1 || B > WA_VLSTM_SEQS) return -1;
+    return wa_guard(__func__, -1, [&]() -> int {
+        whisper_vad_context & v = *vctx;
+        size_t off[WA_VLSTM_SEQS + 1] = { 0 };
+        for (int b = 0; b < B; ++b) {
+            if (n_windows[b] < 0 || (n_windows[b] > 0 && (!gates[b] || !h[b] || !c[b] || !probs[b]))) return -1;
+            off[b + 1] = off[b] + (size_t) n_windows[b];
+        }
+        if (off[B] == 0) return 0;
+        if (!WA_HIP_OK(hipSetDevice(v.device)) || !wa_dev_reserve(v.d_rgates, v.d_rgates_cap, off[B] * WA_VAD_GATES) ||
+            !wa_dev_reserve(v.d_probs, v.d_probs_cap, off[B])) return -1;
+        wa_vlstm_table tab;
+        memset(&tab, 0, sizeof(tab));
+        tab.n_seqs = B;
+        bool ok = true;
+        const size_t hb = WA_VAD_HID * sizeof(float);
+        for (int b = 0; b < B && ok; ++b) {
+            if (n_windows[b] == 0) continue;
+            wa_vlstm_seq & q = tab.s[b];
+            q.n = n_windows[b];
+            q.gates = v.d_rgates + off[b] * WA_VAD_GATES;
+            q.h = v.d_state + (size_t) b * 2 * WA_VAD_HID; q.c = q.h + WA_VAD_HID;
+            q.probs = v.d_probs + off[b];
+            ok = WA_HIP_OK(hipMemcpyAsync((void *) q.gates, gates[b], (size_t) q.n * WA_VAD_GATES * sizeof(float), hipMemcpyHostToDevice, v.stream))
+              && WA_HIP_OK(hipMemcpyAsync(q.h, h[b], hb, hipMemcpyHostToDevice, v.stream)) && WA_HIP_OK(hipMemcpyAsync(q.c, c[b], hb, hipMemcpyHostToDevice, v.stream));
+        }
+        ok = ok && v.span.launch(&v, tab, v.stream);
+        for (int b = 0; b < B && ok; ++b) {
+            const wa_vlstm_seq & q = tab.s[b];
+            if (q.n == 0) continue;
+            ok = WA_HIP_OK(hipMemcpyAsync(probs[b], q.probs, (size_t) q.n * sizeof(float), hipMemcpyDeviceToHost, v.stream))
+              && WA_HIP_OK(hipMemcpyAsync(h[b], q.h, hb, hipMemcpyDeviceToHost, v.stream)) && WA_HIP_OK(hipMemcpyAsync(c[b], q.c, hb, hipMemcpyDeviceToHost, v.stream));
+        }
+        ok = WA_HIP_OK(hipStreamSynchronize(v.stream)) && ok;
+        v.span.publish(&v);
+        if (!ok) { wa_vad_ctx_lstm_off(&v, "whisper_amd_vad_recur"); return -1; }
+        return 0;
+    });
+}
+
 int                  wa_vad_ctx_device(const whisper_vad_context * v) { return v->device; }
 const wa_vad_model & wa_vad_ctx_model (const whisper_vad_context * v) { return v->model; }
 const wa_vad_dev &   wa_vad_ctx_dev   (const whisper_vad_context * v) { return v->dev; }
@@ -234,18 +419,44 @@ const wa_vad_dev &   wa_vad_ctx_dev   (const whisper_vad_context * v) { return v
 // whisper_full / whisper_full_parallel with vad = true (ref: whisper.cpp:6615-6793): the speech-only audio and the state's table
 // -------------------------------------------------------------------------------------------------
 // the state's VAD context (made from params.vad_model_path by the first call) over `samples`, host or device: its segments
-bool wa_vad_segments_for(whisper_context * ctx, whisper_state * st, const whisper_full_params & params, const float * samples, int n_samples,
-                         std::vector<wa_vad_seg> & segs) {
-    segs.clear();
+static bool vad_context_of(whisper_context * ctx, whisper_state * st, const whisper_full_params & params) {
     st->vad_mapping_table.clear();
     st->has_vad_segments = false;
     if (!st->vad_context) {
         st->vad_context = wa_vad_create_from_file(params.vad_model_path, whisper_vad_default_context_params().n_threads, ctx->device);
         if (!st->vad_context) { WA_ERROR("%s: failed to initialize VAD context\n", __func__); return false; }
     }
+    return true;
+}
+
+bool wa_vad_segments_for(whisper_context * ctx, whisper_state * st, const whisper_full_params & params, const float * samples, int n_samples,
+                         std::vector<wa_vad_seg> & segs) {
+    segs.clear();
+    if (!vad_context_of(ctx, st, params)) return false;
     if (!whisper_vad_detect_speech(st->vad_context, samples, n_samples)) { WA_ERROR("%s: failed to detect speech\n", __func__); return false; }
     segs = wa_vad_segments_from_probs(st->vad_context->probs.data(), (int) st->vad_context->probs.size(), st->vad_context->model.n_window, params.vad_params);
     return true;
+}
+
+// the same for the two planes of a two-channel recording: with the device recurrence both walk in the same k_vad_lstm launches (B = 2)
+bool wa_vad_segments_for2(whisper_context * ctx, whisper_state * st, const whisper_full_params & params, const float * const * planes, int n_samples,
+                          std::vector<wa_vad_seg> * segs) {
+    segs[0].clear(); segs[1].clear();
+    if (!vad_context_of(ctx, st, params)) return false;
+    if (st->vad_context->lstm_dev) {
+        whisper_vad_context & v = *st->vad_context;
+        std::vector<float> probs[2];
+        const int n[2] = { n_samples, n_samples };
+        const int64_t t_start = wa_time_us();
+        if (vad_detect_device(v, planes, n, 2, probs)) {
+            v.t_vad_us += wa_time_us() - t_start;
+            for (int c = 0; c < 2; ++c) segs[c] = wa_vad_segments_from_probs(probs[c].data(), (int) probs[c].size(), v.model.n_window, params.vad_params);
+            v.probs.swap(probs[1]);                       // what the second of two calls would have left
+            return true;
+        }
+        wa_vad_ctx_lstm_off(&v, __func__);
+    }
+    return wa_vad_segments_for(ctx, st, params, planes[0], n_samples, segs[0]) && wa_vad_segments_for(ctx, st, params, planes[1], n_samples, segs[1]);
 }
 
 bool wa_vad_for_full(whisper_context * ctx, whisper_state * st, const whisper_full_params & params, const float * samples, int n_samples,

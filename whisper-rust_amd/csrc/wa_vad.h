@@ -7,7 +7,8 @@
 //   Conv1d k=3 pad=1: 129->128 s1, 128->64 s2, 64->64 s2, 64->128 s1 (F16 weights, F32 biases, ReLU),
 //   LSTM 128->128 (F32 weights), final 128->1 (F16 weight), sigmoid.
 // Split ("VAD"): everything that depends on one window alone - up to W_ih x + b_ih - is the device's k_vad_front
-// (wa_vad.hip); the recurrence, which calls libm's expf and tanhf as the reference does, runs here on the host.
+// (wa_vad.hip); the recurrence runs on the device too (k_vad_lstm, wa_vad_lstm.hip, with wa_libm.h's restatements of the expf and tanhf the
+// reference calls) wherever this process's libm is the restated one, and here on the host (wa_vad_step) otherwise.
 // Plain C++ (no HIP, no device types): tests/native/vad_math.cpp compiles wa_vad_host.cpp alone.
 #pragma once
 
@@ -72,6 +73,9 @@ int64_t wa_vad_map_time(int64_t processed_time, const std::vector<wa_vad_map_poi
 struct wa_vad_dev {            // device pointers; F16 rows of K halfs (layer 0: WA_VAD_LD0), index ic * 3 + k
     const uint16_t * stft = nullptr, * enc_w[4] = { nullptr, nullptr, nullptr, nullptr };
     const float    * enc_b[4] = { nullptr, nullptr, nullptr, nullptr }, * w_ih = nullptr, * b_ih = nullptr;
+    const float    * w_hh = nullptr, * b_hh = nullptr;     // the recurrence's (k_vad_lstm): F32 [512][128], [512]
+    const uint16_t * w_f = nullptr;                        // F16 [128]
+    float            b_f = 0.0f;
 };
 // out[c][512] = W_ih x_c + b_ih for windows c < n_chunks of d_samples; samples at and past n_valid count as zero
 bool wa_vad_front_launch(const wa_vad_dev & w, const float * d_samples, int n_valid, int n_chunks, float * d_out, void * stream);
@@ -94,3 +98,19 @@ struct wa_svad_table {
 };
 // false: the table is refused (nothing was launched) or the launch failed.  The caller has made sure the ring holds the samples.
 bool wa_svad_front_launch(const wa_vad_dev & w, const wa_svad_table & t, void * stream);
+
+// The recurrence on the device (k_vad_lstm, wa_vad_lstm.hip): ONE launch walks up to WA_VLSTM_SEQS independent sequences - a recording's slab,
+// a channel plane, a live session's new windows - one workgroup each.  Sequence i reads its n[i] rows of gate inputs [n][512] and its state
+// h, c [128] from device memory, writes one probability per row and the state back.  n[i] = 0: nothing of sequence i is read or written.
+#define WA_VLSTM_SEQS 8
+struct wa_vlstm_seq {
+    const float * gates;
+    float * h, * c, * probs;
+    int32_t n, pad_;
+};
+struct wa_vlstm_table {
+    wa_vlstm_seq s[WA_VLSTM_SEQS];
+    int32_t n_seqs;
+};
+// false: the table is refused (nothing was launched) or the launch failed
+bool wa_vlstm_launch(const wa_vad_dev & w, const wa_vlstm_table & t, void * stream);

@@ -281,6 +281,11 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     if hasattr(lib, "whisper_amd_vad_front"):
         proto("whisper_amd_vad_front", C.c_int64, P, C.POINTER(F), I, C.POINTER(F), C.c_int64)
         proto("whisper_amd_vad_tile", I)
+    if hasattr(lib, "whisper_amd_vad_recur"):
+        PP = C.POINTER(C.POINTER(F))
+        proto("whisper_amd_vad_lstm_path", I, P)
+        proto("whisper_amd_vad_recur", I, P, PP, C.POINTER(I), I, PP, PP, PP)
+        proto("whisper_amd_vad_lstm_stats", None, P, C.POINTER(C.c_int64))
     if hasattr(lib, "whisper_amd_full_batch"):
         proto("whisper_amd_full_batch", I, P, C.POINTER(C.c_void_p), I, whisper_full_params, C.POINTER(C.c_void_p), C.POINTER(C.c_int))
     if hasattr(lib, "whisper_amd_rows_stats"):
@@ -1112,6 +1117,30 @@ class WhisperVadContext:
         if self.lib.whisper_amd_vad_front(self.ptr, pcm.ctypes.data_as(C.POINTER(C.c_float)), len(pcm), out.ctypes.data_as(C.POINTER(C.c_float)), n) != n:
             raise WhisperError("GenericError")
         return out.reshape(-1, 512)
+
+    def lstm_path(self) -> int:
+        """Extension: 1 where this context runs the LSTM recurrence on the device (k_vad_lstm), 0 on the host."""
+        return int(self.lib.whisper_amd_vad_lstm_path(self.ptr))
+
+    def lstm_stats(self) -> list[int]:
+        """Extension: [k_vad_lstm launches, windows walked, device us]."""
+        out = (C.c_int64 * 3)()
+        self.lib.whisper_amd_vad_lstm_stats(self.ptr, out)
+        return [int(x) for x in out]
+
+    def recur(self, gates, h, c):
+        """Extension (whisper_amd_vad_recur): the device recurrence alone over B sequences.  gates: list of [n_b, 512] F32 arrays (n_b may be 0),
+        h, c: [B, 128] F32.  Returns (list of probability arrays, h, c); raises where the device path is off."""
+        B = len(gates)
+        gates = [np.ascontiguousarray(g, dtype=np.float32).reshape(-1, 512) for g in gates]
+        h, c = np.array(h, dtype=np.float32).reshape(B, 128), np.array(c, dtype=np.float32).reshape(B, 128)
+        probs = [np.zeros(len(g), dtype=np.float32) for g in gates]
+        FP = C.POINTER(C.c_float)
+        arr = lambda rows: (FP * B)(*[r.ctypes.data_as(FP) for r in rows])
+        n = (C.c_int * B)(*[len(g) for g in gates])
+        if self.lib.whisper_amd_vad_recur(self.ptr, arr(gates), n, B, arr(list(h)), arr(list(c)), arr(probs)) != 0:
+            raise WhisperError("GenericError")
+        return probs, h, c
 
     def free(self):
         if self.ptr:
