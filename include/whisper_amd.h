@@ -604,6 +604,36 @@ WHISPER_API int  whisper_amd_dtw_path(struct whisper_state * state, const float 
 WHISPER_API void whisper_amd_dtw_stats(struct whisper_state * state, long out[3]);
 WHISPER_API void whisper_amd_dtw_timings(struct whisper_state * state, int64_t out[2]);
 
+/* Heuristic token timestamps (params.token_timestamps, max_len, split_on_word; wa_tts.cpp), the two device steps alone.
+ * With the option set whisper_full* computes the windowed |PCM| energy of the call's audio with one kernel on the state's stream, over the
+ * PCM where it lies in HBM (host PCM: the copy the mel front end staged), keeps it there, and per finished segment turns the text tokens'
+ * sample ends into 24-byte records with one launch (one wave per token); the host keeps the integer work on those records.  Device PCM is
+ * not copied back.  WHISPER_AMD_TTS_HOST=1 in the environment (read once per process) keeps both steps on the host; a failed launch, copy
+ * or allocation sends the call there too, with a warning.  Both paths give the same token times, bit for bit.
+ * `where` = 0: the host functions, 1: the kernels (wa_tts.hip) on the state's stream; both give the same bytes.  `pcm` is a host or a
+ * device pointer to n F32 samples, 0 < n <= 2^30.
+ * whisper_amd_signal_energy: out[i] (host, n floats) = (((|x[lo]| + |x[lo + 1]|) + ...) + |x[hi]|) / 65.0f, lo = max(i - 32, 0),
+ *   hi = min(i + 32, n - 1), F32 additions in ascending order from 0.0f.
+ * whisper_amd_token_snap: the energies of `pcm`, then for token j with sample ends s_lo[j], s_hi[j] (each in [0, n)) and has_prev[j]
+ *   (non-zero: a token precedes it in its segment) the record: level = (float) (0.5 * (double) total / (double) (w_hi - w_lo)) with total
+ *   the F32 chain of the energies in [max(s_lo - 2000, 0), min(s_hi + 2000, n)); with loud(k) = e[k] > level, quiet(k) = e[k] < level:
+ *   back_lo the first index at or below s_lo that is not loud, or 0 (s_lo itself without has_prev); fwd_lo the first index in [s_lo, s_hi)
+ *   that is not quiet, or max(s_lo, s_hi); fwd_hi the first index in [s_hi, n - 1) that is not loud, or n - 1; back_hi the first index at or
+ *   below s_hi that is not quiet, or 0; flags: bit 0 loud(s_lo), bit 1 loud(s_hi), bit 2 has_prev.
+ * Both return 0, WHISPER_AMD_TTS_REFUSED (a null pointer, n out of range, an end outside [0, n), n_tokens <= 0, another `where`; nothing is
+ *   written) or WHISPER_AMD_TTS_HIP_ERROR.
+ * whisper_amd_tts_stats: out = { energy kernel launches, snap kernel launches, device attempts that fell back to the host path, bytes of
+ *   PCM copied device-to-host for timestamps } since the state was created.
+ * whisper_amd_tts_tile: outputs per workgroup of the energy kernel (tests put lengths on either side of it). */
+#define WHISPER_AMD_TTS_REFUSED   (-1)
+#define WHISPER_AMD_TTS_HIP_ERROR (-3)
+struct whisper_amd_tts_record { int32_t back_lo, fwd_lo, fwd_hi, back_hi; uint32_t flags; float level; };
+WHISPER_API int  whisper_amd_signal_energy(struct whisper_state * state, const float * pcm, int n, int where, float * out);
+WHISPER_API int  whisper_amd_token_snap(struct whisper_state * state, const float * pcm, int n, const int32_t * s_lo, const int32_t * s_hi,
+                                        const int32_t * has_prev, int n_tokens, int where, struct whisper_amd_tts_record * records_out);
+WHISPER_API void whisper_amd_tts_stats(struct whisper_state * state, int64_t out[4]);
+WHISPER_API int  whisper_amd_tts_tile(void);
+
 /* Model load (wa_loader.cpp).  By default the tensor bytes go to the device in pinned chunks while the next chunk is being read, and
  * HIP kernels (wa_load.hip) write the kernel layouts straight into the weight arena; WHISPER_AMD_LOAD_HOST=1 in the environment WHEN A CONTEXT IS
  * CREATED takes the host path instead (a host image of the arena, unpacked on the host, one upload).  Both leave the same arena, byte for byte.

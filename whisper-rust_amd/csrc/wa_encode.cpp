@@ -178,6 +178,7 @@ void wa_state_release(whisper_state & st) {
     dev_free(st.d_dyn); dev_free(st.d_att_partial); dev_free(st.d_att_pleft); dev_free(st.d_im2col); dev_free(st.d_logits); dev_free(st.d_aheads_qk);
     st.aheads_qk_cap = 0; dev_free(st.d_dtw); st.d_dtw_cap = 0;
     wa_align_free(st);
+    wa_tts_free(st);
     dev_free(st.d_audio); st.d_audio_cap = 0; dev_free(st.d_audio_in); st.d_audio_in_cap = 0; st.audio_n = -1;
     if (st.h_dtw) { (void) hipHostFree(st.h_dtw); st.h_dtw = nullptr; st.h_dtw_cap = 0; }
     if (st.h_stage_i32)     { (void) hipHostFree(st.h_stage_i32);     st.h_stage_i32 = nullptr; }
@@ -215,6 +216,7 @@ bool wa_mel_compute(whisper_context & ctx, whisper_state & st, const float * sam
     const float * d_pcm = nullptr;
     if (wa_is_device_ptr(samples)) {
         d_pcm = samples;
+        st.d_pcm_n = 0;
     } else {
         if ((size_t) n_samples > st.d_pcm_cap) {
             dev_free(st.d_pcm);
@@ -224,6 +226,7 @@ bool wa_mel_compute(whisper_context & ctx, whisper_state & st, const float * sam
         }
         if (!WA_HIP_OK(hipMemcpyAsync(st.d_pcm, samples, (size_t) n_samples * sizeof(float), hipMemcpyHostToDevice, st.stream))) return false;
         d_pcm = st.d_pcm;
+        st.d_pcm_n = n_samples;
     }
     wa_launch_mel(st.stream, d_pcm, n_samples, m.d_hann, m.d_sincos, m.d_filters, st.mel_n_mel, m.n_fft_filt, st.d_mel, st.mel_n_len,
                   st.d_mel_max);

@@ -7,6 +7,7 @@
 // wa_encode / wa_decode.
 #include "wa_internal.h"
 #include "wa_expf8.h"
+#include "wa_tts.h"
 
 #include <algorithm>
 #include <array>
@@ -104,7 +105,8 @@ void compute_probs(const float * logits, int n, const float * logprobs, float * 
 //   anchors  - tokens whose own timestamp guess is trusted pin a boundary of the time line;
 //   spread   - every run of boundaries still open between two pinned ones is divided in proportion to the tokens' spoken weights;
 //   repair   - boundaries that ended up out of order are pushed forward;
-//   snap     - each text token's ends slide to where the windowed |PCM| energy crosses half of its local mean.
+//   snap     - each text token's ends slide to where the windowed |PCM| energy crosses half of its local mean: the scans over the energy come
+//              as one record per token from the device or the host (wa_tts.cpp), the integer work on them is wa_tts.h's finalisation.
 // Integer / float / double types of every quantity are the contract's (int64 boundaries, float weights and energies, double
 // proportions), which is what makes the results identical.
 // -------------------------------------------------------------------------------------------------
@@ -123,36 +125,21 @@ float spoken_weight(const char * text) {
     return total;
 }
 
-// mean |x| over the window [i - half, i + half] clipped to the signal, always divided by the full window length
-std::vector<float> signal_energy(const float * signal, int n, int half) {
-    std::vector<float> e((size_t) std::max(n, 0));
-    const float full = (float) (2 * half + 1);
-    for (int i = 0; i < n; ++i) {
-        const int lo = std::max(i - half, 0), hi = std::min(i + half, n - 1);
-        float acc = 0;
-        for (int k = lo; k <= hi; ++k) acc += fabsf(signal[k]);
-        e[i] = acc / full;
-    }
-    return e;
-}
-
 struct token_timeline {
     const int n;
     const int64_t seg_lo, seg_hi;                       // the segment's own span, 10 ms units
     std::vector<int64_t> lo, hi;                        // per token: start / end boundary
     std::vector<float> weight;
-    const std::vector<float> & energy;
+    const int n_smp;                                    // samples of the call's audio = entries of its energy
 
-    token_timeline(const std::vector<whisper_token_data> & toks, int64_t t0, int64_t t1, const std::vector<float> & en)
-        : n((int) toks.size()), seg_lo(t0), seg_hi(t1), lo(toks.size()), hi(toks.size()), weight(toks.size()), energy(en) {
+    token_timeline(const std::vector<whisper_token_data> & toks, int64_t t0, int64_t t1, int n_samples)
+        : n((int) toks.size()), seg_lo(t0), seg_hi(t1), lo(toks.size()), hi(toks.size()), weight(toks.size()), n_smp(n_samples) {
         for (int j = 0; j < n; ++j) { lo[j] = toks[j].t0; hi[j] = toks[j].t1; }
     }
-    float energy_at(int k) const { return energy[(size_t) std::min(std::max(k, 0), (int) energy.size() - 1)]; }
     int to_sample(int64_t t) const {
         const int smp = (int) (((t - seg_lo) * WHISPER_SAMPLE_RATE) / 100);
-        return std::min(std::max(smp, 0), (int) energy.size() - 1);
+        return std::min(std::max(smp, 0), n_smp - 1);
     }
-    int64_t to_time(int smp) const { return (100ll * smp) / WHISPER_SAMPLE_RATE + seg_lo; }
 
     // pass 1.  `origin`, `resume`, `high_tid` live in the state: a window's segments continue the previous segment's time line.
     void anchors(whisper_context * ctx, const std::vector<whisper_token_data> & toks, float min_pt, float min_ptsum, int64_t & origin, int64_t & resume,
@@ -199,50 +186,36 @@ struct token_timeline {
             if (j > 0 && hi[j - 1] > lo[j]) { lo[j] = hi[j - 1]; hi[j] = std::max(lo[j], hi[j]); }
         }
     }
-    // pass 4, one text token: both ends move to the nearest crossing of half the mean energy of the token's neighbourhood
-    void snap(int j) {
-        const int reach = WHISPER_SAMPLE_RATE / 8, n_smp = (int) energy.size();
-        int s_lo = to_sample(lo[j]), s_hi = to_sample(hi[j]);
-        const int w_lo = std::max(s_lo - reach, 0), w_hi = std::min(s_hi + reach, n_smp);
-        float total = 0.0f;
-        for (int k = w_lo; k < w_hi; ++k) total += energy_at(k);
-        const float level = 0.5 * total / (w_hi - w_lo);
-        const auto loud = [&](int k) { return energy_at(k) > level; };
-        const auto quiet = [&](int k) { return energy_at(k) < level; };
-        int k = s_lo;
-        if (loud(k) && j > 0) {                              // speech already under way: the start moves back, but not into the previous token
-            while (k > 0 && loud(k)) --k;
-            lo[j] = to_time(k);
-            if (lo[j] < hi[j - 1]) lo[j] = hi[j - 1]; else s_lo = k;
-        } else {                                             // leading silence: the start moves forward
-            while (quiet(k) && k < s_hi) ++k;
-            s_lo = k;
-            lo[j] = to_time(k);
+    // pass 4, the text tokens (id < eot): their sample ends as the repair pass left them go out in one batch, one record per token comes back
+    // (device or host), and the tokens are finalised in order - a start is held against the previous token's final end, an end against the
+    // next token's start before its own snap.  false: no records could be had.
+    bool snap(whisper_state * st, const std::vector<whisper_token_data> & toks, whisper_token eot) {
+        std::vector<int32_t> at, s_lo, s_hi, has_prev;
+        for (int j = 0; j < n; ++j) {
+            if (!(toks[j].id < eot)) continue;
+            at.push_back(j); s_lo.push_back(to_sample(lo[j])); s_hi.push_back(to_sample(hi[j])); has_prev.push_back(j > 0);
         }
-        k = s_hi;
-        if (loud(k)) {                                       // still speaking at the end: it moves forward, but not into the next token
-            while (k < n_smp - 1 && loud(k)) ++k;
-            hi[j] = to_time(k);
-            if (j < n - 1 && hi[j] > lo[j + 1]) hi[j] = lo[j + 1]; else s_hi = k;
-        } else {                                             // trailing silence: the end moves back
-            while (quiet(k) && k > s_lo) --k;
-            s_hi = k;
-            hi[j] = to_time(k);
+        std::vector<wa_tts_record> rec(at.size());
+        if (!wa_tts_records(*st, s_lo.data(), s_hi.data(), has_prev.data(), (int) at.size(), rec.data())) return false;
+        for (size_t t = 0; t < at.size(); ++t) {
+            const int j = at[t];
+            wa_tts_finalise(rec[t], s_lo[t], s_hi[t], seg_lo, j > 0, j > 0 ? hi[j - 1] : 0, j < n - 1, j < n - 1 ? lo[j + 1] : 0, lo[j], hi[j]);
         }
+        return true;
     }
 };
 
 void token_level_timestamps(whisper_context * ctx, whisper_state * st, int i_segment, float thold_pt, float thold_ptsum) {
     auto & seg = st->result_all[i_segment];
     auto & toks = seg.tokens;
-    if (st->energy.empty()) { WA_ERROR("%s: no signal data available\n", __func__); return; }
+    if (!wa_tts_have_energy(*st)) { WA_ERROR("%s: no signal data available\n", __func__); return; }
     if (toks.empty()) return;
     if (toks.size() == 1) { toks[0].t0 = seg.t0; toks[0].t1 = seg.t1; return; }
-    token_timeline line(toks, seg.t0, seg.t1, st->energy);
+    token_timeline line(toks, seg.t0, seg.t1, wa_tts_n_samples(*st));
     line.anchors(ctx, toks, thold_pt, thold_ptsum, st->t_beg, st->t_last, st->tid_last);
     line.spread();
     line.repair();
-    for (int j = 0; j < line.n; ++j) if (toks[j].id < ctx->vocab.token_eot) line.snap(j);
+    if (!line.snap(st, toks, ctx->vocab.token_eot)) { WA_ERROR("%s: no signal data available\n", __func__); return; }
     for (int j = 0; j < line.n; ++j) { toks[j].t0 = line.lo[j]; toks[j].t1 = line.hi[j]; toks[j].vlen = line.weight[j]; }
 }
 
@@ -573,16 +546,7 @@ int runner::run(const float * samples, int n_samples) {
     }
     if (p.token_timestamps) {                       // whisper.cpp:6832-6839
         st->t_beg = 0; st->t_last = 0; st->tid_last = 0;
-        if (n_samples > 0) {
-            std::vector<float> host;
-            const float * pcm = samples;
-            if (wa_is_device_ptr(samples)) {    // PCM handed over in HBM
-                host.resize(n_samples);
-                if (!WA_HIP_OK(hipMemcpy(host.data(), samples, (size_t) n_samples * sizeof(float), hipMemcpyDeviceToHost))) return -2;
-                pcm = host.data();
-            }
-            st->energy = signal_energy(pcm, n_samples, 32);
-        }
+        if (n_samples > 0 && !wa_tts_begin(*st, samples, n_samples)) return -2;     // the windowed energy, on the device where it can be
     }
     if (p.n_grammar_rules > 0 && p.grammar_rules != nullptr) {      // (either one alone: no grammar, whisper.cpp:6335 / 7064)
         if (const char * why = wa_grammar_build(grammar, p.grammar_rules, p.n_grammar_rules, p.i_start_rule)) {
@@ -1034,5 +998,6 @@ int wa_full(whisper_context * ctx, whisper_state * st, whisper_full_params param
         whisper_state * s;
         ~grammar_release() { for (auto & dec : s->decoders) { dec.grammar_cache.release(); dec.grammar = wa_grammar_state(); } }
     } release { st };
+    struct tts_release { whisper_state * s; ~tts_release() { wa_tts_end(*s); } } tts { st };     // (the call's PCM is the caller's again on return)
     return r.run(samples, n_samples);
 }

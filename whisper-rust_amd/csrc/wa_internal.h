@@ -246,6 +246,7 @@ struct whisper_state {
     int mel_n_len = 0, mel_n_len_org = 0, mel_n_mel = 0;
     float * d_mel = nullptr; size_t d_mel_cap = 0;      // [n_mel][n_len] f32 (device is the source of truth)
     float * d_pcm = nullptr; size_t d_pcm_cap = 0;      // staging for host PCM
+    int d_pcm_n = 0;                                    // samples of the last host PCM staged there (0: none, or the last audio came in HBM)
     unsigned int * d_mel_max = nullptr;                 // ordered-uint encoding of the running max
 
     // ---- encoder activations (rows padded to WA_TPAD) ----
@@ -366,7 +367,16 @@ struct whisper_state {
     // heuristic token timestamps (ref: whisper.cpp:937-942): carried from segment to segment within one call
     int64_t t_beg = 0, t_last = 0;
     whisper_token tid_last = 0;
-    std::vector<float> energy;             // PCM signal energy
+    std::vector<float> energy;             // PCM signal energy, where the host path made it (else empty: see energy_n)
+    // the same on the device (wa_tts.cpp / wa_tts.hip): the energy kernel's result stays in d_energy and the boundary scans of
+    // a finished segment read it there; both buffers are grow-only, made by the first call that needs them and freed with the state
+    float * d_energy = nullptr; size_t d_energy_cap = 0;
+    int energy_n = 0;                                       // energies in d_energy while they are the current ones (then `energy` is empty), else 0
+    bool tts_pending = false;                               // the energy kernel was issued and the stream has not been waited for since
+    const float * tts_pcm = nullptr; int tts_pcm_n = 0;     // the running call's PCM (host or device), for a fall-back in the middle of it
+    uint8_t * d_tts_io = nullptr; size_t d_tts_io_cap = 0;  // token ends | records
+    uint8_t * h_tts_io = nullptr; size_t h_tts_io_cap = 0;  // pinned: token ends (up) | records (down)
+    int64_t n_tts_energy = 0, n_tts_snap = 0, n_tts_fallback = 0, tts_bytes_d2h = 0;      // whisper_amd_tts_stats
 
     // DTW (ref: whisper.cpp:856-860, 946-948)
     std::vector<std::vector<int>> aheads;  // per text layer: list of heads
@@ -470,6 +480,16 @@ void wa_batcher_stats(const wa_batcher * b, long * steps, long * rows, long * on
 void wa_long_free(whisper_state & st);            // wa_long.cpp: what whisper_amd_full_long / whisper_amd_long_pack keep on a state
 void wa_channels_free(whisper_state & st);        // wa_channels.cpp: what whisper_amd_audio_split / whisper_amd_channel_energy keep on a state
 void wa_align_free(whisper_state & st);           // wa_align.cpp: what whisper_amd_align / whisper_amd_align_score keep on a state
+// wa_tts.cpp: heuristic token timestamps.  wa_tts_begin makes the windowed energy of a call's PCM (host or device pointer) - on the device, where
+// it stays, or on the host (WHISPER_AMD_TTS_HOST=1, a failed launch or allocation) -; wa_tts_have_energy: there is signal data of either kind;
+// wa_tts_records: the records (wa_tts.h) of n_tokens text tokens with sample ends s_lo / s_hi, from the snap kernel or the host function - a
+// failed launch sends the rest of the call to the host; wa_tts_end: waits for an energy kernel nobody has waited for and forgets the PCM.
+bool wa_tts_begin(whisper_state & st, const float * samples, int n_samples);
+bool wa_tts_have_energy(const whisper_state & st);
+int  wa_tts_n_samples(const whisper_state & st);
+bool wa_tts_records(whisper_state & st, const int32_t * s_lo, const int32_t * s_hi, const int32_t * has_prev, int n_tokens, struct wa_tts_record * out);
+void wa_tts_end(whisper_state & st);
+void wa_tts_free(whisper_state & st);
 // wa_dtw.cpp: the middle of the DTW token timestamps for any token sequence [sot.., not, text.., eot] with sot_len tokens in front of `not`: one
 // decoder pass over it with the alignment heads captured, then the device or the host DTW over n_frames / 2 audio positions.
 // score_rows = false (whisper_full): logits for the last row only; nothing is run where no DTW can follow.

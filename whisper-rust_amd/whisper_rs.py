@@ -303,6 +303,12 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         proto("whisper_amd_dtw_path", I, P, C.POINTER(F), I, I, I, I, I, I, I, C.POINTER(C.c_int32), C.POINTER(C.c_int32), I)
         proto("whisper_amd_dtw_stats", None, P, C.POINTER(C.c_long))
         proto("whisper_amd_dtw_timings", None, P, C.POINTER(C.c_int64))
+    if hasattr(lib, "whisper_amd_token_snap"):
+        I32P = C.POINTER(C.c_int32)
+        proto("whisper_amd_signal_energy", I, P, P, I, I, C.POINTER(F))
+        proto("whisper_amd_token_snap", I, P, P, I, I32P, I32P, I32P, I, I, P)
+        proto("whisper_amd_tts_stats", None, P, C.POINTER(C.c_int64))
+        proto("whisper_amd_tts_tile", I)
     if hasattr(lib, "whisper_amd_qgemm_stats"):
         proto("whisper_amd_qgemm_stats", None, P, C.POINTER(C.c_long))
     if hasattr(lib, "whisper_amd_few_rows_stats"):
@@ -496,6 +502,9 @@ def audio_taps(lib: C.CDLL, sample_rate: int):
 
 
 DTW_REFUSED, DTW_NOT_TAKEN, DTW_HIP_ERROR = -1, -2, -3      # whisper_amd_dtw_path's codes (include/whisper_amd.h)
+TTS_REFUSED, TTS_HIP_ERROR = -1, -3                         # whisper_amd_signal_energy's and whisper_amd_token_snap's codes
+TTS_LOUD_LO, TTS_LOUD_HI, TTS_HAS_PREV = 1, 2, 4            # flag bits of a record
+TTS_RECORD_DTYPE = np.dtype([("back_lo", np.int32), ("fwd_lo", np.int32), ("fwd_hi", np.int32), ("back_hi", np.int32), ("flags", np.uint32), ("level", np.float32)])
 
 _KEEP_LOG_CB = {}
 
@@ -798,6 +807,41 @@ class WhisperState:
         out = (C.c_int64 * 2)()
         self.lib.whisper_amd_dtw_timings(self.ptr, out)
         return int(out[0]), int(out[1])
+
+    # -- heuristic token timestamps (whisper_amd_signal_energy, whisper_amd_token_snap): the two device steps alone ---------------
+    def _pcm_args(self, pcm):
+        """`pcm`: a numpy f32 array on the host, or (device pointer, n)"""
+        if isinstance(pcm, tuple):
+            return pcm
+        self._pcm_keep = pcm = np.ascontiguousarray(pcm, dtype=np.float32)
+        return pcm.ctypes.data, len(pcm)
+
+    def signal_energy(self, pcm, where: int = 1) -> np.ndarray:
+        """Extension (whisper_amd_signal_energy): the 65-sample windowed mean of |pcm|, F32 [n]; where = 0: the host function, 1: the kernel."""
+        ptr, n = self._pcm_args(pcm)
+        out = np.full(max(n, 1), np.nan, np.float32)
+        r = self.lib.whisper_amd_signal_energy(self.ptr, C.c_void_p(ptr), n, where, out.ctypes.data_as(C.POINTER(C.c_float)))
+        if r != 0:
+            raise WhisperError("TtsError(%d)" % r, r)
+        return out[:n]
+
+    def token_snap(self, pcm, s_lo: Sequence[int], s_hi: Sequence[int], has_prev: Sequence[int], where: int = 1) -> np.ndarray:
+        """Extension (whisper_amd_token_snap): one record per token (structured array TTS_RECORD_DTYPE) over the energies of `pcm`."""
+        ptr, n = self._pcm_args(pcm)
+        a, b, c = (np.ascontiguousarray(v, dtype=np.int32) for v in (s_lo, s_hi, has_prev))
+        out = np.zeros(max(len(a), 1), TTS_RECORD_DTYPE)
+        I32P = C.POINTER(C.c_int32)
+        r = self.lib.whisper_amd_token_snap(self.ptr, C.c_void_p(ptr), n, a.ctypes.data_as(I32P), b.ctypes.data_as(I32P), c.ctypes.data_as(I32P), len(a), where,
+                                            C.c_void_p(out.ctypes.data))
+        if r != 0:
+            raise WhisperError("TtsError(%d)" % r, r)
+        return out[:len(a)]
+
+    def tts_stats(self) -> dict:
+        """Extension (whisper_amd_tts_stats): token-timestamp work on this state since it was created."""
+        out = (C.c_int64 * 4)()
+        self.lib.whisper_amd_tts_stats(self.ptr, out)
+        return dict(zip(("energy_launches", "snap_launches", "fallbacks", "bytes_d2h"), [int(v) for v in out]))
 
     # -- forced alignment (whisper_amd_align*): times and log-probabilities of a known transcript --------------------------------
     def align(self, params: "FullParams", pcm, ids: Sequence[int]) -> list[dict]:
