@@ -193,15 +193,27 @@ static void decode_launch_quant(whisper_context & ctx, whisper_state & st, int n
     // Q5_K / Q6_K (wa_quantk.hip): Q8_K operand rows; LayerNorm, attention and GELU hand over F32 (d_q32a / d_q32b) and one more launch quantises.
     const bool QK = wa_wtype_k(m.wtype);
     auto quant = [&](const float * A, int lda, int M, int K) {
-        if (QK) wa_launch_quantize_q8_K(s, A, lda, M, K, st.d_q8, st.d_q8d, st.d_q8bs);
+        if (m.wtype == 12) wa_launch_quantize_q8_K4(s, A, lda, M, K, st.d_q8, st.d_q8d, st.d_q8bs);      // Q4_K: the rows below M - M % 4 by the four-row rule (wa_quant4.h)
+        else if (QK) wa_launch_quantize_q8_K(s, A, lda, M, K, st.d_q8, st.d_q8d, st.d_q8bs);
         else    wa_launch_quantize_q8_0(s, A, lda, M, K, st.d_q8, st.d_q8d, st.d_q8s);
     };
     auto qmul = [&](wa_epi_mode mode, const wa_lin & L, int M, const wa_epi & e) {      // operand already in d_q8 / d_q8d
-        if (QK) {
+        if (L.wtype == 12 && L.plain) {      // Q4_K, the token embedding: the plain product (F32 rows out, no bias)
+            if (M >= 2) st.n_few_rows += 1;
+            wa_launch_q4k_plain(s, st.d_q8, st.d_q8d, st.d_q8bs, M, L.qs, L.qsc, L.qd, L.qm, L.n_out, L.n_in, (float *) e.out, e.ldo);
+        } else if (L.wtype == 12) {          // Q4_K, interleaved (wa_quant4.hip)
+            if (M > 8) (wa_q4gemm_kernel(M, 0) == 3 ? st.n_qgemm_mfma : st.n_qgemm_exact) += 1;
+            else if (M >= 2) st.n_few_rows += 1;
+            wa_launch_q4kgemm(s, mode, st.d_q8, st.d_q8d, st.d_q8bs, M, (const uint8_t *) L.qs, (const uint8_t *) L.qsc, L.qd, L.qm, L.n_out, L.n_in, e);
+        } else if (QK) {
             const int kernel = wa_kgemm_few_kernel(mode, m.wtype, M, L.n_out, L.n_in, e, 0);      // 2: k_kgemv_rows (wa_quantk_rows.hip)
             if (M > 8) (kernel == 3 ? st.n_qgemm_mfma : st.n_qgemm_exact) += 1;
             else if (M >= 2) (kernel == 2 ? st.n_few_rows : st.n_few_general) += 1;
             wa_launch_kgemm_few_route(s, mode, m.wtype, st.d_q8, st.d_q8d, st.d_q8bs, M, L.qs, L.qsc, L.qd, L.qm, L.n_out, L.n_in, e, 0);
+        } else if (L.wtype == 2) {      // Q4_0, interleaved (wa_quant4.hip); the token embedding of such a model carries wtype 6 and takes the branch below
+            if (M > 8) (wa_q4gemm_kernel(M, 0) == 3 ? st.n_qgemm_mfma : st.n_qgemm_exact) += 1;
+            else if (M >= 2) st.n_few_rows += 1;
+            wa_launch_q4gemm(s, mode, st.d_q8, st.d_q8d, M, (const uint8_t *) L.qs, L.qd, L.n_out, L.n_in, e);
         } else {
             const int kernel = wa_qgemm_exact_kernel(mode, M, L.n_out, L.n_in, e, 0);             // 2: k_qgemv_rows
             if (M > 8) (kernel == 3 ? st.n_qgemm_mfma : st.n_qgemm_exact) += 1;
@@ -218,7 +230,7 @@ static void decode_launch_quant(whisper_context & ctx, whisper_state & st, int n
         else if (rows == 1 && d <= 2048) wa_launch_ln_q8_row(s, x, d, ln.w, ln.b, hp.eps, st.d_q8, st.d_q8d, st.d_q8s);
         else wa_launch_layernorm_exact(s, x, d, rows, d, ln.w, ln.b, hp.eps, nullptr, 0, nullptr, 0, st.d_q8, st.d_q8d, st.d_q8s);
     };
-    if (QK) wa_launch_dec_embed_k(s, m.wtype, st.d_tok, st.d_pos, n_tokens, d, m.te_q.qs, m.te_q.qsc, m.te_q.qd, m.te_q.qm, m.d_pe, st.d_dx);
+    if (QK) wa_launch_dec_embed_k(s, m.wtype == 12 ? 13 : m.wtype /* Q4_K's embedding lies in Q5_K's arrays */, st.d_tok, st.d_pos, n_tokens, d, m.te_q.qs, m.te_q.qsc, m.te_q.qd, m.te_q.qm, m.d_pe, st.d_dx);
     else wa_launch_dec_embed_q(s, st.d_tok, st.d_pos, n_tokens, d, m.te_q.qs, m.te_q.qd, m.d_pe, st.d_dx, m.te_q.qm);
     const float KQscale = pow(float(64), -0.25);
     const size_t kv_layer = (size_t) kv.size * d, cross_layer = (size_t) H * st.cross_tpad * 64;
@@ -252,7 +264,7 @@ static void decode_launch_quant(whisper_context & ctx, whisper_state & st, int n
         { wa_epi e; e.bias = L.cross_out.b; e.out = st.d_dx; e.ldo = d; e.resid = st.d_dx; e.ldr = d; qmul(WA_EPI_RESID, L.cross_out, n_tokens, e); }
         ln_q(st.d_dx, n_tokens, L.mlp_ln);
         wa_epi e2; e2.bias = L.fc2.b; e2.out = st.d_dx; e2.ldo = d; e2.resid = st.d_dx; e2.ldr = d;
-        if (n_tokens == 1 && !QK) {
+        if (n_tokens == 1 && !QK && m.wtype != 2) {
             wa_launch_qgemv_gelu_q8(s, st.d_q8, st.d_q8d, L.fc1.qs, L.fc1.qd, 4 * d, d, L.fc1.b, m.d_gelu, q8b, q8bd, st.d_q8s, L.fc1.qm, q8bs);
             wa_launch_qgemm_exact(s, WA_EPI_RESID, q8b, q8bd, 1, L.fc2.qs, L.fc2.qd, d, 4 * d, e2, q8bs, L.fc2.qm);
         } else {
@@ -271,7 +283,8 @@ static void decode_launch_quant(whisper_context & ctx, whisper_state & st, int n
             if (QK) wa_launch_layernorm_exact(s, st.d_dx + (size_t) h_rows[r0 + i] * d, d, 1, d, m.d_ln.w, m.d_ln.b, hp.eps, nullptr, 0, st.d_q32a + (size_t) i * d, d);
             else wa_launch_layernorm_exact(s, st.d_dx + (size_t) h_rows[r0 + i] * d, d, 1, d, m.d_ln.w, m.d_ln.b, hp.eps, nullptr, 0, nullptr, 0,
                                       st.d_q8 + (size_t) i * d, st.d_q8d + (size_t) i * nb, st.d_q8s ? st.d_q8s + (size_t) i * nb : nullptr);
-        if (QK) quant(st.d_q32a, d, nr, d);
+        if (m.wtype == 12) wa_launch_quantize_q8_K(s, st.d_q32a, d, nr, d, st.d_q8, st.d_q8d, st.d_q8bs);      // (the plain product: every row by the row rule)
+        else if (QK) quant(st.d_q32a, d, nr, d);
         wa_epi e; e.out = logits_out + (size_t) r0 * n_vocab; e.ldo = n_vocab;
         qmul(WA_EPI_F32, m.te_q, nr, e);
     }

@@ -109,7 +109,7 @@ bool wa_state_alloc(whisper_context & ctx, whisper_state & st) {
         const int dt = hp.n_text_state, Ht = hp.n_text_head;
         st.mega_form = wa_launch_form(!(g && g[0] == '1') && ctx.model.d_mega_layers && ctx.model.n_loaded > 0 && dt == Ht * 64 && dt % 128 == 0 &&
                                       dt <= WA_MEGA_MAX_D && hp.n_audio_ctx <= 1500 && ctx.model.n_cu >= 5 * Ht + 16 && tpad <= WA_MEGA_MAX_T &&
-                                      !wa_wtype_has_min(ctx.model.wtype) && !wa_wtype_k(ctx.model.wtype));      // (Q4_1 / Q5_1, Q5_K / Q6_K: no one-launch kernel - every pass is the launch sequence)
+                                      !wa_wtype_has_min(ctx.model.wtype) && !wa_wtype_k(ctx.model.wtype) && ctx.model.wtype != 2);      // (Q4_1 / Q5_1, the K formats, Q4_0 / Q4_K: no one-launch kernel - every pass is the launch sequence)
         if (st.mega_form.enabled()) {
             // logits of the step and, right behind them, the status word: one device-to-host copy per token
             if (!dev_alloc(st.d_mega_cgr, (size_t) hp.n_text_layer * Ht * WA_MEGA_CGR)) return false;
@@ -316,13 +316,20 @@ bool wa_encode(whisper_context & ctx, whisper_state & st, int mel_offset, ggml_a
         // Q5_K / Q6_K (wa_quantk.hip): the operand rows are Q8_K; LayerNorm and attention hand over F32 (d_q32a) and one more launch quantises.
         const bool QK = wa_wtype_k(m.wtype);
         auto quant = [&](const float * A, int lda, int M, int K) {
-            if (QK) wa_launch_quantize_q8_K(s, A, lda, M, K, st.d_q8, st.d_q8d, st.d_q8bs);
+            if (m.wtype == 12) wa_launch_quantize_q8_K4(s, A, lda, M, K, st.d_q8, st.d_q8d, st.d_q8bs);      // Q4_K: the rows below M - M % 4 by the four-row rule (wa_quant4.h)
+            else if (QK) wa_launch_quantize_q8_K(s, A, lda, M, K, st.d_q8, st.d_q8d, st.d_q8bs);
             else    wa_launch_quantize_q8_0(s, A, lda, M, K, st.d_q8, st.d_q8d, st.d_q8s);
         };
         auto qmul = [&](wa_epi_mode mode, const wa_lin & L, int M, const wa_epi & e) {       // operand rows already in d_q8 / d_q8d
-            if (QK) {
+            if (L.wtype == 12) {      // Q4_K, interleaved (wa_quant4.hip)
+                if (M > 8) (wa_q4gemm_kernel(M, 0) == 3 ? st.n_qgemm_mfma : st.n_qgemm_exact) += 1;
+                wa_launch_q4kgemm(s, mode, st.d_q8, st.d_q8d, st.d_q8bs, M, (const uint8_t *) L.qs, (const uint8_t *) L.qsc, L.qd, L.qm, L.n_out, L.n_in, e);
+            } else if (QK) {
                 if (M > 8) (wa_kgemm_kernel(mode, m.wtype, M, L.n_out, L.n_in, e, 0) == 3 ? st.n_qgemm_mfma : st.n_qgemm_exact) += 1;
                 wa_launch_kgemm_route(s, mode, m.wtype, st.d_q8, st.d_q8d, st.d_q8bs, M, L.qs, L.qsc, L.qd, L.qm, L.n_out, L.n_in, e, 0);
+            } else if (L.wtype == 2) {      // Q4_0, interleaved (wa_quant4.hip)
+                if (M > 8) (wa_q4gemm_kernel(M, 0) == 3 ? st.n_qgemm_mfma : st.n_qgemm_exact) += 1;
+                wa_launch_q4gemm(s, mode, st.d_q8, st.d_q8d, M, (const uint8_t *) L.qs, L.qd, L.n_out, L.n_in, e);
             } else {
                 if (M > 8) (wa_qgemm_exact_kernel(mode, M, L.n_out, L.n_in, e, 0) == 3 ? st.n_qgemm_mfma : st.n_qgemm_exact) += 1;
                 wa_launch_qgemm_exact(s, mode, st.d_q8, st.d_q8d, M, L.qs, L.qd, L.n_out, L.n_in, e, st.d_q8s, L.qm);

@@ -103,10 +103,11 @@ struct wa_ln  { const float * w = nullptr; const float * b = nullptr; };
 // and - Q5_K and Q2_K only - qm its dmin.
 struct wa_lin {
     const wa_f16 * w = nullptr; const float * b = nullptr; const float * s = nullptr; int n_out = 0, n_in = 0;
+    bool plain = false;       // Q4_K: the plain layout and product (the token embedding), not the interleaved ones (wa_quant4.h)
     int wtype = 1; const int8_t * qs = nullptr; const float * qd = nullptr; const float * qm = nullptr; const int8_t * qsc = nullptr;
 };
 inline bool wa_wtype_has_min(int wtype) { return wtype == 3 || wtype == 7; }     // Q4_1, Q5_1: multiplied with Q8_1 activation rows
-inline bool wa_wtype_k(int wtype) { return wtype == 13 || wtype == 14 || wtype == 10 || wtype == 11; }   // Q5_K, Q6_K, Q2_K, Q3_K: multiplied with Q8_K activation rows (wa_quantk.hip)
+inline bool wa_wtype_k(int wtype) { return wtype == 13 || wtype == 14 || wtype == 10 || wtype == 11 || wtype == 12; }   // Q5_K, Q6_K, Q2_K, Q3_K (wa_quantk.hip), Q4_K (wa_quant4.hip): multiplied with Q8_K activation rows
 
 struct wa_enc_layer {
     wa_ln  attn_ln, mlp_ln;
@@ -128,7 +129,7 @@ struct wa_model {
     int n_mel_filt = 0, n_fft_filt = 0;
     std::vector<float> filters;     // host copy [n_mel][n_fft]
     int n_loaded = 0;               // 0 => header/vocab-only test model (ref: whisper.cpp:1959-1960)
-    int wtype = 1;                  // ggml type of the 2-D weight matrices: 1 F16, 6 Q5_0, 8 Q8_0, 3 Q4_1, 7 Q5_1, 10 Q2_K, 11 Q3_K, 13 Q5_K, 14 Q6_K (whisper.cpp:1567-1573)
+    int wtype = 1;                  // ggml type of the 2-D weight matrices: 1 F16, 6 Q5_0, 8 Q8_0, 3 Q4_1, 7 Q5_1, 10 Q2_K, 11 Q3_K, 13 Q5_K, 14 Q6_K, 2 Q4_0, 12 Q4_K (whisper.cpp:1567-1573)
 
     // ---- device (all inside `arena`) ----
     void * arena = nullptr; size_t arena_size = 0;

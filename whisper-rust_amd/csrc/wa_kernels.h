@@ -157,6 +157,33 @@ int wa_kgemm_few_kernel(wa_epi_mode mode, int wtype, int M, int N, int K, const 
 void wa_launch_dec_embed_k(hipStream_t stream, int wtype, const int32_t * tok, const int32_t * pos, int n_tokens, int d, const int8_t * wq, const int8_t * wsc,
                            const float * wd, const float * wdm, const float * pe, float * x);
 
+// ---- Q4_0 weights in the reference's interleaved form (wa_quant4.hip; the arithmetic and the layouts are stated in wa_quant4.h): one float chain per
+// output over the blocks, no lane sums.  wq u32 [N][4][K/32] nibble words, wd f32 [N][K/32]; the activation rows are those of wa_launch_quantize_q8_0.
+// (The token embedding of such a model is not interleaved: it is stored like Q5_0 and runs through wa_launch_qgemm_exact / wa_launch_dec_embed_q.)
+// C[M][N] = xq . Wq^T, any M >= 1, the epilogues of wa_launch_qgemm_exact: k_q4gemv_rows up to 8 rows, k_q4gemm_mfma above
+void wa_launch_q4gemm(hipStream_t stream, wa_epi_mode mode, const int8_t * xq, const float * xd, int M, const uint8_t * wq, const float * wd, int N, int K,
+                      const wa_epi & e);
+// the same with the kernel named (0: the launcher's own rule; 2: k_q4gemv_rows, more than 8 rows in slices of 8; 3: k_q4gemm_mfma, whatever M)
+void wa_launch_q4gemm_route(hipStream_t stream, wa_epi_mode mode, const int8_t * xq, const float * xd, int M, const uint8_t * wq, const float * wd, int N, int K,
+                            const wa_epi & e, int route);
+// the kernel that launcher takes for a row count and a route: 2 k_q4gemv_rows, 3 k_q4gemm_mfma
+int wa_q4gemm_kernel(int M, int route);
+
+// ---- Q4_K weights in the interleaved form (wa_quant4.hip; wa_quant4.h): two chains per output.  wq u32 [N][8][K/256][4] nibble words, wsc u8 [N][K/256][16]
+// (scales, then minimums), wd / wdm f32 [N][K/256]; the activation rows are Q8_K rows in the buffers of wa_launch_quantize_q8_K.  The rows of a product
+// of M below M - M % 4 (M > 3) are the reference's gemm rows - the four-row quantiser's sign rule, a chain step per pair of sub-blocks - the others its gemv rows:
+// quantiser and product must be given the same M.
+void wa_launch_quantize_q8_K4(hipStream_t stream, const float * x, int ldx, int rows, int K, int8_t * qs, float * qd, int16_t * qbs);
+void wa_launch_q4kgemm(hipStream_t stream, wa_epi_mode mode, const int8_t * xq, const float * xd, const int16_t * xbs, int M, const uint8_t * wq, const uint8_t * wsc,
+                       const float * wd, const float * wdm, int N, int K, const wa_epi & e);
+// the same with the kernel named, as wa_launch_q4gemm_route (wa_q4gemm_kernel names it)
+void wa_launch_q4kgemm_route(hipStream_t stream, wa_epi_mode mode, const int8_t * xq, const float * xd, const int16_t * xbs, int M, const uint8_t * wq,
+                             const uint8_t * wsc, const float * wd, const float * wdm, int N, int K, const wa_epi & e, int route);
+// the plain product (ggml_vec_dot_q4_K_q8_K; the token embedding, stored in Q5_K's arrays with quants 0..15 and fetched by wa_launch_dec_embed_k as type 13):
+// out f32 [M][ldo] = xq . Wq^T, any M; the activation rows by wa_launch_quantize_q8_K
+void wa_launch_q4k_plain(hipStream_t stream, const int8_t * xq, const float * xd, const int16_t * xbs, int M, const int8_t * wq, const int8_t * wsc, const float * wd,
+                         const float * wdm, int N, int K, float * out, int ldo);
+
 // ---- DTW token timestamps (wa_dtw.hip): normalise over tokens, 7-wide median over audio, mean over heads, cost / trace table ----
 #define WA_DTW_MAX_N 512         // most table rows N = n_tokens - sot_len - 1: one thread of ONE workgroup each
 // x(k, t, j) = x[head_off[k] + t * tok_stride + j] (device; wa_dtw_host.h: wa_dtw_view), k < n_heads, t < n_tokens, j < M; M > 7, N <= WA_DTW_MAX_N.

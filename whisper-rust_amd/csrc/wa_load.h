@@ -11,6 +11,12 @@
 // 32-value formats, ggml type 6 Q5_0 / 8 Q8_0 / 3 Q4_1 / 7 Q5_1: quants [row][8][nb][4], scales [row][nb], minimums [row][nb] (types 3 and 7; else null).
 // 16-byte stores where nb % 4 == 0 and the arrays are 16-byte aligned, 4-byte stores otherwise.
 int wa_launch_load_q32(void * stream, int type, const uint8_t * src, size_t rows, size_t nb, int8_t * qs, float * qd, float * qm);
+// Q4_0 (type 2; wa_quant4.h).  plain == 0: the interleaved layout, nibble words qs u32 [row][4][nb] (wa_q4_0_pack_rows); plain != 0: the layout of Q5_0
+// above with the values q - 8 (wa_q4_0_plain_rows: the token embedding).  Scales [row][nb] either way.
+int wa_launch_load_q4_0(void * stream, const uint8_t * src, size_t rows, size_t nb, int plain, void * qs, float * qd);
+// Q4_K (type 12; wa_quant4.h).  plain == 0: nibble words qs u32 [row][8][nb][4], scale bytes [row][nb][16], d, dmin [row][nb] (wa_q4_K_pack_rows); plain != 0:
+// Q5_K's arrays with quants 0..15 (wa_q4_K_plain_rows: the token embedding)
+int wa_launch_load_q4_K(void * stream, const uint8_t * src, size_t rows, size_t nb, int plain, void * qs, int8_t * qsc, float * qd, float * qm);
 // K formats, type 10 Q2_K / 11 Q3_K / 13 Q5_K / 14 Q6_K: quants [row][8][nb][8][4], scale bytes [row][nb][16], d [row][nb], dmin [row][nb] (types 10 and 13; else null)
 int wa_launch_load_qk(void * stream, int type, const uint8_t * src, size_t rows, size_t nb, int8_t * qs, int8_t * qsc, float * qd, float * qm);
 // conv weights, F16: `rows` output channels of file order [oc][ic][3] -> dst [oc][k * IC + ic] with row stride ld elements, and the

@@ -74,6 +74,43 @@ __global__ __launch_bounds__(LD_THREADS) void k_load_q32(const uint8_t * __restr
     }
 }
 
+// ---- Q4_0 (wa_quant4.h) ------------------------------------------------------------------------------------------------------------
+// Interleaved layout: the file's nibble bytes, regrouped.  VEC: nb % 4 == 0, one thread = word plane g of blocks 4 bq .. 4 bq + 3, one 16-byte store
+// (plane 0 adds the four scales); else one thread = one word.
+template <bool VEC>
+__global__ __launch_bounds__(LD_THREADS) void k_load_q4_0(const uint8_t * __restrict__ src, size_t rows, size_t nb, uint32_t * __restrict__ qs, float * __restrict__ qd) {
+    constexpr int NBLK = VEC ? 4 : 1;
+    const size_t per_plane = nb / NBLK, t = (size_t) blockIdx.x * LD_THREADS + threadIdx.x;
+    if (t >= rows * 4 * per_plane) return;
+    const size_t bq = t % per_plane, row = t / (4 * per_plane);
+    const int g = (int) ((t / per_plane) % 4);
+    const uint8_t * blk = src + (row * nb + bq * NBLK) * 18;
+    uint32_t w[NBLK]; float f[NBLK];
+#pragma unroll
+    for (int i = 0; i < NBLK; ++i) { w[i] = ld32(blk + i * 18 + 2 + 4 * g); f[i] = h2f_bits(ld16(blk + i * 18)); }
+    uint32_t * out = qs + (row * 4 + g) * nb + bq * NBLK;
+    float * dst = qd + row * nb + bq * NBLK;
+    if (VEC) {
+        *reinterpret_cast<uint4 *>(out) = make_uint4(w[0], w[NBLK > 1 ? 1 : 0], w[NBLK > 1 ? 2 : 0], w[NBLK > 1 ? 3 : 0]);
+        if (g == 0) *reinterpret_cast<float4 *>(dst) = make_float4(f[0], f[NBLK > 1 ? 1 : 0], f[NBLK > 1 ? 2 : 0], f[NBLK > 1 ? 3 : 0]);
+    } else {
+        *out = w[0];
+        if (g == 0) *dst = f[0];
+    }
+}
+// Plain layout: one thread = lane l of one block, the values q - 8 as signed bytes
+__global__ __launch_bounds__(LD_THREADS) void k_load_q4_0_plain(const uint8_t * __restrict__ src, size_t rows, size_t nb, int8_t * __restrict__ qs, float * __restrict__ qd) {
+    const size_t t = (size_t) blockIdx.x * LD_THREADS + threadIdx.x;
+    if (t >= rows * 8 * nb) return;
+    const size_t b = t % nb, row = t / (8 * nb);
+    const int l = (int) ((t / nb) % 8);
+    const uint8_t * blk = src + (row * nb + b) * 18;
+    const uint32_t w = ld32(blk + 2 + 4 * (l & 3));
+    const uint32_t r = ((l < 4 ? w : w >> 4) & 0x0f0f0f0fu) ^ 0x08080808u;      // minus 8 in every byte (8..15 -> 0..7, 0..7 -> 0xf8..0xff)
+    *reinterpret_cast<uint32_t *>(qs + ((row * 8 + l) * nb + b) * 4) = r | (((r >> 3) & 0x01010101u) * 0xf0u);
+    if (l == 0) qd[row * nb + b] = h2f_bits(ld16(blk));
+}
+
 // ---- K formats ---------------------------------------------------------------------------------------------------------------------
 // elements 32 g + 4 l .. + 3 of a block for g = 0..7, as eight words
 template <int TYPE> __device__ __forceinline__ void qk_words(const uint8_t * blk, int l, uint32_t out[8]) {
@@ -176,6 +213,35 @@ __global__ __launch_bounds__(LD_THREADS) void k_load_qk(const uint8_t * __restri
     }
 }
 
+// ---- Q4_K (wa_quant4.h) ------------------------------------------------------------------------------------------------------------
+// one thread = lane l of one block.  Interleaved: the four nibble words qs[32 j + 4 l ..], one 16-byte store; PLAIN: the eight words of Q5_K's layout with
+// quants 0..15, two 16-byte stores.  Lane 0 adds the block's scale bytes (get_scale_min_k4, as Q5_K), lane 1 its d and dmin.
+template <bool PLAIN>
+__global__ __launch_bounds__(LD_THREADS) void k_load_q4_K(const uint8_t * __restrict__ src, size_t rows, size_t nb, uint8_t * __restrict__ qs,
+                                                          int8_t * __restrict__ qsc, float * __restrict__ qd, float * __restrict__ qm) {
+    const size_t t = (size_t) blockIdx.x * LD_THREADS + threadIdx.x;
+    if (t >= rows * 8 * nb) return;
+    const size_t b = t % nb, row = t / (8 * nb);
+    const int l = (int) ((t / nb) % 8);
+    const uint8_t * blk = src + (row * nb + b) * 144;
+    uint32_t w[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) w[j] = ld32(blk + 16 + 32 * j + 4 * l);
+    if (PLAIN) {
+        uint4 * out = reinterpret_cast<uint4 *>(qs + ((row * 8 + l) * nb + b) * 32);
+        out[0] = make_uint4(w[0] & 0x0f0f0f0fu, (w[0] >> 4) & 0x0f0f0f0fu, w[1] & 0x0f0f0f0fu, (w[1] >> 4) & 0x0f0f0f0fu);
+        out[1] = make_uint4(w[2] & 0x0f0f0f0fu, (w[2] >> 4) & 0x0f0f0f0fu, w[3] & 0x0f0f0f0fu, (w[3] >> 4) & 0x0f0f0f0fu);
+    } else *reinterpret_cast<uint4 *>(qs + ((row * 8 + l) * nb + b) * 16) = make_uint4(w[0], w[1], w[2], w[3]);
+    if (l == 0) {
+        uint32_t sc[4];
+        qk_scales<WA_TYPE_Q5_K>(blk, sc);
+        *reinterpret_cast<uint4 *>(qsc + (row * nb + b) * 16) = make_uint4(sc[0], sc[1], sc[2], sc[3]);
+    } else if (l == 1) {
+        qd[row * nb + b] = h2f_bits(ld16(blk));
+        qm[row * nb + b] = h2f_bits(ld16(blk + 2));
+    }
+}
+
 // ---- conv weights ------------------------------------------------------------------------------------------------------------------
 // IC % 8 == 0, ld % 8 == 0, 16-byte aligned pointers: one thread = eight input channels of one output channel, 48 contiguous bytes in,
 // the same 48 bytes to the copy, three 16-byte stores (one per tap k) to the re-ordered rows
@@ -237,6 +303,17 @@ int wa_launch_load_q32(void * stream, int type, const uint8_t * src, size_t rows
     return (int) hipErrorInvalidValue;
 }
 
+int wa_launch_load_q4_0(void * stream, const uint8_t * src, size_t rows, size_t nb, int plain, void * qs, float * qd) {
+    hipStream_t st = (hipStream_t) stream;
+    if (!src || !qs || !qd || ((uintptr_t) src & 1u) || ((uintptr_t) qs & 3u)) return (int) hipErrorInvalidValue;
+    if (rows == 0 || nb == 0) return 0;
+    if (rows > MAX_THREADS / 8 / nb) return (int) hipErrorInvalidValue;
+    if (plain) k_load_q4_0_plain<<<blocks_for(rows * 8 * nb), LD_THREADS, 0, st>>>(src, rows, nb, (int8_t *) qs, qd);
+    else if (nb % 4 == 0 && aligned16(qs) && aligned16(qd)) k_load_q4_0<true><<<blocks_for(rows * nb), LD_THREADS, 0, st>>>(src, rows, nb, (uint32_t *) qs, qd);
+    else k_load_q4_0<false><<<blocks_for(rows * 4 * nb), LD_THREADS, 0, st>>>(src, rows, nb, (uint32_t *) qs, qd);
+    return (int) hipGetLastError();
+}
+
 int wa_launch_load_qk(void * stream, int type, const uint8_t * src, size_t rows, size_t nb, int8_t * qs, int8_t * qsc, float * qd, float * qm) {
     hipStream_t st = (hipStream_t) stream;
     if (!src || !qs || !qsc || !qd || wa_qk_has_min(type) != (qm != nullptr) || ((uintptr_t) src & 1u) || !aligned16(qs) || !aligned16(qsc)) return (int) hipErrorInvalidValue;
@@ -250,6 +327,16 @@ int wa_launch_load_qk(void * stream, int type, const uint8_t * src, size_t rows,
         case WA_TYPE_Q6_K: k_load_qk<WA_TYPE_Q6_K><<<g, LD_THREADS, 0, st>>>(src, rows, nb, qs, qsc, qd, qm); break;
         default: return (int) hipErrorInvalidValue;
     }
+    return (int) hipGetLastError();
+}
+
+int wa_launch_load_q4_K(void * stream, const uint8_t * src, size_t rows, size_t nb, int plain, void * qs, int8_t * qsc, float * qd, float * qm) {
+    hipStream_t st = (hipStream_t) stream;
+    if (!src || !qs || !qsc || !qd || !qm || ((uintptr_t) src & 1u) || !aligned16(qs) || !aligned16(qsc)) return (int) hipErrorInvalidValue;
+    if (rows == 0 || nb == 0) return 0;
+    if (rows > MAX_THREADS / 8 / nb) return (int) hipErrorInvalidValue;
+    if (plain) k_load_q4_K<true><<<blocks_for(rows * 8 * nb), LD_THREADS, 0, st>>>(src, rows, nb, (uint8_t *) qs, qsc, qd, qm);
+    else k_load_q4_K<false><<<blocks_for(rows * 8 * nb), LD_THREADS, 0, st>>>(src, rows, nb, (uint8_t *) qs, qsc, qd, qm);
     return (int) hipGetLastError();
 }
 

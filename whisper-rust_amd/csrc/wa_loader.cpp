@@ -20,6 +20,7 @@
 #include "wa_load_plan.h"
 #include "wa_mega.h"
 #include "wa_quant1.h"
+#include "wa_quant4.h"
 #include "wa_quantk.h"
 
 #include <cmath>
@@ -47,7 +48,8 @@ struct slot {             // where a named tensor goes
     int    kind;          // 0 raw copy, 1 conv weight re-order ([oc][ic][3] -> [oc][3][ic], row stride ld),
                           // 2 quantised blocks -> kernel layout (off = signed quant bytes [row][8][block][4], off3 = scales [row][block],
                           //   off4 = minimums [row][block] of the formats that have one; K formats, 256-value blocks (wa_quantk.h): off = quants
-                          //   [row][8][block][8][4], off5 = scale bytes [row][block][16], off3 = d [row][block], off4 = dmin [row][block] of Q5_K / Q2_K)
+                          //   [row][8][block][8][4], off5 = scale bytes [row][block][16], off3 = d [row][block], off4 = dmin [row][block] of Q5_K / Q2_K;
+                          //   Q4_0 (wa_quant4.h): off = nibble words [row][4][block] of an interleaved matrix, or - plain - signed bytes as for Q5_0)
     size_t off;           // byte offset in the arena
     int    type;          // expected ggml type: 0 f32, 1 f16
     int64_t ne[3];        // expected ne[] (fastest first)
@@ -56,6 +58,7 @@ struct slot {             // where a named tensor goes
     size_t off3 = 0;
     size_t off4 = 0;
     size_t off5 = 0;
+    bool   plain = false; // Q4_0: the plain layout (the token embedding), not the interleaved one
     bool   seen = false;
 };
 
@@ -173,14 +176,19 @@ bool wa_model_load(whisper_model_loader * loader, whisper_context & wctx) {
                      hp.n_text_ctx, hp.n_vocab);
             return false;
         }
-        // ftype % 1000 names the type of the 2-D weights (whisper.cpp:1567-1573; ggml_ftype: 1 F16, 3 Q4_1, 7 Q8_0, 8 Q5_0, 9 Q5_1, 10 Q2_K, 11 Q3_K, 13 Q5_K, 14 Q6_K - for the
-        // K formats the ftype number is the ggml type number too).  ftype 0
+        // ftype % 1000 names the type of the 2-D weights (whisper.cpp:1567-1573; ggml_ftype: 1 F16, 2 Q4_0, 3 Q4_1, 7 Q8_0, 8 Q5_0, 9 Q5_1, 10 Q2_K, 11 Q3_K, 12 Q4_K, 13 Q5_K, 14 Q6_K -
+        // for Q4_0 and the K formats the ftype number is the ggml type number too).  ftype 0
         // (all-F32) aborts in the reference's own conv path; Q4_0 runs through the reference's repacked 8-row product, a
-        // summation order of its own that is not restated here, and so does Q4_K; the other quantised formats (the IQ family) are not built.
+        // summation order of its own, and so does Q4_K (wa_quant4.h); the other quantised formats (the IQ family) are not built.
+        // Q4_0 and Q4_K are the only formats whose bits are those of ONE build of the reference - AVX2 with its CPU repack; a reference built without
+        // the repack multiplies them in plain order - so they load only where the caller names that build: WHISPER_AMD_REPACK_ORDER=1, read at every load.
+        // Without it such a file is refused as before.
         const int ft = hp.ftype % 1000;
-        model.wtype = ft == 1 ? 1 : ft == 8 ? 6 : ft == 7 ? 8 : ft == 3 ? 3 : ft == 9 ? 7 : ft == 13 ? 13 : ft == 14 ? 14 : ft == 10 ? 10 : ft == 11 ? 11 : -1;
+        const char * rp = getenv("WHISPER_AMD_REPACK_ORDER");
+        const bool repack_order = rp && *rp && strcmp(rp, "0") != 0;
+        model.wtype = ft == 1 ? 1 : ft == 2 && repack_order ? 2 : ft == 8 ? 6 : ft == 7 ? 8 : ft == 3 ? 3 : ft == 9 ? 7 : ft == 13 ? 13 : ft == 12 && repack_order ? 12 : ft == 14 ? 14 : ft == 10 ? 10 : ft == 11 ? 11 : -1;
         if (model.wtype < 0) {
-            WA_ERROR("%s: unsupported ftype %d (this backend loads F16, Q8_0, Q5_0, Q5_1, Q4_1, Q2_K, Q3_K, Q5_K and Q6_K models)\n", __func__, hp.ftype);
+            WA_ERROR("%s: unsupported ftype %d (this backend loads F16, Q8_0, Q5_0, Q5_1, Q4_1, Q2_K, Q3_K, Q5_K and Q6_K models, and Q4_0 and Q4_K in the order of the reference's AVX2 repack build where WHISPER_AMD_REPACK_ORDER=1 asks for it)\n", __func__, hp.ftype);
             return false;
         }
     }
@@ -250,7 +258,7 @@ bool wa_model_load(whisper_model_loader * loader, whisper_context & wctx) {
         return false;
     }
     if (wa_wtype_k(model.wtype) && d % WA_QK_K != 0) {      // every quantised row is d or 4 d long (tiny's 384 does not qualify)
-        WA_ERROR("%s: a %s model needs row lengths that are a multiple of 256, n_audio_state is %d\n", __func__, model.wtype == 13 ? "Q5_K" : model.wtype == 14 ? "Q6_K" : model.wtype == 10 ? "Q2_K" : "Q3_K", d);
+        WA_ERROR("%s: a %s model needs row lengths that are a multiple of 256, n_audio_state is %d\n", __func__, model.wtype == 13 ? "Q5_K" : model.wtype == 12 ? "Q4_K" : model.wtype == 14 ? "Q6_K" : model.wtype == 10 ? "Q2_K" : "Q3_K", d);
         return false;
     }
     if (model.n_mel_filt != hp.n_mels) { WA_ERROR("%s: mel filter count %d != n_mels %d\n", __func__, model.n_mel_filt, hp.n_mels); return false; }
@@ -272,14 +280,21 @@ bool wa_model_load(whisper_model_loader * loader, whisper_context & wctx) {
     const size_t o_gelu    = ab.take(65536 * H);
 
     struct lin_off { size_t w, b, s; size_t qs = 0, qh = 0, qd = 0, qm = 0, qsc = 0; };
-    const int QT = model.wtype;                                  // 1, 6, 8, 3, 7, 10, 11, 13 or 14
+    const int QT = model.wtype;                                  // 1, 2, 6, 8, 3, 7, 10, 11, 12, 13 or 14
     // Kernel layout of a quantised [n_out][n_in] matrix: the quants as signed bytes (Q5_0's 5-bit values are expanded once, here),
     // ordered [row][lane l = 0..7][block][4] - lane l of a row's 8-lane group owns elements 4l..4l+3 of EVERY block, so its bytes
     // are contiguous over the blocks (16-byte loads cover four blocks) - and the block scales [row][block] as F32.  Q4_1 / Q5_1: the
     // quants are the unsigned 4- / 5-bit values, and a third array holds the block minimums [row][block] as F32 (wa_quant1.h).
     // K formats (wa_quantk.h): 256-value blocks - quants [row][lane][block][group][4], 16 scale bytes and d (Q5_K, Q2_K: and dmin) per block.
     const bool QMIN = wa_wtype_has_min(QT), QK = wa_wtype_k(QT);
-    auto take_q = [&](lin_off & o, size_t n_out, size_t n_in) {
+    // Q4_0 (wa_quant4.h): an interleaved matrix is nibble words [row][4][block], half a byte per weight; the plain one (the token embedding) is Q5_0's layout.
+    auto take_q = [&](lin_off & o, size_t n_out, size_t n_in, bool plain = false) {
+        if (QT == 2 && !plain) { o.qs = ab.take(n_out * n_in / 2); o.qd = ab.take(n_out * (n_in / 32) * 4); return; }
+        if (QT == 12) {      // Q4_K: nibble words [row][8][block][4] (plain: Q5_K's signed bytes), scale bytes, d, dmin
+            o.qs = ab.take(plain ? n_out * n_in : n_out * n_in / 2); o.qsc = ab.take(n_out * (n_in / 256) * 16);
+            o.qd = ab.take(n_out * (n_in / 256) * 4); o.qm = ab.take(n_out * (n_in / 256) * 4);
+            return;
+        }
         if (QK) {
             o.qs = ab.take(n_out * n_in); o.qsc = ab.take(n_out * (n_in / 256) * 16); o.qd = ab.take(n_out * (n_in / 256) * 4);
             if (wa_qk_has_min(QT)) o.qm = ab.take(n_out * (n_in / 256) * 4);
@@ -288,8 +303,8 @@ bool wa_model_load(whisper_model_loader * loader, whisper_context & wctx) {
         o.qs = ab.take(n_out * n_in); o.qh = 0; o.qd = ab.take(n_out * (n_in / 32) * 4);
         if (QMIN) o.qm = ab.take(n_out * (n_in / 32) * 4);
     };
-    auto add_q = [&](const std::string & name, const lin_off & o, size_t row0, int64_t n_in, int64_t n_rows) {
-        slot s; s.kind = 2; s.off = o.qs + row0 * (size_t) n_in; s.off2 = 0; s.off3 = o.qd + row0 * (size_t) (n_in / 32) * 4; s.type = QT;
+    auto add_q = [&](const std::string & name, const lin_off & o, size_t row0, int64_t n_in, int64_t n_rows, bool plain = false) {
+        slot s; s.kind = 2; s.off = o.qs + row0 * (size_t) n_in / ((QT == 2 || QT == 12) && !plain ? 2 : 1); s.plain = plain; s.off2 = 0; s.off3 = o.qd + row0 * (size_t) (n_in / 32) * 4; s.type = QT;
         s.off4 = QMIN ? o.qm + row0 * (size_t) (n_in / 32) * 4 : 0;
         if (QK) {
             s.off3 = o.qd + row0 * (size_t) (n_in / 256) * 4; s.off4 = o.qm ? o.qm + row0 * (size_t) (n_in / 256) * 4 : 0;
@@ -359,7 +374,7 @@ bool wa_model_load(whisper_model_loader * loader, whisper_context & wctx) {
     lin_off o_teq{ 0, 0, 0 };
     add("decoder.positional_embedding",   0, o_dpe, 0, d, hp.n_text_ctx, 1);
     if (QT == 1) add("decoder.token_embedding.weight", 0, o_dte, 1, d, hp.n_vocab, 1);
-    else { take_q(o_teq, hp.n_vocab, d); add_q("decoder.token_embedding.weight", o_teq, 0, d, hp.n_vocab); }
+    else { take_q(o_teq, hp.n_vocab, d, true); add_q("decoder.token_embedding.weight", o_teq, 0, d, hp.n_vocab, true); }
     const ln_off o_dln = take_ln("decoder.ln");
 
     // cross k|v of all layers fused: rows [il*2d, il*2d+d) key, [il*2d+d, (il+1)*2d) value
@@ -417,6 +432,8 @@ bool wa_model_load(whisper_model_loader * loader, whisper_context & wctx) {
     size_t row_bytes_max = 0;                     // the longest row of any tensor: no staging buffer may be smaller
     auto slot_row_bytes = [&](const slot & s) -> size_t {
         if (s.kind == 1) return (size_t) s.ne[1] * 3 * H;                                    // one output channel
+        if (s.kind == 2 && s.type == WA_TYPE_Q4_0) return (size_t) s.ne[0] / 32 * WA_Q4_0_BYTES;
+        if (s.kind == 2 && s.type == WA_TYPE_Q4_K) return (size_t) s.ne[0] / WA_QK_K * WA_Q4_K_BYTES;
         if (s.kind == 2) return wa_qk_block_bytes(s.type) ? (size_t) s.ne[0] / WA_QK_K * wa_qk_block_bytes(s.type)
                               : (size_t) s.ne[0] / 32 * (wa_q0_block_bytes(s.type) ? wa_q0_block_bytes(s.type) : wa_q1_block_bytes(s.type));
         return (size_t) s.ne[0] * (s.type == 0 ? F : H);
@@ -485,6 +502,13 @@ bool wa_model_load(whisper_model_loader * loader, whisper_context & wctx) {
         if (s.kind == 2 && wa_qk_block_bytes(s.type)) {        // block_q2_K / q3_K / q5_K / q6_K -> the arrays of wa_quantk.h
             wa_qk_unpack_rows(s.type, tmp.data(), (size_t) s.ne[1], (size_t) s.ne[0] / WA_QK_K, (int8_t *) (img.data() + s.off), (int8_t *) (img.data() + s.off5),
                               (float *) (img.data() + s.off3), s.off4 ? (float *) (img.data() + s.off4) : nullptr);
+        } else if (s.kind == 2 && s.type == WA_TYPE_Q4_K) {        // block_q4_K -> nibble words, or - the token embedding - Q5_K's arrays (wa_quant4.h)
+            const size_t rows = (size_t) s.ne[1], nb = (size_t) s.ne[0] / WA_QK_K;
+            if (s.plain) wa_q4_K_plain_rows(tmp.data(), rows, nb, (int8_t *) (img.data() + s.off), (int8_t *) (img.data() + s.off5), (float *) (img.data() + s.off3), (float *) (img.data() + s.off4));
+            else wa_q4_K_pack_rows(tmp.data(), rows, nb, img.data() + s.off, img.data() + s.off5, (float *) (img.data() + s.off3), (float *) (img.data() + s.off4));
+        } else if (s.kind == 2 && s.type == WA_TYPE_Q4_0) {        // block_q4_0 -> nibble words, or - the token embedding - signed bytes (wa_quant4.h)
+            if (s.plain) wa_q4_0_plain_rows(tmp.data(), (size_t) s.ne[1], (size_t) s.ne[0] / 32, (int8_t *) (img.data() + s.off), (float *) (img.data() + s.off3));
+            else wa_q4_0_pack_rows(tmp.data(), (size_t) s.ne[1], (size_t) s.ne[0] / 32, img.data() + s.off, (float *) (img.data() + s.off3));
         } else if (s.kind == 2) {        // block_q5_0 / block_q8_0, and block_q4_1 / block_q5_1 with their minimum (wa_quant1.h) -> arrays
             wa_q32_unpack_rows(s.type, tmp.data(), (size_t) s.ne[1], (size_t) s.ne[0] / 32, (int8_t *) (img.data() + s.off), (float *) (img.data() + s.off3),
                                s.off4 ? (float *) (img.data() + s.off4) : nullptr);
@@ -517,6 +541,13 @@ bool wa_model_load(whisper_model_loader * loader, whisper_context & wctx) {
                     const size_t nb = (size_t) s.ne[0] / WA_QK_K;
                     err = wa_launch_load_qk(pipe.stream, s.type, dv, c.rows, nb, (int8_t *) (base + s.off) + c.row0 * nb * WA_QK_K, (int8_t *) (base + s.off5) + c.row0 * nb * 16,
                                             (float *) (base + s.off3) + c.row0 * nb, s.off4 ? (float *) (base + s.off4) + c.row0 * nb : nullptr);
+                } else if (s.type == WA_TYPE_Q4_K) {
+                    const size_t nb = (size_t) s.ne[0] / WA_QK_K;
+                    err = wa_launch_load_q4_K(pipe.stream, dv, c.rows, nb, s.plain ? 1 : 0, base + s.off + c.row0 * nb * (s.plain ? 256 : 128), (int8_t *) (base + s.off5) + c.row0 * nb * 16,
+                                              (float *) (base + s.off3) + c.row0 * nb, (float *) (base + s.off4) + c.row0 * nb);
+                } else if (s.type == WA_TYPE_Q4_0) {
+                    const size_t nb = (size_t) s.ne[0] / 32;
+                    err = wa_launch_load_q4_0(pipe.stream, dv, c.rows, nb, s.plain ? 1 : 0, base + s.off + c.row0 * nb * (s.plain ? 32 : 16), (float *) (base + s.off3) + c.row0 * nb);
                 } else {
                     const size_t nb = (size_t) s.ne[0] / 32;
                     err = wa_launch_load_q32(pipe.stream, s.type, dv, c.rows, nb, (int8_t *) (base + s.off) + c.row0 * nb * 32, (float *) (base + s.off3) + c.row0 * nb,
@@ -556,11 +587,11 @@ bool wa_model_load(whisper_model_loader * loader, whisper_context & wctx) {
             return false;
         }
         if (ttype != s.type) { WA_ERROR("%s: tensor '%s' has type %d in model file, expected %d\n", __func__, name.c_str(), ttype, s.type); return false; }
-        if (wa_qk_block_bytes(s.type) && s.ne[0] % WA_QK_K != 0) {
+        if ((wa_qk_block_bytes(s.type) || s.type == WA_TYPE_Q4_K) && s.ne[0] % WA_QK_K != 0) {
             WA_ERROR("%s: tensor '%s' has rows of %d values, not a multiple of 256\n", __func__, name.c_str(), (int) s.ne[0]);
             return false;
         }
-        const size_t nbytes = wa_qk_block_bytes(s.type) ? (size_t) nelements / WA_QK_K * wa_qk_block_bytes(s.type) : s.type == 6 ? (size_t) nelements / 32 * 22 : s.type == 8 ? (size_t) nelements / 32 * 34 :
+        const size_t nbytes = wa_qk_block_bytes(s.type) ? (size_t) nelements / WA_QK_K * wa_qk_block_bytes(s.type) : s.type == 6 ? (size_t) nelements / 32 * 22 : s.type == WA_TYPE_Q4_0 ? (size_t) nelements / 32 * WA_Q4_0_BYTES : s.type == WA_TYPE_Q4_K ? (size_t) nelements / WA_QK_K * WA_Q4_K_BYTES : s.type == 8 ? (size_t) nelements / 32 * 34 :
                               wa_q1_block_bytes(s.type) ? (size_t) nelements / 32 * wa_q1_block_bytes(s.type) : (size_t) nelements * (s.type == 0 ? F : H);
         const int rc = on_device ? device_tensor(s, nbytes) : host_tensor(s, nbytes);
         if (rc == 1) { WA_ERROR("%s: truncated tensor '%s'\n", __func__, name.c_str()); return false; }
@@ -619,7 +650,7 @@ bool wa_model_load(whisper_model_loader * loader, whisper_context & wctx) {
         model.enc[i].fc1 = LIN(eo[i].fc1, 4 * d, d);  model.enc[i].fc2 = LIN(eo[i].fc2, d, 4 * d);
     }
     model.d_pe = PF(o_dpe); model.d_te = QT == 1 ? PH(o_dte) : nullptr; model.d_ln = LN(o_dln);
-    if (QT != 1) { lin_off t = o_teq; t.b = 0; model.te_q = LIN(t, hp.n_vocab, d); model.te_q.b = nullptr; }
+    if (QT != 1) { lin_off t = o_teq; t.b = 0; model.te_q = LIN(t, hp.n_vocab, d); model.te_q.b = nullptr; if (QT == 2) model.te_q.wtype = 6; model.te_q.plain = QT == 12; }      // (Q4_0: the plain layout IS Q5_0's, and so is its product; Q4_K: Q5_K's arrays, a product of its own)
     model.dec.resize(Ld);
     for (int i = 0; i < Ld; ++i) {
         auto & L = model.dec[i];
