@@ -644,6 +644,39 @@ WHISPER_API int  whisper_amd_tts_tile(void);
 WHISPER_API int64_t whisper_amd_arena_read(struct whisper_context * ctx, int64_t offset, void * dst, int64_t cap);
 WHISPER_API void    whisper_amd_load_stats(struct whisper_context * ctx, int64_t out[6]);
 
+/* Weight quantisation (wa_quantw.hip / wa_quantw.h): F32 or F16 values -> standard ggml blocks, byte for byte what the reference's
+ * quantize tool writes for them.  type: ggml type 2 Q4_0, 3 Q4_1, 6 Q5_0, 7 Q5_1, 8 Q8_0, 12 Q4_K, 13 Q5_K, 14 Q6_K.
+ * whisper_amd_quantize_rows: `n` values at `src` (F32, or IEEE halfs when src_is_f16 != 0; n a multiple of the type's block, 32 or 256) ->
+ *   n / block blocks at `dst` (host).  where = 1: the HIP kernels on the current device; `src` is a host or a device pointer (device values
+ *   are read where they lie when 16-byte aligned).  where = 0: the host statement; `src` is a host pointer.  Both give the same bytes.
+ *   Returns 0, WHISPER_AMD_QUANTIZE_REFUSED (a type this library does not quantise - Q2_K and Q3_K are named in the log as out of scope -, a
+ *   null pointer, a ragged n, another `where`), WHISPER_AMD_QUANTIZE_NOT_FINITE (an infinity or NaN among the values; both paths refuse the
+ *   same inputs and `dst` then means nothing) or WHISPER_AMD_QUANTIZE_FAILED (a HIP call failed; logged). */
+#define WHISPER_AMD_QUANTIZE_REFUSED    (-1)
+#define WHISPER_AMD_QUANTIZE_NOT_FINITE (-2)
+#define WHISPER_AMD_QUANTIZE_FAILED     (-3)
+WHISPER_API int whisper_amd_quantize_rows(int type, const void * src, int src_is_f16, int64_t n, void * dst, int where);
+/* whisper_amd_quantize_rows is the kernel-level entry (tests, probes): every where = 1 call creates a stream and allocates and frees its device
+ *   buffers, so it is not meant to be called per tensor; where = 0 touches nothing of HIP.  Managed memory counts as host memory (a staged copy).
+ * whisper_amd_quantize_file: reads the F16 / F32 model at path_in and writes at path_out the file the reference's quantize tool writes for `type`,
+ *   byte for byte: the header with ftype = 2 * 1000 + ftype, mel filters and vocabulary copied through, every tensor record in order - quantised
+ *   where it is 2-D, F16 or F32 and not one of the positional embeddings or conv biases, copied otherwise.  Tensor bytes go through pinned
+ *   buffers in chunks of 1 Mi values (up, quantised by the kernels, back, written; WHISPER_AMD_LOAD_HOST=1: the host statement instead); the file
+ *   is never wholly in memory.  whisper_amd_quantize_loader: the same from a whisper_model_loader, which it closes.  Both return 0,
+ *   WHISPER_AMD_QUANTIZE_REFUSED (logged: a type out of scope, a file that cannot be opened, a model that is already quantised, a tensor whose
+ *   rows are no multiple of the block - a d = 384 model with a K type -, a value that is not finite, a corrupt file) or WHISPER_AMD_QUANTIZE_FAILED
+ *   (a HIP call or the write failed); nothing is left at path_out then.
+ * whisper_amd_init_from_file_quantized / whisper_amd_init_quantized_with_params: as whisper_init_from_file_with_params / whisper_init_with_params on
+ *   an F16 / F32 model, but the context is the one that loading the quantised file would give - the same weight arena byte for byte, the same
+ *   whisper_model_ftype: the loader reads the quantised stream as it is produced, chunk by chunk (each chunk: pinned buffer -> quantise kernel ->
+ *   pinned buffer -> the loader's own staging -> unpack kernel -> arena; the blocks cross the bus once more than a fused path would).  Q4_0 / Q4_K
+ *   need WHISPER_AMD_REPACK_ORDER=1 exactly as their files do.  Null, with the reason logged, for everything the file writer refuses.  The
+ *   quantise launches count among whisper_amd_load_stats' unpack kernels. */
+WHISPER_API int whisper_amd_quantize_file(const char * path_in, const char * path_out, int type);
+WHISPER_API int whisper_amd_quantize_loader(struct whisper_model_loader * loader, const char * path_out, int type);
+WHISPER_API struct whisper_context * whisper_amd_init_from_file_quantized(const char * path, struct whisper_context_params cparams, int type);
+WHISPER_API struct whisper_context * whisper_amd_init_quantized_with_params(struct whisper_model_loader * loader, struct whisper_context_params cparams, int type);
+
 /* Audio front end (wa_audio.cpp): a recording as it comes out of a WAV file (whisper_amd_wav_parse reads the header) - 8-, 16-, 24- or
  * 32-bit PCM, F32, F64 or G.711 mu-law / A-law samples, one or two interleaved channels, 8 .. 192 kHz - converted, down-mixed and resampled to the 16 kHz mono F32 that whisper_full* takes, by HIP kernels on the
  * state's stream.  whisper-rs callers do the first two steps on the host (src/utilities.rs) and its examples refuse every rate but 16 kHz.

@@ -1,12 +1,14 @@
 """Model load time (wa_model_load): wall time of whisper_init_from_file_with_params_no_state and the loader's own stages.
 
-    WA_LIB=<libwhisper.so> python tools/load_probe.py [--repeat N] [--path device|host|both] [--chunk BYTES] MODEL ...
+    WA_LIB=<libwhisper.so> python tools/load_probe.py [--repeat N] [--path device|host|both] [--chunk BYTES] [--quantize TYPE] MODEL ...
 
 MODEL is a synthetic model of tools/wsynth.py ("small", "small:q5_1", "large-v3:q5_0", ...), written on first use; the file is read once
 before the first load so that it sits in the page cache.  Every model is loaded N times per path.  The FIRST load of the process is printed
 apart from the later ones: it pays the runtime's start-up (device initialisation, the code objects) whatever the loader does.  One JSON line
 per model and path: wall times in ms, and - where the library has whisper_amd_load_stats - the stages of the median later load:
 read = in loader->read, wait = waiting for the device, load = the whole wa_model_load, kernels = unpack kernels launched.
+--quantize TYPE ("q5_0", "q5_k", ...): MODEL is an F16 model and is loaded through whisper_amd_init_from_file_quantized (quantise-at-load); set the
+line against the one of MODEL:TYPE, the file the reference's quantize tool wrote.
 A library without the device path (no whisper_amd_load_stats) is timed on its only path whatever --path says."""
 import argparse
 import ctypes as C
@@ -27,7 +29,9 @@ def main():
     ap.add_argument("--repeat", type=int, default=3)
     ap.add_argument("--path", choices=("device", "host", "both"), default="both")
     ap.add_argument("--chunk", type=int, default=None, help="WHISPER_AMD_LOAD_CHUNK for the device path")
+    ap.add_argument("--quantize", default=None, help="quantise-at-load to this type (q4_0 q4_1 q5_0 q5_1 q8_0 q4_k q5_k q6_k)")
     a = ap.parse_args()
+    qtype = None if a.quantize is None else dict(q4_0=2, q4_1=3, q5_0=6, q5_1=7, q8_0=8, q4_k=12, q5_k=13, q6_k=14)[a.quantize]
     lib = W.load_library(os.environ.get("WA_LIB"))
     W.set_log_callback(lib, lambda l, t: None)
     has_stats = hasattr(lib, "whisper_amd_load_stats")
@@ -47,7 +51,10 @@ def main():
             walls, stats, first_ms = [], [], None
             for _ in range(a.repeat + (1 if first else 0)):
                 t = time.perf_counter()
-                ctx = W.WhisperContext.new_with_params(mp, W.WhisperContextParameters(lib), lib=lib)
+                if qtype is None:
+                    ctx = W.WhisperContext.new_with_params(mp, W.WhisperContextParameters(lib), lib=lib)
+                else:
+                    ctx = W.WhisperContext.new_quantized(mp, qtype, W.WhisperContextParameters(lib), lib=lib)
                 ms = (time.perf_counter() - t) * 1e3
                 s = ctx.load_stats() if has_stats else None
                 ctx.free()
@@ -55,7 +62,7 @@ def main():
                     first, first_ms = False, ms
                     continue
                 walls.append(ms); stats.append(s)
-            out = dict(model=name, file_mb=round(os.path.getsize(mp) / 1e6, 1), path=path, chunk=a.chunk if path == "device" else None,
+            out = dict(model=name, quantize=a.quantize, file_mb=round(os.path.getsize(mp) / 1e6, 1), path=path, chunk=a.chunk if path == "device" else None,
                        first_load_of_process_ms=None if first_ms is None else round(first_ms, 1), later_ms=[round(w, 1) for w in walls])
             if walls:
                 out["later_median_ms"] = round(statistics.median(walls), 1)

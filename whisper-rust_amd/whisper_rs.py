@@ -316,6 +316,12 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     if hasattr(lib, "whisper_amd_arena_read"):
         proto("whisper_amd_arena_read", C.c_int64, P, C.c_int64, P, C.c_int64)
         proto("whisper_amd_load_stats", None, P, C.POINTER(C.c_int64))
+    if hasattr(lib, "whisper_amd_quantize_rows"):
+        proto("whisper_amd_quantize_rows", I, I, P, I, C.c_int64, P, I)
+        proto("whisper_amd_quantize_file", I, C.c_char_p, C.c_char_p, I)
+        proto("whisper_amd_quantize_loader", I, C.POINTER(whisper_model_loader), C.c_char_p, I)
+        proto("whisper_amd_init_from_file_quantized", P, C.c_char_p, whisper_context_params, I)
+        proto("whisper_amd_init_quantized_with_params", P, C.POINTER(whisper_model_loader), whisper_context_params, I)
     if hasattr(lib, "whisper_amd_audio_to_pcm"):
         proto("whisper_amd_audio_n_samples", C.c_int64, C.c_int64, I)
         proto("whisper_amd_audio_to_pcm", P, P, P, C.c_int64, I, I, I, C.POINTER(C.c_int64))
@@ -501,7 +507,26 @@ def audio_taps(lib: C.CDLL, sample_rate: int):
     return t[:n].reshape(L.value, K.value), L.value, M.value, K.value
 
 
-DTW_REFUSED, DTW_NOT_TAKEN, DTW_HIP_ERROR = -1, -2, -3      # whisper_amd_dtw_path's codes (include/whisper_amd.h)
+QUANTIZE_REFUSED, QUANTIZE_NOT_FINITE, QUANTIZE_FAILED = -1, -2, -3      # whisper_amd_quantize_rows' codes
+QUANTIZE_BLOCK = {2: (32, 18), 3: (32, 20), 6: (32, 22), 7: (32, 24), 8: (32, 34), 12: (256, 144), 13: (256, 176), 14: (256, 210)}      # ggml type: (values, bytes)
+
+
+def quantize_rows(lib: C.CDLL, ggml_type: int, values, where: int = 1, device_ptr: Optional[int] = None, n: Optional[int] = None, f16: bool = False):
+    """Extension (whisper_amd_quantize_rows): F32 / F16 values -> the ggml blocks of `ggml_type` as a uint8 array; an int (a code above) when refused.
+    values: a float32 or float16 numpy array, or - with device_ptr, n and f16 - values that lie in device memory."""
+    if device_ptr is None:
+        values = np.ascontiguousarray(values)
+        assert values.dtype in (np.float32, np.float16)
+        f16, n, ptr = values.dtype == np.float16, values.size, C.c_void_p(values.ctypes.data)
+    else:
+        ptr = C.c_void_p(device_ptr)
+    bv, bs = QUANTIZE_BLOCK.get(ggml_type, (32, 34))
+    out = np.zeros(max(n // bv, 1) * bs, np.uint8)
+    rc = lib.whisper_amd_quantize_rows(ggml_type, ptr, 1 if f16 else 0, n, C.c_void_p(out.ctypes.data), where)
+    return out[:n // bv * bs] if rc == 0 else rc
+
+
+DTW_REFUSED, DTW_NOT_TAKEN, DTW_HIP_ERROR = -1, -2, -3     # whisper_amd_dtw_path's codes (include/whisper_amd.h)
 TTS_REFUSED, TTS_HIP_ERROR = -1, -3                         # whisper_amd_signal_energy's and whisper_amd_token_snap's codes
 TTS_LOUD_LO, TTS_LOUD_HI, TTS_HAS_PREV = 1, 2, 4            # flag bits of a record
 TTS_RECORD_DTYPE = np.dtype([("back_lo", np.int32), ("fwd_lo", np.int32), ("fwd_hi", np.int32), ("back_hi", np.int32), ("flags", np.uint32), ("level", np.float32)])
@@ -603,6 +628,18 @@ class WhisperContext:
         ptr = lib.whisper_init_from_file_with_params_no_state(path.encode(), params.c)
         if not ptr:
             raise WhisperError("InitError")  # src/whisper_ctx.rs:38-42
+        ctx = cls(lib, ptr)
+        ctx._params = params
+        return ctx
+
+    @classmethod
+    def new_quantized(cls, path: str, ggml_type: int, params: Optional[WhisperContextParameters] = None, lib: Optional[C.CDLL] = None) -> "WhisperContext":
+        """Extension (whisper_amd_init_from_file_quantized): an F16 / F32 model loaded as if it were the file quantised to `ggml_type`."""
+        lib = lib or load_library()
+        params = params or WhisperContextParameters(lib)
+        ptr = lib.whisper_amd_init_from_file_quantized(path.encode(), params.c, ggml_type)
+        if not ptr:
+            raise WhisperError("InitError")
         ctx = cls(lib, ptr)
         ctx._params = params
         return ctx
