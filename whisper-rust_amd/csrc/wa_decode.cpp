@@ -319,7 +319,7 @@ template <class A> static bool one_launch_args(const whisper_context & ctx, cons
     memset(&a, 0, sizeof(a));
     a.layers = (const wa_mega_layer *) m.d_mega_layers;
     a.n_layer = hp.n_text_layer; a.d = hp.n_text_state; a.n_head = hp.n_text_head; a.n_vocab = hp.n_vocab; a.eps = hp.eps; a.rn_d = 1.0 / (double) hp.n_text_state;
-    a.te = m.d_te; a.pe = m.d_pe; a.lnf_w = m.d_ln.w; a.lnf_b = m.d_ln.b; a.gelu = m.d_gelu; a.quant = m.wtype != 1 ? 1 : 0;
+    a.te = m.d_te; a.pe = m.d_pe; a.lnf_w = m.d_ln.w; a.lnf_b = m.d_ln.b; a.gelu = m.d_gelu; a.quant = wa_one_launch_quant(m.wtype);
     if (a.quant) { a.te = (const wa_f16 *) m.te_q.qs; a.te_d = m.te_q.qd; }
     a.kv_layer_stride = (unsigned long long) kv_size * hp.n_text_state;
     a.cross_layer_stride = (unsigned long long) hp.n_text_head * st.cross_tpad * 64; a.cross_tpad = st.cross_tpad; a.T = T;
@@ -385,6 +385,7 @@ static bool rows_args(whisper_context & ctx, whisper_state & own, wa_rows_args &
     for (int i = 0; i < B; ++i)
         if (rows[i].n_kv < 1 || rows[i].n_kv > WA_ROWS_MAXKV || rows[i].kv_head < 0 || rows[i].kv_head >= rows[i].n_kv) return false;
     if (wa_rows_lds_bytes(hp.n_text_state, B, std::min(ctx.model.n_cu, 256), a.quant, &a.slot_bytes) == 0 || !wa_rows_prepare(ctx, own)) return false;
+    if (a.quant == 2) a.te_m = ctx.model.te_q.qm;      // (Q4_1 / Q5_1: k_decode_rows_q1_np*)
     a.force_inorder = rows_force_inorder();
     a.granules = own.d_rows_gr; a.row_gr = 2 * hp.n_text_state; a.cross_gr = own.d_rows_cgr;
     a.B = a.n_out = B;
@@ -1313,7 +1314,7 @@ extern "C" int whisper_amd_kv_op(struct whisper_state * st, int op, int a, int b
 extern "C" int whisper_amd_rows_fits(struct whisper_context * ctx, int B) {
     if (!ctx || ctx->model.n_loaded == 0) return 0;
     int slot = 0;
-    return wa_rows_lds_bytes(ctx->model.hp.n_text_state, B, std::min(ctx->model.n_cu, 256), ctx->model.wtype != 1 ? 1 : 0, &slot) != 0 ? 1 : 0;
+    return wa_rows_lds_bytes(ctx->model.hp.n_text_state, B, std::min(ctx->model.n_cu, 256), wa_one_launch_quant(ctx->model.wtype), &slot) != 0 ? 1 : 0;
 }
 
 // whisper_amd_rows_debug with a state, a token and a context length per row (the shape of a lock-step pass): row i attends over cells [0, n_past[i]]

@@ -107,24 +107,32 @@ bool wa_state_alloc(whisper_context & ctx, whisper_state & st) {
     {   // one-launch decode step: needs one workgroup per CU with all of them resident, d_head 64, d <= 1280
         const char * g = getenv("WHISPER_AMD_NO_MEGA");
         const int dt = hp.n_text_state, Ht = hp.n_text_head;
-        st.mega_form = wa_launch_form(!(g && g[0] == '1') && ctx.model.d_mega_layers && ctx.model.n_loaded > 0 && dt == Ht * 64 && dt % 128 == 0 &&
-                                      dt <= WA_MEGA_MAX_D && hp.n_audio_ctx <= 1500 && ctx.model.n_cu >= 5 * Ht + 16 && tpad <= WA_MEGA_MAX_T &&
-                                      !wa_wtype_has_min(ctx.model.wtype) && !wa_wtype_k(ctx.model.wtype) && ctx.model.wtype != 2);      // (Q4_1 / Q5_1, the K formats, Q4_0 / Q4_K: no one-launch kernel - every pass is the launch sequence)
+        const bool shape_ok = !(g && g[0] == '1') && ctx.model.d_mega_layers && ctx.model.n_loaded > 0 && dt == Ht * 64 && dt % 128 == 0 &&
+                              dt <= WA_MEGA_MAX_D && hp.n_audio_ctx <= 1500 && ctx.model.n_cu >= 5 * Ht + 16 && tpad <= WA_MEGA_MAX_T;
+        st.mega_form = wa_launch_form(shape_ok && !wa_wtype_has_min(ctx.model.wtype) && !wa_wtype_k(ctx.model.wtype) && ctx.model.wtype != 2);      // (Q4_1 / Q5_1, the K formats, Q4_0 / Q4_K: no k_decode_mega kernel)
+        // Q4_1 / Q5_1: the several-rows kernel has a form for them (k_decode_rows_q1_np*), opt-in by WHISPER_AMD_ROWS_Q1=1 when the state is made; a
+        // single token is then that kernel with one row, at every width.  Without the switch every pass of these models is the launch sequence.
+        const char * q1 = getenv("WHISPER_AMD_ROWS_Q1");
+        const bool rows_q1 = shape_ok && wa_wtype_has_min(ctx.model.wtype) && q1 && q1[0] == '1';
         if (st.mega_form.enabled()) {
-            // logits of the step and, right behind them, the status word: one device-to-host copy per token
             if (!dev_alloc(st.d_mega_cgr, (size_t) hp.n_text_layer * Ht * WA_MEGA_CGR)) return false;
-            if (!dev_alloc(st.d_mega_gr, (size_t) hp.n_text_layer * WA_MEGA_EDGES * 4 * dt) || !dev_alloc(st.d_mega_out, (size_t) hp.n_vocab + 64)) return false;
+            if (!dev_alloc(st.d_mega_gr, (size_t) hp.n_text_layer * WA_MEGA_EDGES * 4 * dt)) return false;
+        }
+        if (st.mega_form.enabled() || rows_q1) {
+            // logits of the step and, right behind them, the status word: one device-to-host copy per token
+            if (!dev_alloc(st.d_mega_out, (size_t) hp.n_vocab + 64)) return false;
             st.d_mega_status = (unsigned *) (st.d_mega_out + hp.n_vocab);
             if (!dev_alloc(st.d_mega_out2, (size_t) hp.n_vocab + 64) || !dev_alloc(st.d_mega_smask, (size_t) hp.n_vocab / 32 + 2)) return false;
             for (int b = 0; b < 2; ++b)
                 if (!dev_alloc(st.d_mega_rec[b], (size_t) 512 * 8) || !dev_alloc(st.d_mega_ps[b], 8)) return false;
             {   // the several-rows form shares the one-launch step's preconditions (its buffers come with the first such pass: wa_rows_prepare)
                 const char * r = getenv("WHISPER_AMD_NO_ROWS");
+                const int quant = wa_one_launch_quant(ctx.model.wtype);
                 int slot = 0;
-                st.rows_form = wa_launch_form(!(r && r[0] == '1') && wa_rows_lds_bytes(dt, 2, std::min(ctx.model.n_cu, 256), ctx.model.wtype != 1 ? 1 : 0, &slot) != 0);
+                st.rows_form = wa_launch_form(!(r && r[0] == '1') && wa_rows_lds_bytes(dt, 2, std::min(ctx.model.n_cu, 256), quant, &slot) != 0);
                 const char * sr = getenv("WHISPER_AMD_SINGLE_ROWS");
-                st.single_via_rows = st.rows_form.enabled() && wa_rows_lds_bytes(dt, 1, std::min(ctx.model.n_cu, 256), ctx.model.wtype != 1 ? 1 : 0, &slot) != 0 &&
-                                     (sr ? sr[0] == '1' : (ctx.model.wtype != 1 && dt > 768));
+                st.single_via_rows = st.rows_form.enabled() && wa_rows_lds_bytes(dt, 1, std::min(ctx.model.n_cu, 256), quant, &slot) != 0 &&
+                                     (rows_q1 || (sr ? sr[0] == '1' : (ctx.model.wtype != 1 && dt > 768)));
             }
             // (the copy stream, events and pinned buffers of the host overlap are created on first use, wa_spec_begin: a state that
             //  only ever runs inside whisper_amd_full_batch keeps ONE stream - extra streams cost the concurrent chunks their overlap)

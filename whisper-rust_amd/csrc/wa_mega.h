@@ -18,6 +18,9 @@ struct wa_mega_layer {          // device-resident table, one entry per decoder 
     // quantised model (Q5_0 / Q8_0 files): the *_w pointers then hold the signed-byte quants in the kernel layout of wa_quant.hip
     // ([row][lane 0..7][block][4]) and these the F32 block scales [row][block]; null for an F16 model
     const float * qkv_d, * out_d, * cq_d, * co_d, * fc1_d, * fc2_d;
+    // Q4_1 / Q5_1 files: the F32 block minimums [row][block], null otherwise.  At the end: only the several-rows kernel for these formats
+    // (wa_rows.hip: k_decode_rows_q1_np*) reads them, every other kernel reads the fields above where they always were.
+    const float * qkv_m, * out_m, * cq_m, * co_m, * fc1_m, * fc2_m;
 };
 
 struct wa_mega_args {

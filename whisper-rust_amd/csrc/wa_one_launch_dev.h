@@ -128,17 +128,43 @@ __device__ __forceinline__ unsigned mq_quant32(float y, float & dq) {
     return q | (dpp_u32<0x101>(q) << 8) | (dpp_u32<0x102>(q) << 16) | (dpp_u32<0x103>(q) << 24);      // row_shl:1..3
 }
 
+// A Q8_1 block (the operand of a Q4_1 / Q5_1 product, wa_quant1.h) carries d = f16(max|x| / 127) and s = f16(d32 * (float) sum of its quants), d32 the
+// F32 quotient before its rounding.  Both are exact F16 values, so the pair is ONE 32-bit word - d low, s high - wherever a Q8_0 block carries its
+// F32 scale: the ninth granule of a block's hand-off and the scale word of an operand row in LDS.  An s beyond the F16 range is the pair's infinity.
+__device__ __forceinline__ unsigned mq_pack_ds(float d, float s) { return (unsigned) f2h(d) | ((unsigned) f2h(s) << 16); }
+__device__ __forceinline__ float mq_ds_d(unsigned w) { return h2f((wa_f16) (w & 0xffffu)); }
+__device__ __forceinline__ float mq_ds_s(unsigned w) { return h2f((wa_f16) (w >> 16)); }
+
+// quantize_row_q8_1 of a block held as for mq_quant32: the same quad, and in ds the block's {d, s} pair.  The integer sum is exact: a DPP reduction
+// beside the maximum's (as wa_q8_store).  All lanes take part.
+__device__ __forceinline__ unsigned mq_quant32_q1(float y, unsigned & ds) {
+    float a = fabsf(y);
+    a = fmaxf(a, dpp_f32<0x128>(a)); a = fmaxf(a, dpp_f32<0x124>(a)); a = fmaxf(a, dpp_f32<0x122>(a)); a = fmaxf(a, dpp_f32<0x121>(a));
+    a = fmaxf(a, __shfl_xor(a, 16, 32));
+    const float id = a != 0.0f ? 127.f / a : 0.0f;
+    const float d32 = a / 127.f;
+    const int qi = (int) rintf(y * id);
+    int t = qi;
+    t += __builtin_amdgcn_update_dpp(0, t, 0x128, 0xf, 0xf, true); t += __builtin_amdgcn_update_dpp(0, t, 0x124, 0xf, 0xf, true);
+    t += __builtin_amdgcn_update_dpp(0, t, 0x122, 0xf, 0xf, true); t += __builtin_amdgcn_update_dpp(0, t, 0x121, 0xf, 0xf, true);
+    t += __shfl_xor(t, 16, 32);
+    ds = mq_pack_ds(d32, d32 * (float) t);
+    const unsigned q = (unsigned) qi & 0xffu;
+    return q | (dpp_u32<0x101>(q) << 8) | (dpp_u32<0x102>(q) << 16) | (dpp_u32<0x103>(q) << 24);      // row_shl:1..3
+}
+
 // Threads 0..63 publish a head's 64 attention outputs (y = output tid of head h) into the row's run of `edge`: as 32 packed-F16 granules,
 // or - Q: they are two Q8_0 blocks of the out-projection's operand - quantised HERE, once, instead of by every consumer: a block leaves as
-// 8 quads + its scale (9 granules instead of 32 F32 values).
-template <bool Q>
+// 8 quads + its scale (9 granules instead of 32 F32 values).  Q1: Q8_1 blocks, the ninth granule is the {d, s} pair.
+template <bool Q, bool Q1 = false>
 __device__ __forceinline__ void mo_attn_publish(float y, gu64 * edge, int h, unsigned seq, int tid) {
     if constexpr (Q) {
-        float dq;
-        const unsigned w = mq_quant32(y, dq);
+        unsigned w, sw;
+        if constexpr (Q1) w = mq_quant32_q1(y, sw);
+        else { float dq; w = mq_quant32(y, dq); sw = __float_as_uint(dq); }
         gu64 * eb = edge + (size_t) (2 * h + (tid >> 5)) * 9;
         if ((tid & 3) == 0) gr_store(eb + ((tid & 31) >> 2), seq, w);
-        if ((tid & 31) == 0) gr_store(eb + 8, seq, __float_as_uint(dq));
+        if ((tid & 31) == 0) gr_store(eb + 8, seq, sw);
     } else {
         const unsigned hv = (unsigned) f2h(y);
         const unsigned hi = dpp_u32<0x101>(hv);          // row_shl:1: lane i reads lane i + 1

@@ -11,6 +11,12 @@
 //     is off the vector-memory queues of the waves that poll hand-offs, and the products read weights AND activations from LDS;
 //   * LayerNorm is one wave per token row (no cross-wave reductions);
 //   * hand-offs are the 8-byte {tag, value} granules of wa_mega.hip.
+// Three kernels per LayerNorm width, one per weight format family (wa_rows_args::quant), each with its own code and registers:
+//   k_decode_rows_np*     F16 weights, F16 operand rows;
+//   k_decode_rows_q_np*   Q5_0 / Q8_0 weights (quants + block scales), operand rows quantised to Q8_0, blocks handed over as 8 quads + scale;
+//   k_decode_rows_q1_np*  Q4_1 / Q5_1 weights (quants + block scales + block minimums), operand rows quantised to Q8_1: the word that holds a
+//                         Q8_0 block's F32 scale holds the F16 pair {d, s} instead, in LDS and in the ninth granule alike, and every product
+//                         adds the block-ordered chain of m_w * s_x after the lane chains (wa_quant1.h).  Opt-in: WHISPER_AMD_ROWS_Q1=1, 1..8 rows.
 // Arithmetic is the reference order throughout (same chains, trees, certified F64 sums as wa_exact.hip): logits are bit-identical to
 // the launch sequence, which stays as the fallback.
 #pragma once
@@ -41,7 +47,8 @@ struct wa_rows_args {
     const wa_mega_layer * layers; int n_layer, d, n_head, n_vocab; float eps;
     double rn_d;
     const wa_f16 * te; const float * pe; const float * lnf_w, * lnf_b; const wa_f16 * gelu;
-    const float * te_d; int quant;
+    const float * te_d; int quant;                      // quant: 0 F16 weights, 1 Q5_0 / Q8_0 (Q8_0 operand rows), 2 Q4_1 / Q5_1 (Q8_1 operand rows, block minimums)
+    const float * te_m;                                 // quant == 2: block minimums of the token embedding (the layers' are in wa_mega_layer)
     unsigned long long kv_layer_stride, cross_layer_stride;
     int cross_tpad, T;
     unsigned long long * granules; int row_gr;          // [layer][8][B][row_gr] hand-off granules (row_gr = 2 d)

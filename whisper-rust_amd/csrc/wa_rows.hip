@@ -203,10 +203,64 @@ __device__ __forceinline__ void mb_dotq8(const unsigned char * wq, const unsigne
         res[j] = v + dpp_f32<0x101>(v);
     }
 }
-// product tasks of a quantised chunk: the slot holds the rows' quants (row stride K + MB_PAD), then - `soff` bytes in - their block scales
-template <int BC, typename EPI>
+// lane 0 of an 8-lane group reads lane m's value (m = 0..7, a constant once the caller's loop is unrolled): row_shl:m
+__device__ __forceinline__ float mb_from_lane(float v, int m) {
+    switch (m) {
+        case 1: return dpp_f32<0x101>(v); case 2: return dpp_f32<0x102>(v); case 3: return dpp_f32<0x103>(v); case 4: return dpp_f32<0x104>(v);
+        case 5: return dpp_f32<0x105>(v); case 6: return dpp_f32<0x106>(v); case 7: return dpp_f32<0x107>(v); default: return v;
+    }
+}
+// The same for a model whose blocks carry a minimum (Q4_1 / Q5_1 files; wa_quant1.h: ggml_vec_dot_q5_1_q8_1).  The weight row gains its block minimums
+// `wm` (F32, as the scales); the operand rows are Q8_1: the word where a Q8_0 row holds its F32 scale is the {d, s} pair (mq_pack_ds), read with the
+// same 16-byte pattern.  The lane chain is the one above.  The minimum chain  summs = summs + (m_w * s_x)  - a multiplication, then an addition,
+// block after block - is ONE scalar chain per (weight row, token row): lane u of the group runs the chain of token row b0 + u, picking that row's
+// pair out of the words every lane has loaded for the lane chains anyway (BC - 1 selects; no second LDS read, one accumulator instead of BC), and
+// lane 0 takes chain j from lane j by one DPP move.  Lanes u >= BC repeat token row b0's chain; nobody reads it.
+typedef unsigned mq_u4 __attribute__((ext_vector_type(4)));
+template <int BC>
+__device__ __forceinline__ void mb_dotq8_q1(const unsigned char * wq, const unsigned char * wd, const unsigned char * wm, const unsigned char * xop, size_t op_bytes,
+                                            int u, int nb, int b0, int B, float (&res)[BC]) {
+    float acc[BC], summs = 0.0f;
+    const unsigned char * xq[BC], * xd[BC];
+#pragma unroll
+    for (int j = 0; j < BC; ++j) {
+        acc[j] = 0.0f;
+        const unsigned char * r = xop + (size_t) (b0 + j < B ? b0 + j : B - 1) * op_bytes;
+        xq[j] = r + (size_t) u * mq_ld(nb) * 4; xd[j] = r + (size_t) 32 * mq_ld(nb);
+    }
+#pragma unroll 2
+    for (int c = 0; c < (nb >> 2); ++c) {
+        const mq_i4 w = *(const mq_i4 *) (wq + 16 * c);
+        const mq_f4 sd = *(const mq_f4 *) (wd + 16 * c);
+        const mq_f4 mw = *(const mq_f4 *) (wm + 16 * c);
+        mq_u4 mine;
+#pragma unroll
+        for (int j = 0; j < BC; ++j) {
+            const mq_i4 x = *(const mq_i4 *) (xq[j] + 16 * c);
+            const mq_u4 ds = *(const mq_u4 *) (xd[j] + 16 * c);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                acc[j] = fmaf(sd[e] * mq_ds_d(ds[e]), (float) __builtin_amdgcn_sdot4(w[e], x[e], 0, false), acc[j]);
+                mine[e] = (j == 0 || u == j) ? ds[e] : mine[e];
+            }
+        }
+#pragma unroll
+        for (int e = 0; e < 4; ++e) { const float p = mw[e] * mq_ds_s(mine[e]); summs = summs + p; }
+    }
+#pragma unroll
+    for (int j = 0; j < BC; ++j) {
+        float v = acc[j];
+        v = v + dpp_f32<0x104>(v);          // row_shl:4  acc[l] + acc[l+4]
+        v = v + dpp_f32<0x102>(v);
+        v = v + dpp_f32<0x101>(v);          // hsum_float_8
+        res[j] = v + mb_from_lane(summs, j);
+    }
+}
+// product tasks of a quantised chunk: the slot holds the rows' quants (row stride K + MB_PAD), then - `soff` bytes in - their block scales and - Q1,
+// `moff` bytes in - their block minimums
+template <int BC, bool Q1 = false, typename EPI>
 __device__ __forceinline__ void mb_products_q(const unsigned char * slot, int soff, int Rc, int row_base, int N, const float * bias_l, const float * scale_l,
-                                              const unsigned char * xop, size_t op_bytes, int K, int B, int wave, int lane, EPI epi) {
+                                              const unsigned char * xop, size_t op_bytes, int K, int B, int wave, int lane, EPI epi, int moff = 0) {
     const int nb = K >> 5, stride_q = K + MB_PAD, stride_s = 4 * nb + MB_PAD;
     const int groups = (Rc + 7) >> 3, nsub = (B + BC - 1) / BC, per = (B + nsub - 1) / nsub, ntasks = groups * nsub;
     const int u = lane & 7;
@@ -216,7 +270,8 @@ __device__ __forceinline__ void mb_products_q(const unsigned char * slot, int so
         const bool has = ri < Rc && row_base + ri < N && u == 0;
         const float bv = bias_l[ri < 64 ? ri : 63], sv = scale_l ? scale_l[ri < 64 ? ri : 63] : 1.0f;
         float res[BC];
-        mb_dotq8<BC>(slot + (size_t) rr * stride_q + (size_t) u * nb * 4, slot + soff + (size_t) rr * stride_s, xop, op_bytes, u, nb, b0, B, res);
+        if constexpr (Q1) mb_dotq8_q1<BC>(slot + (size_t) rr * stride_q + (size_t) u * nb * 4, slot + soff + (size_t) rr * stride_s, slot + moff + (size_t) rr * stride_s, xop, op_bytes, u, nb, b0, B, res);
+        else mb_dotq8<BC>(slot + (size_t) rr * stride_q + (size_t) u * nb * 4, slot + soff + (size_t) rr * stride_s, xop, op_bytes, u, nb, b0, B, res);
         epi(res, b0, b1, row_base + ri, has, bv, sv);
     }
 }
@@ -246,7 +301,7 @@ __device__ __forceinline__ double mb_seq_sum(const float (&xv)[NP], int d, bool 
     }
     return t;
 }
-template <int NP, bool Q = false>         // Q: the normalised row leaves as Q8_0 (the next product's operand), not as F16
+template <int NP, bool Q = false, bool Q1 = false>       // Q: the normalised row leaves as Q8_0 (the next product's operand), not as F16; Q1: as Q8_1
 __device__ __forceinline__ void mb_ln_row(mb_kargs A, mo_ctl & c, gu64 * edge_row /* null: embeddings */, const float * lnp /* LDS: gamma | beta, each d floats in whole KB */, const float * gw_g, const float * gb_g /* global, when non-null */,
                                           int b, int lane_, wa_f16 * dst, float * xres_b, int row_d, int r_d, unsigned code, int token = 0, bool tw = false, int tslot = 0) {
     // (nothing derived from the lane index may live across calls: hoisted out of the layer loop the per-element LDS addresses went to scratch, and every
@@ -270,10 +325,13 @@ __device__ __forceinline__ void mb_ln_row(mb_kargs A, mo_ctl & c, gu64 * edge_ro
             const int nb = d >> 5;
             const GAS int8_t * tq = (const GAS int8_t *) A->te + (size_t) token * 8 * nb * 4;
             const gcf td = (gcf) A->te_d + (size_t) token * nb;
+            const gcf tm = (gcf) A->te_m + (size_t) token * nb;
 #pragma unroll
             for (int k = 0; k < NP; ++k) {
                 const int i = lane + 64 * k, ic = i < d ? i : d - 1, bb = ic >> 5, el = ic & 31;
-                const float e = (float) (int) tq[(((size_t) (el >> 2)) * nb + bb) * 4 + (el & 3)] * td[bb] + pe[ic];
+                float e = (float) (int) tq[(((size_t) (el >> 2)) * nb + bb) * 4 + (el & 3)] * td[bb];
+                if constexpr (Q1) e = e + tm[bb];           // dequantize_row_q5_1: q * d, then + m (two roundings)
+                e = e + pe[ic];
                 xv[k] = i < d ? e : 0.0f;
             }
         }
@@ -335,11 +393,12 @@ __device__ __forceinline__ void mb_ln_row(mb_kargs A, mo_ctl & c, gu64 * edge_ro
         y = y + bet[k];
         if constexpr (!Q) { if (i < d) dst[i] = f2h(y); }
         else {                  // a half-wave holds one 32-element block (d % 64 == 0: every block of k < d / 64 is whole)
-            float dq;
-            const unsigned w = mq_quant32(i < d ? y : 0.0f, dq);
+            unsigned w, sw;
+            if constexpr (Q1) w = mq_quant32_q1(i < d ? y : 0.0f, sw);
+            else { float dq; w = mq_quant32(i < d ? y : 0.0f, dq); sw = __float_as_uint(dq); }
             const int nb = d >> 5, blk = (lane >> 5) + 2 * k;
             if (i < d && (lane & 3) == 0) mq_quads((unsigned char *) dst, nb, (lane & 31) >> 2)[blk] = w;
-            if (i < d && (lane & 31) == 0) mq_scales((unsigned char *) dst, nb)[blk] = dq;
+            if (i < d && (lane & 31) == 0) ((unsigned *) mq_scales((unsigned char *) dst, nb))[blk] = sw;
         }
     }
 }
@@ -377,7 +436,7 @@ __device__ __forceinline__ unsigned mb_pack_h2(unsigned h) { return (h & 0xffffu
 
 // the head's 64 outputs from the 32 chain sums + the leftover cells in F64, index order (vec.cpp:221-223), by threads 0..63; published packed
 // (Q: as two Q8_0 blocks)
-template <bool Q = false>
+template <bool Q = false, bool Q1 = false>
 __device__ __forceinline__ void mb_attn_finish(const float * part, const wa_f16 * vleft /* [nl][64] LDS */, const wa_f16 * pleft /* [nl] */, int nl,
                                                gu64 * edge_row, int h, unsigned seq, int tid) {
     if (tid < 64) {
@@ -386,7 +445,7 @@ __device__ __forceinline__ void mb_attn_finish(const float * part, const wa_f16 
         for (int r = 0; r < 32; ++r) s32[r] = part[r * 64 + tid];
         double sumf = (double) wa_tree32(s32);
         for (int cc = 0; cc < nl; ++cc) sumf += (double) (h2f(vleft[cc * 64 + tid]) * h2f(pleft[cc]));
-        mo_attn_publish<Q>((float) sumf, edge_row, h, seq, tid);
+        mo_attn_publish<Q, Q1>((float) sumf, edge_row, h, seq, tid);
     }
 }
 
@@ -395,7 +454,7 @@ __device__ __forceinline__ void mb_attn_finish(const float * part, const wa_f16 
 // tokens come from the row's own cells in HBM; the cells written by THIS launch - the row's own and those of every other row that shares
 // its cache (earlier tokens of a small batch; other beams, which the mask hides) - arrive as granules, like the query.
 // -------------------------------------------------------------------------------------------------
-template <bool Q = false>
+template <bool Q = false, bool Q1 = false>
 __device__ __forceinline__ void mb_unit_self(mb_kargs A, mo_ctl & c, unsigned char * area, int l, int b, int h, int tid, bool tw = false) {
 #define MB_TS(k) mb_trace(A, tw, 4096 + l * 16 + (k))
     MB_TS(0);
@@ -587,7 +646,7 @@ __device__ __forceinline__ void mb_unit_self(mb_kargs A, mo_ctl & c, unsigned ch
     }
     MB_TS(7);
     wa_barrier_lds();
-    mb_attn_finish<Q>(part, vleft, p16 + np, nl, mb_edge(A, l, E_AO) + (size_t) b * A->row_gr, h, c.seq, tid);
+    mb_attn_finish<Q, Q1>(part, vleft, p16 + np, nl, mb_edge(A, l, E_AO) + (size_t) b * A->row_gr, h, c.seq, tid);
     MB_TS(8);
     wa_barrier_lds();
     MB_TS(9);
@@ -629,7 +688,7 @@ __device__ __forceinline__ void mb_cross_load(mb_kargs A, int l, int b, int h, i
         }
 }
 
-template <bool Q, int P>
+template <bool Q, int P, bool Q1 = false>
 __device__ __forceinline__ void mb_unit_cross(mb_kargs A, mo_ctl & c, unsigned char * area, int l, int b, int h, int w, int tid, bool tw, const mb_cross_regs<P> & R) {
     constexpr int NCH = 32 / P, CPW = 4 / P, NK = NCH * MB_CSTEPS;          // chains of this part, chains per wave, local cell slots
     const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -843,7 +902,7 @@ __device__ __forceinline__ void mb_unit_cross(mb_kargs A, mo_ctl & c, unsigned c
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int cc = 0; cc < 32; ++cc) sumf += dv[cc];
-            mo_attn_publish<Q>((float) sumf, mb_edge(A, l, E_AO2) + (size_t) b * A->row_gr, h, seq, tid);
+            mo_attn_publish<Q, Q1>((float) sumf, mb_edge(A, l, E_AO2) + (size_t) b * A->row_gr, h, seq, tid);
         }
         MB_TC(10);
     }
@@ -873,11 +932,22 @@ __device__ __forceinline__ void mb_logits_out(mb_kargs A, const float * lg, int 
 }
 
 // the first piece of a wave's first embedding rows, asked for BEFORE the final LayerNorm waits for its row (piece 0 of mb_logits / mb_logits_q)
-__device__ __forceinline__ void mb_te_first(mb_kargs A, bool quant, unsigned (&buf)[48], int lane, int wave) {
+__device__ __forceinline__ void mb_te_first(mb_kargs A, bool quant, bool q1, unsigned (&buf)[48], int lane, int wave) {
     const int d = A->d, ns = d >> 5, n_vocab = A->n_vocab, u = lane & 7;
     int g1_; const int g0_ = mb_share(n_vocab, &g1_);
     const int row = (g0_ + wave) * 8 + (lane >> 3), rc = row < n_vocab ? row : 0;
-    if (!quant) {
+    if (q1) {                   // pieces of 16 blocks: quads | scales | minimums (mb_logits_q)
+        const GAS unsigned * wl = (const GAS unsigned *) A->te + ((size_t) rc * 8 + u) * ns;
+        const GAS unsigned * dl = (const GAS unsigned *) A->te_d + (size_t) rc * ns, * ml = (const GAS unsigned *) A->te_m + (size_t) rc * ns;
+#pragma unroll
+        for (int k4 = 0; k4 < 4; ++k4) {
+            const int bc = 4 * k4 < ns ? 4 * k4 : ns - 4;
+            const u32x4 q = *(const GAS u32x4 *) (wl + bc), sd = *(const GAS u32x4 *) (dl + bc), mn = *(const GAS u32x4 *) (ml + bc);
+            buf[4 * k4] = q.x; buf[4 * k4 + 1] = q.y; buf[4 * k4 + 2] = q.z; buf[4 * k4 + 3] = q.w;
+            buf[16 + 4 * k4] = sd.x; buf[16 + 4 * k4 + 1] = sd.y; buf[16 + 4 * k4 + 2] = sd.z; buf[16 + 4 * k4 + 3] = sd.w;
+            buf[32 + 4 * k4] = mn.x; buf[32 + 4 * k4 + 1] = mn.y; buf[32 + 4 * k4 + 2] = mn.z; buf[32 + 4 * k4 + 3] = mn.w;
+        }
+    } else if (!quant) {
         const gch wrow = (gch) A->te + (size_t) rc * d + 4 * u;
 #pragma unroll
         for (int k = 0; k < 24; ++k) { const u32x2 t = *(const GAS u32x2 *) (wrow + (size_t) (k < ns ? k : ns - 1) * 32); buf[2 * k] = t.x; buf[2 * k + 1] = t.y; }
@@ -1028,6 +1098,78 @@ __device__ __forceinline__ void mb_logits_q(mb_kargs A, const unsigned char * xo
     }
 }
 
+// the same for a token embedding with block minimums (Q4_1 / Q5_1): a piece is 16 blocks of quads | scales | minimums - the same 48 registers per
+// buffer as the 24 blocks of two arrays above, 72 would have gone to scratch - and the token rows are Q8_1 (mb_dotq8_q1).  The minimum chain of
+// logits row m runs in lane m of the weight row's group (BT <= 8 = the group's lanes), which reads its row's pair from LDS itself; the chain
+// goes on across the pieces of a row and is added to hsum_float_8 last.
+template <int BT>
+__device__ __forceinline__ void mb_logits_q1(mb_kargs A, const unsigned char * xop, size_t op_bytes, int B, int lane, int wave, unsigned (&pfa)[48], float * lg) {
+    const int d = A->d, nb = d >> 5, nbat = (nb + 15) / 16, n_vocab = A->n_vocab;
+    const int u = lane & 7;
+    GAS float * logits = (GAS float *) A->logits;
+    unsigned pfb[48];
+    int g1; const int g0 = mb_share(n_vocab, &g1);
+    auto grp = [&](int j) { return g0 + wave + MB_NW * j; };
+    int n_items = 0;
+    for (int j = 0; grp(j) < g1; ++j) n_items += nbat;
+    auto load = [&](int it, unsigned (&buf)[48]) {
+        const int j = it / nbat, bt = it - j * nbat, row = grp(j) * 8 + (lane >> 3), rc = row < n_vocab ? row : 0;
+        const GAS unsigned * wl = (const GAS unsigned *) A->te + ((size_t) rc * 8 + u) * nb;
+        const GAS unsigned * dl = (const GAS unsigned *) A->te_d + (size_t) rc * nb, * ml = (const GAS unsigned *) A->te_m + (size_t) rc * nb;
+#pragma unroll
+        for (int k4 = 0; k4 < 4; ++k4) {         // (16-byte loads: mb_te_first)
+            const int bb = bt * 16 + 4 * k4, bc = bb < nb ? bb : nb - 4;
+            const u32x4 q = *(const GAS u32x4 *) (wl + bc), sd = *(const GAS u32x4 *) (dl + bc), mn = *(const GAS u32x4 *) (ml + bc);
+            buf[4 * k4] = q.x; buf[4 * k4 + 1] = q.y; buf[4 * k4 + 2] = q.z; buf[4 * k4 + 3] = q.w;
+            buf[16 + 4 * k4] = sd.x; buf[16 + 4 * k4 + 1] = sd.y; buf[16 + 4 * k4 + 2] = sd.z; buf[16 + 4 * k4 + 3] = sd.w;
+            buf[32 + 4 * k4] = mn.x; buf[32 + 4 * k4 + 1] = mn.y; buf[32 + 4 * k4 + 2] = mn.z; buf[32 + 4 * k4 + 3] = mn.w;
+        }
+    };
+    float acc[BT], summs = 0.0f;
+    const unsigned char * xq[BT], * xd[BT];
+#pragma unroll
+    for (int m = 0; m < BT; ++m) { const unsigned char * r = xop + (size_t) (m < B ? m : B - 1) * op_bytes; xq[m] = r + (size_t) u * mq_ld(nb) * 4; xd[m] = r + (size_t) 32 * mq_ld(nb); }
+    const unsigned * xs_u = (const unsigned *) (xop + (size_t) (u < B ? u : B - 1) * op_bytes + (size_t) 32 * mq_ld(nb));      // the pairs of this lane's chain: logits row u
+    auto one = [&](int it, unsigned (&buf)[48]) {
+        const int j = it / nbat, bt = it - j * nbat;
+        if (bt == 0) {
+            summs = 0.0f;
+#pragma unroll
+            for (int m = 0; m < BT; ++m) acc[m] = 0.0f;
+        }
+#pragma unroll
+        for (int k = 0; k < 16; ++k) {
+            const int bb = bt * 16 + k;
+            if (bb < nb) {
+#pragma unroll
+                for (int m = 0; m < BT; ++m)
+                    acc[m] = fmaf(__uint_as_float(buf[16 + k]) * mq_ds_d(((const unsigned *) xd[m])[bb]), (float) __builtin_amdgcn_sdot4((int) buf[k], ((const int *) xq[m])[bb], 0, false), acc[m]);
+                const float p = __uint_as_float(buf[32 + k]) * mq_ds_s(xs_u[bb]);
+                summs = summs + p;
+            }
+        }
+        if (bt == nbat - 1) {
+            const int row = grp(j) * 8 + (lane >> 3);
+#pragma unroll
+            for (int m = 0; m < BT; ++m) {
+                float v = acc[m];
+                v = v + dpp_f32<0x104>(v); v = v + dpp_f32<0x102>(v); v = v + dpp_f32<0x101>(v);
+                v = v + mb_from_lane(summs, m);
+                if (u == 0 && j < 4) lg[m * 256 + (8 * j + wave) * 8 + (lane >> 3)] = v;
+                else if (u == 0 && row < n_vocab && m < B) logits[(size_t) m * n_vocab + row] = v;
+            }
+        }
+    };
+    // (piece 0 is on its way since before the final LayerNorm: mb_te_first)
+    for (int it = 0; it < n_items; it += 2) {
+        if (it + 1 < n_items) load(it + 1, pfb);
+        one(it, pfa);
+        if (it + 1 >= n_items) break;
+        if (it + 2 < n_items) load(it + 2, pfa);
+        one(it + 1, pfb);
+    }
+}
+
 // -------------------------------------------------------------------------------------------------
 // next-token prediction per row (the protocol and its records: wa_one_launch_dev.h).  mb_pick: one wave, the row's token and the sampling state
 // after it -> pk (MO_PK_*).
@@ -1062,9 +1204,18 @@ __device__ __forceinline__ void mb_record(mb_kargs A, int br, const float * lg_m
 // -------------------------------------------------------------------------------------------------
 // the kernel
 // -------------------------------------------------------------------------------------------------
-struct mb_phase { const wa_f16 * W; const float * D; const float * bias; const float * scale; int N, K, r, rc, nck, soff; };
+struct mb_phase { const wa_f16 * W; const float * D; const float * M; const float * bias; const float * scale; int N, K, r, rc, nck, soff, moff; };
 
-template <int NP, bool Q>
+// (Q4_1 / Q5_1) a slot's image of rc weight rows of length K: quants | block scales | block minimums, each region in whole KB - an LDS-DMA instruction
+// writes a KB, so a region's last piece may run that far past its rows -, then the KB of bias and column scale.  mq1_soff / mq1_moff: where the second
+// and third region start; mq1_slot_need: the bytes a slot must have.  The kernel and wa_rows_lds_bytes share this rule exactly: at d = 1280 the
+// eight rows of the second MLP product fill a slot to the last KB.
+__host__ __device__ __forceinline__ int mq1_soff(int rc, int K) { return (rc * (K + MB_PAD) + 1023) & ~1023; }
+__host__ __device__ __forceinline__ int mq1_moff(int rc, int K) { return mq1_soff(rc, K) + ((rc * ((K >> 3) + MB_PAD) + 1023) & ~1023); }
+__host__ __device__ __forceinline__ int mq1_slot_need(int rc, int K) { return mq1_moff(rc, K) + ((rc * ((K >> 3) + MB_PAD) + 1023) & ~1023) + 1024; }
+
+// Q: a quantised model (Q5_0 / Q8_0); Q1 (with Q): its blocks carry a minimum (Q4_1 / Q5_1) and every operand row is Q8_1
+template <int NP, bool Q, bool Q1 = false>
 __device__ __forceinline__ void mb_body(mb_kargs A_) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const mb_kargs A = mo_uniform(A_);
@@ -1112,10 +1263,20 @@ __device__ __forceinline__ void mb_body(mb_kargs A_) {
         else if (p == 4) { ph.W = Y.fc1_w; ph.D = Y.fc1_d; ph.bias = Y.fc1_b; ph.N = d4; ph.K = d; ph.r = r_ff; }
         else             { ph.W = Y.fc2_w; ph.D = Y.fc2_d; ph.bias = Y.fc2_b; ph.N = d; ph.K = d4; ph.r = r_d; }
         const int gp = (!Q && p == 5) ? 4 : 8;
-        const int stride = Q ? ph.K + MB_PAD + (ph.K >> 3) + MB_PAD : 2 * ph.K + MB_PAD;          // LDS bytes per weight row (quantised: quants + block scales)
-        int rc = ((slot_bytes - (Q ? 3072 : 1024)) / stride) / gp * gp;
         const int rmax = (ph.r + gp - 1) / gp * gp;
-        ph.rc = rc > rmax ? rmax : rc;
+        ph.M = nullptr; ph.moff = 0;
+        if constexpr (Q1) {     // the most octets of rows whose three regions fit the slot (wa_rows_lds_bytes admits a slot that holds one)
+            ph.M = p == 0 ? Y.qkv_m : p == 1 ? Y.out_m : p == 2 ? Y.cq_m : p == 3 ? Y.co_m : p == 4 ? Y.fc1_m : Y.fc2_m;
+            int rc = ((slot_bytes - 1024) / (ph.K + MB_PAD + 2 * ((ph.K >> 3) + MB_PAD))) / 8 * 8;
+            rc = rc > rmax ? rmax : rc;
+            while (rc > 8 && mq1_slot_need(rc, ph.K) > slot_bytes) rc -= 8;
+            ph.rc = rc;
+            ph.moff = mq1_moff(rc, ph.K);
+        } else {
+            const int stride = Q ? ph.K + MB_PAD + (ph.K >> 3) + MB_PAD : 2 * ph.K + MB_PAD;      // LDS bytes per weight row (quantised: quants + block scales)
+            int rc = ((slot_bytes - (Q ? 3072 : 1024)) / stride) / gp * gp;
+            ph.rc = rc > rmax ? rmax : rc;
+        }
         ph.nck = (ph.r + ph.rc - 1) / ph.rc;
         ph.soff = (ph.rc * (ph.K + MB_PAD) + 1023) & ~1023;                                       // (quantised) where the scales' image starts
         return ph;
@@ -1130,6 +1291,7 @@ __device__ __forceinline__ void mb_body(mb_kargs A_) {
         if constexpr (Q) {
             mb_dma_rows((const GAS unsigned char *) ph.W, ph.K, row0, R, ph.N, slot, lane);
             mb_dma_rows((const GAS unsigned char *) ph.D, ph.K >> 3, row0, R, ph.N, slot + ph.soff, lane);
+            if constexpr (Q1) mb_dma_rows((const GAS unsigned char *) ph.M, ph.K >> 3, row0, R, ph.N, slot + ph.moff, lane);
         } else mb_dma_rows((const GAS unsigned char *) ph.W, 2 * ph.K, row0, R, ph.N, slot, lane);
         mb_dma_f32(ph.bias, row0, ph.N, (float *) (slot + slot_bytes - 512), lane);
         if (ph.scale) mb_dma_f32(ph.scale, row0, ph.N, (float *) (slot + slot_bytes - 256), lane);
@@ -1174,9 +1336,9 @@ __device__ __forceinline__ void mb_body(mb_kargs A_) {
         const int groups = (Rc + 7) >> 3;
         const int bc = groups * B <= MB_NCW ? 1 : groups * ((B + 1) >> 1) <= MB_NCW ? 2 : 3;
         if constexpr (Q) {
-            if (bc == 1)      mb_products_q<1>(slot, ph.soff, Rc, row_base, ph.N, bias_l, scale_l, xop, opb, ph.K, B, wave, lane, epi);
-            else if (bc == 2) mb_products_q<2>(slot, ph.soff, Rc, row_base, ph.N, bias_l, scale_l, xop, opb, ph.K, B, wave, lane, epi);
-            else              mb_products_q<3>(slot, ph.soff, Rc, row_base, ph.N, bias_l, scale_l, xop, opb, ph.K, B, wave, lane, epi);
+            if (bc == 1)      mb_products_q<1, Q1>(slot, ph.soff, Rc, row_base, ph.N, bias_l, scale_l, xop, opb, ph.K, B, wave, lane, epi, ph.moff);
+            else if (bc == 2) mb_products_q<2, Q1>(slot, ph.soff, Rc, row_base, ph.N, bias_l, scale_l, xop, opb, ph.K, B, wave, lane, epi, ph.moff);
+            else              mb_products_q<3, Q1>(slot, ph.soff, Rc, row_base, ph.N, bias_l, scale_l, xop, opb, ph.K, B, wave, lane, epi, ph.moff);
         } else {
             if (bc == 1)      mb_products<8, 1>(slot, 2 * ph.K + MB_PAD, Rc, row_base, ph.N, bias_l, scale_l, (const wa_f16 *) xop, (int) (opb >> 1), ph.K, B, wave, lane, epi);
             else if (bc == 2) mb_products<8, 2>(slot, 2 * ph.K + MB_PAD, Rc, row_base, ph.N, bias_l, scale_l, (const wa_f16 *) xop, (int) (opb >> 1), ph.K, B, wave, lane, epi);
@@ -1213,11 +1375,11 @@ __device__ __forceinline__ void mb_body(mb_kargs A_) {
         // quantised kernels keep one instance: they are short of registers (99-198 spilled VGPRs) and a second copy cost more than it won (large-v3-q5_0: 3.22 -> 3.65 ms).
         if (wave < B) {
             if constexpr (Q) {
-                mb_ln_row<NP, Q>(A, c, l == 0 ? nullptr : mb_edge(A, l - 1, E_X3) + (size_t) wave * RG, lnp, l == 0 ? Y.ln1_w : nullptr, l == 0 ? Y.ln1_b : nullptr,
+                mb_ln_row<NP, Q, Q1>(A, c, l == 0 ? nullptr : mb_edge(A, l - 1, E_X3) + (size_t) wave * RG, lnp, l == 0 ? Y.ln1_w : nullptr, l == 0 ? Y.ln1_b : nullptr,
                                  wave, lane, (wa_f16 *) (xinB + (size_t) wave * opB), xres + wave * 8, row_d, r_d, 100u + l, pk[8 * wave], tw, l * 32 + 29);
             } else {
-                if (l == 0) mb_ln_row<NP, Q>(A, c, nullptr, lnp, Y.ln1_w, Y.ln1_b, wave, lane, (wa_f16 *) (xinB + (size_t) wave * opB), xres + wave * 8, row_d, r_d, 100u, pk[8 * wave]);
-                else        mb_ln_row<NP, Q>(A, c, mb_edge(A, l - 1, E_X3) + (size_t) wave * RG, lnp, nullptr, nullptr, wave, lane, (wa_f16 *) (xinB + (size_t) wave * opB), nullptr, 0, 0, 100u + l, 0, tw, l * 32 + 29);
+                if (l == 0) mb_ln_row<NP, Q, Q1>(A, c, nullptr, lnp, Y.ln1_w, Y.ln1_b, wave, lane, (wa_f16 *) (xinB + (size_t) wave * opB), xres + wave * 8, row_d, r_d, 100u, pk[8 * wave]);
+                else        mb_ln_row<NP, Q, Q1>(A, c, mb_edge(A, l - 1, E_X3) + (size_t) wave * RG, lnp, nullptr, nullptr, wave, lane, (wa_f16 *) (xinB + (size_t) wave * opB), nullptr, 0, 0, 100u + l, 0, tw, l * 32 + 29);
             }
         }
         MB_T(1);
@@ -1244,7 +1406,7 @@ __device__ __forceinline__ void mb_body(mb_kargs A_) {
         MB_T(2);
         // ---------------- P2: self-attention ----------------
         MB_CHAOS_WG(20u); MB_CHAOS_AT(21u);
-        for (int u = wg; u < B * H; u += nwg) mb_unit_self<Q>(A, c, area, l, u / H, u % H, tid, tw);
+        for (int u = wg; u < B * H; u += nwg) mb_unit_self<Q, Q1>(A, c, area, l, u / H, u % H, tid, tw);
         MB_T(3);
         // ---------------- P3: out-projection + residual ----------------
         MB_CHAOS_AT(22u);
@@ -1267,7 +1429,7 @@ __device__ __forceinline__ void mb_body(mb_kargs A_) {
         run_phase(l, 1, [&](const mb_phase & ph, const unsigned char * slot, int row_base, int Rc, int) { prod8(ph, slot, row_base, Rc, nullptr, xin, opD, resid_epi(mb_edge(A, l, E_X1))); });
         MB_T(5);
         // ---------------- P4: LayerNorm + cross query ----------------
-        if (wave < B) mb_ln_row<NP, Q>(A, c, mb_edge(A, l, E_X1) + (size_t) wave * RG, lnp, nullptr, nullptr, wave, lane, (wa_f16 *) (xinB + (size_t) wave * opB), nullptr, 0, 0, 300u + l);
+        if (wave < B) mb_ln_row<NP, Q, Q1>(A, c, mb_edge(A, l, E_X1) + (size_t) wave * RG, lnp, nullptr, nullptr, wave, lane, (wa_f16 *) (xinB + (size_t) wave * opB), nullptr, 0, 0, 300u + l);
         MB_T(6);
         run_phase(l, 2, [&](const mb_phase & ph, const unsigned char * slot, int row_base, int Rc, int) {
             gu64 * eq = mb_edge(A, l, E_QC);
@@ -1292,7 +1454,7 @@ __device__ __forceinline__ void mb_body(mb_kargs A_) {
             const int bh = u >> 2;
             mb_cross_regs<4> CR;    // (asked for here: earlier - across the cross-query products - the 72 registers cost those products 2 us and won 0.8)
             mb_cross_load<4>(A, l, bh / H, bh % H, u & 3, tid, CR);
-            mb_unit_cross<Q, 4>(A, c, area, l, bh / H, bh % H, u & 3, tid, tw, CR);
+            mb_unit_cross<Q, 4, Q1>(A, c, area, l, bh / H, bh % H, u & 3, tid, tw, CR);
         }
         MB_T(8);
         // ---------------- P6: out-projection + residual ----------------
@@ -1302,7 +1464,7 @@ __device__ __forceinline__ void mb_body(mb_kargs A_) {
         run_phase(l, 3, [&](const mb_phase & ph, const unsigned char * slot, int row_base, int Rc, int) { prod8(ph, slot, row_base, Rc, nullptr, xin, opD, resid_epi(mb_edge(A, l, E_X2))); });
         MB_T(10);
         // ---------------- P7: LayerNorm + FC1 + GELU ----------------
-        if (wave < B) mb_ln_row<NP, Q>(A, c, mb_edge(A, l, E_X2) + (size_t) wave * RG, lnp, nullptr, nullptr, wave, lane, (wa_f16 *) (xinB + (size_t) wave * opB), nullptr, 0, 0, 500u + l);
+        if (wave < B) mb_ln_row<NP, Q, Q1>(A, c, mb_edge(A, l, E_X2) + (size_t) wave * RG, lnp, nullptr, nullptr, wave, lane, (wa_f16 *) (xinB + (size_t) wave * opB), nullptr, 0, 0, 500u + l);
         MB_T(11);
         run_phase(l, 4, [&](const mb_phase & ph, const unsigned char * slot, int row_base, int Rc, int ck_row) {
             gu64 * eh = mb_edge(A, l, E_HF);
@@ -1330,11 +1492,12 @@ __device__ __forceinline__ void mb_body(mb_kargs A_) {
         if constexpr (Q) {      // this workgroup's block of every token row: quantize_row_q8_0, published as 9 granules (wave b: row b)
             wa_barrier_lds();
             if (wave < B && 32 * wg < d4) {
-                float dq;
-                const unsigned w = mq_quant32(fc1x[wave * 32 + (lane & 31)], dq);
+                unsigned w, sw;
+                if constexpr (Q1) w = mq_quant32_q1(fc1x[wave * 32 + (lane & 31)], sw);
+                else { float dq; w = mq_quant32(fc1x[wave * 32 + (lane & 31)], dq); sw = __float_as_uint(dq); }
                 gu64 * eb = mb_edge(A, l, E_HF) + (size_t) wave * RG + (size_t) wg * 9;
                 if (lane < 32 && (lane & 3) == 0) gr_store(eb + (lane >> 2), seq, w);
-                if (lane == 0) gr_store(eb + 8, seq, __float_as_uint(dq));
+                if (lane == 0) gr_store(eb + 8, seq, sw);
             }
         }
         MB_T(12);
@@ -1346,8 +1509,8 @@ __device__ __forceinline__ void mb_body(mb_kargs A_) {
             const float * bias_l = (const float *) (slot + slot_bytes - 512);
             const int groups = (Rc + (Q ? 7 : 3)) / (Q ? 8 : 4);
             if constexpr (Q) {
-                if (groups * B <= MB_NCW) mb_products_q<1>(slot, ph.soff, Rc, row_base, ph.N, bias_l, nullptr, xin, op4, ph.K, B, wave, lane, resid_epi(mb_edge(A, l, E_X3)));
-                else                      mb_products_q<2>(slot, ph.soff, Rc, row_base, ph.N, bias_l, nullptr, xin, op4, ph.K, B, wave, lane, resid_epi(mb_edge(A, l, E_X3)));
+                if (groups * B <= MB_NCW) mb_products_q<1, Q1>(slot, ph.soff, Rc, row_base, ph.N, bias_l, nullptr, xin, op4, ph.K, B, wave, lane, resid_epi(mb_edge(A, l, E_X3)), ph.moff);
+                else                      mb_products_q<2, Q1>(slot, ph.soff, Rc, row_base, ph.N, bias_l, nullptr, xin, op4, ph.K, B, wave, lane, resid_epi(mb_edge(A, l, E_X3)), ph.moff);
             } else {
                 if (groups * B <= MB_NCW) mb_products<16, 1>(slot, 2 * ph.K + MB_PAD, Rc, row_base, ph.N, bias_l, nullptr, (const wa_f16 *) xin, d4, ph.K, B, wave, lane, resid_epi(mb_edge(A, l, E_X3)));
                 else                      mb_products<16, 2>(slot, 2 * ph.K + MB_PAD, Rc, row_base, ph.N, bias_l, nullptr, (const wa_f16 *) xin, d4, ph.K, B, wave, lane, resid_epi(mb_edge(A, l, E_X3)));
@@ -1358,22 +1521,25 @@ __device__ __forceinline__ void mb_body(mb_kargs A_) {
     // ---------------- final LayerNorm + logits (of the token rows that want them) ----------------
     const int n_out = A->n_out;
     unsigned pf0[48];
-    mb_te_first(A, Q, pf0, lane, wave);
+    mb_te_first(A, Q, Q1, pf0, lane, wave);
     if (wave < n_out) {
         const int br = A->out_row[wave];
         if constexpr (Q) {
-            mb_ln_row<NP, Q>(A, c, L > 0 ? mb_edge(A, L - 1, E_X3) + (size_t) br * RG : nullptr, lnp, L > 0 ? nullptr : A->lnf_w, L > 0 ? nullptr : A->lnf_b, br, lane,
+            mb_ln_row<NP, Q, Q1>(A, c, L > 0 ? mb_edge(A, L - 1, E_X3) + (size_t) br * RG : nullptr, lnp, L > 0 ? nullptr : A->lnf_w, L > 0 ? nullptr : A->lnf_b, br, lane,
                              (wa_f16 *) (xinB + (size_t) wave * opB), nullptr, 0, 0, 3000u, pk[8 * br]);
         } else {
-            if (L > 0) mb_ln_row<NP, Q>(A, c, mb_edge(A, L - 1, E_X3) + (size_t) br * RG, lnp, nullptr, nullptr, br, lane, (wa_f16 *) (xinB + (size_t) wave * opB), nullptr, 0, 0, 3000u);
-            else       mb_ln_row<NP, Q>(A, c, nullptr, lnp, A->lnf_w, A->lnf_b, br, lane, (wa_f16 *) (xinB + (size_t) wave * opB), nullptr, 0, 0, 3000u, pk[8 * br]);      // (a model without layers: tests)
+            if (L > 0) mb_ln_row<NP, Q, Q1>(A, c, mb_edge(A, L - 1, E_X3) + (size_t) br * RG, lnp, nullptr, nullptr, br, lane, (wa_f16 *) (xinB + (size_t) wave * opB), nullptr, 0, 0, 3000u);
+            else       mb_ln_row<NP, Q, Q1>(A, c, nullptr, lnp, A->lnf_w, A->lnf_b, br, lane, (wa_f16 *) (xinB + (size_t) wave * opB), nullptr, 0, 0, 3000u, pk[8 * br]);      // (a model without layers: tests)
         }
     }
     bool want_rec = false;
     for (int m = 0; m < n_out; ++m) want_rec = want_rec || A->rows[A->out_row[m]].smask != nullptr;
     float * lg = (float *) area;            // (the gathered-inputs area holds nothing any more) the workgroup's logits, staged for whole-line stores and the records
     wa_barrier_lds();
-    if constexpr (Q) {
+    if constexpr (Q1) {
+        if (n_out <= 2) mb_logits_q1<2>(A, xinB, opB, n_out, lane, wave, pf0, lg); else if (n_out <= 4) mb_logits_q1<4>(A, xinB, opB, n_out, lane, wave, pf0, lg);
+        else if (n_out <= 5) mb_logits_q1<5>(A, xinB, opB, n_out, lane, wave, pf0, lg); else mb_logits_q1<8>(A, xinB, opB, n_out, lane, wave, pf0, lg);
+    } else if constexpr (Q) {
         if (n_out <= 2) mb_logits_q<2>(A, xinB, opB, n_out, lane, wave, pf0, lg); else if (n_out <= 4) mb_logits_q<4>(A, xinB, opB, n_out, lane, wave, pf0, lg);
         else if (n_out <= 5) mb_logits_q<5>(A, xinB, opB, n_out, lane, wave, pf0, lg); else mb_logits_q<8>(A, xinB, opB, n_out, lane, wave, pf0, lg);
     } else {
@@ -1393,13 +1559,32 @@ __device__ __forceinline__ void mb_body(mb_kargs A_) {
 }
 
 // One kernel per LayerNorm width (elements per lane: 12 for d <= 768, 16 for <= 1024, 20 for <= 1280) and weight format, each in a translation unit
-// of its own (the Makefile compiles this file three times, -DWA_ROWS_NP=12 / 16 / 20): with every width in ONE kernel the register allocation was
+// of its own (the Makefile compiles this file three times, -DWA_ROWS_NP=12 / 16 / 20, and three more for Q4_1 / Q5_1): with every width in ONE kernel the register allocation was
 // the widest variant's for all of them (1525 spilled SGPRs and 32-113 VGPRs against 503 and 18 for the d <= 768 kernel alone).
 #ifndef WA_ROWS_NP
 #define WA_ROWS_NP 12
 #endif
 #define MB_CAT_(a, b) a##b
 #define MB_CAT(a, b) MB_CAT_(a, b)
+#ifdef WA_ROWS_Q1_TU
+// The step for a model whose blocks carry a minimum (Q4_1 / Q5_1 files, Q8_1 operand rows): a kernel of its own per width, in a code object of its
+// own (the Makefile compiles this file three more times, -DWA_ROWS_Q1_TU), so that the objects of the F16 and Q5_0 / Q8_0 kernels are what they were.
+__global__ __launch_bounds__(MB_THREADS) void MB_CAT(k_decode_rows_q1_np, WA_ROWS_NP)(const wa_rows_args A) {
+    mb_body<WA_ROWS_NP, true, true>((mb_kargs) __builtin_amdgcn_kernarg_segment_ptr());
+}
+bool MB_CAT(wa_rows_launch_q1_np, WA_ROWS_NP)(hipStream_t s, const wa_rows_args & a, int n_wg, size_t lds) {
+    int dev = 0;
+    (void) hipGetDevice(&dev);
+    static bool attr_set[64] = {};
+    if (!attr_set[dev & 63]) {
+        if (hipFuncSetAttribute((const void *) MB_CAT(k_decode_rows_q1_np, WA_ROWS_NP), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return false;
+        attr_set[dev & 63] = true;
+    }
+    if (!a.te_d || !a.te_m) return false;
+    hipLaunchKernelGGL(MB_CAT(k_decode_rows_q1_np, WA_ROWS_NP), dim3(n_wg), dim3(MB_THREADS), lds, s, a);
+    return hipGetLastError() == hipSuccess;
+}
+#else
 __global__ __launch_bounds__(MB_THREADS) void MB_CAT(k_decode_rows_np, WA_ROWS_NP)(const wa_rows_args A) {
     mb_body<WA_ROWS_NP, false>((mb_kargs) __builtin_amdgcn_kernarg_segment_ptr());
 }
@@ -1407,7 +1592,9 @@ __global__ __launch_bounds__(MB_THREADS) void MB_CAT(k_decode_rows_np, WA_ROWS_N
 __global__ __launch_bounds__(MB_THREADS) void MB_CAT(k_decode_rows_q_np, WA_ROWS_NP)(const wa_rows_args A) {
     mb_body<WA_ROWS_NP, true>((mb_kargs) __builtin_amdgcn_kernarg_segment_ptr());
 }
+bool MB_CAT(wa_rows_launch_q1_np, WA_ROWS_NP)(hipStream_t s, const wa_rows_args & a, int n_wg, size_t lds);
 bool MB_CAT(wa_rows_launch_np, WA_ROWS_NP)(hipStream_t s, const wa_rows_args & a, int n_wg, size_t lds) {
+    if (a.quant == 2) return MB_CAT(wa_rows_launch_q1_np, WA_ROWS_NP)(s, a, n_wg, lds);
     int dev = 0;
     (void) hipGetDevice(&dev);
     static bool attr_set[64] = {};
@@ -1438,7 +1625,12 @@ size_t wa_rows_lds_bytes(int d, int B, int n_wg, int quant, int * slot_bytes) {
     if (quant && (4 * d) / 32 > n_wg) return 0;     // (whole-block ownership of the first MLP product: one workgroup per block)
     // a slot holds at least one task group of every phase; the whole chunk of a phase when there is room (fewer barriers)
     size_t need_min, want = 0;
-    if (quant) {
+    if (quant == 2) {           // a third region per row, the block minimums: the kernel's own rule (mq1_slot_need), no slack beyond it
+        need_min = (size_t) mq1_slot_need(8, 4 * d);
+        want = std::max(want, (size_t) mq1_slot_need((rpw(3 * d) + 7) / 8 * 8, d));
+        want = std::max(want, (size_t) mq1_slot_need(32, d));
+        want = std::max(want, (size_t) mq1_slot_need((rpw(d) + 7) / 8 * 8, 4 * d));
+    } else if (quant) {
         auto rowb = [&](int K) { return (size_t) K + MB_PAD + (size_t) (K >> 3) + MB_PAD; };
         need_min = 8 * rowb(4 * d) + 3072;
         want = std::max(want, (size_t) ((rpw(3 * d) + 7) / 8 * 8) * rowb(d));
@@ -1453,7 +1645,8 @@ size_t wa_rows_lds_bytes(int d, int B, int n_wg, int quant, int * slot_bytes) {
         want = ((want + 1023) & ~(size_t) 1023) + 1024;
     }
     const size_t total_max = 160 * 1024;
-    if (fixed + 2 * (need_min + 1024) > total_max) return 0;
+    if (quant != 2 && fixed + 2 * (need_min + 1024) > total_max) return 0;
+    if (fixed + 2 * need_min > total_max) return 0;
     size_t slot = std::min(want, (total_max - fixed) / 2);
     slot &= ~(size_t) 1023;                         // whole LDS-DMA pieces
     if (slot < need_min) return 0;
@@ -1470,3 +1663,4 @@ bool wa_launch_decode_rows(hipStream_t s, const wa_rows_args & a, int n_wg) {
     return wa_rows_launch_np20(s, a, n_wg, lds);
 }
 #endif
+#endif      // WA_ROWS_Q1_TU
