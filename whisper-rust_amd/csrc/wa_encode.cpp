@@ -51,7 +51,7 @@ bool wa_rows_prepare(whisper_context & ctx, whisper_state & st) {
     if (st.d_rows_gr) return true;
     const auto & hp = ctx.model.hp;
     const int dt = hp.n_text_state, Ht = hp.n_text_head;
-    const size_t row_gr = (size_t) 2 * dt;
+    const size_t row_gr = (size_t) wa_rows_row_gr(wa_one_launch_quant(ctx.model.wtype), dt);
     if (!dev_alloc(st.d_rows_gr, (size_t) hp.n_text_layer * WA_MEGA_EDGES * WA_ROWS_MAX * row_gr) ||
         !dev_alloc(st.d_rows_cgr, (size_t) hp.n_text_layer * WA_ROWS_MAX * Ht * WA_ROWS_CGR) || !dev_alloc(st.d_rows_status, 32)) {
         dev_free(st.d_rows_gr); dev_free(st.d_rows_cgr); dev_free(st.d_rows_status);
@@ -114,11 +114,14 @@ bool wa_state_alloc(whisper_context & ctx, whisper_state & st) {
         // single token is then that kernel with one row, at every width.  Without the switch every pass of these models is the launch sequence.
         const char * q1 = getenv("WHISPER_AMD_ROWS_Q1");
         const bool rows_q1 = shape_ok && wa_wtype_has_min(ctx.model.wtype) && q1 && q1[0] == '1';
+        // Q6_K / Q3_K: the same with k_decode_rows_k_np*, opt-in by WHISPER_AMD_ROWS_K=1.  Q5_K, Q2_K and Q4_K have no such kernel: the switch does nothing for them.
+        const char * qk = getenv("WHISPER_AMD_ROWS_K");
+        const bool rows_k = shape_ok && wa_wtype_rows_k(ctx.model.wtype) && dt % 256 == 0 && qk && qk[0] == '1';
         if (st.mega_form.enabled()) {
             if (!dev_alloc(st.d_mega_cgr, (size_t) hp.n_text_layer * Ht * WA_MEGA_CGR)) return false;
             if (!dev_alloc(st.d_mega_gr, (size_t) hp.n_text_layer * WA_MEGA_EDGES * 4 * dt)) return false;
         }
-        if (st.mega_form.enabled() || rows_q1) {
+        if (st.mega_form.enabled() || rows_q1 || rows_k) {
             // logits of the step and, right behind them, the status word: one device-to-host copy per token
             if (!dev_alloc(st.d_mega_out, (size_t) hp.n_vocab + 64)) return false;
             st.d_mega_status = (unsigned *) (st.d_mega_out + hp.n_vocab);
@@ -132,7 +135,7 @@ bool wa_state_alloc(whisper_context & ctx, whisper_state & st) {
                 st.rows_form = wa_launch_form(!(r && r[0] == '1') && wa_rows_lds_bytes(dt, 2, std::min(ctx.model.n_cu, 256), quant, &slot) != 0);
                 const char * sr = getenv("WHISPER_AMD_SINGLE_ROWS");
                 st.single_via_rows = st.rows_form.enabled() && wa_rows_lds_bytes(dt, 1, std::min(ctx.model.n_cu, 256), quant, &slot) != 0 &&
-                                     (rows_q1 || (sr ? sr[0] == '1' : (ctx.model.wtype != 1 && dt > 768)));
+                                     (rows_q1 || rows_k || (sr ? sr[0] == '1' : (ctx.model.wtype != 1 && dt > 768)));
             }
             // (the copy stream, events and pinned buffers of the host overlap are created on first use, wa_spec_begin: a state that
             //  only ever runs inside whisper_amd_full_batch keeps ONE stream - extra streams cost the concurrent chunks their overlap)

@@ -21,6 +21,9 @@ struct wa_mega_layer {          // device-resident table, one entry per decoder 
     // Q4_1 / Q5_1 files: the F32 block minimums [row][block], null otherwise.  At the end: only the several-rows kernel for these formats
     // (wa_rows.hip: k_decode_rows_q1_np*) reads them, every other kernel reads the fields above where they always were.
     const float * qkv_m, * out_m, * cq_m, * co_m, * fc1_m, * fc2_m;
+    // K-format files (wa_quantk.h): the *_w pointers hold the quants [row][lane][block][group][4], the *_d pointers the blocks' F32 d [row][block],
+    // and these the 16 scale bytes of every block; null otherwise.  At the end for the same reason: only k_decode_rows_k_np* (Q6_K / Q3_K) reads them.
+    const int8_t * qkv_sc, * out_sc, * cq_sc, * co_sc, * fc1_sc, * fc2_sc;
 };
 
 struct wa_mega_args {

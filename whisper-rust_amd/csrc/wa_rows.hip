@@ -8,6 +8,7 @@
 // chunk of a phase was requested by wave 7 at the barrier of the phase before (LDS-DMA into the other slot) and is waited for by wave 7
 // alone, right before the barrier that starts the products.
 #include "wa_one_launch_dev.h"
+#include "wa_quantk_dev.h"      // wk_block, wk_hsum8: the per-block work of a K-format product (k_decode_rows_k_np*)
 #include "wa_rows.h"
 #include <algorithm>
 
@@ -277,6 +278,94 @@ __device__ __forceinline__ void mb_products_q(const unsigned char * slot, int so
 }
 
 // -------------------------------------------------------------------------------------------------
+// K-format models whose product has no minimum term (Q6_K files, and Q3_K as the loader unpacks it; contract: wa_quantk.hip -
+// ggml_vec_dot_q6_K_q8_K in the AVX2 order).  Blocks are 256 values.  A weight row is the arena's: quants [lane u = 0..7][block][group 0..7][4]
+// signed bytes, 16 scale bytes per block (lanes 0..3 read the first eight, lanes 4..7 the second), one F32 d per block.  An operand row sits in LDS
+// quantised to Q8_K in the same quant order - lane u's 32 bytes of a block are two 16-byte reads, the eight lanes' runs an odd number of 16-byte
+// cells apart (mk_ls), so the reads of a step fall on disjoint banks - followed by its F32 d per block; Q6_K's product reads no block sums, the row carries none.  Lane u forms wk_block's integer sum of its 32
+// elements of a block and chains  acc = fma(d_x d_w, (float) sumi, acc)  over the blocks in order; three DPP adds are hsum_float_8.
+// -------------------------------------------------------------------------------------------------
+__host__ __device__ __forceinline__ int mk_ls(int nbk) { return 32 * nbk + 16; }         // bytes between the lanes' runs of an operand row
+__host__ __device__ __forceinline__ size_t mk_row_bytes(int nbk) { return ((size_t) 8 * mk_ls(nbk) + (size_t) 4 * nbk + 15) & ~(size_t) 15; }
+// A slot's image of rc weight rows of length K: quants (row stride K + MB_PAD) | scale bytes (row stride K / 16 + MB_PAD) | the rows' d, rc K / 256
+// consecutive floats - a row of K = 256 has ONE, too short for the 16-byte cells of mb_dma_rows, so they come as dwords, 64 per instruction -, each
+// region in whole KB, then the KB of bias and column scale.  The kernel and wa_rows_lds_bytes share this rule exactly (as mq1_slot_need).
+__host__ __device__ __forceinline__ int mk_soff(int rc, int K) { return (rc * (K + MB_PAD) + 1023) & ~1023; }
+__host__ __device__ __forceinline__ int mk_doff(int rc, int K) { return mk_soff(rc, K) + ((rc * ((K >> 4) + MB_PAD) + 1023) & ~1023); }
+__host__ __device__ __forceinline__ int mk_slot_need(int rc, int K) { return mk_doff(rc, K) + ((rc * (K >> 8) * 4 + 1023) & ~1023) + 1024; }
+
+// quantize_row_q8_K_ref of one block held by a wave, lane i with elements i, 64 + i, 128 + i, 192 + i of it (v[0..3]: how a LayerNorm row and a
+// swept run of granules lie in a wave) -> the operand row `op` (block blk of nbk).  The scale comes from the FIRST element of largest magnitude, with
+// its sign: a lane's lowest such element by strict comparison in index order, then the lowest index over the wave (k_quantize_q8_K's rule for
+// this distribution of the elements).  All lanes take part.
+__device__ __forceinline__ void mk_quant_block(const float (&v)[4], int lane, unsigned char * op, int nbk, int blk) {
+    float amax = fabsf(v[0]); int at = lane;
+#pragma unroll
+    for (int k = 1; k < 4; ++k) if (fabsf(v[k]) > amax) { amax = fabsf(v[k]); at = 64 * k + lane; }
+    const float wmax = wave_max(amax);
+    int first = amax == wmax ? at : 256;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) first = min(first, __shfl_xor(first, o, WAVE));
+    const int fk = first >> 6;
+    const float max = __shfl(fk == 0 ? v[0] : fk == 1 ? v[1] : fk == 2 ? v[2] : v[3], first & 63, WAVE);
+    const float iscale = wmax != 0.0f ? -127.f / max : 0.0f;
+    const float dq = wmax != 0.0f ? 1.0f / iscale : 0.0f;
+    unsigned char * run = op + (size_t) ((lane & 31) >> 2) * mk_ls(nbk) + (size_t) blk * 32 + (lane >> 5) * 4;      // element 64 k + i: group 2 k + (i >> 5), lane (i & 31) >> 2, byte i & 3
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const unsigned q = (unsigned) (wmax != 0.0f ? min(127, (int) rintf(iscale * v[k])) : 0) & 0xffu;
+        const unsigned w = q | (dpp_u32<0x101>(q) << 8) | (dpp_u32<0x102>(q) << 16) | (dpp_u32<0x103>(q) << 24);      // row_shl:1..3
+        if ((lane & 3) == 0) *(unsigned *) (run + 8 * k) = w;
+    }
+    if (lane == 0) ((float *) (op + (size_t) 8 * mk_ls(nbk)))[blk] = dq;
+}
+
+template <int BC>
+__device__ __forceinline__ void mb_dotk(const unsigned char * wq, const unsigned char * ws, const float * wd, const unsigned char * xop, size_t op_bytes, int u, int nbk,
+                                        int b0, int B, float (&res)[BC]) {
+    float acc[BC];
+    const unsigned char * xq[BC]; const float * xd[BC];
+#pragma unroll
+    for (int j = 0; j < BC; ++j) {
+        acc[j] = 0.0f;
+        const unsigned char * r = xop + (size_t) (b0 + j < B ? b0 + j : B - 1) * op_bytes;
+        xq[j] = r + (size_t) u * mk_ls(nbk); xd[j] = (const float *) (r + (size_t) 8 * mk_ls(nbk));
+    }
+#pragma unroll 2
+    for (int b = 0; b < nbk; ++b) {
+        const wk_i4 w0 = *(const wk_i4 *) (wq + 32 * b), w1 = *(const wk_i4 *) (wq + 32 * b + 16);
+        const wk_i2 s = *(const wk_i2 *) (ws + 16 * b);
+        const float dw = wd[b];
+#pragma unroll
+        for (int j = 0; j < BC; ++j) {
+            const wk_i4 x0 = *(const wk_i4 *) (xq[j] + 32 * b), x1 = *(const wk_i4 *) (xq[j] + 32 * b + 16);
+            const float dd = xd[j][b] * dw;
+            acc[j] = fmaf(dd, (float) wk_block<WK_Q6>(w0, w1, x0, x1, s), acc[j]);
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < BC; ++j) res[j] = wk_hsum8(acc[j]);
+}
+// product tasks of a K-format chunk (as mb_products_q): the slot holds the rows' quants, then - `soff` bytes in - their scale bytes and - `doff` - their d
+template <int BC, typename EPI>
+__device__ __forceinline__ void mb_products_k(const unsigned char * slot, int soff, int doff, int Rc, int row_base, int N, const float * bias_l, const float * scale_l,
+                                              const unsigned char * xop, size_t op_bytes, int K, int B, int wave, int lane, EPI epi) {
+    const int nbk = K >> 8, stride_q = K + MB_PAD, stride_s = 16 * nbk + MB_PAD;
+    const int groups = (Rc + 7) >> 3, nsub = (B + BC - 1) / BC, per = (B + nsub - 1) / nsub, ntasks = groups * nsub;
+    const int u = lane & 7;
+    for (int t = wave; t < ntasks; t += MB_NCW) {
+        const int g = t / nsub, sb = t - g * nsub, b0 = sb * per, b1 = min(B, b0 + per);
+        const int ri = g * 8 + (lane >> 3), rr = ri < Rc ? ri : Rc - 1;
+        const bool has = ri < Rc && row_base + ri < N && u == 0;
+        const float bv = bias_l[ri < 64 ? ri : 63], sv = scale_l ? scale_l[ri < 64 ? ri : 63] : 1.0f;
+        float res[BC];
+        mb_dotk<BC>(slot + (size_t) rr * stride_q + (size_t) u * nbk * 32, slot + soff + (size_t) rr * stride_s + 8 * (u >> 2), (const float *) (slot + doff) + (size_t) rr * nbk,
+                    xop, op_bytes, u, nbk, b0, B, res);
+        epi(res, b0, b1, row_base + ri, has, bv, sv);
+    }
+}
+
+// -------------------------------------------------------------------------------------------------
 // LayerNorm of ONE token row by ONE wave (ops.cpp:3225-3242 semantics as wa_exact.hip: wa_ln_stats - F64 sums in any order, accepted
 // when certified order-independent, else redone in index order): the row comes from granules (or the embeddings), stays in registers,
 // and leaves as F16 in `dst`.  The in-order fallback walks the registers lane by lane (no LDS copy of the row).
@@ -301,7 +390,7 @@ __device__ __forceinline__ double mb_seq_sum(const float (&xv)[NP], int d, bool 
     }
     return t;
 }
-template <int NP, bool Q = false, bool Q1 = false>       // Q: the normalised row leaves as Q8_0 (the next product's operand), not as F16; Q1: as Q8_1
+template <int NP, bool Q = false, bool Q1 = false, bool QK = false>       // Q: the normalised row leaves as Q8_0 (the next product's operand), not as F16; Q1: as Q8_1; QK: as Q8_K
 __device__ __forceinline__ void mb_ln_row(mb_kargs A, mo_ctl & c, gu64 * edge_row /* null: embeddings */, const float * lnp /* LDS: gamma | beta, each d floats in whole KB */, const float * gw_g, const float * gb_g /* global, when non-null */,
                                           int b, int lane_, wa_f16 * dst, float * xres_b, int row_d, int r_d, unsigned code, int token = 0, bool tw = false, int tslot = 0) {
     // (nothing derived from the lane index may live across calls: hoisted out of the layer loop the per-element LDS addresses went to scratch, and every
@@ -321,6 +410,20 @@ __device__ __forceinline__ void mb_ln_row(mb_kargs A, mo_ctl & c, gu64 * edge_ro
             const gch te = (gch) A->te + (size_t) token * d;
 #pragma unroll
             for (int k = 0; k < NP; ++k) { const int i = lane + 64 * k, ic = i < d ? i : d - 1; const float e = h2f(te[ic]) + pe[ic]; xv[k] = i < d ? e : 0.0f; }
+        } else if constexpr (QK) {      // k_dec_embed_k: dequantize_row_q6_K, (d * sc) * q - two roundings -, then + the positional embedding
+            const int nbk = d >> 8;
+            const GAS int8_t * tq = (const GAS int8_t *) A->te + (size_t) token * 8 * nbk * 32;
+            const GAS int8_t * tsc = (const GAS int8_t *) A->te_sc + (size_t) token * nbk * 16;
+            const gcf td = (gcf) A->te_d + (size_t) token * nbk;
+#pragma unroll
+            for (int k = 0; k < NP; ++k) {
+                const int i = lane + 64 * k, ic = i < d ? i : d - 1, bb = ic >> 8, el = ic & 255;
+                const int q = (int) tq[((size_t) ((el & 31) >> 2) * nbk + bb) * 32 + (el >> 5) * 4 + (el & 3)];
+                const float d1 = td[bb] * (float) (int) tsc[bb * 16 + 8 * ((el >> 4) & 1) + (el >> 5)];
+                float e = d1 * (float) q;
+                e = e + pe[ic];
+                xv[k] = i < d ? e : 0.0f;
+            }
         } else {                // k_dec_embed_q: the row dequantised (q * d, ggml-quants.c)
             const int nb = d >> 5;
             const GAS int8_t * tq = (const GAS int8_t *) A->te + (size_t) token * 8 * nb * 4;
@@ -392,6 +495,7 @@ __device__ __forceinline__ void mb_ln_row(mb_kargs A, mo_ctl & c, gu64 * edge_ro
         y = y * gam[k];
         y = y + bet[k];
         if constexpr (!Q) { if (i < d) dst[i] = f2h(y); }
+        else if constexpr (QK) xv[k] = i < d ? y : 0.0f;      // (quantised below, four values per lane = one block of 256)
         else {                  // a half-wave holds one 32-element block (d % 64 == 0: every block of k < d / 64 is whole)
             unsigned w, sw;
             if constexpr (Q1) w = mq_quant32_q1(i < d ? y : 0.0f, sw);
@@ -400,6 +504,11 @@ __device__ __forceinline__ void mb_ln_row(mb_kargs A, mo_ctl & c, gu64 * edge_ro
             if (i < d && (lane & 3) == 0) mq_quads((unsigned char *) dst, nb, (lane & 31) >> 2)[blk] = w;
             if (i < d && (lane & 31) == 0) ((unsigned *) mq_scales((unsigned char *) dst, nb))[blk] = sw;
         }
+    }
+    if constexpr (QK) {         // d % 256 == 0: every block below d / 256 is whole
+#pragma unroll
+        for (int bk = 0; bk < NP / 4; ++bk)
+            if (256 * bk < d) { const float v4[4] = { xv[4 * bk], xv[4 * bk + 1], xv[4 * bk + 2], xv[4 * bk + 3] }; mk_quant_block(v4, lane, (unsigned char *) dst, d >> 8, bk); }
     }
 }
 
@@ -436,7 +545,7 @@ __device__ __forceinline__ unsigned mb_pack_h2(unsigned h) { return (h & 0xffffu
 
 // the head's 64 outputs from the 32 chain sums + the leftover cells in F64, index order (vec.cpp:221-223), by threads 0..63; published packed
 // (Q: as two Q8_0 blocks)
-template <bool Q = false, bool Q1 = false>
+template <bool Q = false, bool Q1 = false, bool QK = false>
 __device__ __forceinline__ void mb_attn_finish(const float * part, const wa_f16 * vleft /* [nl][64] LDS */, const wa_f16 * pleft /* [nl] */, int nl,
                                                gu64 * edge_row, int h, unsigned seq, int tid) {
     if (tid < 64) {
@@ -445,7 +554,8 @@ __device__ __forceinline__ void mb_attn_finish(const float * part, const wa_f16 
         for (int r = 0; r < 32; ++r) s32[r] = part[r * 64 + tid];
         double sumf = (double) wa_tree32(s32);
         for (int cc = 0; cc < nl; ++cc) sumf += (double) (h2f(vleft[cc * 64 + tid]) * h2f(pleft[cc]));
-        mo_attn_publish<Q, Q1>((float) sumf, edge_row, h, seq, tid);
+        if constexpr (QK) gr_store(edge_row + h * 64 + tid, seq, __float_as_uint((float) sumf));      // F32: a Q8_K block spans four heads, the gathering side quantises
+        else mo_attn_publish<Q, Q1>((float) sumf, edge_row, h, seq, tid);
     }
 }
 
@@ -454,7 +564,7 @@ __device__ __forceinline__ void mb_attn_finish(const float * part, const wa_f16 
 // tokens come from the row's own cells in HBM; the cells written by THIS launch - the row's own and those of every other row that shares
 // its cache (earlier tokens of a small batch; other beams, which the mask hides) - arrive as granules, like the query.
 // -------------------------------------------------------------------------------------------------
-template <bool Q = false, bool Q1 = false>
+template <bool Q = false, bool Q1 = false, bool QK = false>
 __device__ __forceinline__ void mb_unit_self(mb_kargs A, mo_ctl & c, unsigned char * area, int l, int b, int h, int tid, bool tw = false) {
 #define MB_TS(k) mb_trace(A, tw, 4096 + l * 16 + (k))
     MB_TS(0);
@@ -646,7 +756,7 @@ __device__ __forceinline__ void mb_unit_self(mb_kargs A, mo_ctl & c, unsigned ch
     }
     MB_TS(7);
     wa_barrier_lds();
-    mb_attn_finish<Q, Q1>(part, vleft, p16 + np, nl, mb_edge(A, l, E_AO) + (size_t) b * A->row_gr, h, c.seq, tid);
+    mb_attn_finish<Q, Q1, QK>(part, vleft, p16 + np, nl, mb_edge(A, l, E_AO) + (size_t) b * A->row_gr, h, c.seq, tid);
     MB_TS(8);
     wa_barrier_lds();
     MB_TS(9);
@@ -688,7 +798,7 @@ __device__ __forceinline__ void mb_cross_load(mb_kargs A, int l, int b, int h, i
         }
 }
 
-template <bool Q, int P, bool Q1 = false>
+template <bool Q, int P, bool Q1 = false, bool QK = false>
 __device__ __forceinline__ void mb_unit_cross(mb_kargs A, mo_ctl & c, unsigned char * area, int l, int b, int h, int w, int tid, bool tw, const mb_cross_regs<P> & R) {
     constexpr int NCH = 32 / P, CPW = 4 / P, NK = NCH * MB_CSTEPS;          // chains of this part, chains per wave, local cell slots
     const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -902,7 +1012,8 @@ __device__ __forceinline__ void mb_unit_cross(mb_kargs A, mo_ctl & c, unsigned c
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int cc = 0; cc < 32; ++cc) sumf += dv[cc];
-            mo_attn_publish<Q, Q1>((float) sumf, mb_edge(A, l, E_AO2) + (size_t) b * A->row_gr, h, seq, tid);
+            if constexpr (QK) gr_store(mb_edge(A, l, E_AO2) + (size_t) b * A->row_gr + h * 64 + tid, seq, __float_as_uint((float) sumf));
+            else mo_attn_publish<Q, Q1>((float) sumf, mb_edge(A, l, E_AO2) + (size_t) b * A->row_gr, h, seq, tid);
         }
         MB_TC(10);
     }
@@ -932,11 +1043,31 @@ __device__ __forceinline__ void mb_logits_out(mb_kargs A, const float * lg, int 
 }
 
 // the first piece of a wave's first embedding rows, asked for BEFORE the final LayerNorm waits for its row (piece 0 of mb_logits / mb_logits_q)
+// one piece of a K-format embedding row for lane u of its group: blocks 4 bt .. 4 bt + 3 (clamped to the row) as quants [8 k .. 8 k + 7] | the lane's
+// eight scale bytes [32 + 2 k, 33 + 2 k] | d [40 + k] - 44 registers of the buffer's 48
+__device__ __forceinline__ void mk_te_piece(mb_kargs A, int rc, int u, int bt, unsigned (&buf)[48]) {
+    const int nbk = A->d >> 8;
+    const GAS u32x4 * wl = (const GAS u32x4 *) ((const GAS unsigned char *) A->te + ((size_t) rc * 8 + u) * nbk * 32);
+    const GAS u32x2 * sl = (const GAS u32x2 *) ((const GAS unsigned char *) A->te_sc + (size_t) rc * nbk * 16 + 8 * (u >> 2));
+    const GAS unsigned * dl = (const GAS unsigned *) A->te_d + (size_t) rc * nbk;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int bb = 4 * bt + k, bc = bb < nbk ? bb : nbk - 1;
+        const u32x4 q0 = wl[2 * bc], q1 = wl[2 * bc + 1];
+        const u32x2 sc = sl[2 * bc];
+        buf[8 * k] = q0.x; buf[8 * k + 1] = q0.y; buf[8 * k + 2] = q0.z; buf[8 * k + 3] = q0.w;
+        buf[8 * k + 4] = q1.x; buf[8 * k + 5] = q1.y; buf[8 * k + 6] = q1.z; buf[8 * k + 7] = q1.w;
+        buf[32 + 2 * k] = sc.x; buf[33 + 2 * k] = sc.y; buf[40 + k] = dl[bc];
+    }
+}
+
+template <bool QK = false>
 __device__ __forceinline__ void mb_te_first(mb_kargs A, bool quant, bool q1, unsigned (&buf)[48], int lane, int wave) {
     const int d = A->d, ns = d >> 5, n_vocab = A->n_vocab, u = lane & 7;
     int g1_; const int g0_ = mb_share(n_vocab, &g1_);
     const int row = (g0_ + wave) * 8 + (lane >> 3), rc = row < n_vocab ? row : 0;
-    if (q1) {                   // pieces of 16 blocks: quads | scales | minimums (mb_logits_q)
+    if constexpr (QK) { mk_te_piece(A, rc, u, 0, buf); return; }
+    if (q1) {                 // pieces of 16 blocks: quads | scales | minimums (mb_logits_q)
         const GAS unsigned * wl = (const GAS unsigned *) A->te + ((size_t) rc * 8 + u) * ns;
         const GAS unsigned * dl = (const GAS unsigned *) A->te_d + (size_t) rc * ns, * ml = (const GAS unsigned *) A->te_m + (size_t) rc * ns;
 #pragma unroll
@@ -1170,6 +1301,69 @@ __device__ __forceinline__ void mb_logits_q1(mb_kargs A, const unsigned char * x
     }
 }
 
+// the same for a K-format token embedding (Q6_K, Q3_K): a piece is 4 blocks of 256 (mk_te_piece: 11 registers a block), the token rows are Q8_K
+// (mb_dotk's chain, which goes on across the pieces of a row)
+template <int BT>
+__device__ __forceinline__ void mb_logits_k(mb_kargs A, const unsigned char * xop, size_t op_bytes, int B, int lane, int wave, unsigned (&pfa)[48], float * lg) {
+    const int d = A->d, nbk = d >> 8, nbat = (nbk + 3) / 4, n_vocab = A->n_vocab;
+    const int u = lane & 7;
+    GAS float * logits = (GAS float *) A->logits;
+    unsigned pfb[48];
+    int g1; const int g0 = mb_share(n_vocab, &g1);
+    auto grp = [&](int j) { return g0 + wave + MB_NW * j; };
+    int n_items = 0;
+    for (int j = 0; grp(j) < g1; ++j) n_items += nbat;
+    auto load = [&](int it, unsigned (&buf)[48]) {
+        const int j = it / nbat, bt = it - j * nbat, row = grp(j) * 8 + (lane >> 3);
+        mk_te_piece(A, row < n_vocab ? row : 0, u, bt, buf);
+    };
+    float acc[BT];
+    const unsigned char * xq[BT]; const float * xd[BT];
+#pragma unroll
+    for (int m = 0; m < BT; ++m) { const unsigned char * r = xop + (size_t) (m < B ? m : B - 1) * op_bytes; xq[m] = r + (size_t) u * mk_ls(nbk); xd[m] = (const float *) (r + (size_t) 8 * mk_ls(nbk)); }
+    auto one = [&](int it, unsigned (&buf)[48]) {
+        const int j = it / nbat, bt = it - j * nbat;
+        if (bt == 0) {
+#pragma unroll
+            for (int m = 0; m < BT; ++m) acc[m] = 0.0f;
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int bb = 4 * bt + k;
+            if (bb < nbk) {
+                wk_i4 w0, w1; wk_i2 s;
+                w0.x = (int) buf[8 * k]; w0.y = (int) buf[8 * k + 1]; w0.z = (int) buf[8 * k + 2]; w0.w = (int) buf[8 * k + 3];
+                w1.x = (int) buf[8 * k + 4]; w1.y = (int) buf[8 * k + 5]; w1.z = (int) buf[8 * k + 6]; w1.w = (int) buf[8 * k + 7];
+                s.x = (int) buf[32 + 2 * k]; s.y = (int) buf[33 + 2 * k];
+                const float dw = __uint_as_float(buf[40 + k]);
+#pragma unroll
+                for (int m = 0; m < BT; ++m) {
+                    const wk_i4 x0 = *(const wk_i4 *) (xq[m] + 32 * bb), x1 = *(const wk_i4 *) (xq[m] + 32 * bb + 16);
+                    const float dd = xd[m][bb] * dw;
+                    acc[m] = fmaf(dd, (float) wk_block<WK_Q6>(w0, w1, x0, x1, s), acc[m]);
+                }
+            }
+        }
+        if (bt == nbat - 1) {
+            const int row = grp(j) * 8 + (lane >> 3);
+#pragma unroll
+            for (int m = 0; m < BT; ++m) {
+                const float v = wk_hsum8(acc[m]);
+                if (u == 0 && j < 4) lg[m * 256 + (8 * j + wave) * 8 + (lane >> 3)] = v;
+                else if (u == 0 && row < n_vocab && m < B) logits[(size_t) m * n_vocab + row] = v;
+            }
+        }
+    };
+    // (piece 0 is on its way since before the final LayerNorm: mb_te_first)
+    for (int it = 0; it < n_items; it += 2) {
+        if (it + 1 < n_items) load(it + 1, pfb);
+        one(it, pfa);
+        if (it + 1 >= n_items) break;
+        if (it + 2 < n_items) load(it + 2, pfa);
+        one(it + 1, pfb);
+    }
+}
+
 // -------------------------------------------------------------------------------------------------
 // next-token prediction per row (the protocol and its records: wa_one_launch_dev.h).  mb_pick: one wave, the row's token and the sampling state
 // after it -> pk (MO_PK_*).
@@ -1204,7 +1398,7 @@ __device__ __forceinline__ void mb_record(mb_kargs A, int br, const float * lg_m
 // -------------------------------------------------------------------------------------------------
 // the kernel
 // -------------------------------------------------------------------------------------------------
-struct mb_phase { const wa_f16 * W; const float * D; const float * M; const float * bias; const float * scale; int N, K, r, rc, nck, soff, moff; };
+struct mb_phase { const wa_f16 * W; const float * D; const float * M; const int8_t * S; const float * bias; const float * scale; int N, K, r, rc, nck, soff, moff; };
 
 // (Q4_1 / Q5_1) a slot's image of rc weight rows of length K: quants | block scales | block minimums, each region in whole KB - an LDS-DMA instruction
 // writes a KB, so a region's last piece may run that far past its rows -, then the KB of bias and column scale.  mq1_soff / mq1_moff: where the second
@@ -1214,8 +1408,9 @@ __host__ __device__ __forceinline__ int mq1_soff(int rc, int K) { return (rc * (
 __host__ __device__ __forceinline__ int mq1_moff(int rc, int K) { return mq1_soff(rc, K) + ((rc * ((K >> 3) + MB_PAD) + 1023) & ~1023); }
 __host__ __device__ __forceinline__ int mq1_slot_need(int rc, int K) { return mq1_moff(rc, K) + ((rc * ((K >> 3) + MB_PAD) + 1023) & ~1023) + 1024; }
 
-// Q: a quantised model (Q5_0 / Q8_0); Q1 (with Q): its blocks carry a minimum (Q4_1 / Q5_1) and every operand row is Q8_1
-template <int NP, bool Q, bool Q1 = false>
+// Q: a quantised model (Q5_0 / Q8_0); Q1 (with Q): its blocks carry a minimum (Q4_1 / Q5_1) and every operand row is Q8_1; QK (with Q): a K-format
+// model (Q6_K / Q3_K), every operand row is Q8_K
+template <int NP, bool Q, bool Q1 = false, bool QK = false>
 __device__ __forceinline__ void mb_body(mb_kargs A_) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const mb_kargs A = mo_uniform(A_);
@@ -1236,7 +1431,7 @@ __device__ __forceinline__ void mb_body(mb_kargs A_) {
     unsigned * rscr = (unsigned *) (smem + 1536);     // [8][8] scratch of mb_record
     float  * lnp  = (float *) (smem + 1792);
     const size_t lnp_bytes = 2 * (((size_t) d * 4 + 1023) & ~(size_t) 1023);      // (an LDS-DMA instruction writes a whole KB: each vector ends on one)
-    const size_t opB = Q ? mq_row_bytes(d >> 5) : (size_t) d * 2, op4 = Q ? mq_row_bytes(d4 >> 5) : (size_t) d4 * 2;      // bytes of an operand row
+    const size_t opB = QK ? mk_row_bytes(d >> 8) : Q ? mq_row_bytes(d >> 5) : (size_t) d * 2, op4 = QK ? mk_row_bytes(d4 >> 8) : Q ? mq_row_bytes(d4 >> 5) : (size_t) d4 * 2;      // bytes of an operand row
     unsigned char * xinB = smem + 1792 + lnp_bytes;
     const size_t xinB_bytes = ((size_t) B * opB + 255) & ~(size_t) 255;
     unsigned char * area = xinB + xinB_bytes;
@@ -1250,7 +1445,7 @@ __device__ __forceinline__ void mb_body(mb_kargs A_) {
     // rows of every matrix this workgroup owns (an even count, the same for every workgroup: mg_rpw).  Quantised models: the first MLP product by
     // WHOLE Q8_0 blocks - workgroup b < 4d / 32 owns rows 32 b .. 32 b + 31 - so that a block leaves already quantised (9 granules, not 32 F32 values)
     auto rpw = [&](int N) { const int r = (N + nwg - 1) / nwg; return (r + 1) & ~1; };
-    const int r_qkv = rpw(3 * d), r_d = rpw(d), r_ff = Q ? 32 : rpw(d4);
+    const int r_qkv = rpw(3 * d), r_d = rpw(d), r_ff = Q && !QK ? 32 : rpw(d4);      // (QK: nobody quantises what it owns, the rows are dealt evenly)
     const int row_d = wg * r_d;
     auto phase_of = [&](int l, int p) {
         const __attribute__((address_space(4))) wa_mega_layer & Y = Ly[l];
@@ -1264,8 +1459,14 @@ __device__ __forceinline__ void mb_body(mb_kargs A_) {
         else             { ph.W = Y.fc2_w; ph.D = Y.fc2_d; ph.bias = Y.fc2_b; ph.N = d; ph.K = d4; ph.r = r_d; }
         const int gp = (!Q && p == 5) ? 4 : 8;
         const int rmax = (ph.r + gp - 1) / gp * gp;
-        ph.M = nullptr; ph.moff = 0;
-        if constexpr (Q1) {     // the most octets of rows whose three regions fit the slot (wa_rows_lds_bytes admits a slot that holds one)
+        ph.M = nullptr; ph.moff = 0; ph.S = nullptr;
+        if constexpr (QK) {     // the most octets of rows whose three regions fit the slot (mk_slot_need; moff: where the rows' d start)
+            ph.S = p == 0 ? Y.qkv_sc : p == 1 ? Y.out_sc : p == 2 ? Y.cq_sc : p == 3 ? Y.co_sc : p == 4 ? Y.fc1_sc : Y.fc2_sc;
+            int rc = rmax;
+            while (rc > 8 && mk_slot_need(rc, ph.K) > slot_bytes) rc -= 8;
+            ph.rc = rc;
+            ph.moff = mk_doff(rc, ph.K);
+        } else if constexpr (Q1) {     // the most octets of rows whose three regions fit the slot (wa_rows_lds_bytes admits a slot that holds one)
             ph.M = p == 0 ? Y.qkv_m : p == 1 ? Y.out_m : p == 2 ? Y.cq_m : p == 3 ? Y.co_m : p == 4 ? Y.fc1_m : Y.fc2_m;
             int rc = ((slot_bytes - 1024) / (ph.K + MB_PAD + 2 * ((ph.K >> 3) + MB_PAD))) / 8 * 8;
             rc = rc > rmax ? rmax : rc;
@@ -1288,7 +1489,15 @@ __device__ __forceinline__ void mb_body(mb_kargs A_) {
         if (row0 >= ph.N) return;
         const int R = min(ph.rc, ph.r - ck * ph.rc);
         unsigned char * slot = slot0 + (size_t) par * slot_bytes;
-        if constexpr (Q) {
+        if constexpr (QK) {
+            const int nbk = ph.K >> 8, nd = R * nbk, last = ph.N * nbk - 1;
+            mb_dma_rows((const GAS unsigned char *) ph.W, ph.K, row0, R, ph.N, slot, lane);
+            mb_dma_rows((const GAS unsigned char *) ph.S, ph.K >> 4, row0, R, ph.N, slot + ph.soff, lane);
+            for (int p64 = 0; p64 * 64 < nd; ++p64) {       // the rows' d: consecutive floats, a dword per lane (clamped to the matrix)
+                const int i = row0 * nbk + p64 * 64 + lane;
+                __builtin_amdgcn_global_load_lds((const GAS void *) ((gcf) ph.D + (i < last ? i : last)), (LAS void *) (slot + ph.moff + p64 * 256), 4, 0, 0);
+            }
+        } else if constexpr (Q) {
             mb_dma_rows((const GAS unsigned char *) ph.W, ph.K, row0, R, ph.N, slot, lane);
             mb_dma_rows((const GAS unsigned char *) ph.D, ph.K >> 3, row0, R, ph.N, slot + ph.soff, lane);
             if constexpr (Q1) mb_dma_rows((const GAS unsigned char *) ph.M, ph.K >> 3, row0, R, ph.N, slot + ph.moff, lane);
@@ -1335,7 +1544,11 @@ __device__ __forceinline__ void mb_body(mb_kargs A_) {
         const float * bias_l = (const float *) (slot + slot_bytes - 512);
         const int groups = (Rc + 7) >> 3;
         const int bc = groups * B <= MB_NCW ? 1 : groups * ((B + 1) >> 1) <= MB_NCW ? 2 : 3;
-        if constexpr (Q) {
+        if constexpr (QK) {
+            if (bc == 1)      mb_products_k<1>(slot, ph.soff, ph.moff, Rc, row_base, ph.N, bias_l, scale_l, xop, opb, ph.K, B, wave, lane, epi);
+            else if (bc == 2) mb_products_k<2>(slot, ph.soff, ph.moff, Rc, row_base, ph.N, bias_l, scale_l, xop, opb, ph.K, B, wave, lane, epi);
+            else              mb_products_k<3>(slot, ph.soff, ph.moff, Rc, row_base, ph.N, bias_l, scale_l, xop, opb, ph.K, B, wave, lane, epi);
+        } else if constexpr (Q) {
             if (bc == 1)      mb_products_q<1, Q1>(slot, ph.soff, Rc, row_base, ph.N, bias_l, scale_l, xop, opb, ph.K, B, wave, lane, epi, ph.moff);
             else if (bc == 2) mb_products_q<2, Q1>(slot, ph.soff, Rc, row_base, ph.N, bias_l, scale_l, xop, opb, ph.K, B, wave, lane, epi, ph.moff);
             else              mb_products_q<3, Q1>(slot, ph.soff, Rc, row_base, ph.N, bias_l, scale_l, xop, opb, ph.K, B, wave, lane, epi, ph.moff);
@@ -1346,8 +1559,26 @@ __device__ __forceinline__ void mb_body(mb_kargs A_) {
         }
     };
     // gathered attention outputs / MLP activations -> operand rows in `xin`: packed F16 pairs, or - quantised - blocks of 9 granules (8 quads + scale)
+    // QK: the producers publish F32 (a Q8_K block is four heads' outputs, or eight workgroups' of the first MLP product: no producer holds one);
+    // a wave sweeps up to four blocks of one granule per value, four values of a block per lane, and quantises them into the operand row
     auto gather_rows = [&](gu64 * edge, int len, unsigned code) {
-        if constexpr (Q) {
+        if constexpr (QK) {
+            const int nbk = len >> 8, total = B * nbk;
+            const size_t opb = len == d ? opB : op4;
+            for (int f0 = 4 * wave; f0 < total; f0 += 4 * MB_NW) {
+                unsigned v[16];
+                mo_sweep<MO_POLL_ALL, 16>(edge, [&](int k) { const int f = f0 + (k >> 2); if (f >= total) return -1; const int b = f / nbk; return b * RG + (f - b * nbk) * 256 + 64 * (k & 3) + lane; }, c, lane, v, code);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const int f = f0 + j;
+                    if (f < total) {        // (wave-uniform)
+                        const int b = f / nbk;
+                        const float v4[4] = { __uint_as_float(v[4 * j]), __uint_as_float(v[4 * j + 1]), __uint_as_float(v[4 * j + 2]), __uint_as_float(v[4 * j + 3]) };
+                        mk_quant_block(v4, lane, xin + (size_t) b * opb, nbk, f - b * nbk);
+                    }
+                }
+            }
+        } else if constexpr (Q) {
             const int nb = len >> 5;
             mb_gather<8>(c, edge, B, 9 * nb, RG, tid, lane, [&](int b, int j, unsigned v) {
                 const int blk = j / 9, kq = j - 9 * blk;
@@ -1375,11 +1606,11 @@ __device__ __forceinline__ void mb_body(mb_kargs A_) {
         // quantised kernels keep one instance: they are short of registers (99-198 spilled VGPRs) and a second copy cost more than it won (large-v3-q5_0: 3.22 -> 3.65 ms).
         if (wave < B) {
             if constexpr (Q) {
-                mb_ln_row<NP, Q, Q1>(A, c, l == 0 ? nullptr : mb_edge(A, l - 1, E_X3) + (size_t) wave * RG, lnp, l == 0 ? Y.ln1_w : nullptr, l == 0 ? Y.ln1_b : nullptr,
+                mb_ln_row<NP, Q, Q1, QK>(A, c, l == 0 ? nullptr : mb_edge(A, l - 1, E_X3) + (size_t) wave * RG, lnp, l == 0 ? Y.ln1_w : nullptr, l == 0 ? Y.ln1_b : nullptr,
                                  wave, lane, (wa_f16 *) (xinB + (size_t) wave * opB), xres + wave * 8, row_d, r_d, 100u + l, pk[8 * wave], tw, l * 32 + 29);
             } else {
-                if (l == 0) mb_ln_row<NP, Q, Q1>(A, c, nullptr, lnp, Y.ln1_w, Y.ln1_b, wave, lane, (wa_f16 *) (xinB + (size_t) wave * opB), xres + wave * 8, row_d, r_d, 100u, pk[8 * wave]);
-                else        mb_ln_row<NP, Q, Q1>(A, c, mb_edge(A, l - 1, E_X3) + (size_t) wave * RG, lnp, nullptr, nullptr, wave, lane, (wa_f16 *) (xinB + (size_t) wave * opB), nullptr, 0, 0, 100u + l, 0, tw, l * 32 + 29);
+                if (l == 0) mb_ln_row<NP, Q, Q1, QK>(A, c, nullptr, lnp, Y.ln1_w, Y.ln1_b, wave, lane, (wa_f16 *) (xinB + (size_t) wave * opB), xres + wave * 8, row_d, r_d, 100u, pk[8 * wave]);
+                else        mb_ln_row<NP, Q, Q1, QK>(A, c, mb_edge(A, l - 1, E_X3) + (size_t) wave * RG, lnp, nullptr, nullptr, wave, lane, (wa_f16 *) (xinB + (size_t) wave * opB), nullptr, 0, 0, 100u + l, 0, tw, l * 32 + 29);
             }
         }
         MB_T(1);
@@ -1406,7 +1637,7 @@ __device__ __forceinline__ void mb_body(mb_kargs A_) {
         MB_T(2);
         // ---------------- P2: self-attention ----------------
         MB_CHAOS_WG(20u); MB_CHAOS_AT(21u);
-        for (int u = wg; u < B * H; u += nwg) mb_unit_self<Q, Q1>(A, c, area, l, u / H, u % H, tid, tw);
+        for (int u = wg; u < B * H; u += nwg) mb_unit_self<Q, Q1, QK>(A, c, area, l, u / H, u % H, tid, tw);
         MB_T(3);
         // ---------------- P3: out-projection + residual ----------------
         MB_CHAOS_AT(22u);
@@ -1429,7 +1660,7 @@ __device__ __forceinline__ void mb_body(mb_kargs A_) {
         run_phase(l, 1, [&](const mb_phase & ph, const unsigned char * slot, int row_base, int Rc, int) { prod8(ph, slot, row_base, Rc, nullptr, xin, opD, resid_epi(mb_edge(A, l, E_X1))); });
         MB_T(5);
         // ---------------- P4: LayerNorm + cross query ----------------
-        if (wave < B) mb_ln_row<NP, Q, Q1>(A, c, mb_edge(A, l, E_X1) + (size_t) wave * RG, lnp, nullptr, nullptr, wave, lane, (wa_f16 *) (xinB + (size_t) wave * opB), nullptr, 0, 0, 300u + l);
+        if (wave < B) mb_ln_row<NP, Q, Q1, QK>(A, c, mb_edge(A, l, E_X1) + (size_t) wave * RG, lnp, nullptr, nullptr, wave, lane, (wa_f16 *) (xinB + (size_t) wave * opB), nullptr, 0, 0, 300u + l);
         MB_T(6);
         run_phase(l, 2, [&](const mb_phase & ph, const unsigned char * slot, int row_base, int Rc, int) {
             gu64 * eq = mb_edge(A, l, E_QC);
@@ -1454,7 +1685,7 @@ __device__ __forceinline__ void mb_body(mb_kargs A_) {
             const int bh = u >> 2;
             mb_cross_regs<4> CR;    // (asked for here: earlier - across the cross-query products - the 72 registers cost those products 2 us and won 0.8)
             mb_cross_load<4>(A, l, bh / H, bh % H, u & 3, tid, CR);
-            mb_unit_cross<Q, 4, Q1>(A, c, area, l, bh / H, bh % H, u & 3, tid, tw, CR);
+            mb_unit_cross<Q, 4, Q1, QK>(A, c, area, l, bh / H, bh % H, u & 3, tid, tw, CR);
         }
         MB_T(8);
         // ---------------- P6: out-projection + residual ----------------
@@ -1464,7 +1695,7 @@ __device__ __forceinline__ void mb_body(mb_kargs A_) {
         run_phase(l, 3, [&](const mb_phase & ph, const unsigned char * slot, int row_base, int Rc, int) { prod8(ph, slot, row_base, Rc, nullptr, xin, opD, resid_epi(mb_edge(A, l, E_X2))); });
         MB_T(10);
         // ---------------- P7: LayerNorm + FC1 + GELU ----------------
-        if (wave < B) mb_ln_row<NP, Q, Q1>(A, c, mb_edge(A, l, E_X2) + (size_t) wave * RG, lnp, nullptr, nullptr, wave, lane, (wa_f16 *) (xinB + (size_t) wave * opB), nullptr, 0, 0, 500u + l);
+        if (wave < B) mb_ln_row<NP, Q, Q1, QK>(A, c, mb_edge(A, l, E_X2) + (size_t) wave * RG, lnp, nullptr, nullptr, wave, lane, (wa_f16 *) (xinB + (size_t) wave * opB), nullptr, 0, 0, 500u + l);
         MB_T(11);
         run_phase(l, 4, [&](const mb_phase & ph, const unsigned char * slot, int row_base, int Rc, int ck_row) {
             gu64 * eh = mb_edge(A, l, E_HF);
@@ -1480,7 +1711,8 @@ __device__ __forceinline__ void mb_body(mb_kargs A_) {
                     const float v = res[j];
                     float gl = v;
                     if (v <= -10.0f) gl = 0.0f; else if (v < 10.0f) gl = tv[j];
-                    if constexpr (Q) { if (has && b < b1) fc1x[b * 32 + (n - wg * 32)] = gl; }      // F32: quantised below, once the block's 32 rows are through
+                    if constexpr (QK) { if (has && b < b1) gr_store(eh + (size_t) b * RG + n, seq, __float_as_uint(gl)); }      // F32, a granule per value (row_gr = 4 d): the gathering side quantises
+                    else if constexpr (Q) { if (has && b < b1) fc1x[b * 32 + (n - wg * 32)] = gl; }      // F32: quantised below, once the block's 32 rows are through
                     else {
                         const unsigned pk = mb_pack_h2((unsigned) f2h(gl));
                         if (has && b < b1 && (lane & 15) == 0) gr_store(eh + (size_t) b * RG + (n >> 1), seq, pk);
@@ -1489,7 +1721,7 @@ __device__ __forceinline__ void mb_body(mb_kargs A_) {
             });
             (void) ck_row;
         });
-        if constexpr (Q) {      // this workgroup's block of every token row: quantize_row_q8_0, published as 9 granules (wave b: row b)
+        if constexpr (Q && !QK) {      // this workgroup's block of every token row: quantize_row_q8_0, published as 9 granules (wave b: row b)
             wa_barrier_lds();
             if (wave < B && 32 * wg < d4) {
                 unsigned w, sw;
@@ -1508,7 +1740,10 @@ __device__ __forceinline__ void mb_body(mb_kargs A_) {
         run_phase(l, 5, [&](const mb_phase & ph, const unsigned char * slot, int row_base, int Rc, int) {
             const float * bias_l = (const float *) (slot + slot_bytes - 512);
             const int groups = (Rc + (Q ? 7 : 3)) / (Q ? 8 : 4);
-            if constexpr (Q) {
+            if constexpr (QK) {
+                if (groups * B <= MB_NCW) mb_products_k<1>(slot, ph.soff, ph.moff, Rc, row_base, ph.N, bias_l, nullptr, xin, op4, ph.K, B, wave, lane, resid_epi(mb_edge(A, l, E_X3)));
+                else                      mb_products_k<2>(slot, ph.soff, ph.moff, Rc, row_base, ph.N, bias_l, nullptr, xin, op4, ph.K, B, wave, lane, resid_epi(mb_edge(A, l, E_X3)));
+            } else if constexpr (Q) {
                 if (groups * B <= MB_NCW) mb_products_q<1, Q1>(slot, ph.soff, Rc, row_base, ph.N, bias_l, nullptr, xin, op4, ph.K, B, wave, lane, resid_epi(mb_edge(A, l, E_X3)), ph.moff);
                 else                      mb_products_q<2, Q1>(slot, ph.soff, Rc, row_base, ph.N, bias_l, nullptr, xin, op4, ph.K, B, wave, lane, resid_epi(mb_edge(A, l, E_X3)), ph.moff);
             } else {
@@ -1521,22 +1756,25 @@ __device__ __forceinline__ void mb_body(mb_kargs A_) {
     // ---------------- final LayerNorm + logits (of the token rows that want them) ----------------
     const int n_out = A->n_out;
     unsigned pf0[48];
-    mb_te_first(A, Q, Q1, pf0, lane, wave);
+    mb_te_first<QK>(A, Q, Q1, pf0, lane, wave);
     if (wave < n_out) {
         const int br = A->out_row[wave];
         if constexpr (Q) {
-            mb_ln_row<NP, Q, Q1>(A, c, L > 0 ? mb_edge(A, L - 1, E_X3) + (size_t) br * RG : nullptr, lnp, L > 0 ? nullptr : A->lnf_w, L > 0 ? nullptr : A->lnf_b, br, lane,
+            mb_ln_row<NP, Q, Q1, QK>(A, c, L > 0 ? mb_edge(A, L - 1, E_X3) + (size_t) br * RG : nullptr, lnp, L > 0 ? nullptr : A->lnf_w, L > 0 ? nullptr : A->lnf_b, br, lane,
                              (wa_f16 *) (xinB + (size_t) wave * opB), nullptr, 0, 0, 3000u, pk[8 * br]);
         } else {
-            if (L > 0) mb_ln_row<NP, Q, Q1>(A, c, mb_edge(A, L - 1, E_X3) + (size_t) br * RG, lnp, nullptr, nullptr, br, lane, (wa_f16 *) (xinB + (size_t) wave * opB), nullptr, 0, 0, 3000u);
-            else       mb_ln_row<NP, Q, Q1>(A, c, nullptr, lnp, A->lnf_w, A->lnf_b, br, lane, (wa_f16 *) (xinB + (size_t) wave * opB), nullptr, 0, 0, 3000u, pk[8 * br]);      // (a model without layers: tests)
+            if (L > 0) mb_ln_row<NP, Q, Q1, QK>(A, c, mb_edge(A, L - 1, E_X3) + (size_t) br * RG, lnp, nullptr, nullptr, br, lane, (wa_f16 *) (xinB + (size_t) wave * opB), nullptr, 0, 0, 3000u);
+            else       mb_ln_row<NP, Q, Q1, QK>(A, c, nullptr, lnp, A->lnf_w, A->lnf_b, br, lane, (wa_f16 *) (xinB + (size_t) wave * opB), nullptr, 0, 0, 3000u, pk[8 * br]);      // (a model without layers: tests)
         }
     }
     bool want_rec = false;
     for (int m = 0; m < n_out; ++m) want_rec = want_rec || A->rows[A->out_row[m]].smask != nullptr;
     float * lg = (float *) area;            // (the gathered-inputs area holds nothing any more) the workgroup's logits, staged for whole-line stores and the records
     wa_barrier_lds();
-    if constexpr (Q1) {
+    if constexpr (QK) {
+        if (n_out <= 2) mb_logits_k<2>(A, xinB, opB, n_out, lane, wave, pf0, lg); else if (n_out <= 4) mb_logits_k<4>(A, xinB, opB, n_out, lane, wave, pf0, lg);
+        else if (n_out <= 5) mb_logits_k<5>(A, xinB, opB, n_out, lane, wave, pf0, lg); else mb_logits_k<8>(A, xinB, opB, n_out, lane, wave, pf0, lg);
+    } else if constexpr (Q1) {
         if (n_out <= 2) mb_logits_q1<2>(A, xinB, opB, n_out, lane, wave, pf0, lg); else if (n_out <= 4) mb_logits_q1<4>(A, xinB, opB, n_out, lane, wave, pf0, lg);
         else if (n_out <= 5) mb_logits_q1<5>(A, xinB, opB, n_out, lane, wave, pf0, lg); else mb_logits_q1<8>(A, xinB, opB, n_out, lane, wave, pf0, lg);
     } else if constexpr (Q) {
@@ -1584,6 +1822,23 @@ bool MB_CAT(wa_rows_launch_q1_np, WA_ROWS_NP)(hipStream_t s, const wa_rows_args 
     hipLaunchKernelGGL(MB_CAT(k_decode_rows_q1_np, WA_ROWS_NP), dim3(n_wg), dim3(MB_THREADS), lds, s, a);
     return hipGetLastError() == hipSuccess;
 }
+#elif defined(WA_ROWS_K_TU)
+// The step for a Q6_K / Q3_K model (Q8_K operand rows): again a kernel of its own per width in a code object of its own (-DWA_ROWS_K_TU)
+__global__ __launch_bounds__(MB_THREADS) void MB_CAT(k_decode_rows_k_np, WA_ROWS_NP)(const wa_rows_args A) {
+    mb_body<WA_ROWS_NP, true, false, true>((mb_kargs) __builtin_amdgcn_kernarg_segment_ptr());
+}
+bool MB_CAT(wa_rows_launch_k_np, WA_ROWS_NP)(hipStream_t s, const wa_rows_args & a, int n_wg, size_t lds) {
+    int dev = 0;
+    (void) hipGetDevice(&dev);
+    static bool attr_set[64] = {};
+    if (!attr_set[dev & 63]) {
+        if (hipFuncSetAttribute((const void *) MB_CAT(k_decode_rows_k_np, WA_ROWS_NP), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return false;
+        attr_set[dev & 63] = true;
+    }
+    if (!a.te_d || !a.te_sc || a.row_gr < 4 * a.d) return false;
+    hipLaunchKernelGGL(MB_CAT(k_decode_rows_k_np, WA_ROWS_NP), dim3(n_wg), dim3(MB_THREADS), lds, s, a);
+    return hipGetLastError() == hipSuccess;
+}
 #else
 __global__ __launch_bounds__(MB_THREADS) void MB_CAT(k_decode_rows_np, WA_ROWS_NP)(const wa_rows_args A) {
     mb_body<WA_ROWS_NP, false>((mb_kargs) __builtin_amdgcn_kernarg_segment_ptr());
@@ -1593,8 +1848,10 @@ __global__ __launch_bounds__(MB_THREADS) void MB_CAT(k_decode_rows_q_np, WA_ROWS
     mb_body<WA_ROWS_NP, true>((mb_kargs) __builtin_amdgcn_kernarg_segment_ptr());
 }
 bool MB_CAT(wa_rows_launch_q1_np, WA_ROWS_NP)(hipStream_t s, const wa_rows_args & a, int n_wg, size_t lds);
+bool MB_CAT(wa_rows_launch_k_np, WA_ROWS_NP)(hipStream_t s, const wa_rows_args & a, int n_wg, size_t lds);
 bool MB_CAT(wa_rows_launch_np, WA_ROWS_NP)(hipStream_t s, const wa_rows_args & a, int n_wg, size_t lds) {
     if (a.quant == 2) return MB_CAT(wa_rows_launch_q1_np, WA_ROWS_NP)(s, a, n_wg, lds);
+    if (a.quant == 3) return MB_CAT(wa_rows_launch_k_np, WA_ROWS_NP)(s, a, n_wg, lds);
     int dev = 0;
     (void) hipGetDevice(&dev);
     static bool attr_set[64] = {};
@@ -1614,7 +1871,9 @@ bool wa_rows_launch_np20(hipStream_t s, const wa_rows_args & a, int n_wg, size_t
 
 size_t wa_rows_lds_bytes(int d, int B, int n_wg, int quant, int * slot_bytes) {
     if (B < 1 || B > WA_ROWS_MAX || d < 64 || d > WA_MEGA_MAX_D || (d & 127) != 0 || n_wg < 1) return 0;
-    const size_t opB = quant ? mq_row_bytes(d >> 5) : (size_t) d * 2, op4 = quant ? mq_row_bytes((4 * d) >> 5) : (size_t) 4 * d * 2;
+    if (quant == 3 && (d & 255) != 0) return 0;     // (K formats: blocks of 256)
+    const size_t opB = quant == 3 ? mk_row_bytes(d >> 8) : quant ? mq_row_bytes(d >> 5) : (size_t) d * 2;
+    const size_t op4 = quant == 3 ? mk_row_bytes((4 * d) >> 8) : quant ? mq_row_bytes((4 * d) >> 5) : (size_t) 4 * d * 2;
     const size_t xinB_bytes = ((size_t) B * opB + 255) & ~(size_t) 255;
     size_t area = (size_t) B * op4;
     if (area < MB_ATT_BYTES) area = MB_ATT_BYTES;
@@ -1622,7 +1881,7 @@ size_t wa_rows_lds_bytes(int d, int B, int n_wg, int quant, int * slot_bytes) {
     const size_t fixed = 1792 + 2 * (((size_t) d * 4 + 1023) & ~(size_t) 1023) + xinB_bytes + area;
     auto rpw = [&](int N) { const int r = (N + n_wg - 1) / n_wg; return (r + 1) & ~1; };
     if (rpw(d) > 8) return 0;                       // (xres holds 8 residual values per token row)
-    if (quant && (4 * d) / 32 > n_wg) return 0;     // (whole-block ownership of the first MLP product: one workgroup per block)
+    if (quant && quant != 3 && (4 * d) / 32 > n_wg) return 0;     // (whole-block ownership of the first MLP product: one workgroup per block)
     // a slot holds at least one task group of every phase; the whole chunk of a phase when there is room (fewer barriers)
     size_t need_min, want = 0;
     if (quant == 2) {           // a third region per row, the block minimums: the kernel's own rule (mq1_slot_need), no slack beyond it
@@ -1630,6 +1889,11 @@ size_t wa_rows_lds_bytes(int d, int B, int n_wg, int quant, int * slot_bytes) {
         want = std::max(want, (size_t) mq1_slot_need((rpw(3 * d) + 7) / 8 * 8, d));
         want = std::max(want, (size_t) mq1_slot_need(32, d));
         want = std::max(want, (size_t) mq1_slot_need((rpw(d) + 7) / 8 * 8, 4 * d));
+    } else if (quant == 3) {    // Q6_K / Q3_K: quants | scale bytes | d, the kernel's own rule (mk_slot_need); the first MLP product's rows are dealt evenly
+        need_min = (size_t) mk_slot_need(8, 4 * d);
+        want = std::max(want, (size_t) mk_slot_need((rpw(3 * d) + 7) / 8 * 8, d));
+        want = std::max(want, (size_t) mk_slot_need((rpw(4 * d) + 7) / 8 * 8, d));
+        want = std::max(want, (size_t) mk_slot_need((rpw(d) + 7) / 8 * 8, 4 * d));
     } else if (quant) {
         auto rowb = [&](int K) { return (size_t) K + MB_PAD + (size_t) (K >> 3) + MB_PAD; };
         need_min = 8 * rowb(4 * d) + 3072;
@@ -1645,7 +1909,7 @@ size_t wa_rows_lds_bytes(int d, int B, int n_wg, int quant, int * slot_bytes) {
         want = ((want + 1023) & ~(size_t) 1023) + 1024;
     }
     const size_t total_max = 160 * 1024;
-    if (quant != 2 && fixed + 2 * (need_min + 1024) > total_max) return 0;
+    if (quant < 2 && fixed + 2 * (need_min + 1024) > total_max) return 0;
     if (fixed + 2 * need_min > total_max) return 0;
     size_t slot = std::min(want, (total_max - fixed) / 2);
     slot &= ~(size_t) 1023;                         // whole LDS-DMA pieces
@@ -1663,4 +1927,4 @@ bool wa_launch_decode_rows(hipStream_t s, const wa_rows_args & a, int n_wg) {
     return wa_rows_launch_np20(s, a, n_wg, lds);
 }
 #endif
-#endif      // WA_ROWS_Q1_TU
+#endif      // WA_ROWS_Q1_TU, WA_ROWS_K_TU
