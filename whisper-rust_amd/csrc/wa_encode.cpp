@@ -114,9 +114,10 @@ bool wa_state_alloc(whisper_context & ctx, whisper_state & st) {
         // single token is then that kernel with one row, at every width.  Without the switch every pass of these models is the launch sequence.
         const char * q1 = getenv("WHISPER_AMD_ROWS_Q1");
         const bool rows_q1 = shape_ok && wa_wtype_has_min(ctx.model.wtype) && q1 && q1[0] == '1';
-        // Q6_K / Q3_K: the same with k_decode_rows_k_np*, opt-in by WHISPER_AMD_ROWS_K=1.  Q5_K, Q2_K and Q4_K have no such kernel: the switch does nothing for them.
-        const char * qk = getenv("WHISPER_AMD_ROWS_K");
-        const bool rows_k = shape_ok && wa_wtype_rows_k(ctx.model.wtype) && dt % 256 == 0 && qk && qk[0] == '1';
+        // Q6_K / Q3_K: the same with k_decode_rows_k_np*, opt-in by WHISPER_AMD_ROWS_K=1; Q5_K / Q2_K: with k_decode_rows_k5_np* / _k2_np*, opt-in by a switch
+        // of their own, WHISPER_AMD_ROWS_KM=1.  Either switch does nothing for any other format.  Q4_K has no such kernel.
+        const char * qk = getenv("WHISPER_AMD_ROWS_K"), * qkm = getenv("WHISPER_AMD_ROWS_KM");
+        const bool rows_k = shape_ok && dt % 256 == 0 && ((wa_wtype_rows_k(ctx.model.wtype) && qk && qk[0] == '1') || (wa_wtype_rows_km(ctx.model.wtype) && qkm && qkm[0] == '1'));
         if (st.mega_form.enabled()) {
             if (!dev_alloc(st.d_mega_cgr, (size_t) hp.n_text_layer * Ht * WA_MEGA_CGR)) return false;
             if (!dev_alloc(st.d_mega_gr, (size_t) hp.n_text_layer * WA_MEGA_EDGES * 4 * dt)) return false;
@@ -136,6 +137,10 @@ bool wa_state_alloc(whisper_context & ctx, whisper_state & st) {
                 const char * sr = getenv("WHISPER_AMD_SINGLE_ROWS");
                 st.single_via_rows = st.rows_form.enabled() && wa_rows_lds_bytes(dt, 1, std::min(ctx.model.n_cu, 256), quant, &slot) != 0 &&
                                      (rows_q1 || rows_k || (sr ? sr[0] == '1' : (ctx.model.wtype != 1 && dt > 768)));
+                // Q5_K / Q2_K: the form's buffers now, not with the first pass.  Every pass of such a state is a rows pass, so nothing is saved by waiting, and a
+                // lock-step group of more members than fit one launch (8 at d = 1280, where 7 fit) sends its members off alone at once: a member allocating
+                // (a memset on the legacy stream) while another captures its launch sequence fails that capture.
+                if (wa_wtype_rows_km(ctx.model.wtype) && st.rows_form.enabled()) (void) wa_rows_prepare(ctx, st);      // (no memory: the form is off, the launch sequence serves)
             }
             // (the copy stream, events and pinned buffers of the host overlap are created on first use, wa_spec_begin: a state that
             //  only ever runs inside whisper_amd_full_batch keeps ONE stream - extra streams cost the concurrent chunks their overlap)

@@ -18,11 +18,12 @@ struct wa_mega_layer {          // device-resident table, one entry per decoder 
     // quantised model (Q5_0 / Q8_0 files): the *_w pointers then hold the signed-byte quants in the kernel layout of wa_quant.hip
     // ([row][lane 0..7][block][4]) and these the F32 block scales [row][block]; null for an F16 model
     const float * qkv_d, * out_d, * cq_d, * co_d, * fc1_d, * fc2_d;
-    // Q4_1 / Q5_1 files: the F32 block minimums [row][block], null otherwise.  At the end: only the several-rows kernel for these formats
-    // (wa_rows.hip: k_decode_rows_q1_np*) reads them, every other kernel reads the fields above where they always were.
+    // Q4_1 / Q5_1 files: the F32 block minimums [row][block]; Q5_K / Q2_K files: the blocks' F32 dmin [row][block]; null otherwise.  At the end: only
+    // the several-rows kernels for these formats (wa_rows.hip: k_decode_rows_q1_np*, _k5_np*, _k2_np*) read them, every other kernel reads the fields
+    // above where they always were.
     const float * qkv_m, * out_m, * cq_m, * co_m, * fc1_m, * fc2_m;
     // K-format files (wa_quantk.h): the *_w pointers hold the quants [row][lane][block][group][4], the *_d pointers the blocks' F32 d [row][block],
-    // and these the 16 scale bytes of every block; null otherwise.  At the end for the same reason: only k_decode_rows_k_np* (Q6_K / Q3_K) reads them.
+    // and these the 16 scale bytes of every block; null otherwise.  At the end for the same reason: only k_decode_rows_k_np* (Q6_K / Q3_K), _k5_np* and _k2_np* read them.
     const int8_t * qkv_sc, * out_sc, * cq_sc, * co_sc, * fc1_sc, * fc2_sc;
 };
 

@@ -11,7 +11,7 @@
 //     is off the vector-memory queues of the waves that poll hand-offs, and the products read weights AND activations from LDS;
 //   * LayerNorm is one wave per token row (no cross-wave reductions);
 //   * hand-offs are the 8-byte {tag, value} granules of wa_mega.hip.
-// Three kernels per LayerNorm width, one per weight format family (wa_rows_args::quant), each with its own code and registers:
+// One kernel per LayerNorm width and weight format family (wa_rows_args::quant), each with its own code and registers:
 //   k_decode_rows_np*     F16 weights, F16 operand rows;
 //   k_decode_rows_q_np*   Q5_0 / Q8_0 weights (quants + block scales), operand rows quantised to Q8_0, blocks handed over as 8 quads + scale;
 //   k_decode_rows_q1_np*  Q4_1 / Q5_1 weights (quants + block scales + block minimums), operand rows quantised to Q8_1: the word that holds a
@@ -20,7 +20,11 @@
 //   k_decode_rows_k_np*   Q6_K / Q3_K weights (quants + 16 scale bytes and one F32 d per block of 256), operand rows quantised to Q8_K.  No producer
 //                         holds a whole block of what it publishes, so attention outputs and the MLP's hidden row travel in F32, one granule
 //                         per value, and the gathering waves quantise them into LDS; LayerNorm rows are quantised by the wave that holds
-//                         them.  Opt-in: WHISPER_AMD_ROWS_K=1, 1..8 rows.  Q5_K, Q2_K and Q4_K keep the launch sequence.
+//                         them.  Opt-in: WHISPER_AMD_ROWS_K=1, 1..8 rows.
+//   k_decode_rows_k5_np*, Q5_K and Q2_K weights, the K formats whose product has a minimum term (a dmin per block beside the d): as above, and the
+//   k_decode_rows_k2_np*  quantising waves store each block's 16 sums with the row.  Q5_K: one lane of a weight row's eight runs the minimum chain of a
+//                         token row beside the lane chains; Q2_K: the minimums enter the lane chains, per block before the product term.  Opt-in:
+//                         WHISPER_AMD_ROWS_KM=1, 1..8 rows.  Q4_K (the interleaved 8-row product of wa_quant4.h) keeps the launch sequence.
 // Arithmetic is the reference order throughout (same chains, trees, certified F64 sums as wa_exact.hip): logits are bit-identical to
 // the launch sequence, which stays as the fallback.
 #pragma once
@@ -51,11 +55,11 @@ struct wa_rows_args {
     const wa_mega_layer * layers; int n_layer, d, n_head, n_vocab; float eps;
     double rn_d;
     const wa_f16 * te; const float * pe; const float * lnf_w, * lnf_b; const wa_f16 * gelu;
-    const float * te_d; int quant;                      // quant: 0 F16 weights, 1 Q5_0 / Q8_0 (Q8_0 operand rows), 2 Q4_1 / Q5_1 (Q8_1 operand rows, block minimums), 3 Q6_K / Q3_K (Q8_K operand rows)
-    const float * te_m;                                 // quant == 2: block minimums of the token embedding (the layers' are in wa_mega_layer)
+    const float * te_d; int quant;                      // quant: 0 F16 weights, 1 Q5_0 / Q8_0 (Q8_0 operand rows), 2 Q4_1 / Q5_1 (Q8_1 operand rows, block minimums), 3 Q6_K / Q3_K (Q8_K operand rows), 4 Q5_K / Q2_K (Q8_K operand rows with block sums, dmin)
+    const float * te_m;                                 // quant == 2: block minimums of the token embedding (the layers' are in wa_mega_layer); quant == 4: its blocks' dmin
     unsigned long long kv_layer_stride, cross_layer_stride;
     int cross_tpad, T;
-    unsigned long long * granules; int row_gr;          // [layer][8][B][row_gr] hand-off granules (row_gr = 2 d; quant == 3: 4 d, the MLP's hidden row travels in F32)
+    unsigned long long * granules; int row_gr;          // [layer][8][B][row_gr] hand-off granules (row_gr = 2 d; quant >= 3: 4 d, the MLP's hidden row travels in F32)
     unsigned long long * cross_gr;                      // [layer][B][head][WA_ROWS_CGR]
     float * logits;                                     // [B][n_vocab]
     unsigned * status;                                  // [0] 0 = ok, else the code of the hand-off that timed out; [1] = seq once the launch has run
@@ -69,7 +73,8 @@ struct wa_rows_args {
     int token_beg, token_eot;                           // (records) first timestamp token, end-of-text token
     int n_out, out_row[WA_ROWS_MAX];                    // token rows whose logits are wanted (the reference flags batch.logits rows): logits row m = token row out_row[m]
     wa_rows_row rows[WA_ROWS_MAX];
-    const int8_t * te_sc;                               // quant == 3: the token embedding's 16 scale bytes per block (te: its quants, te_d: its d)
+    const int8_t * te_sc;                               // quant >= 3: the token embedding's 16 scale bytes per block (te: its quants, te_d: its d)
+    int wtype;                                          // quant == 4: the ggml type of the weights, 13 Q5_K or 10 Q2_K - which of the two kernels is launched
 };
 
 // LDS the kernel needs for B rows of a d-wide model with `n_wg` workgroups; 0 when it does not fit (the caller keeps the launch sequence).

@@ -286,18 +286,31 @@ __device__ __forceinline__ void mb_products_q(const unsigned char * slot, int so
 // elements of a block and chains  acc = fma(d_x d_w, (float) sumi, acc)  over the blocks in order; three DPP adds are hsum_float_8.
 // -------------------------------------------------------------------------------------------------
 __host__ __device__ __forceinline__ int mk_ls(int nbk) { return 32 * nbk + 16; }         // bytes between the lanes' runs of an operand row
-__host__ __device__ __forceinline__ size_t mk_row_bytes(int nbk) { return ((size_t) 8 * mk_ls(nbk) + (size_t) 4 * nbk + 15) & ~(size_t) 15; }
+// (sums: the formats with a minimum term, Q5_K and Q2_K - k_decode_rows_k5_np* / _k2_np* -, read the operand's block sums.  Their rows hold, between the
+//  quants and the d, the 16 int16 sums of 16 elements of every block, as block_q8_K::bsums orders them - ONE layout for both: Q2_K's lane u reads sums 2 u
+//  and 2 u + 1 as dword u of the block, Q5_K's chain the same dwords, four to a 16-byte read, and adds the halves; pair sums alone would have saved 16
+//  bytes a block and served Q5_K only.  In front of the d, so that they start on a 16-byte boundary whatever the block count.)
+__host__ __device__ __forceinline__ size_t mk_xd_off(int nbk, bool sums = false) { return (size_t) 8 * mk_ls(nbk) + (sums ? (size_t) 32 * nbk : 0); }       // where a row's d start
+__host__ __device__ __forceinline__ size_t mk_row_bytes(int nbk, bool sums = false) { return (mk_xd_off(nbk, sums) + (size_t) 4 * nbk + 15) & ~(size_t) 15; }
 // A slot's image of rc weight rows of length K: quants (row stride K + MB_PAD) | scale bytes (row stride K / 16 + MB_PAD) | the rows' d, rc K / 256
 // consecutive floats - a row of K = 256 has ONE, too short for the 16-byte cells of mb_dma_rows, so they come as dwords, 64 per instruction -, each
 // region in whole KB, then the KB of bias and column scale.  The kernel and wa_rows_lds_bytes share this rule exactly (as mq1_slot_need).
 __host__ __device__ __forceinline__ int mk_soff(int rc, int K) { return (rc * (K + MB_PAD) + 1023) & ~1023; }
 __host__ __device__ __forceinline__ int mk_doff(int rc, int K) { return mk_soff(rc, K) + ((rc * ((K >> 4) + MB_PAD) + 1023) & ~1023); }
 __host__ __device__ __forceinline__ int mk_slot_need(int rc, int K) { return mk_doff(rc, K) + ((rc * (K >> 8) * 4 + 1023) & ~1023) + 1024; }
+// Q5_K / Q2_K: a fourth region, the rows' dmin, of the size of the d and brought in the same way - quants | scale bytes | d | dmin | the KB of bias and column scale
+__host__ __device__ __forceinline__ int mkm_moff(int rc, int K) { return mk_doff(rc, K) + ((rc * (K >> 8) * 4 + 1023) & ~1023); }
+__host__ __device__ __forceinline__ int mkm_slot_need(int rc, int K) { return mkm_moff(rc, K) + ((rc * (K >> 8) * 4 + 1023) & ~1023) + 1024; }
+// the format of a K-format instantiation (mb_body's QK): none, Q6_K / Q3_K, Q5_K, Q2_K; minus one it is wa_quantk_dev.h's WK_* of the product
+enum { MK_NO = 0, MK_Q6 = 1, MK_Q5 = 2, MK_Q2 = 3 };
+static_assert(MK_Q6 - 1 == WK_Q6 && MK_Q5 - 1 == WK_Q5 && MK_Q2 - 1 == WK_Q2, "mb_dotk hands QK - 1 to wk_block");
 
 // quantize_row_q8_K_ref of one block held by a wave, lane i with elements i, 64 + i, 128 + i, 192 + i of it (v[0..3]: how a LayerNorm row and a
 // swept run of granules lie in a wave) -> the operand row `op` (block blk of nbk).  The scale comes from the FIRST element of largest magnitude, with
 // its sign: a lane's lowest such element by strict comparison in index order, then the lowest index over the wave (k_quantize_q8_K's rule for
-// this distribution of the elements).  All lanes take part.
+// this distribution of the elements).  All lanes take part.  SUMS: the block's bsums as well (mk_xd_off) - register k holds element 64 k + lane, so sum
+// 4 k + (lane >> 4) is register k's quant added up over one 16-lane DPP row (integers: exact in any order; an all-zero block has zero quants and zero sums)
+template <bool SUMS = false>
 __device__ __forceinline__ void mk_quant_block(const float (&v)[4], int lane, unsigned char * op, int nbk, int blk) {
     float amax = fabsf(v[0]); int at = lane;
 #pragma unroll
@@ -313,43 +326,116 @@ __device__ __forceinline__ void mk_quant_block(const float (&v)[4], int lane, un
     unsigned char * run = op + (size_t) ((lane & 31) >> 2) * mk_ls(nbk) + (size_t) blk * 32 + (lane >> 5) * 4;      // element 64 k + i: group 2 k + (i >> 5), lane (i & 31) >> 2, byte i & 3
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-        const unsigned q = (unsigned) (wmax != 0.0f ? min(127, (int) rintf(iscale * v[k])) : 0) & 0xffu;
+        const int qi = wmax != 0.0f ? min(127, (int) rintf(iscale * v[k])) : 0;
+        const unsigned q = (unsigned) qi & 0xffu;
         const unsigned w = q | (dpp_u32<0x101>(q) << 8) | (dpp_u32<0x102>(q) << 16) | (dpp_u32<0x103>(q) << 24);      // row_shl:1..3
         if ((lane & 3) == 0) *(unsigned *) (run + 8 * k) = w;
+        if constexpr (SUMS) {
+            int s = qi;
+            s += __builtin_amdgcn_update_dpp(0, s, 0x128, 0xf, 0xf, true);      // row_ror:8, 4, 2, 1: the row's sum in every lane of it
+            s += __builtin_amdgcn_update_dpp(0, s, 0x124, 0xf, 0xf, true);
+            s += __builtin_amdgcn_update_dpp(0, s, 0x122, 0xf, 0xf, true);
+            s += __builtin_amdgcn_update_dpp(0, s, 0x121, 0xf, 0xf, true);
+            if ((lane & 15) == 0) ((short *) (op + (size_t) 8 * mk_ls(nbk)))[16 * blk + 4 * k + (lane >> 4)] = (short) s;
+        }
     }
-    if (lane == 0) ((float *) (op + (size_t) 8 * mk_ls(nbk)))[blk] = dq;
+    if (lane == 0) ((float *) (op + mk_xd_off(nbk, SUMS)))[blk] = dq;
 }
 
-template <int BC>
+// The block's 16 scale bytes in every lane of an output's eight, from the halves they hold (lanes 0..3 the first eight bytes, lanes 4..7 the second, as
+// the Q6_K form reads them): one DPP exchange of the two registers.  Q5_K: lo = the eight scales, hi = the eight minimums.  Q2_K: the lane's own half
+// is its scale pair; its two minimums are the high nibbles of byte u of lo and byte u of hi.
+__device__ __forceinline__ void mk_sc16(const wk_i2 half, int u, wk_i2 & lo, wk_i2 & hi) {
+    wk_i2 up, dn;
+    up.x = (int) dpp_u32<0x104>((unsigned) half.x); up.y = (int) dpp_u32<0x104>((unsigned) half.y);      // row_shl:4: lane u reads lane u + 4
+    dn.x = (int) dpp_u32<0x114>((unsigned) half.x); dn.y = (int) dpp_u32<0x114>((unsigned) half.y);      // row_shr:4: lane u reads lane u - 4
+    lo = u < 4 ? half : dn; hi = u < 4 ? up : half;
+}
+__device__ __forceinline__ int mk_pair_sum(int bs2) { return ((bs2 << 16) >> 16) + (bs2 >> 16); }      // bsums[2 g] + bsums[2 g + 1] of the dword that holds both
+// Q5_K: one block's step of the minimum chain of ONE token row (wa_qk_dot: summs = summs + (-d_x dmin_w) * (float) sum_g m[g] (bsums[2 g] + bsums[2 g + 1]),
+// a multiplication, then an addition) - mm: the block's eight minimums, xs: the token row's 16 sums of this block
+__device__ __forceinline__ float mk_min5(wk_i2 mm, const unsigned char * xs, float dx, float dwm, float summs) {
+    const wk_i4 g0 = *(const wk_i4 *) xs, g1 = *(const wk_i4 *) (xs + 16);
+    const int tot = wk_byte<WK_Q5>(mm, 0) * mk_pair_sum(g0.x) + wk_byte<WK_Q5>(mm, 1) * mk_pair_sum(g0.y) + wk_byte<WK_Q5>(mm, 2) * mk_pair_sum(g0.z) + wk_byte<WK_Q5>(mm, 3) * mk_pair_sum(g0.w) +
+                    wk_byte<WK_Q5>(mm, 4) * mk_pair_sum(g1.x) + wk_byte<WK_Q5>(mm, 5) * mk_pair_sum(g1.y) + wk_byte<WK_Q5>(mm, 6) * mk_pair_sum(g1.z) + wk_byte<WK_Q5>(mm, 7) * mk_pair_sum(g1.w);
+    const float dm = -dx * dwm;
+    const float p = dm * (float) tot;
+    return summs + p;
+}
+// Q2_K: lane u's minimum term of one block and one token row, (float) (m[2 u] bsums[2 u] + m[2 u + 1] bsums[2 u + 1]) - ma, mb: the two minimums, bs2: dword u of the row's sums
+__device__ __forceinline__ float mk_min2(int ma, int mb, int bs2) { return (float) (ma * ((bs2 << 16) >> 16) + mb * (bs2 >> 16)); }
+
+
+// F: the weight format (WK_Q6, WK_Q5, WK_Q2).  The two with a minimum term (wm: the row's dmin) in the reference's order, wa_quantk.h:
+//   Q5_K: lane u of the output's eight runs the minimum chain of the task's token row u beside the lane chains (k_kgemm_exact's way: no exchange
+//         per block, one DPP move hands the total to lane 0 at the end); the result is hsum_float_8(acc) + summs
+//   Q2_K: lane u adds its two sub-blocks' minimums into acc by an fma of their own, per block before the product term
+// the running sum of the minimum chain a lane keeps beside its lane chains: Q5_K only (an empty member elsewhere, so that the other formats' code is what it was)
+template <int F> struct mk_min_chain {};
+template <> struct mk_min_chain<WK_Q5> { float summs = 0.0f; };
+// Q5_K, Q2_K: one weight block (quants w0 | w1, its 16 scale bytes lo | hi, d, dmin) against block b of BC token rows, the step of both chains
+template <int BC, int F>
+__device__ __forceinline__ void mk_block_step(wk_i4 w0, wk_i4 w1, wk_i2 lo, wk_i2 hi, float dw, float dwm, int u, int nbk, int b, const unsigned char * const (&xq)[BC], const float * const (&xd)[BC],
+                                              const unsigned char * xown /* Q5_K: the token row whose minimum chain this lane runs */, float (&acc)[BC], mk_min_chain<F> & mc) {
+    wk_i2 s = lo;
+    int ma = 0, mb = 0;
+    if constexpr (F == WK_Q5) mc.summs = mk_min5(hi, xown + (size_t) 8 * mk_ls(nbk) + 32 * b, ((const float *) (xown + mk_xd_off(nbk, true)))[b], dwm, mc.summs);
+    if constexpr (F == WK_Q2) {
+        const int sh = 8 * (u & 3) + 4;
+        s = u < 4 ? lo : hi;
+        ma = ((u < 4 ? lo.x : lo.y) >> sh) & 15; mb = ((u < 4 ? hi.x : hi.y) >> sh) & 15;
+    }
+#pragma unroll
+    for (int j = 0; j < BC; ++j) {
+        const wk_i4 x0 = *(const wk_i4 *) (xq[j] + 32 * b), x1 = *(const wk_i4 *) (xq[j] + 32 * b + 16);
+        const float dx = xd[j][b];
+        const float dd = dx * dw;
+        if constexpr (F == WK_Q2) {
+            const float dn = -dx * dwm;
+            acc[j] = fmaf(dn, mk_min2(ma, mb, ((const int *) xd[j] - 8 * nbk)[8 * b + u]), acc[j]);      // (a row's sums end where its d start)
+        }
+        acc[j] = fmaf(dd, (float) wk_block<F>(w0, w1, x0, x1, s), acc[j]);
+    }
+}
+template <int BC, int F = WK_Q6>
 __device__ __forceinline__ void mb_dotk(const unsigned char * wq, const unsigned char * ws, const float * wd, const unsigned char * xop, size_t op_bytes, int u, int nbk,
-                                        int b0, int B, float (&res)[BC]) {
+                                        int b0, int B, float (&res)[BC], const float * wm = nullptr) {
+    constexpr bool KM = F != WK_Q6;
     float acc[BC];
     const unsigned char * xq[BC]; const float * xd[BC];
 #pragma unroll
     for (int j = 0; j < BC; ++j) {
         acc[j] = 0.0f;
         const unsigned char * r = xop + (size_t) (b0 + j < B ? b0 + j : B - 1) * op_bytes;
-        xq[j] = r + (size_t) u * mk_ls(nbk); xd[j] = (const float *) (r + (size_t) 8 * mk_ls(nbk));
+        xq[j] = r + (size_t) u * mk_ls(nbk); xd[j] = (const float *) (r + mk_xd_off(nbk, KM));
     }
+    mk_min_chain<F> mc;
 #pragma unroll 2
     for (int b = 0; b < nbk; ++b) {
         const wk_i4 w0 = *(const wk_i4 *) (wq + 32 * b), w1 = *(const wk_i4 *) (wq + 32 * b + 16);
-        const wk_i2 s = *(const wk_i2 *) (ws + 16 * b);
+        const wk_i2 s = *(const wk_i2 *) (ws + 16 * b);      // (ws: Q6_K the lane's half, else the block's 16 bytes)
         const float dw = wd[b];
+        if constexpr (KM) mk_block_step<BC, F>(w0, w1, s, *(const wk_i2 *) (ws + 16 * b + 8), dw, wm[b], u, nbk, b, xq, xd, xop + (size_t) (b0 + u < B ? b0 + u : B - 1) * op_bytes, acc, mc);
+        else {
 #pragma unroll
-        for (int j = 0; j < BC; ++j) {
-            const wk_i4 x0 = *(const wk_i4 *) (xq[j] + 32 * b), x1 = *(const wk_i4 *) (xq[j] + 32 * b + 16);
-            const float dd = xd[j][b] * dw;
-            acc[j] = fmaf(dd, (float) wk_block<WK_Q6>(w0, w1, x0, x1, s), acc[j]);
+            for (int j = 0; j < BC; ++j) {
+                const wk_i4 x0 = *(const wk_i4 *) (xq[j] + 32 * b), x1 = *(const wk_i4 *) (xq[j] + 32 * b + 16);
+                const float dd = xd[j][b] * dw;
+                acc[j] = fmaf(dd, (float) wk_block<WK_Q6>(w0, w1, x0, x1, s), acc[j]);
+            }
         }
     }
 #pragma unroll
-    for (int j = 0; j < BC; ++j) res[j] = wk_hsum8(acc[j]);
+    for (int j = 0; j < BC; ++j) {
+        res[j] = wk_hsum8(acc[j]);
+        if constexpr (F == WK_Q5) res[j] = res[j] + wk_from_lane(mc.summs, j);
+    }
 }
-// product tasks of a K-format chunk (as mb_products_q): the slot holds the rows' quants, then - `soff` bytes in - their scale bytes and - `doff` - their d
-template <int BC, typename EPI>
+// product tasks of a K-format chunk (as mb_products_q): the slot holds the rows' quants, then - `soff` bytes in - their scale bytes, - `doff` - their d and
+// (Q5_K, Q2_K) - `moff` - their dmin
+template <int BC, int F = WK_Q6, typename EPI>
 __device__ __forceinline__ void mb_products_k(const unsigned char * slot, int soff, int doff, int Rc, int row_base, int N, const float * bias_l, const float * scale_l,
-                                              const unsigned char * xop, size_t op_bytes, int K, int B, int wave, int lane, EPI epi) {
+                                              const unsigned char * xop, size_t op_bytes, int K, int B, int wave, int lane, EPI epi, int moff = 0) {
     const int nbk = K >> 8, stride_q = K + MB_PAD, stride_s = 16 * nbk + MB_PAD;
     const int groups = (Rc + 7) >> 3, nsub = (B + BC - 1) / BC, per = (B + nsub - 1) / nsub, ntasks = groups * nsub;
     const int u = lane & 7;
@@ -359,8 +445,8 @@ __device__ __forceinline__ void mb_products_k(const unsigned char * slot, int so
         const bool has = ri < Rc && row_base + ri < N && u == 0;
         const float bv = bias_l[ri < 64 ? ri : 63], sv = scale_l ? scale_l[ri < 64 ? ri : 63] : 1.0f;
         float res[BC];
-        mb_dotk<BC>(slot + (size_t) rr * stride_q + (size_t) u * nbk * 32, slot + soff + (size_t) rr * stride_s + 8 * (u >> 2), (const float *) (slot + doff) + (size_t) rr * nbk,
-                    xop, op_bytes, u, nbk, b0, B, res);
+        mb_dotk<BC, F>(slot + (size_t) rr * stride_q + (size_t) u * nbk * 32, slot + soff + (size_t) rr * stride_s + (F == WK_Q6 ? 8 * (u >> 2) : 0), (const float *) (slot + doff) + (size_t) rr * nbk,
+                       xop, op_bytes, u, nbk, b0, B, res, (const float *) (slot + moff) + (size_t) rr * nbk);
         epi(res, b0, b1, row_base + ri, has, bv, sv);
     }
 }
@@ -390,7 +476,7 @@ __device__ __forceinline__ double mb_seq_sum(const float (&xv)[NP], int d, bool 
     }
     return t;
 }
-template <int NP, bool Q = false, bool Q1 = false, bool QK = false>       // Q: the normalised row leaves as Q8_0 (the next product's operand), not as F16; Q1: as Q8_1; QK: as Q8_K
+template <int NP, bool Q = false, bool Q1 = false, int QK = MK_NO>       // Q: the normalised row leaves as Q8_0 (the next product's operand), not as F16; Q1: as Q8_1; QK: as Q8_K
 __device__ __forceinline__ void mb_ln_row(mb_kargs A, mo_ctl & c, gu64 * edge_row /* null: embeddings */, const float * lnp /* LDS: gamma | beta, each d floats in whole KB */, const float * gw_g, const float * gb_g /* global, when non-null */,
                                           int b, int lane_, wa_f16 * dst, float * xres_b, int row_d, int r_d, unsigned code, int token = 0, bool tw = false, int tslot = 0) {
     // (nothing derived from the lane index may live across calls: hoisted out of the layer loop the per-element LDS addresses went to scratch, and every
@@ -410,7 +496,7 @@ __device__ __forceinline__ void mb_ln_row(mb_kargs A, mo_ctl & c, gu64 * edge_ro
             const gch te = (gch) A->te + (size_t) token * d;
 #pragma unroll
             for (int k = 0; k < NP; ++k) { const int i = lane + 64 * k, ic = i < d ? i : d - 1; const float e = h2f(te[ic]) + pe[ic]; xv[k] = i < d ? e : 0.0f; }
-        } else if constexpr (QK) {      // k_dec_embed_k: dequantize_row_q6_K, (d * sc) * q - two roundings -, then + the positional embedding
+        } else if constexpr (QK != MK_NO) {      // k_dec_embed_k: dequantize_row_q6_K, (d * sc) * q - two roundings -, then + the positional embedding
             const int nbk = d >> 8;
             const GAS int8_t * tq = (const GAS int8_t *) A->te + (size_t) token * 8 * nbk * 32;
             const GAS int8_t * tsc = (const GAS int8_t *) A->te_sc + (size_t) token * nbk * 16;
@@ -419,8 +505,20 @@ __device__ __forceinline__ void mb_ln_row(mb_kargs A, mo_ctl & c, gu64 * edge_ro
             for (int k = 0; k < NP; ++k) {
                 const int i = lane + 64 * k, ic = i < d ? i : d - 1, bb = ic >> 8, el = ic & 255;
                 const int q = (int) tq[((size_t) ((el & 31) >> 2) * nbk + bb) * 32 + (el >> 5) * 4 + (el & 3)];
-                const float d1 = td[bb] * (float) (int) tsc[bb * 16 + 8 * ((el >> 4) & 1) + (el >> 5)];
-                float e = d1 * (float) q;
+                float e;
+                if constexpr (QK == MK_Q6) {
+                    const float d1 = td[bb] * (float) (int) tsc[bb * 16 + 8 * ((el >> 4) & 1) + (el >> 5)];
+                    e = d1 * (float) q;
+                } else {        // dequantize_row_q5_K / q2_K: (d * sc) * q, then - (dmin * m), no fma
+                    const gcf tm = (gcf) A->te_m + (size_t) token * nbk;
+                    int sc, mn;
+                    if constexpr (QK == MK_Q5) { sc = (int) (unsigned char) tsc[bb * 16 + (el >> 5)]; mn = (int) (unsigned char) tsc[bb * 16 + 8 + (el >> 5)]; }
+                    else { const int sb = (int) (unsigned char) tsc[bb * 16 + 8 * ((el >> 4) & 1) + (el >> 5)]; sc = sb & 15; mn = sb >> 4; }
+                    const float d1 = td[bb] * (float) sc;
+                    const float m1 = tm[bb] * (float) mn;
+                    const float tq1 = d1 * (float) q;
+                    e = tq1 - m1;
+                }
                 e = e + pe[ic];
                 xv[k] = i < d ? e : 0.0f;
             }
@@ -495,7 +593,7 @@ __device__ __forceinline__ void mb_ln_row(mb_kargs A, mo_ctl & c, gu64 * edge_ro
         y = y * gam[k];
         y = y + bet[k];
         if constexpr (!Q) { if (i < d) dst[i] = f2h(y); }
-        else if constexpr (QK) xv[k] = i < d ? y : 0.0f;      // (quantised below, four values per lane = one block of 256)
+        else if constexpr (QK != MK_NO) xv[k] = i < d ? y : 0.0f;      // (quantised below, four values per lane = one block of 256)
         else {                  // a half-wave holds one 32-element block (d % 64 == 0: every block of k < d / 64 is whole)
             unsigned w, sw;
             if constexpr (Q1) w = mq_quant32_q1(i < d ? y : 0.0f, sw);
@@ -505,10 +603,10 @@ __device__ __forceinline__ void mb_ln_row(mb_kargs A, mo_ctl & c, gu64 * edge_ro
             if (i < d && (lane & 31) == 0) ((unsigned *) mq_scales((unsigned char *) dst, nb))[blk] = sw;
         }
     }
-    if constexpr (QK) {         // d % 256 == 0: every block below d / 256 is whole
+    if constexpr (QK != MK_NO) {         // d % 256 == 0: every block below d / 256 is whole
 #pragma unroll
         for (int bk = 0; bk < NP / 4; ++bk)
-            if (256 * bk < d) { const float v4[4] = { xv[4 * bk], xv[4 * bk + 1], xv[4 * bk + 2], xv[4 * bk + 3] }; mk_quant_block(v4, lane, (unsigned char *) dst, d >> 8, bk); }
+            if (256 * bk < d) { const float v4[4] = { xv[4 * bk], xv[4 * bk + 1], xv[4 * bk + 2], xv[4 * bk + 3] }; mk_quant_block<(QK >= MK_Q5)>(v4, lane, (unsigned char *) dst, d >> 8, bk); }
     }
 }
 
@@ -545,7 +643,7 @@ __device__ __forceinline__ unsigned mb_pack_h2(unsigned h) { return (h & 0xffffu
 
 // the head's 64 outputs from the 32 chain sums + the leftover cells in F64, index order (vec.cpp:221-223), by threads 0..63; published packed
 // (Q: as two Q8_0 blocks)
-template <bool Q = false, bool Q1 = false, bool QK = false>
+template <bool Q = false, bool Q1 = false, int QK = MK_NO>
 __device__ __forceinline__ void mb_attn_finish(const float * part, const wa_f16 * vleft /* [nl][64] LDS */, const wa_f16 * pleft /* [nl] */, int nl,
                                                gu64 * edge_row, int h, unsigned seq, int tid) {
     if (tid < 64) {
@@ -554,7 +652,7 @@ __device__ __forceinline__ void mb_attn_finish(const float * part, const wa_f16 
         for (int r = 0; r < 32; ++r) s32[r] = part[r * 64 + tid];
         double sumf = (double) wa_tree32(s32);
         for (int cc = 0; cc < nl; ++cc) sumf += (double) (h2f(vleft[cc * 64 + tid]) * h2f(pleft[cc]));
-        if constexpr (QK) gr_store(edge_row + h * 64 + tid, seq, __float_as_uint((float) sumf));      // F32: a Q8_K block spans four heads, the gathering side quantises
+        if constexpr (QK != MK_NO) gr_store(edge_row + h * 64 + tid, seq, __float_as_uint((float) sumf));      // F32: a Q8_K block spans four heads, the gathering side quantises
         else mo_attn_publish<Q, Q1>((float) sumf, edge_row, h, seq, tid);
     }
 }
@@ -564,7 +662,7 @@ __device__ __forceinline__ void mb_attn_finish(const float * part, const wa_f16 
 // tokens come from the row's own cells in HBM; the cells written by THIS launch - the row's own and those of every other row that shares
 // its cache (earlier tokens of a small batch; other beams, which the mask hides) - arrive as granules, like the query.
 // -------------------------------------------------------------------------------------------------
-template <bool Q = false, bool Q1 = false, bool QK = false>
+template <bool Q = false, bool Q1 = false, int QK = MK_NO>
 __device__ __forceinline__ void mb_unit_self(mb_kargs A, mo_ctl & c, unsigned char * area, int l, int b, int h, int tid, bool tw = false) {
 #define MB_TS(k) mb_trace(A, tw, 4096 + l * 16 + (k))
     MB_TS(0);
@@ -798,7 +896,7 @@ __device__ __forceinline__ void mb_cross_load(mb_kargs A, int l, int b, int h, i
         }
 }
 
-template <bool Q, int P, bool Q1 = false, bool QK = false>
+template <bool Q, int P, bool Q1 = false, int QK = MK_NO>
 __device__ __forceinline__ void mb_unit_cross(mb_kargs A, mo_ctl & c, unsigned char * area, int l, int b, int h, int w, int tid, bool tw, const mb_cross_regs<P> & R) {
     constexpr int NCH = 32 / P, CPW = 4 / P, NK = NCH * MB_CSTEPS;          // chains of this part, chains per wave, local cell slots
     const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -1012,7 +1110,7 @@ __device__ __forceinline__ void mb_unit_cross(mb_kargs A, mo_ctl & c, unsigned c
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int cc = 0; cc < 32; ++cc) sumf += dv[cc];
-            if constexpr (QK) gr_store(mb_edge(A, l, E_AO2) + (size_t) b * A->row_gr + h * 64 + tid, seq, __float_as_uint((float) sumf));
+            if constexpr (QK != MK_NO) gr_store(mb_edge(A, l, E_AO2) + (size_t) b * A->row_gr + h * 64 + tid, seq, __float_as_uint((float) sumf));
             else mo_attn_publish<Q, Q1>((float) sumf, mb_edge(A, l, E_AO2) + (size_t) b * A->row_gr, h, seq, tid);
         }
         MB_TC(10);
@@ -1044,7 +1142,8 @@ __device__ __forceinline__ void mb_logits_out(mb_kargs A, const float * lg, int 
 
 // the first piece of a wave's first embedding rows, asked for BEFORE the final LayerNorm waits for its row (piece 0 of mb_logits / mb_logits_q)
 // one piece of a K-format embedding row for lane u of its group: blocks 4 bt .. 4 bt + 3 (clamped to the row) as quants [8 k .. 8 k + 7] | the lane's
-// eight scale bytes [32 + 2 k, 33 + 2 k] | d [40 + k] - 44 registers of the buffer's 48
+// eight scale bytes [32 + 2 k, 33 + 2 k] | d [40 + k] - 44 registers of the buffer's 48; KM (Q5_K, Q2_K): | dmin [44 + k], all 48
+template <bool KM = false>
 __device__ __forceinline__ void mk_te_piece(mb_kargs A, int rc, int u, int bt, unsigned (&buf)[48]) {
     const int nbk = A->d >> 8;
     const GAS u32x4 * wl = (const GAS u32x4 *) ((const GAS unsigned char *) A->te + ((size_t) rc * 8 + u) * nbk * 32);
@@ -1058,15 +1157,16 @@ __device__ __forceinline__ void mk_te_piece(mb_kargs A, int rc, int u, int bt, u
         buf[8 * k] = q0.x; buf[8 * k + 1] = q0.y; buf[8 * k + 2] = q0.z; buf[8 * k + 3] = q0.w;
         buf[8 * k + 4] = q1.x; buf[8 * k + 5] = q1.y; buf[8 * k + 6] = q1.z; buf[8 * k + 7] = q1.w;
         buf[32 + 2 * k] = sc.x; buf[33 + 2 * k] = sc.y; buf[40 + k] = dl[bc];
+        if constexpr (KM) buf[44 + k] = ((const GAS unsigned *) A->te_m + (size_t) rc * nbk)[bc];
     }
 }
 
-template <bool QK = false>
+template <int QK = MK_NO>
 __device__ __forceinline__ void mb_te_first(mb_kargs A, bool quant, bool q1, unsigned (&buf)[48], int lane, int wave) {
     const int d = A->d, ns = d >> 5, n_vocab = A->n_vocab, u = lane & 7;
     int g1_; const int g0_ = mb_share(n_vocab, &g1_);
     const int row = (g0_ + wave) * 8 + (lane >> 3), rc = row < n_vocab ? row : 0;
-    if constexpr (QK) { mk_te_piece(A, rc, u, 0, buf); return; }
+    if constexpr (QK != MK_NO) { mk_te_piece<(QK >= MK_Q5)>(A, rc, u, 0, buf); return; }
     if (q1) {                 // pieces of 16 blocks: quads | scales | minimums (mb_logits_q)
         const GAS unsigned * wl = (const GAS unsigned *) A->te + ((size_t) rc * 8 + u) * ns;
         const GAS unsigned * dl = (const GAS unsigned *) A->te_d + (size_t) rc * ns, * ml = (const GAS unsigned *) A->te_m + (size_t) rc * ns;
@@ -1301,10 +1401,11 @@ __device__ __forceinline__ void mb_logits_q1(mb_kargs A, const unsigned char * x
     }
 }
 
-// the same for a K-format token embedding (Q6_K, Q3_K): a piece is 4 blocks of 256 (mk_te_piece: 11 registers a block), the token rows are Q8_K
-// (mb_dotk's chain, which goes on across the pieces of a row)
-template <int BT>
+// the same for a K-format token embedding: a piece is 4 blocks of 256 (mk_te_piece: 11 registers a block, 12 with dmin), the token rows are Q8_K
+// (mb_dotk's chains, which go on across the pieces of a row; Q5_K: lane u runs the minimum chain of token row u)
+template <int BT, int F = WK_Q6>
 __device__ __forceinline__ void mb_logits_k(mb_kargs A, const unsigned char * xop, size_t op_bytes, int B, int lane, int wave, unsigned (&pfa)[48], float * lg) {
+    constexpr bool KM = F != WK_Q6;
     const int d = A->d, nbk = d >> 8, nbat = (nbk + 3) / 4, n_vocab = A->n_vocab;
     const int u = lane & 7;
     GAS float * logits = (GAS float *) A->logits;
@@ -1315,17 +1416,19 @@ __device__ __forceinline__ void mb_logits_k(mb_kargs A, const unsigned char * xo
     for (int j = 0; grp(j) < g1; ++j) n_items += nbat;
     auto load = [&](int it, unsigned (&buf)[48]) {
         const int j = it / nbat, bt = it - j * nbat, row = grp(j) * 8 + (lane >> 3);
-        mk_te_piece(A, row < n_vocab ? row : 0, u, bt, buf);
+        mk_te_piece<KM>(A, row < n_vocab ? row : 0, u, bt, buf);
     };
     float acc[BT];
+    mk_min_chain<F> mc;
     const unsigned char * xq[BT]; const float * xd[BT];
 #pragma unroll
-    for (int m = 0; m < BT; ++m) { const unsigned char * r = xop + (size_t) (m < B ? m : B - 1) * op_bytes; xq[m] = r + (size_t) u * mk_ls(nbk); xd[m] = (const float *) (r + (size_t) 8 * mk_ls(nbk)); }
+    for (int m = 0; m < BT; ++m) { const unsigned char * r = xop + (size_t) (m < B ? m : B - 1) * op_bytes; xq[m] = r + (size_t) u * mk_ls(nbk); xd[m] = (const float *) (r + mk_xd_off(nbk, KM)); }
     auto one = [&](int it, unsigned (&buf)[48]) {
         const int j = it / nbat, bt = it - j * nbat;
         if (bt == 0) {
 #pragma unroll
             for (int m = 0; m < BT; ++m) acc[m] = 0.0f;
+            if constexpr (F == WK_Q5) mc.summs = 0.0f;
         }
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
@@ -1336,11 +1439,17 @@ __device__ __forceinline__ void mb_logits_k(mb_kargs A, const unsigned char * xo
                 w1.x = (int) buf[8 * k + 4]; w1.y = (int) buf[8 * k + 5]; w1.z = (int) buf[8 * k + 6]; w1.w = (int) buf[8 * k + 7];
                 s.x = (int) buf[32 + 2 * k]; s.y = (int) buf[33 + 2 * k];
                 const float dw = __uint_as_float(buf[40 + k]);
+                if constexpr (KM) {
+                    wk_i2 lo, hi;
+                    mk_sc16(s, u, lo, hi);
+                    mk_block_step<BT, F>(w0, w1, lo, hi, dw, __uint_as_float(buf[44 + k]), u, nbk, bb, xq, xd, xop + (size_t) (u < B ? u : B - 1) * op_bytes, acc, mc);
+                } else {
 #pragma unroll
-                for (int m = 0; m < BT; ++m) {
-                    const wk_i4 x0 = *(const wk_i4 *) (xq[m] + 32 * bb), x1 = *(const wk_i4 *) (xq[m] + 32 * bb + 16);
-                    const float dd = xd[m][bb] * dw;
-                    acc[m] = fmaf(dd, (float) wk_block<WK_Q6>(w0, w1, x0, x1, s), acc[m]);
+                    for (int m = 0; m < BT; ++m) {
+                        const wk_i4 x0 = *(const wk_i4 *) (xq[m] + 32 * bb), x1 = *(const wk_i4 *) (xq[m] + 32 * bb + 16);
+                        const float dd = xd[m][bb] * dw;
+                        acc[m] = fmaf(dd, (float) wk_block<WK_Q6>(w0, w1, x0, x1, s), acc[m]);
+                    }
                 }
             }
         }
@@ -1348,7 +1457,8 @@ __device__ __forceinline__ void mb_logits_k(mb_kargs A, const unsigned char * xo
             const int row = grp(j) * 8 + (lane >> 3);
 #pragma unroll
             for (int m = 0; m < BT; ++m) {
-                const float v = wk_hsum8(acc[m]);
+                float v = wk_hsum8(acc[m]);
+                if constexpr (F == WK_Q5) v = v + wk_from_lane(mc.summs, m);
                 if (u == 0 && j < 4) lg[m * 256 + (8 * j + wave) * 8 + (lane >> 3)] = v;
                 else if (u == 0 && row < n_vocab && m < B) logits[(size_t) m * n_vocab + row] = v;
             }
@@ -1409,9 +1519,12 @@ __host__ __device__ __forceinline__ int mq1_moff(int rc, int K) { return mq1_sof
 __host__ __device__ __forceinline__ int mq1_slot_need(int rc, int K) { return mq1_moff(rc, K) + ((rc * ((K >> 3) + MB_PAD) + 1023) & ~1023) + 1024; }
 
 // Q: a quantised model (Q5_0 / Q8_0); Q1 (with Q): its blocks carry a minimum (Q4_1 / Q5_1) and every operand row is Q8_1; QK (with Q): a K-format
-// model (Q6_K / Q3_K), every operand row is Q8_K
-template <int NP, bool Q, bool Q1 = false, bool QK = false>
+// model, every operand row is Q8_K - MK_Q6: Q6_K / Q3_K; MK_Q5, MK_Q2: Q5_K, Q2_K, the formats with a minimum term (operand rows with their block
+// sums, weight slots with a dmin region)
+template <int NP, bool Q, bool Q1 = false, int QK = MK_NO>
 __device__ __forceinline__ void mb_body(mb_kargs A_) {
+    constexpr bool KM = QK >= MK_Q5;
+    constexpr int WF = QK != MK_NO ? QK - 1 : WK_Q6;       // wa_quantk_dev.h's name of the format
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const mb_kargs A = mo_uniform(A_);
     const int tid = threadIdx.x, lane = tid & 63;
@@ -1431,7 +1544,7 @@ __device__ __forceinline__ void mb_body(mb_kargs A_) {
     unsigned * rscr = (unsigned *) (smem + 1536);     // [8][8] scratch of mb_record
     float  * lnp  = (float *) (smem + 1792);
     const size_t lnp_bytes = 2 * (((size_t) d * 4 + 1023) & ~(size_t) 1023);      // (an LDS-DMA instruction writes a whole KB: each vector ends on one)
-    const size_t opB = QK ? mk_row_bytes(d >> 8) : Q ? mq_row_bytes(d >> 5) : (size_t) d * 2, op4 = QK ? mk_row_bytes(d4 >> 8) : Q ? mq_row_bytes(d4 >> 5) : (size_t) d4 * 2;      // bytes of an operand row
+    const size_t opB = QK ? mk_row_bytes(d >> 8, KM) : Q ? mq_row_bytes(d >> 5) : (size_t) d * 2, op4 = QK ? mk_row_bytes(d4 >> 8, KM) : Q ? mq_row_bytes(d4 >> 5) : (size_t) d4 * 2;      // bytes of an operand row
     unsigned char * xinB = smem + 1792 + lnp_bytes;
     const size_t xinB_bytes = ((size_t) B * opB + 255) & ~(size_t) 255;
     unsigned char * area = xinB + xinB_bytes;
@@ -1460,10 +1573,11 @@ __device__ __forceinline__ void mb_body(mb_kargs A_) {
         const int gp = (!Q && p == 5) ? 4 : 8;
         const int rmax = (ph.r + gp - 1) / gp * gp;
         ph.M = nullptr; ph.moff = 0; ph.S = nullptr;
-        if constexpr (QK) {     // the most octets of rows whose three regions fit the slot (mk_slot_need; moff: where the rows' d start)
+        if constexpr (QK != MK_NO) {     // the most octets of rows whose three regions fit the slot (mk_slot_need; moff: where the rows' d start)
             ph.S = p == 0 ? Y.qkv_sc : p == 1 ? Y.out_sc : p == 2 ? Y.cq_sc : p == 3 ? Y.co_sc : p == 4 ? Y.fc1_sc : Y.fc2_sc;
+            if constexpr (KM) ph.M = p == 0 ? Y.qkv_m : p == 1 ? Y.out_m : p == 2 ? Y.cq_m : p == 3 ? Y.co_m : p == 4 ? Y.fc1_m : Y.fc2_m;      // (the rows' dmin, behind their d: mkm_moff)
             int rc = rmax;
-            while (rc > 8 && mk_slot_need(rc, ph.K) > slot_bytes) rc -= 8;
+            while (rc > 8 && (KM ? mkm_slot_need(rc, ph.K) : mk_slot_need(rc, ph.K)) > slot_bytes) rc -= 8;
             ph.rc = rc;
             ph.moff = mk_doff(rc, ph.K);
         } else if constexpr (Q1) {     // the most octets of rows whose three regions fit the slot (wa_rows_lds_bytes admits a slot that holds one)
@@ -1489,13 +1603,14 @@ __device__ __forceinline__ void mb_body(mb_kargs A_) {
         if (row0 >= ph.N) return;
         const int R = min(ph.rc, ph.r - ck * ph.rc);
         unsigned char * slot = slot0 + (size_t) par * slot_bytes;
-        if constexpr (QK) {
+        if constexpr (QK != MK_NO) {
             const int nbk = ph.K >> 8, nd = R * nbk, last = ph.N * nbk - 1;
             mb_dma_rows((const GAS unsigned char *) ph.W, ph.K, row0, R, ph.N, slot, lane);
             mb_dma_rows((const GAS unsigned char *) ph.S, ph.K >> 4, row0, R, ph.N, slot + ph.soff, lane);
             for (int p64 = 0; p64 * 64 < nd; ++p64) {       // the rows' d: consecutive floats, a dword per lane (clamped to the matrix)
                 const int i = row0 * nbk + p64 * 64 + lane;
                 __builtin_amdgcn_global_load_lds((const GAS void *) ((gcf) ph.D + (i < last ? i : last)), (LAS void *) (slot + ph.moff + p64 * 256), 4, 0, 0);
+                if constexpr (KM) __builtin_amdgcn_global_load_lds((const GAS void *) ((gcf) ph.M + (i < last ? i : last)), (LAS void *) (slot + mkm_moff(ph.rc, ph.K) + p64 * 256), 4, 0, 0);
             }
         } else if constexpr (Q) {
             mb_dma_rows((const GAS unsigned char *) ph.W, ph.K, row0, R, ph.N, slot, lane);
@@ -1544,10 +1659,10 @@ __device__ __forceinline__ void mb_body(mb_kargs A_) {
         const float * bias_l = (const float *) (slot + slot_bytes - 512);
         const int groups = (Rc + 7) >> 3;
         const int bc = groups * B <= MB_NCW ? 1 : groups * ((B + 1) >> 1) <= MB_NCW ? 2 : 3;
-        if constexpr (QK) {
-            if (bc == 1)      mb_products_k<1>(slot, ph.soff, ph.moff, Rc, row_base, ph.N, bias_l, scale_l, xop, opb, ph.K, B, wave, lane, epi);
-            else if (bc == 2) mb_products_k<2>(slot, ph.soff, ph.moff, Rc, row_base, ph.N, bias_l, scale_l, xop, opb, ph.K, B, wave, lane, epi);
-            else              mb_products_k<3>(slot, ph.soff, ph.moff, Rc, row_base, ph.N, bias_l, scale_l, xop, opb, ph.K, B, wave, lane, epi);
+        if constexpr (QK != MK_NO) {
+            if (bc == 1)      mb_products_k<1, WF>(slot, ph.soff, ph.moff, Rc, row_base, ph.N, bias_l, scale_l, xop, opb, ph.K, B, wave, lane, epi, KM ? mkm_moff(ph.rc, ph.K) : 0);
+            else if (bc == 2) mb_products_k<2, WF>(slot, ph.soff, ph.moff, Rc, row_base, ph.N, bias_l, scale_l, xop, opb, ph.K, B, wave, lane, epi, KM ? mkm_moff(ph.rc, ph.K) : 0);
+            else              mb_products_k<3, WF>(slot, ph.soff, ph.moff, Rc, row_base, ph.N, bias_l, scale_l, xop, opb, ph.K, B, wave, lane, epi, KM ? mkm_moff(ph.rc, ph.K) : 0);
         } else if constexpr (Q) {
             if (bc == 1)      mb_products_q<1, Q1>(slot, ph.soff, Rc, row_base, ph.N, bias_l, scale_l, xop, opb, ph.K, B, wave, lane, epi, ph.moff);
             else if (bc == 2) mb_products_q<2, Q1>(slot, ph.soff, Rc, row_base, ph.N, bias_l, scale_l, xop, opb, ph.K, B, wave, lane, epi, ph.moff);
@@ -1562,7 +1677,7 @@ __device__ __forceinline__ void mb_body(mb_kargs A_) {
     // QK: the producers publish F32 (a Q8_K block is four heads' outputs, or eight workgroups' of the first MLP product: no producer holds one);
     // a wave sweeps up to four blocks of one granule per value, four values of a block per lane, and quantises them into the operand row
     auto gather_rows = [&](gu64 * edge, int len, unsigned code) {
-        if constexpr (QK) {
+        if constexpr (QK != MK_NO) {
             const int nbk = len >> 8, total = B * nbk;
             const size_t opb = len == d ? opB : op4;
             for (int f0 = 4 * wave; f0 < total; f0 += 4 * MB_NW) {
@@ -1574,7 +1689,7 @@ __device__ __forceinline__ void mb_body(mb_kargs A_) {
                     if (f < total) {        // (wave-uniform)
                         const int b = f / nbk;
                         const float v4[4] = { __uint_as_float(v[4 * j]), __uint_as_float(v[4 * j + 1]), __uint_as_float(v[4 * j + 2]), __uint_as_float(v[4 * j + 3]) };
-                        mk_quant_block(v4, lane, xin + (size_t) b * opb, nbk, f - b * nbk);
+                        mk_quant_block<KM>(v4, lane, xin + (size_t) b * opb, nbk, f - b * nbk);
                     }
                 }
             }
@@ -1711,7 +1826,7 @@ __device__ __forceinline__ void mb_body(mb_kargs A_) {
                     const float v = res[j];
                     float gl = v;
                     if (v <= -10.0f) gl = 0.0f; else if (v < 10.0f) gl = tv[j];
-                    if constexpr (QK) { if (has && b < b1) gr_store(eh + (size_t) b * RG + n, seq, __float_as_uint(gl)); }      // F32, a granule per value (row_gr = 4 d): the gathering side quantises
+                    if constexpr (QK != MK_NO) { if (has && b < b1) gr_store(eh + (size_t) b * RG + n, seq, __float_as_uint(gl)); }      // F32, a granule per value (row_gr = 4 d): the gathering side quantises
                     else if constexpr (Q) { if (has && b < b1) fc1x[b * 32 + (n - wg * 32)] = gl; }      // F32: quantised below, once the block's 32 rows are through
                     else {
                         const unsigned pk = mb_pack_h2((unsigned) f2h(gl));
@@ -1740,9 +1855,9 @@ __device__ __forceinline__ void mb_body(mb_kargs A_) {
         run_phase(l, 5, [&](const mb_phase & ph, const unsigned char * slot, int row_base, int Rc, int) {
             const float * bias_l = (const float *) (slot + slot_bytes - 512);
             const int groups = (Rc + (Q ? 7 : 3)) / (Q ? 8 : 4);
-            if constexpr (QK) {
-                if (groups * B <= MB_NCW) mb_products_k<1>(slot, ph.soff, ph.moff, Rc, row_base, ph.N, bias_l, nullptr, xin, op4, ph.K, B, wave, lane, resid_epi(mb_edge(A, l, E_X3)));
-                else                      mb_products_k<2>(slot, ph.soff, ph.moff, Rc, row_base, ph.N, bias_l, nullptr, xin, op4, ph.K, B, wave, lane, resid_epi(mb_edge(A, l, E_X3)));
+            if constexpr (QK != MK_NO) {
+                if (groups * B <= MB_NCW) mb_products_k<1, WF>(slot, ph.soff, ph.moff, Rc, row_base, ph.N, bias_l, nullptr, xin, op4, ph.K, B, wave, lane, resid_epi(mb_edge(A, l, E_X3)), KM ? mkm_moff(ph.rc, ph.K) : 0);
+                else                      mb_products_k<2, WF>(slot, ph.soff, ph.moff, Rc, row_base, ph.N, bias_l, nullptr, xin, op4, ph.K, B, wave, lane, resid_epi(mb_edge(A, l, E_X3)), KM ? mkm_moff(ph.rc, ph.K) : 0);
             } else if constexpr (Q) {
                 if (groups * B <= MB_NCW) mb_products_q<1, Q1>(slot, ph.soff, Rc, row_base, ph.N, bias_l, nullptr, xin, op4, ph.K, B, wave, lane, resid_epi(mb_edge(A, l, E_X3)), ph.moff);
                 else                      mb_products_q<2, Q1>(slot, ph.soff, Rc, row_base, ph.N, bias_l, nullptr, xin, op4, ph.K, B, wave, lane, resid_epi(mb_edge(A, l, E_X3)), ph.moff);
@@ -1771,9 +1886,9 @@ __device__ __forceinline__ void mb_body(mb_kargs A_) {
     for (int m = 0; m < n_out; ++m) want_rec = want_rec || A->rows[A->out_row[m]].smask != nullptr;
     float * lg = (float *) area;            // (the gathered-inputs area holds nothing any more) the workgroup's logits, staged for whole-line stores and the records
     wa_barrier_lds();
-    if constexpr (QK) {
-        if (n_out <= 2) mb_logits_k<2>(A, xinB, opB, n_out, lane, wave, pf0, lg); else if (n_out <= 4) mb_logits_k<4>(A, xinB, opB, n_out, lane, wave, pf0, lg);
-        else if (n_out <= 5) mb_logits_k<5>(A, xinB, opB, n_out, lane, wave, pf0, lg); else mb_logits_k<8>(A, xinB, opB, n_out, lane, wave, pf0, lg);
+    if constexpr (QK != MK_NO) {
+        if (n_out <= 2) mb_logits_k<2, WF>(A, xinB, opB, n_out, lane, wave, pf0, lg); else if (n_out <= 4) mb_logits_k<4, WF>(A, xinB, opB, n_out, lane, wave, pf0, lg);
+        else if (n_out <= 5) mb_logits_k<5, WF>(A, xinB, opB, n_out, lane, wave, pf0, lg); else mb_logits_k<8, WF>(A, xinB, opB, n_out, lane, wave, pf0, lg);
     } else if constexpr (Q1) {
         if (n_out <= 2) mb_logits_q1<2>(A, xinB, opB, n_out, lane, wave, pf0, lg); else if (n_out <= 4) mb_logits_q1<4>(A, xinB, opB, n_out, lane, wave, pf0, lg);
         else if (n_out <= 5) mb_logits_q1<5>(A, xinB, opB, n_out, lane, wave, pf0, lg); else mb_logits_q1<8>(A, xinB, opB, n_out, lane, wave, pf0, lg);
@@ -1825,7 +1940,7 @@ bool MB_CAT(wa_rows_launch_q1_np, WA_ROWS_NP)(hipStream_t s, const wa_rows_args 
 #elif defined(WA_ROWS_K_TU)
 // The step for a Q6_K / Q3_K model (Q8_K operand rows): again a kernel of its own per width in a code object of its own (-DWA_ROWS_K_TU)
 __global__ __launch_bounds__(MB_THREADS) void MB_CAT(k_decode_rows_k_np, WA_ROWS_NP)(const wa_rows_args A) {
-    mb_body<WA_ROWS_NP, true, false, true>((mb_kargs) __builtin_amdgcn_kernarg_segment_ptr());
+    mb_body<WA_ROWS_NP, true, false, MK_Q6>((mb_kargs) __builtin_amdgcn_kernarg_segment_ptr());
 }
 bool MB_CAT(wa_rows_launch_k_np, WA_ROWS_NP)(hipStream_t s, const wa_rows_args & a, int n_wg, size_t lds) {
     int dev = 0;
@@ -1839,6 +1954,29 @@ bool MB_CAT(wa_rows_launch_k_np, WA_ROWS_NP)(hipStream_t s, const wa_rows_args &
     hipLaunchKernelGGL(MB_CAT(k_decode_rows_k_np, WA_ROWS_NP), dim3(n_wg), dim3(MB_THREADS), lds, s, a);
     return hipGetLastError() == hipSuccess;
 }
+#elif defined(WA_ROWS_KM_TU)
+// The step for a Q5_K or a Q2_K model, the K formats whose product has a minimum term: a kernel per format and width, the pair of a width in a code
+// object of its own (-DWA_ROWS_KM_TU)
+__global__ __launch_bounds__(MB_THREADS) void MB_CAT(k_decode_rows_k5_np, WA_ROWS_NP)(const wa_rows_args A) {
+    mb_body<WA_ROWS_NP, true, false, MK_Q5>((mb_kargs) __builtin_amdgcn_kernarg_segment_ptr());
+}
+__global__ __launch_bounds__(MB_THREADS) void MB_CAT(k_decode_rows_k2_np, WA_ROWS_NP)(const wa_rows_args A) {
+    mb_body<WA_ROWS_NP, true, false, MK_Q2>((mb_kargs) __builtin_amdgcn_kernarg_segment_ptr());
+}
+bool MB_CAT(wa_rows_launch_km_np, WA_ROWS_NP)(hipStream_t s, const wa_rows_args & a, int n_wg, size_t lds) {
+    int dev = 0;
+    (void) hipGetDevice(&dev);
+    static bool attr_set[64] = {};
+    if (!attr_set[dev & 63]) {
+        if (hipFuncSetAttribute((const void *) MB_CAT(k_decode_rows_k5_np, WA_ROWS_NP), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
+            hipFuncSetAttribute((const void *) MB_CAT(k_decode_rows_k2_np, WA_ROWS_NP), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return false;
+        attr_set[dev & 63] = true;
+    }
+    if (!a.te_d || !a.te_sc || !a.te_m || a.row_gr < 4 * a.d || (a.wtype != 13 && a.wtype != 10)) return false;
+    if (a.wtype == 13) hipLaunchKernelGGL(MB_CAT(k_decode_rows_k5_np, WA_ROWS_NP), dim3(n_wg), dim3(MB_THREADS), lds, s, a);
+    else               hipLaunchKernelGGL(MB_CAT(k_decode_rows_k2_np, WA_ROWS_NP), dim3(n_wg), dim3(MB_THREADS), lds, s, a);
+    return hipGetLastError() == hipSuccess;
+}
 #else
 __global__ __launch_bounds__(MB_THREADS) void MB_CAT(k_decode_rows_np, WA_ROWS_NP)(const wa_rows_args A) {
     mb_body<WA_ROWS_NP, false>((mb_kargs) __builtin_amdgcn_kernarg_segment_ptr());
@@ -1849,9 +1987,11 @@ __global__ __launch_bounds__(MB_THREADS) void MB_CAT(k_decode_rows_q_np, WA_ROWS
 }
 bool MB_CAT(wa_rows_launch_q1_np, WA_ROWS_NP)(hipStream_t s, const wa_rows_args & a, int n_wg, size_t lds);
 bool MB_CAT(wa_rows_launch_k_np, WA_ROWS_NP)(hipStream_t s, const wa_rows_args & a, int n_wg, size_t lds);
+bool MB_CAT(wa_rows_launch_km_np, WA_ROWS_NP)(hipStream_t s, const wa_rows_args & a, int n_wg, size_t lds);
 bool MB_CAT(wa_rows_launch_np, WA_ROWS_NP)(hipStream_t s, const wa_rows_args & a, int n_wg, size_t lds) {
     if (a.quant == 2) return MB_CAT(wa_rows_launch_q1_np, WA_ROWS_NP)(s, a, n_wg, lds);
     if (a.quant == 3) return MB_CAT(wa_rows_launch_k_np, WA_ROWS_NP)(s, a, n_wg, lds);
+    if (a.quant == 4) return MB_CAT(wa_rows_launch_km_np, WA_ROWS_NP)(s, a, n_wg, lds);
     int dev = 0;
     (void) hipGetDevice(&dev);
     static bool attr_set[64] = {};
@@ -1871,9 +2011,11 @@ bool wa_rows_launch_np20(hipStream_t s, const wa_rows_args & a, int n_wg, size_t
 
 size_t wa_rows_lds_bytes(int d, int B, int n_wg, int quant, int * slot_bytes) {
     if (B < 1 || B > WA_ROWS_MAX || d < 64 || d > WA_MEGA_MAX_D || (d & 127) != 0 || n_wg < 1) return 0;
-    if (quant == 3 && (d & 255) != 0) return 0;     // (K formats: blocks of 256)
-    const size_t opB = quant == 3 ? mk_row_bytes(d >> 8) : quant ? mq_row_bytes(d >> 5) : (size_t) d * 2;
-    const size_t op4 = quant == 3 ? mk_row_bytes((4 * d) >> 8) : quant ? mq_row_bytes((4 * d) >> 5) : (size_t) 4 * d * 2;
+    if (quant < 0 || quant > 4) return 0;
+    const bool qk = quant >= 3, km = quant == 4;    // K formats; Q5_K / Q2_K: operand rows with their block sums, weight slots with a dmin region
+    if (qk && (d & 255) != 0) return 0;             // (K formats: blocks of 256)
+    const size_t opB = qk ? mk_row_bytes(d >> 8, km) : quant ? mq_row_bytes(d >> 5) : (size_t) d * 2;
+    const size_t op4 = qk ? mk_row_bytes((4 * d) >> 8, km) : quant ? mq_row_bytes((4 * d) >> 5) : (size_t) 4 * d * 2;
     const size_t xinB_bytes = ((size_t) B * opB + 255) & ~(size_t) 255;
     size_t area = (size_t) B * op4;
     if (area < MB_ATT_BYTES) area = MB_ATT_BYTES;
@@ -1881,7 +2023,7 @@ size_t wa_rows_lds_bytes(int d, int B, int n_wg, int quant, int * slot_bytes) {
     const size_t fixed = 1792 + 2 * (((size_t) d * 4 + 1023) & ~(size_t) 1023) + xinB_bytes + area;
     auto rpw = [&](int N) { const int r = (N + n_wg - 1) / n_wg; return (r + 1) & ~1; };
     if (rpw(d) > 8) return 0;                       // (xres holds 8 residual values per token row)
-    if (quant && quant != 3 && (4 * d) / 32 > n_wg) return 0;     // (whole-block ownership of the first MLP product: one workgroup per block)
+    if (quant && !qk && (4 * d) / 32 > n_wg) return 0;     // (whole-block ownership of the first MLP product: one workgroup per block)
     // a slot holds at least one task group of every phase; the whole chunk of a phase when there is room (fewer barriers)
     size_t need_min, want = 0;
     if (quant == 2) {           // a third region per row, the block minimums: the kernel's own rule (mq1_slot_need), no slack beyond it
@@ -1889,11 +2031,12 @@ size_t wa_rows_lds_bytes(int d, int B, int n_wg, int quant, int * slot_bytes) {
         want = std::max(want, (size_t) mq1_slot_need((rpw(3 * d) + 7) / 8 * 8, d));
         want = std::max(want, (size_t) mq1_slot_need(32, d));
         want = std::max(want, (size_t) mq1_slot_need((rpw(d) + 7) / 8 * 8, 4 * d));
-    } else if (quant == 3) {    // Q6_K / Q3_K: quants | scale bytes | d, the kernel's own rule (mk_slot_need); the first MLP product's rows are dealt evenly
-        need_min = (size_t) mk_slot_need(8, 4 * d);
-        want = std::max(want, (size_t) mk_slot_need((rpw(3 * d) + 7) / 8 * 8, d));
-        want = std::max(want, (size_t) mk_slot_need((rpw(4 * d) + 7) / 8 * 8, d));
-        want = std::max(want, (size_t) mk_slot_need((rpw(d) + 7) / 8 * 8, 4 * d));
+    } else if (qk) {            // K formats: quants | scale bytes | d (| dmin), the kernel's own rule (mk_slot_need, mkm_slot_need); the first MLP product's rows are dealt evenly
+        auto slot_need = [&](int rc, int K) { return (size_t) (km ? mkm_slot_need(rc, K) : mk_slot_need(rc, K)); };
+        need_min = slot_need(8, 4 * d);
+        want = std::max(want, slot_need((rpw(3 * d) + 7) / 8 * 8, d));
+        want = std::max(want, slot_need((rpw(4 * d) + 7) / 8 * 8, d));
+        want = std::max(want, slot_need((rpw(d) + 7) / 8 * 8, 4 * d));
     } else if (quant) {
         auto rowb = [&](int K) { return (size_t) K + MB_PAD + (size_t) (K >> 3) + MB_PAD; };
         need_min = 8 * rowb(4 * d) + 3072;
@@ -1927,4 +2070,4 @@ bool wa_launch_decode_rows(hipStream_t s, const wa_rows_args & a, int n_wg) {
     return wa_rows_launch_np20(s, a, n_wg, lds);
 }
 #endif
-#endif      // WA_ROWS_Q1_TU, WA_ROWS_K_TU
+#endif      // WA_ROWS_Q1_TU, WA_ROWS_K_TU, WA_ROWS_KM_TU
