@@ -501,7 +501,8 @@ WHISPER_API int whisper_amd_decode_step_probe(struct whisper_context * ctx, stru
  * captured launch sequence (WHISPER_AMD_NO_MEGA=1, unsupported shape, after a hand-off time-out, or a model whose weight format has no
  * one-launch kernel of this form: Q5_1 / Q4_1, Q2_K / Q3_K / Q5_K / Q6_K and Q4_0 / Q4_K files.  Those run the launch sequence in every decode mode, and
  * whisper_amd_rows_enabled is 0 too, unless the state was made under the switch of their several-rows kernel - WHISPER_AMD_ROWS_Q1=1 for Q5_1 / Q4_1,
- * WHISPER_AMD_ROWS_K=1 for Q6_K / Q3_K, WHISPER_AMD_ROWS_KM=1 for Q5_K / Q2_K -, which then serves single tokens as well; Q4_0 / Q4_K have none). */
+ * WHISPER_AMD_ROWS_K=1 for Q6_K / Q3_K, WHISPER_AMD_ROWS_KM=1 for Q5_K / Q2_K, WHISPER_AMD_ROWS_Q4=1 for Q4_0 -, which then serves single tokens as well;
+ * Q4_K has none and keeps the launch sequence). */
 WHISPER_API int whisper_amd_mega_enabled(struct whisper_state * state);
 /* Role of workgroup `wg` of the n_wg workgroups of the one-launch step for a model with n_head text heads (no device needed): role 0 =
  * weight streaming (index = its rank), 1 = self-attention of head `index`, 2 = cross-attention (index = 4 head + quarter). */

@@ -387,7 +387,7 @@ static bool rows_args(whisper_context & ctx, whisper_state & own, wa_rows_args &
     if (wa_rows_lds_bytes(hp.n_text_state, B, std::min(ctx.model.n_cu, 256), a.quant, &a.slot_bytes) == 0 || !wa_rows_prepare(ctx, own)) return false;
     if (a.quant == 2) a.te_m = ctx.model.te_q.qm;      // (Q4_1 / Q5_1: k_decode_rows_q1_np*)
     a.force_inorder = rows_force_inorder();
-    if (a.quant >= 3) a.te_sc = ctx.model.te_q.qsc;    // (Q6_K / Q3_K: k_decode_rows_k_np*)
+    if (a.quant == 3 || a.quant == 4) a.te_sc = ctx.model.te_q.qsc;    // (Q6_K / Q3_K: k_decode_rows_k_np*; quant 5, Q4_0 - k_decode_rows_q4_np* - needs no more than the Q form: its embedding is in Q5_0's layout)
     if (a.quant == 4) { a.te_m = ctx.model.te_q.qm; a.wtype = ctx.model.wtype; }      // (Q5_K / Q2_K: k_decode_rows_k5_np* / _k2_np*)
     a.granules = own.d_rows_gr; a.row_gr = wa_rows_row_gr(a.quant, hp.n_text_state); a.cross_gr = own.d_rows_cgr;
     a.B = a.n_out = B;

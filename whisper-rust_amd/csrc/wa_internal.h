@@ -109,8 +109,9 @@ struct wa_lin {
 inline bool wa_wtype_has_min(int wtype) { return wtype == 3 || wtype == 7; }     // Q4_1, Q5_1: multiplied with Q8_1 activation rows
 inline bool wa_wtype_rows_k(int wtype) { return wtype == 14 || wtype == 11; }    // Q6_K, Q3_K: the K formats whose product has no minimum term (wa_rows.hip: k_decode_rows_k_np*)
 inline bool wa_wtype_rows_km(int wtype) { return wtype == 13 || wtype == 10; }   // Q5_K, Q2_K: the K formats whose product has a minimum term (wa_rows.hip: k_decode_rows_k5_np*, _k2_np*)
-inline int wa_one_launch_quant(int wtype) { return wtype == 1 ? 0 : wa_wtype_has_min(wtype) ? 2 : wa_wtype_rows_k(wtype) ? 3 : wa_wtype_rows_km(wtype) ? 4 : 1; }      // wa_mega_args / wa_rows_args::quant
-inline int wa_rows_row_gr(int quant, int d) { return quant >= 3 ? 4 * d : 2 * d; }       // wa_rows_args::row_gr: hand-off granules per token row and edge
+inline bool wa_wtype_rows_q4(int wtype) { return wtype == 2; }                    // Q4_0: the interleaved 8-row product, one chain per output (wa_rows.hip: k_decode_rows_q4_np*)
+inline int wa_one_launch_quant(int wtype) { return wtype == 1 ? 0 : wa_wtype_has_min(wtype) ? 2 : wa_wtype_rows_k(wtype) ? 3 : wa_wtype_rows_km(wtype) ? 4 : wa_wtype_rows_q4(wtype) ? 5 : 1; }      // wa_mega_args / wa_rows_args::quant
+inline int wa_rows_row_gr(int quant, int d) { return quant == 3 || quant == 4 ? 4 * d : 2 * d; }       // wa_rows_args::row_gr: hand-off granules per token row and edge (the K formats hand F32 values over)
 inline bool wa_wtype_k(int wtype) { return wtype == 13 || wtype == 14 || wtype == 10 || wtype == 11 || wtype == 12; }   // Q5_K, Q6_K, Q2_K, Q3_K (wa_quantk.hip), Q4_K (wa_quant4.hip): multiplied with Q8_K activation rows
 
 struct wa_enc_layer {

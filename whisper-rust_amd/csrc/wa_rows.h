@@ -24,7 +24,13 @@
 //   k_decode_rows_k5_np*, Q5_K and Q2_K weights, the K formats whose product has a minimum term (a dmin per block beside the d): as above, and the
 //   k_decode_rows_k2_np*  quantising waves store each block's 16 sums with the row.  Q5_K: one lane of a weight row's eight runs the minimum chain of a
 //                         token row beside the lane chains; Q2_K: the minimums enter the lane chains, per block before the product term.  Opt-in:
-//                         WHISPER_AMD_ROWS_KM=1, 1..8 rows.  Q4_K (the interleaved 8-row product of wa_quant4.h) keeps the launch sequence.
+//                         WHISPER_AMD_ROWS_KM=1, 1..8 rows.
+//   k_decode_rows_q4_np*  Q4_0 weights in the arena's packed form (wa_quant4.h: nibble words [g = 0..3][block] + F32 block scales; a slot row is K / 2 bytes,
+//                         then - mq4_soff in - the scales), operand rows Q8_0 and everything but the seven layer products as k_decode_rows_q_np* (the
+//                         token embedding is stored in Q5_0's layout).  The interleaved product has ONE chain per output: the eight lanes of a weight row
+//                         split the blocks, four each in a round of 32, and hand the exact block sums as int16 through a per-wave LDS exchange area to the
+//                         lane that runs a token row's chain.  Opt-in: WHISPER_AMD_ROWS_Q4=1, 1..8 rows.  Q4_K (the interleaved product whose chain
+//                         steps and quantiser depend on the row's place in the pass) keeps the launch sequence.
 // Arithmetic is the reference order throughout (same chains, trees, certified F64 sums as wa_exact.hip): logits are bit-identical to
 // the launch sequence, which stays as the fallback.
 #pragma once
@@ -55,11 +61,11 @@ struct wa_rows_args {
     const wa_mega_layer * layers; int n_layer, d, n_head, n_vocab; float eps;
     double rn_d;
     const wa_f16 * te; const float * pe; const float * lnf_w, * lnf_b; const wa_f16 * gelu;
-    const float * te_d; int quant;                      // quant: 0 F16 weights, 1 Q5_0 / Q8_0 (Q8_0 operand rows), 2 Q4_1 / Q5_1 (Q8_1 operand rows, block minimums), 3 Q6_K / Q3_K (Q8_K operand rows), 4 Q5_K / Q2_K (Q8_K operand rows with block sums, dmin)
+    const float * te_d; int quant;                      // quant: 0 F16 weights, 1 Q5_0 / Q8_0 (Q8_0 operand rows), 2 Q4_1 / Q5_1 (Q8_1 operand rows, block minimums), 3 Q6_K / Q3_K (Q8_K operand rows), 4 Q5_K / Q2_K (Q8_K operand rows with block sums, dmin), 5 Q4_0 (Q8_0 operand rows, packed nibble rows, one chain per output)
     const float * te_m;                                 // quant == 2: block minimums of the token embedding (the layers' are in wa_mega_layer); quant == 4: its blocks' dmin
     unsigned long long kv_layer_stride, cross_layer_stride;
     int cross_tpad, T;
-    unsigned long long * granules; int row_gr;          // [layer][8][B][row_gr] hand-off granules (row_gr = 2 d; quant >= 3: 4 d, the MLP's hidden row travels in F32)
+    unsigned long long * granules; int row_gr;          // [layer][8][B][row_gr] hand-off granules (row_gr = 2 d; quant 3, 4: 4 d, the MLP's hidden row travels in F32)
     unsigned long long * cross_gr;                      // [layer][B][head][WA_ROWS_CGR]
     float * logits;                                     // [B][n_vocab]
     unsigned * status;                                  // [0] 0 = ok, else the code of the hand-off that timed out; [1] = seq once the launch has run
@@ -73,7 +79,7 @@ struct wa_rows_args {
     int token_beg, token_eot;                           // (records) first timestamp token, end-of-text token
     int n_out, out_row[WA_ROWS_MAX];                    // token rows whose logits are wanted (the reference flags batch.logits rows): logits row m = token row out_row[m]
     wa_rows_row rows[WA_ROWS_MAX];
-    const int8_t * te_sc;                               // quant >= 3: the token embedding's 16 scale bytes per block (te: its quants, te_d: its d)
+    const int8_t * te_sc;                               // quant 3, 4: the token embedding's 16 scale bytes per block (te: its quants, te_d: its d)
     int wtype;                                          // quant == 4: the ggml type of the weights, 13 Q5_K or 10 Q2_K - which of the two kernels is launched
 };
 

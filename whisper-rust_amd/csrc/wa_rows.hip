@@ -278,6 +278,104 @@ __device__ __forceinline__ void mb_products_q(const unsigned char * slot, int so
 }
 
 // -------------------------------------------------------------------------------------------------
+// Q4_0 models (k_decode_rows_q4_np*; contract: wa_quant4.h - wa_q4_0_dot8, the reference's interleaved 8-row product).  Every output carries ONE chain over
+// the 32-value blocks, in block order,  acc = fma((float) isum_b, d_w * d_x, acc): no lane chains and no horizontal sum, so the eight lanes of a weight row
+// cannot each own a share of every block as above.  They SPLIT THE BLOCKS instead (k_q4gemv_rows' way, on weights and operand rows that lie in LDS): in a
+// round of 32 blocks lane u takes blocks 4 u .. 4 u + 3, forms their exact integer sums for each token row of the task and hands them, as int16
+// (|isum_b| <= 32 * 8 * 127), to the lane that runs the token row's chain through a per-wave exchange area in LDS - [token row][weight row of the octet]
+// [block of the round], 512 bytes per token row.  Lane r < BC of the group then runs token row r's chain over the round: it reads d_w from the slot and d_x
+// from the operand row itself and rounds their product once, as the reference does.  BC chains side by side; nothing is re-associated.
+//
+// A weight row in the slot is the arena's: nibble words u32 [g = 0..3][block] (K / 2 bytes; byte e of word (g, b): low nibble element 4 g + e, high
+// nibble element 16 + 4 g + e, unsigned), then - `soff` bytes in - its F32 block scales.  Low nibbles of plane g meet the operand row's lane g, high
+// nibbles its lane 4 + g (mq_quads); lane u's four blocks are one 16-byte read of either.
+// The slot's image of rc weight rows of length K: nibble rows (stride K / 2 + MB_PAD) | block scales (stride K / 8 + MB_PAD), each region in whole KB (an
+// LDS-DMA instruction writes a KB), then the KB of bias and column scale.  The kernel and wa_rows_lds_bytes share this rule exactly (as mq1_slot_need).
+// -------------------------------------------------------------------------------------------------
+#define MQ4_EXCH_ROW 512                                       // bytes of a token row's block sums of a round: 8 weight rows x 32 blocks x int16
+#define MQ4_EXCH_BYTES (MB_NCW * 3 * MQ4_EXCH_ROW)             // the exchange areas of the computing waves, up to three token rows per task
+__host__ __device__ __forceinline__ int mq4_soff(int rc, int K) { return (rc * ((K >> 1) + MB_PAD) + 1023) & ~1023; }
+__host__ __device__ __forceinline__ int mq4_slot_need(int rc, int K) { return mq4_soff(rc, K) + ((rc * ((K >> 3) + MB_PAD) + 1023) & ~1023) + 1024; }
+typedef short mq_s4 __attribute__((ext_vector_type(4)));
+// four unsigned nibble values 0..15, one per byte -> minus 8 in every byte (wa_quant4.hip: q4_s8)
+__device__ __forceinline__ int mq4_s8(unsigned nib) {
+    const unsigned r = nib ^ 0x08080808u;                       // 8..15 -> 0..7; 0..7 -> 8..15, bit 3 set: the sign
+    return (int) (r | (((r >> 3) & 0x01010101u) * 0xf0u));
+}
+// a wave's own LDS writes are complete, and the compiler moves no LDS access across: what orders the exchange (a wave's lanes run one instruction
+// stream, so no barrier is needed)
+__device__ __forceinline__ void mq4_wave_lds() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
+template <int BC>
+__device__ __forceinline__ void mb_dotq4(const unsigned char * wrow, const unsigned char * wd, const unsigned char * xop, size_t op_bytes, unsigned char * exch /* the wave's */,
+                                         int lane_, int nb, int b0, int B, float (&res)[BC]) {
+    int lane = lane_;
+    asm volatile("" : "+v"(lane));      // (as mb_ln_row: hoisted out of the layer loop, the per-lane addresses of every inlined copy of this body cost registers all kernel long)
+    const int u = lane & 7;
+    const unsigned char * xr[BC];
+#pragma unroll
+    for (int j = 0; j < BC; ++j) xr[j] = xop + (size_t) (b0 + j < B ? b0 + j : B - 1) * op_bytes;
+    // the chain this lane runs: token row b0 + u of the task (lanes u >= BC run none)
+    const unsigned char * xd_own = xop + (size_t) (b0 + (u < BC ? u : 0) < B ? b0 + (u < BC ? u : 0) : B - 1) * op_bytes + (size_t) 32 * mq_ld(nb);
+    const unsigned char * ex_own = exch + (u < BC ? u : 0) * MQ4_EXCH_ROW + (lane >> 3) * 64;
+    float acc = 0.0f;
+    for (int r0 = 0; r0 < nb; r0 += 32) {
+        const bool mine = r0 + 4 * u < nb;                      // (nb % 4 == 0: a lane's four blocks are all inside the row or all beyond it)
+        const int bo = mine ? r0 + 4 * u : 0;
+        int s[BC][4];                                           // [token row][block]: the integer sums, exact in any order - plane after plane, so that few words are live
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            const mq_u4 w = *(const mq_u4 *) (wrow + ((size_t) g * nb + bo) * 4);
+            int lo[4], hi[4];                                   // the signed bytes of operand lanes g and 4 + g, unpacked once for all token rows
+#pragma unroll
+            for (int e = 0; e < 4; ++e) { lo[e] = mq4_s8(w[e] & 0x0f0f0f0fu); hi[e] = mq4_s8((w[e] >> 4) & 0x0f0f0f0fu); }
+#pragma unroll
+            for (int j = 0; j < BC; ++j) {
+                const mq_i4 xl = *(const mq_i4 *) (xr[j] + ((size_t) g * mq_ld(nb) + bo) * 4), xh = *(const mq_i4 *) (xr[j] + ((size_t) (4 + g) * mq_ld(nb) + bo) * 4);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) { s[j][e] = __builtin_amdgcn_sdot4(lo[e], xl[e], g == 0 ? 0 : s[j][e], false); s[j][e] = __builtin_amdgcn_sdot4(hi[e], xh[e], s[j][e], false); }
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < BC; ++j) {
+            const mq_s4 s16 = { (short) s[j][0], (short) s[j][1], (short) s[j][2], (short) s[j][3] };
+            if (mine) *(mq_s4 *) (exch + j * MQ4_EXCH_ROW + lane * 8) = s16;      // [weight row lane >> 3][blocks 4 u .. 4 u + 3 of the round]
+        }
+        mq4_wave_lds();
+        if (u < BC) {
+#pragma unroll
+            for (int q = 0; q < 8; ++q) {
+                if (r0 + 4 * q < nb) {                          // (wave-uniform: the chain runs min(32, nb - r0) steps)
+                    const mq_s4 s16 = *(const mq_s4 *) (ex_own + 8 * q);
+                    const mq_f4 dw = *(const mq_f4 *) (wd + (size_t) (r0 + 4 * q) * 4), dx = *(const mq_f4 *) (xd_own + (size_t) (r0 + 4 * q) * 4);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) { const float p = dw[e] * dx[e]; acc = fmaf((float) (int) s16[e], p, acc); }
+                }
+            }
+        }
+        mq4_wave_lds();                                         // (the next round's sums, or the next task's, go where these were read)
+    }
+#pragma unroll
+    for (int j = 0; j < BC; ++j) res[j] = mb_from_lane(acc, j);      // lane 0 of the group takes chain j from lane j
+}
+// product tasks of a Q4_0 chunk (as mb_products_q); exch: the exchange areas of the computing waves
+template <int BC, typename EPI>
+__device__ __forceinline__ void mb_products_q4(const unsigned char * slot, int soff, int Rc, int row_base, int N, const float * bias_l, const float * scale_l,
+                                               const unsigned char * xop, size_t op_bytes, int K, int B, int wave, int lane, unsigned char * exch, EPI epi) {
+    const int nb = K >> 5, stride_q = (K >> 1) + MB_PAD, stride_s = 4 * nb + MB_PAD;
+    const int groups = (Rc + 7) >> 3, nsub = (B + BC - 1) / BC, per = (B + nsub - 1) / nsub, ntasks = groups * nsub;
+    const int u = lane & 7;
+    for (int t = wave; t < ntasks; t += MB_NCW) {
+        const int g = t / nsub, sb = t - g * nsub, b0 = sb * per, b1 = min(B, b0 + per);
+        const int ri = g * 8 + (lane >> 3), rr = ri < Rc ? ri : Rc - 1;
+        const bool has = ri < Rc && row_base + ri < N && u == 0;
+        const float bv = bias_l[ri < 64 ? ri : 63], sv = scale_l ? scale_l[ri < 64 ? ri : 63] : 1.0f;
+        float res[BC];
+        mb_dotq4<BC>(slot + (size_t) rr * stride_q, slot + soff + (size_t) rr * stride_s, xop, op_bytes, exch + (size_t) wave * 3 * MQ4_EXCH_ROW, lane, nb, b0, B, res);
+        epi(res, b0, b1, row_base + ri, has, bv, sv);
+    }
+}
+
+// -------------------------------------------------------------------------------------------------
 // K-format models whose product has no minimum term (Q6_K files, and Q3_K as the loader unpacks it; contract: wa_quantk.hip -
 // ggml_vec_dot_q6_K_q8_K in the AVX2 order).  Blocks are 256 values.  A weight row is the arena's: quants [lane u = 0..7][block][group 0..7][4]
 // signed bytes, 16 scale bytes per block (lanes 0..3 read the first eight, lanes 4..7 the second), one F32 d per block.  An operand row sits in LDS
@@ -1520,8 +1618,9 @@ __host__ __device__ __forceinline__ int mq1_slot_need(int rc, int K) { return mq
 
 // Q: a quantised model (Q5_0 / Q8_0); Q1 (with Q): its blocks carry a minimum (Q4_1 / Q5_1) and every operand row is Q8_1; QK (with Q): a K-format
 // model, every operand row is Q8_K - MK_Q6: Q6_K / Q3_K; MK_Q5, MK_Q2: Q5_K, Q2_K, the formats with a minimum term (operand rows with their block
-// sums, weight slots with a dmin region)
-template <int NP, bool Q, bool Q1 = false, int QK = MK_NO>
+// sums, weight slots with a dmin region); Q4 (with Q): a Q4_0 model - everything is the Q form's but the seven layer products, whose weight rows stay
+// nibbles and whose body is mb_dotq4
+template <int NP, bool Q, bool Q1 = false, int QK = MK_NO, bool Q4 = false>
 __device__ __forceinline__ void mb_body(mb_kargs A_) {
     constexpr bool KM = QK >= MK_Q5;
     constexpr int WF = QK != MK_NO ? QK - 1 : WK_Q6;       // wa_quantk_dev.h's name of the format
@@ -1536,7 +1635,7 @@ __device__ __forceinline__ void mb_body(mb_kargs A_) {
     const mb_layers Ly = (mb_layers) A->layers;
 
     // LDS: xres [8][8] f32 | fc1x [8][32] f32 (quantised models: a block of FC1 outputs) | pk, record scratch | lnp: gamma | beta of the next LayerNorm | xinB: B operand rows
-    // of length d (LayerNorm outputs) | area: B operand rows of length 4d (gathered inputs) / attention scratch | slot 0 | slot 1 (weight rows, then - in
+    // of length d (LayerNorm outputs) | area: B operand rows of length 4d (gathered inputs) / attention scratch | (Q4: the waves' exchange areas) | slot 0 | slot 1 (weight rows, then - in
     // the last KB - the rows' bias and scale).  An operand row is [len] F16, or - quantised models - Q8_0 in the order of mb_dotq8.
     float  * xres = (float *) smem;
     float  * fc1x = (float *) (smem + 256);
@@ -1552,7 +1651,8 @@ __device__ __forceinline__ void mb_body(mb_kargs A_) {
     size_t area_bytes = (size_t) B * op4;
     if (area_bytes < MB_ATT_BYTES) area_bytes = MB_ATT_BYTES;
     area_bytes = (area_bytes + 255) & ~(size_t) 255;
-    unsigned char * slot0 = area + area_bytes;
+    unsigned char * exch = area + area_bytes;           // (Q4) mb_dotq4's block sums on their way to the chain lanes, MQ4_EXCH_BYTES
+    unsigned char * slot0 = exch + (Q4 ? MQ4_EXCH_BYTES : 0);
     const int slot_bytes = A->slot_bytes;
 
     // rows of every matrix this workgroup owns (an even count, the same for every workgroup: mg_rpw).  Quantised models: the first MLP product by
@@ -1587,13 +1687,17 @@ __device__ __forceinline__ void mb_body(mb_kargs A_) {
             while (rc > 8 && mq1_slot_need(rc, ph.K) > slot_bytes) rc -= 8;
             ph.rc = rc;
             ph.moff = mq1_moff(rc, ph.K);
+        } else if constexpr (Q4) {     // the most octets of rows whose two regions fit the slot (mq4_slot_need)
+            int rc = rmax;
+            while (rc > 8 && mq4_slot_need(rc, ph.K) > slot_bytes) rc -= 8;
+            ph.rc = rc;
         } else {
             const int stride = Q ? ph.K + MB_PAD + (ph.K >> 3) + MB_PAD : 2 * ph.K + MB_PAD;      // LDS bytes per weight row (quantised: quants + block scales)
             int rc = ((slot_bytes - (Q ? 3072 : 1024)) / stride) / gp * gp;
             ph.rc = rc > rmax ? rmax : rc;
         }
         ph.nck = (ph.r + ph.rc - 1) / ph.rc;
-        ph.soff = (ph.rc * (ph.K + MB_PAD) + 1023) & ~1023;                                       // (quantised) where the scales' image starts
+        ph.soff = Q4 ? mq4_soff(ph.rc, ph.K) : (ph.rc * (ph.K + MB_PAD) + 1023) & ~1023;          // (quantised) where the scales' image starts
         return ph;
     };
     // wave 7: request chunk ck of phase (l, p) into the slot of parity `par`
@@ -1613,7 +1717,7 @@ __device__ __forceinline__ void mb_body(mb_kargs A_) {
                 if constexpr (KM) __builtin_amdgcn_global_load_lds((const GAS void *) ((gcf) ph.M + (i < last ? i : last)), (LAS void *) (slot + mkm_moff(ph.rc, ph.K) + p64 * 256), 4, 0, 0);
             }
         } else if constexpr (Q) {
-            mb_dma_rows((const GAS unsigned char *) ph.W, ph.K, row0, R, ph.N, slot, lane);
+            mb_dma_rows((const GAS unsigned char *) ph.W, Q4 ? ph.K >> 1 : ph.K, row0, R, ph.N, slot, lane);      // (Q4: the nibble rows as the arena holds them)
             mb_dma_rows((const GAS unsigned char *) ph.D, ph.K >> 3, row0, R, ph.N, slot + ph.soff, lane);
             if constexpr (Q1) mb_dma_rows((const GAS unsigned char *) ph.M, ph.K >> 3, row0, R, ph.N, slot + ph.moff, lane);
         } else mb_dma_rows((const GAS unsigned char *) ph.W, 2 * ph.K, row0, R, ph.N, slot, lane);
@@ -1663,6 +1767,10 @@ __device__ __forceinline__ void mb_body(mb_kargs A_) {
             if (bc == 1)      mb_products_k<1, WF>(slot, ph.soff, ph.moff, Rc, row_base, ph.N, bias_l, scale_l, xop, opb, ph.K, B, wave, lane, epi, KM ? mkm_moff(ph.rc, ph.K) : 0);
             else if (bc == 2) mb_products_k<2, WF>(slot, ph.soff, ph.moff, Rc, row_base, ph.N, bias_l, scale_l, xop, opb, ph.K, B, wave, lane, epi, KM ? mkm_moff(ph.rc, ph.K) : 0);
             else              mb_products_k<3, WF>(slot, ph.soff, ph.moff, Rc, row_base, ph.N, bias_l, scale_l, xop, opb, ph.K, B, wave, lane, epi, KM ? mkm_moff(ph.rc, ph.K) : 0);
+        } else if constexpr (Q4) {
+            if (bc == 1)      mb_products_q4<1>(slot, ph.soff, Rc, row_base, ph.N, bias_l, scale_l, xop, opb, ph.K, B, wave, lane, exch, epi);
+            else if (bc == 2) mb_products_q4<2>(slot, ph.soff, Rc, row_base, ph.N, bias_l, scale_l, xop, opb, ph.K, B, wave, lane, exch, epi);
+            else              mb_products_q4<3>(slot, ph.soff, Rc, row_base, ph.N, bias_l, scale_l, xop, opb, ph.K, B, wave, lane, exch, epi);
         } else if constexpr (Q) {
             if (bc == 1)      mb_products_q<1, Q1>(slot, ph.soff, Rc, row_base, ph.N, bias_l, scale_l, xop, opb, ph.K, B, wave, lane, epi, ph.moff);
             else if (bc == 2) mb_products_q<2, Q1>(slot, ph.soff, Rc, row_base, ph.N, bias_l, scale_l, xop, opb, ph.K, B, wave, lane, epi, ph.moff);
@@ -1858,6 +1966,9 @@ __device__ __forceinline__ void mb_body(mb_kargs A_) {
             if constexpr (QK != MK_NO) {
                 if (groups * B <= MB_NCW) mb_products_k<1, WF>(slot, ph.soff, ph.moff, Rc, row_base, ph.N, bias_l, nullptr, xin, op4, ph.K, B, wave, lane, resid_epi(mb_edge(A, l, E_X3)), KM ? mkm_moff(ph.rc, ph.K) : 0);
                 else                      mb_products_k<2, WF>(slot, ph.soff, ph.moff, Rc, row_base, ph.N, bias_l, nullptr, xin, op4, ph.K, B, wave, lane, resid_epi(mb_edge(A, l, E_X3)), KM ? mkm_moff(ph.rc, ph.K) : 0);
+            } else if constexpr (Q4) {
+                if (groups * B <= MB_NCW) mb_products_q4<1>(slot, ph.soff, Rc, row_base, ph.N, bias_l, nullptr, xin, op4, ph.K, B, wave, lane, exch, resid_epi(mb_edge(A, l, E_X3)));
+                else                      mb_products_q4<2>(slot, ph.soff, Rc, row_base, ph.N, bias_l, nullptr, xin, op4, ph.K, B, wave, lane, exch, resid_epi(mb_edge(A, l, E_X3)));
             } else if constexpr (Q) {
                 if (groups * B <= MB_NCW) mb_products_q<1, Q1>(slot, ph.soff, Rc, row_base, ph.N, bias_l, nullptr, xin, op4, ph.K, B, wave, lane, resid_epi(mb_edge(A, l, E_X3)), ph.moff);
                 else                      mb_products_q<2, Q1>(slot, ph.soff, Rc, row_base, ph.N, bias_l, nullptr, xin, op4, ph.K, B, wave, lane, resid_epi(mb_edge(A, l, E_X3)), ph.moff);
@@ -1954,6 +2065,24 @@ bool MB_CAT(wa_rows_launch_k_np, WA_ROWS_NP)(hipStream_t s, const wa_rows_args &
     hipLaunchKernelGGL(MB_CAT(k_decode_rows_k_np, WA_ROWS_NP), dim3(n_wg), dim3(MB_THREADS), lds, s, a);
     return hipGetLastError() == hipSuccess;
 }
+#elif defined(WA_ROWS_Q4_TU)
+// The step for a Q4_0 model (Q8_0 operand rows, the interleaved product's one chain per output): again a kernel of its own per width in a code object
+// of its own (-DWA_ROWS_Q4_TU)
+__global__ __launch_bounds__(MB_THREADS) void MB_CAT(k_decode_rows_q4_np, WA_ROWS_NP)(const wa_rows_args A) {
+    mb_body<WA_ROWS_NP, true, false, MK_NO, true>((mb_kargs) __builtin_amdgcn_kernarg_segment_ptr());
+}
+bool MB_CAT(wa_rows_launch_q4_np, WA_ROWS_NP)(hipStream_t s, const wa_rows_args & a, int n_wg, size_t lds) {
+    int dev = 0;
+    (void) hipGetDevice(&dev);
+    static bool attr_set[64] = {};
+    if (!attr_set[dev & 63]) {
+        if (hipFuncSetAttribute((const void *) MB_CAT(k_decode_rows_q4_np, WA_ROWS_NP), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return false;
+        attr_set[dev & 63] = true;
+    }
+    if (!a.te_d) return false;
+    hipLaunchKernelGGL(MB_CAT(k_decode_rows_q4_np, WA_ROWS_NP), dim3(n_wg), dim3(MB_THREADS), lds, s, a);
+    return hipGetLastError() == hipSuccess;
+}
 #elif defined(WA_ROWS_KM_TU)
 // The step for a Q5_K or a Q2_K model, the K formats whose product has a minimum term: a kernel per format and width, the pair of a width in a code
 // object of its own (-DWA_ROWS_KM_TU)
@@ -1988,10 +2117,12 @@ __global__ __launch_bounds__(MB_THREADS) void MB_CAT(k_decode_rows_q_np, WA_ROWS
 bool MB_CAT(wa_rows_launch_q1_np, WA_ROWS_NP)(hipStream_t s, const wa_rows_args & a, int n_wg, size_t lds);
 bool MB_CAT(wa_rows_launch_k_np, WA_ROWS_NP)(hipStream_t s, const wa_rows_args & a, int n_wg, size_t lds);
 bool MB_CAT(wa_rows_launch_km_np, WA_ROWS_NP)(hipStream_t s, const wa_rows_args & a, int n_wg, size_t lds);
+bool MB_CAT(wa_rows_launch_q4_np, WA_ROWS_NP)(hipStream_t s, const wa_rows_args & a, int n_wg, size_t lds);
 bool MB_CAT(wa_rows_launch_np, WA_ROWS_NP)(hipStream_t s, const wa_rows_args & a, int n_wg, size_t lds) {
     if (a.quant == 2) return MB_CAT(wa_rows_launch_q1_np, WA_ROWS_NP)(s, a, n_wg, lds);
     if (a.quant == 3) return MB_CAT(wa_rows_launch_k_np, WA_ROWS_NP)(s, a, n_wg, lds);
     if (a.quant == 4) return MB_CAT(wa_rows_launch_km_np, WA_ROWS_NP)(s, a, n_wg, lds);
+    if (a.quant == 5) return MB_CAT(wa_rows_launch_q4_np, WA_ROWS_NP)(s, a, n_wg, lds);
     int dev = 0;
     (void) hipGetDevice(&dev);
     static bool attr_set[64] = {};
@@ -2011,8 +2142,8 @@ bool wa_rows_launch_np20(hipStream_t s, const wa_rows_args & a, int n_wg, size_t
 
 size_t wa_rows_lds_bytes(int d, int B, int n_wg, int quant, int * slot_bytes) {
     if (B < 1 || B > WA_ROWS_MAX || d < 64 || d > WA_MEGA_MAX_D || (d & 127) != 0 || n_wg < 1) return 0;
-    if (quant < 0 || quant > 4) return 0;
-    const bool qk = quant >= 3, km = quant == 4;    // K formats; Q5_K / Q2_K: operand rows with their block sums, weight slots with a dmin region
+    if (quant < 0 || quant > 5) return 0;
+    const bool qk = quant == 3 || quant == 4, km = quant == 4, q4 = quant == 5;    // K formats; Q5_K / Q2_K: operand rows with their block sums, weight slots with a dmin region; Q4_0: nibble rows, an exchange area
     if (qk && (d & 255) != 0) return 0;             // (K formats: blocks of 256)
     const size_t opB = qk ? mk_row_bytes(d >> 8, km) : quant ? mq_row_bytes(d >> 5) : (size_t) d * 2;
     const size_t op4 = qk ? mk_row_bytes((4 * d) >> 8, km) : quant ? mq_row_bytes((4 * d) >> 5) : (size_t) 4 * d * 2;
@@ -2020,7 +2151,7 @@ size_t wa_rows_lds_bytes(int d, int B, int n_wg, int quant, int * slot_bytes) {
     size_t area = (size_t) B * op4;
     if (area < MB_ATT_BYTES) area = MB_ATT_BYTES;
     area = (area + 255) & ~(size_t) 255;
-    const size_t fixed = 1792 + 2 * (((size_t) d * 4 + 1023) & ~(size_t) 1023) + xinB_bytes + area;
+    const size_t fixed = 1792 + 2 * (((size_t) d * 4 + 1023) & ~(size_t) 1023) + xinB_bytes + area + (q4 ? MQ4_EXCH_BYTES : 0);
     auto rpw = [&](int N) { const int r = (N + n_wg - 1) / n_wg; return (r + 1) & ~1; };
     if (rpw(d) > 8) return 0;                       // (xres holds 8 residual values per token row)
     if (quant && !qk && (4 * d) / 32 > n_wg) return 0;     // (whole-block ownership of the first MLP product: one workgroup per block)
@@ -2037,6 +2168,11 @@ size_t wa_rows_lds_bytes(int d, int B, int n_wg, int quant, int * slot_bytes) {
         want = std::max(want, slot_need((rpw(3 * d) + 7) / 8 * 8, d));
         want = std::max(want, slot_need((rpw(4 * d) + 7) / 8 * 8, d));
         want = std::max(want, slot_need((rpw(d) + 7) / 8 * 8, 4 * d));
+    } else if (q4) {            // Q4_0: nibble rows | block scales, the kernel's own rule (mq4_slot_need); the first MLP product by whole Q8_0 blocks, as the Q form
+        need_min = (size_t) mq4_slot_need(8, 4 * d);
+        want = std::max(want, (size_t) mq4_slot_need((rpw(3 * d) + 7) / 8 * 8, d));
+        want = std::max(want, (size_t) mq4_slot_need(32, d));
+        want = std::max(want, (size_t) mq4_slot_need((rpw(d) + 7) / 8 * 8, 4 * d));
     } else if (quant) {
         auto rowb = [&](int K) { return (size_t) K + MB_PAD + (size_t) (K >> 3) + MB_PAD; };
         need_min = 8 * rowb(4 * d) + 3072;
@@ -2070,4 +2206,4 @@ bool wa_launch_decode_rows(hipStream_t s, const wa_rows_args & a, int n_wg) {
     return wa_rows_launch_np20(s, a, n_wg, lds);
 }
 #endif
-#endif      // WA_ROWS_Q1_TU, WA_ROWS_K_TU, WA_ROWS_KM_TU
+#endif      // WA_ROWS_Q1_TU, WA_ROWS_K_TU, WA_ROWS_Q4_TU, WA_ROWS_KM_TU
