@@ -501,8 +501,8 @@ WHISPER_API int whisper_amd_decode_step_probe(struct whisper_context * ctx, stru
  * captured launch sequence (WHISPER_AMD_NO_MEGA=1, unsupported shape, after a hand-off time-out, or a model whose weight format has no
  * one-launch kernel of this form: Q5_1 / Q4_1, Q2_K / Q3_K / Q5_K / Q6_K and Q4_0 / Q4_K files.  Those run the launch sequence in every decode mode, and
  * whisper_amd_rows_enabled is 0 too, unless the state was made under the switch of their several-rows kernel - WHISPER_AMD_ROWS_Q1=1 for Q5_1 / Q4_1,
- * WHISPER_AMD_ROWS_K=1 for Q6_K / Q3_K, WHISPER_AMD_ROWS_KM=1 for Q5_K / Q2_K, WHISPER_AMD_ROWS_Q4=1 for Q4_0 -, which then serves single tokens as well;
- * Q4_K has none and keeps the launch sequence). */
+ * WHISPER_AMD_ROWS_K=1 for Q6_K / Q3_K, WHISPER_AMD_ROWS_KM=1 for Q5_K / Q2_K, WHISPER_AMD_ROWS_Q4=1 for Q4_0,
+ * WHISPER_AMD_ROWS_Q4K=1 for Q4_K -, which then serves single tokens as well). */
 WHISPER_API int whisper_amd_mega_enabled(struct whisper_state * state);
 /* Role of workgroup `wg` of the n_wg workgroups of the one-launch step for a model with n_head text heads (no device needed): role 0 =
  * weight streaming (index = its rank), 1 = self-attention of head `index`, 2 = cross-attention (index = 4 head + quarter). */
@@ -552,7 +552,8 @@ WHISPER_API int whisper_amd_rows_step_probe(struct whisper_context * ctx, struct
  *   cells, as whisper_full makes one for several decoders (at most 5120 cells; the state then counts as prepared for as many decoders as whisper_full's
  *   rule, 512 cells x (decoders + 2), fits into `a`); 4, 5, 6: return the cells in use (n), the cell the next batch is tried at (head), the cache's
  *   size.  -1: bad arguments or a failed allocation.
- * whisper_amd_rows_fits: 1 where the several-rows one-launch step takes B rows of this model on this device, else 0.
+ * whisper_amd_rows_fits: 1 where the several-rows one-launch step takes B rows of this model on this device, else 0.  (A Q4_K model wider than 1024: in
+ *   lock-step passes only - a whisper_decode pass and whisper_amd_rows_debug keep the launch sequence there, whatever this says.)
  * whisper_amd_rows_debug_rows: whisper_amd_rows_debug with a state, a token and a context length per row - row i attends over cells [0, n_past[i]] of
  *   states[i] and that state's encoder K / V, and writes cell n_past[i] with the values a decode would write; the cell bookkeeping is left alone.  The
  *   states are distinct and agree in cache size and audio context (-2 otherwise).  logits_out [B][n_vocab]; row_status_out [B]: 0, or 9000 for a row

@@ -7,6 +7,7 @@
 #include "wa_kernels.h"
 #include "wa_mega.h"
 #include "wa_rows.h"
+#include "wa_quant4.h"     // wa_q4_K_rows4: which rows of a pass of M are the reference's gemm rows
 
 #include <cmath>
 #include <mutex>
@@ -387,8 +388,9 @@ static bool rows_args(whisper_context & ctx, whisper_state & own, wa_rows_args &
     if (wa_rows_lds_bytes(hp.n_text_state, B, std::min(ctx.model.n_cu, 256), a.quant, &a.slot_bytes) == 0 || !wa_rows_prepare(ctx, own)) return false;
     if (a.quant == 2) a.te_m = ctx.model.te_q.qm;      // (Q4_1 / Q5_1: k_decode_rows_q1_np*)
     a.force_inorder = rows_force_inorder();
-    if (a.quant == 3 || a.quant == 4) a.te_sc = ctx.model.te_q.qsc;    // (Q6_K / Q3_K: k_decode_rows_k_np*; quant 5, Q4_0 - k_decode_rows_q4_np* - needs no more than the Q form: its embedding is in Q5_0's layout)
+    if (a.quant == 3 || a.quant == 4 || a.quant == 6) a.te_sc = ctx.model.te_q.qsc;    // (Q6_K / Q3_K: k_decode_rows_k_np*; quant 5, Q4_0 - k_decode_rows_q4_np* - needs no more than the Q form: its embedding is in Q5_0's layout)
     if (a.quant == 4) { a.te_m = ctx.model.te_q.qm; a.wtype = ctx.model.wtype; }      // (Q5_K / Q2_K: k_decode_rows_k5_np* / _k2_np*)
+    if (a.quant == 6) a.te_m = ctx.model.te_q.qm;      // (Q4_K: k_decode_rows_q4k_np*; rows4 stays 0 - every row a pass of its own - unless the caller's rows are ONE pass of the reference)
     a.granules = own.d_rows_gr; a.row_gr = wa_rows_row_gr(a.quant, hp.n_text_state); a.cross_gr = own.d_rows_cgr;
     a.B = a.n_out = B;
     for (int i = 0; i < B; ++i) { a.rows[i] = rows[i]; a.out_row[i] = i; }
@@ -406,9 +408,11 @@ static float * rows_host_out(float * h_rows) {
 static int rows_step(whisper_context & ctx, whisper_state & bst, int B, const wa_rows_row * rows, int n_out, const int32_t * out_row, bool wait_slot) {
     const int n_vocab = ctx.model.hp.n_vocab;
     wa_rows_args a;
+    if (wa_rows_lockstep_only(wa_one_launch_quant(ctx.model.wtype), ctx.model.hp.n_text_state)) return 0;      // (the rows of a whisper_decode pass: the launch sequence at this width)
     if (!bst.rows_form.take_pass() || n_out < 1 || n_out > B || !rows_args(ctx, bst, a, B, rows, audio_ctx(bst), bst.kv_self.size)) return 0;
     a.logits = bst.d_logits; a.status = bst.d_rows_status; a.row_status = bst.d_rows_status + 4;
     a.n_out = n_out;
+    if (a.quant == 6) a.rows4 = wa_q4_K_rows4(B);       // (the token rows of one whisper_decode batch, in its order: one pass of M = B rows in the reference)
     if (out_row) for (int i = 0; i < n_out; ++i) a.out_row[i] = out_row[i];
     hipStream_t s = bst.stream;
     unsigned * h_status = (unsigned *) (bst.h_logits_pinned + (size_t) WA_MAX_DECODERS * n_vocab);      // (the staging buffer has 64 spare words)
@@ -1210,10 +1214,12 @@ static bool rows_probe_args(whisper_context & ctx, whisper_state & own, whisper_
 extern "C" int whisper_amd_rows_debug(struct whisper_context * ctx, struct whisper_state * st, int B, int token, int n_past,
                                       unsigned long long * granules_out, float * logits_out) {
     if (!ctx || !st) return -1;
+    if (wa_rows_lockstep_only(wa_one_launch_quant(ctx->model.wtype), ctx->model.hp.n_text_state)) return -2;      // (a B-token batch of one state: not served at this width)
     if (!WA_HIP_OK(hipSetDevice(ctx->device))) return -1;
     int toks[WA_ROWS_MAX]; for (int i = 0; i < WA_ROWS_MAX; ++i) toks[i] = token;
     wa_rows_args a;
     if (!rows_probe_args(*ctx, *st, nullptr, B, toks, n_past, a)) return -2;
+    if (a.quant == 6) a.rows4 = wa_q4_K_rows4(B);       // (as the B-token batch the launch sequence would run)
     static float * d_dbg = nullptr;
     if (const char * e = getenv("WHISPER_AMD_ROWS_TRACE")) {       // stamps of workgroup `e` (tools/rows_trace.py)
         if (!d_dbg) (void) hipMalloc((void **) &d_dbg, 16384 * 4);

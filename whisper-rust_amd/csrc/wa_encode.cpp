@@ -109,17 +109,19 @@ bool wa_state_alloc(whisper_context & ctx, whisper_state & st) {
         const int dt = hp.n_text_state, Ht = hp.n_text_head;
         const bool shape_ok = !(g && g[0] == '1') && ctx.model.d_mega_layers && ctx.model.n_loaded > 0 && dt == Ht * 64 && dt % 128 == 0 &&
                               dt <= WA_MEGA_MAX_D && hp.n_audio_ctx <= 1500 && ctx.model.n_cu >= 5 * Ht + 16 && tpad <= WA_MEGA_MAX_T;
-        st.mega_form = wa_launch_form(shape_ok && !wa_wtype_has_min(ctx.model.wtype) && !wa_wtype_k(ctx.model.wtype) && ctx.model.wtype != 2);      // (Q4_1 / Q5_1, the K formats, Q4_0 / Q4_K: no k_decode_mega kernel; all but Q4_K have a several-rows kernel behind a switch, below)
+        st.mega_form = wa_launch_form(shape_ok && !wa_wtype_has_min(ctx.model.wtype) && !wa_wtype_k(ctx.model.wtype) && ctx.model.wtype != 2);      // (Q4_1 / Q5_1, the K formats, Q4_0 / Q4_K: no k_decode_mega kernel; each has a several-rows kernel behind a switch, below)
         // Q4_1 / Q5_1: the several-rows kernel has a form for them (k_decode_rows_q1_np*), opt-in by WHISPER_AMD_ROWS_Q1=1 when the state is made; a
         // single token is then that kernel with one row, at every width.  Without the switch every pass of these models is the launch sequence.
         const char * q1 = getenv("WHISPER_AMD_ROWS_Q1");
         const bool rows_q1 = shape_ok && wa_wtype_has_min(ctx.model.wtype) && q1 && q1[0] == '1';
         // Q6_K / Q3_K: the same with k_decode_rows_k_np*, opt-in by WHISPER_AMD_ROWS_K=1; Q5_K / Q2_K: with k_decode_rows_k5_np* / _k2_np*, opt-in by a switch
         // of their own, WHISPER_AMD_ROWS_KM=1; Q4_0: with k_decode_rows_q4_np*, opt-in by WHISPER_AMD_ROWS_Q4=1.  Each switch does nothing for any other format.
-        // Q4_K has no such kernel and keeps the launch sequence: its interleaved product gives a row bits that depend on its place in the pass.
-        const char * qk = getenv("WHISPER_AMD_ROWS_K"), * qkm = getenv("WHISPER_AMD_ROWS_KM"), * q4 = getenv("WHISPER_AMD_ROWS_Q4");
+        // Q4_K: with k_decode_rows_q4k_np*, opt-in by WHISPER_AMD_ROWS_Q4K=1 - its interleaved product gives a row bits that depend on its place in the pass,
+        // which the kernel is told per launch (wa_rows_args::rows4).
+        const char * qk = getenv("WHISPER_AMD_ROWS_K"), * qkm = getenv("WHISPER_AMD_ROWS_KM"), * q4 = getenv("WHISPER_AMD_ROWS_Q4"), * q4k = getenv("WHISPER_AMD_ROWS_Q4K");
         const bool rows_q4 = shape_ok && wa_wtype_rows_q4(ctx.model.wtype) && q4 && q4[0] == '1';
-        const bool rows_k = shape_ok && dt % 256 == 0 && ((wa_wtype_rows_k(ctx.model.wtype) && qk && qk[0] == '1') || (wa_wtype_rows_km(ctx.model.wtype) && qkm && qkm[0] == '1'));
+        const bool rows_k = shape_ok && dt % 256 == 0 && ((wa_wtype_rows_k(ctx.model.wtype) && qk && qk[0] == '1') || (wa_wtype_rows_km(ctx.model.wtype) && qkm && qkm[0] == '1') ||
+                                                           (wa_wtype_rows_q4k(ctx.model.wtype) && q4k && q4k[0] == '1'));
         if (st.mega_form.enabled()) {
             if (!dev_alloc(st.d_mega_cgr, (size_t) hp.n_text_layer * Ht * WA_MEGA_CGR)) return false;
             if (!dev_alloc(st.d_mega_gr, (size_t) hp.n_text_layer * WA_MEGA_EDGES * 4 * dt)) return false;
@@ -137,12 +139,12 @@ bool wa_state_alloc(whisper_context & ctx, whisper_state & st) {
                 int slot = 0;
                 st.rows_form = wa_launch_form(!(r && r[0] == '1') && wa_rows_lds_bytes(dt, 2, std::min(ctx.model.n_cu, 256), quant, &slot) != 0);
                 const char * sr = getenv("WHISPER_AMD_SINGLE_ROWS");
-                st.single_via_rows = st.rows_form.enabled() && wa_rows_lds_bytes(dt, 1, std::min(ctx.model.n_cu, 256), quant, &slot) != 0 &&
+                st.single_via_rows = st.rows_form.enabled() && !wa_rows_lockstep_only(quant, dt) && wa_rows_lds_bytes(dt, 1, std::min(ctx.model.n_cu, 256), quant, &slot) != 0 &&
                                      (rows_q1 || rows_k || rows_q4 || (sr ? sr[0] == '1' : (ctx.model.wtype != 1 && dt > 768)));
-                // Q5_K / Q2_K: the form's buffers now, not with the first pass.  Every pass of such a state is a rows pass, so nothing is saved by waiting, and a
+                // Q5_K / Q2_K / Q4_K: the form's buffers now, not with the first pass.  Every pass of such a state is a rows pass, so nothing is saved by waiting, and a
                 // lock-step group of more members than fit one launch (8 at d = 1280, where 7 fit) sends its members off alone at once: a member allocating
                 // (a memset on the legacy stream) while another captures its launch sequence fails that capture.
-                if (wa_wtype_rows_km(ctx.model.wtype) && st.rows_form.enabled()) (void) wa_rows_prepare(ctx, st);      // (no memory: the form is off, the launch sequence serves)
+                if ((wa_wtype_rows_km(ctx.model.wtype) || wa_wtype_rows_q4k(ctx.model.wtype)) && st.rows_form.enabled()) (void) wa_rows_prepare(ctx, st);      // (no memory: the form is off, the launch sequence serves)
             }
             // (the copy stream, events and pinned buffers of the host overlap are created on first use, wa_spec_begin: a state that
             //  only ever runs inside whisper_amd_full_batch keeps ONE stream - extra streams cost the concurrent chunks their overlap)

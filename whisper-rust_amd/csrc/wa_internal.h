@@ -110,8 +110,12 @@ inline bool wa_wtype_has_min(int wtype) { return wtype == 3 || wtype == 7; }    
 inline bool wa_wtype_rows_k(int wtype) { return wtype == 14 || wtype == 11; }    // Q6_K, Q3_K: the K formats whose product has no minimum term (wa_rows.hip: k_decode_rows_k_np*)
 inline bool wa_wtype_rows_km(int wtype) { return wtype == 13 || wtype == 10; }   // Q5_K, Q2_K: the K formats whose product has a minimum term (wa_rows.hip: k_decode_rows_k5_np*, _k2_np*)
 inline bool wa_wtype_rows_q4(int wtype) { return wtype == 2; }                    // Q4_0: the interleaved 8-row product, one chain per output (wa_rows.hip: k_decode_rows_q4_np*)
-inline int wa_one_launch_quant(int wtype) { return wtype == 1 ? 0 : wa_wtype_has_min(wtype) ? 2 : wa_wtype_rows_k(wtype) ? 3 : wa_wtype_rows_km(wtype) ? 4 : wa_wtype_rows_q4(wtype) ? 5 : 1; }      // wa_mega_args / wa_rows_args::quant
-inline int wa_rows_row_gr(int quant, int d) { return quant == 3 || quant == 4 ? 4 * d : 2 * d; }       // wa_rows_args::row_gr: hand-off granules per token row and edge (the K formats hand F32 values over)
+inline bool wa_wtype_rows_q4k(int wtype) { return wtype == 12; }                  // Q4_K: the interleaved 8-row product, two chains per output, stepped by the row's place in the pass (wa_rows.hip: k_decode_rows_q4k_np*)
+inline int wa_one_launch_quant(int wtype) { return wtype == 1 ? 0 : wa_wtype_has_min(wtype) ? 2 : wa_wtype_rows_k(wtype) ? 3 : wa_wtype_rows_km(wtype) ? 4 : wa_wtype_rows_q4(wtype) ? 5 : wa_wtype_rows_q4k(wtype) ? 6 : 1; }      // wa_mega_args / wa_rows_args::quant
+// Q4_K beyond d = 1024: the several-rows form serves LOCK-STEP passes only (the batcher, whisper_amd_full_batch, whisper_amd_rows_debug_rows).  Measured at
+// d = 1280 a group of eight gains 1.8x, but a whisper_decode pass - a single token, a beam step - is slower than the launch sequence, which keeps it
+inline bool wa_rows_lockstep_only(int quant, int d) { return quant == 6 && d > 1024; }
+inline int wa_rows_row_gr(int quant, int d) { return quant == 3 || quant == 4 || quant == 6 ? 4 * d : 2 * d; }       // wa_rows_args::row_gr: hand-off granules per token row and edge (the K formats hand F32 values over)
 inline bool wa_wtype_k(int wtype) { return wtype == 13 || wtype == 14 || wtype == 10 || wtype == 11 || wtype == 12; }   // Q5_K, Q6_K, Q2_K, Q3_K (wa_quantk.hip), Q4_K (wa_quant4.hip): multiplied with Q8_K activation rows
 
 struct wa_enc_layer {

@@ -675,8 +675,8 @@ bool wa_model_load(whisper_model_loader * loader, whisper_context & wctx) {
             t.co_w  = W(L.cross_out); t.co_b = L.cross_out.b; t.co_d = D(L.cross_out);
             t.ln3_w = L.mlp_ln.w;   t.ln3_b = L.mlp_ln.b;   t.fc1_w = W(L.fc1); t.fc1_b = L.fc1.b; t.fc1_d = D(L.fc1);
             t.fc2_w = W(L.fc2);     t.fc2_b = L.fc2.b;      t.fc2_d = D(L.fc2);
-            // (Q4_1 / Q5_1: the block minimums; Q5_K / Q2_K: the blocks' dmin)
-            if (QMIN || wa_qk_has_min(QT)) { t.qkv_m = L.qkv.qm; t.out_m = L.out.qm; t.cq_m = L.cross_q.qm; t.co_m = L.cross_out.qm; t.fc1_m = L.fc1.qm; t.fc2_m = L.fc2.qm; }
+            // (Q4_1 / Q5_1: the block minimums; Q5_K / Q2_K / Q4_K: the blocks' dmin)
+            if (QMIN || wa_qk_has_min(QT) || wa_wtype_rows_q4k(QT)) { t.qkv_m = L.qkv.qm; t.out_m = L.out.qm; t.cq_m = L.cross_q.qm; t.co_m = L.cross_out.qm; t.fc1_m = L.fc1.qm; t.fc2_m = L.fc2.qm; }
             else t.qkv_m = t.out_m = t.cq_m = t.co_m = t.fc1_m = t.fc2_m = nullptr;
             if (QK) { t.qkv_sc = L.qkv.qsc; t.out_sc = L.out.qsc; t.cq_sc = L.cross_q.qsc; t.co_sc = L.cross_out.qsc; t.fc1_sc = L.fc1.qsc; t.fc2_sc = L.fc2.qsc; }
             else t.qkv_sc = t.out_sc = t.cq_sc = t.co_sc = t.fc1_sc = t.fc2_sc = nullptr;

@@ -29,8 +29,14 @@
 //                         then - mq4_soff in - the scales), operand rows Q8_0 and everything but the seven layer products as k_decode_rows_q_np* (the
 //                         token embedding is stored in Q5_0's layout).  The interleaved product has ONE chain per output: the eight lanes of a weight row
 //                         split the blocks, four each in a round of 32, and hand the exact block sums as int16 through a per-wave LDS exchange area to the
-//                         lane that runs a token row's chain.  Opt-in: WHISPER_AMD_ROWS_Q4=1, 1..8 rows.  Q4_K (the interleaved product whose chain
-//                         steps and quantiser depend on the row's place in the pass) keeps the launch sequence.
+//                         lane that runs a token row's chain.  Opt-in: WHISPER_AMD_ROWS_Q4=1, 1..8 rows.
+//   k_decode_rows_q4k_np* Q4_K weights in the arena's packed form (wa_quant4.h: nibble words [l = 0..7][block][j = 0..3], 16 scale bytes, d and dmin per block),
+//                         operand rows Q8_K with block sums, embedding fetch and logits as k_decode_rows_k5_np* (the token embedding lies in Q5_K's arrays;
+//                         the logits' minimum term runs in four chains).  The interleaved product gives a token row bits that depend on its PLACE in
+//                         the pass the reference would have run: rows below rows4 are gemm rows (four chain steps a block, operand rows by the
+//                         four-row quantiser), the others gemv rows (one step, the row quantiser) - per chain lane and per quantising wave, so one
+//                         launch serves rows of both kinds.  Lane l of an output's eight is activation lane l; the pair sums go round the eight
+//                         lanes by DPP.  Opt-in: WHISPER_AMD_ROWS_Q4K=1, 1..8 rows.
 // Arithmetic is the reference order throughout (same chains, trees, certified F64 sums as wa_exact.hip): logits are bit-identical to
 // the launch sequence, which stays as the fallback.
 #pragma once
@@ -61,11 +67,11 @@ struct wa_rows_args {
     const wa_mega_layer * layers; int n_layer, d, n_head, n_vocab; float eps;
     double rn_d;
     const wa_f16 * te; const float * pe; const float * lnf_w, * lnf_b; const wa_f16 * gelu;
-    const float * te_d; int quant;                      // quant: 0 F16 weights, 1 Q5_0 / Q8_0 (Q8_0 operand rows), 2 Q4_1 / Q5_1 (Q8_1 operand rows, block minimums), 3 Q6_K / Q3_K (Q8_K operand rows), 4 Q5_K / Q2_K (Q8_K operand rows with block sums, dmin), 5 Q4_0 (Q8_0 operand rows, packed nibble rows, one chain per output)
-    const float * te_m;                                 // quant == 2: block minimums of the token embedding (the layers' are in wa_mega_layer); quant == 4: its blocks' dmin
+    const float * te_d; int quant;                      // quant: 0 F16 weights, 1 Q5_0 / Q8_0 (Q8_0 operand rows), 2 Q4_1 / Q5_1 (Q8_1 operand rows, block minimums), 3 Q6_K / Q3_K (Q8_K operand rows), 4 Q5_K / Q2_K (Q8_K operand rows with block sums, dmin), 5 Q4_0 (Q8_0 operand rows, packed nibble rows, one chain per output), 6 Q4_K (Q8_K operand rows with block sums, packed nibble rows, two chains per output stepped by the row's rule: rows4)
+    const float * te_m;                                 // quant == 2: block minimums of the token embedding (the layers' are in wa_mega_layer); quant 4, 6: its blocks' dmin
     unsigned long long kv_layer_stride, cross_layer_stride;
     int cross_tpad, T;
-    unsigned long long * granules; int row_gr;          // [layer][8][B][row_gr] hand-off granules (row_gr = 2 d; quant 3, 4: 4 d, the MLP's hidden row travels in F32)
+    unsigned long long * granules; int row_gr;          // [layer][8][B][row_gr] hand-off granules (row_gr = 2 d; quant 3, 4, 6: 4 d, the MLP's hidden row travels in F32)
     unsigned long long * cross_gr;                      // [layer][B][head][WA_ROWS_CGR]
     float * logits;                                     // [B][n_vocab]
     unsigned * status;                                  // [0] 0 = ok, else the code of the hand-off that timed out; [1] = seq once the launch has run
@@ -79,8 +85,10 @@ struct wa_rows_args {
     int token_beg, token_eot;                           // (records) first timestamp token, end-of-text token
     int n_out, out_row[WA_ROWS_MAX];                    // token rows whose logits are wanted (the reference flags batch.logits rows): logits row m = token row out_row[m]
     wa_rows_row rows[WA_ROWS_MAX];
-    const int8_t * te_sc;                               // quant 3, 4: the token embedding's 16 scale bytes per block (te: its quants, te_d: its d)
+    const int8_t * te_sc;                               // quant 3, 4, 6: the token embedding's 16 scale bytes per block (te: its quants, te_d: its d)
     int wtype;                                          // quant == 4: the ggml type of the weights, 13 Q5_K or 10 Q2_K - which of the two kernels is launched
+    int rows4;                                          // quant == 6: token rows below this are gemm rows of the reference's pass (wa_q4_K_rows4(M) where the rows are ONE pass of M rows in token
+                                                        // order - a whisper_decode batch, a beam step), the others gemv rows; 0 where every row is a pass of its own (lock-step rows, a single token)
 };
 
 // LDS the kernel needs for B rows of a d-wide model with `n_wg` workgroups; 0 when it does not fit (the caller keeps the launch sequence).

@@ -9,6 +9,7 @@
 // alone, right before the barrier that starts the products.
 #include "wa_one_launch_dev.h"
 #include "wa_quantk_dev.h"      // wk_block, wk_hsum8: the per-block work of a K-format product (k_decode_rows_k_np*)
+#include "wa_rows_q8k_dev.h"    // the Q8_K operand rows of the K-format kernels: their layout and their quantiser, both rules of it
 #include "wa_rows.h"
 #include <algorithm>
 
@@ -383,13 +384,7 @@ __device__ __forceinline__ void mb_products_q4(const unsigned char * slot, int s
 // cells apart (mk_ls), so the reads of a step fall on disjoint banks - followed by its F32 d per block; Q6_K's product reads no block sums, the row carries none.  Lane u forms wk_block's integer sum of its 32
 // elements of a block and chains  acc = fma(d_x d_w, (float) sumi, acc)  over the blocks in order; three DPP adds are hsum_float_8.
 // -------------------------------------------------------------------------------------------------
-__host__ __device__ __forceinline__ int mk_ls(int nbk) { return 32 * nbk + 16; }         // bytes between the lanes' runs of an operand row
-// (sums: the formats with a minimum term, Q5_K and Q2_K - k_decode_rows_k5_np* / _k2_np* -, read the operand's block sums.  Their rows hold, between the
-//  quants and the d, the 16 int16 sums of 16 elements of every block, as block_q8_K::bsums orders them - ONE layout for both: Q2_K's lane u reads sums 2 u
-//  and 2 u + 1 as dword u of the block, Q5_K's chain the same dwords, four to a 16-byte read, and adds the halves; pair sums alone would have saved 16
-//  bytes a block and served Q5_K only.  In front of the d, so that they start on a 16-byte boundary whatever the block count.)
-__host__ __device__ __forceinline__ size_t mk_xd_off(int nbk, bool sums = false) { return (size_t) 8 * mk_ls(nbk) + (sums ? (size_t) 32 * nbk : 0); }       // where a row's d start
-__host__ __device__ __forceinline__ size_t mk_row_bytes(int nbk, bool sums = false) { return (mk_xd_off(nbk, sums) + (size_t) 4 * nbk + 15) & ~(size_t) 15; }
+// (mk_ls, mk_xd_off, mk_row_bytes - the layout of such an operand row - and mk_quant_block, the quantiser of one block: wa_rows_q8k_dev.h)
 // A slot's image of rc weight rows of length K: quants (row stride K + MB_PAD) | scale bytes (row stride K / 16 + MB_PAD) | the rows' d, rc K / 256
 // consecutive floats - a row of K = 256 has ONE, too short for the 16-byte cells of mb_dma_rows, so they come as dwords, 64 per instruction -, each
 // region in whole KB, then the KB of bias and column scale.  The kernel and wa_rows_lds_bytes share this rule exactly (as mq1_slot_need).
@@ -400,45 +395,8 @@ __host__ __device__ __forceinline__ int mk_slot_need(int rc, int K) { return mk_
 __host__ __device__ __forceinline__ int mkm_moff(int rc, int K) { return mk_doff(rc, K) + ((rc * (K >> 8) * 4 + 1023) & ~1023); }
 __host__ __device__ __forceinline__ int mkm_slot_need(int rc, int K) { return mkm_moff(rc, K) + ((rc * (K >> 8) * 4 + 1023) & ~1023) + 1024; }
 // the format of a K-format instantiation (mb_body's QK): none, Q6_K / Q3_K, Q5_K, Q2_K; minus one it is wa_quantk_dev.h's WK_* of the product
-enum { MK_NO = 0, MK_Q6 = 1, MK_Q5 = 2, MK_Q2 = 3 };
+enum { MK_NO = 0, MK_Q6 = 1, MK_Q5 = 2, MK_Q2 = 3, MK_Q4K = 4 };      // (MK_Q4K: Q4_K - products of its own, mb_dotq4k; embedding and logits in Q5_K's arrays)
 static_assert(MK_Q6 - 1 == WK_Q6 && MK_Q5 - 1 == WK_Q5 && MK_Q2 - 1 == WK_Q2, "mb_dotk hands QK - 1 to wk_block");
-
-// quantize_row_q8_K_ref of one block held by a wave, lane i with elements i, 64 + i, 128 + i, 192 + i of it (v[0..3]: how a LayerNorm row and a
-// swept run of granules lie in a wave) -> the operand row `op` (block blk of nbk).  The scale comes from the FIRST element of largest magnitude, with
-// its sign: a lane's lowest such element by strict comparison in index order, then the lowest index over the wave (k_quantize_q8_K's rule for
-// this distribution of the elements).  All lanes take part.  SUMS: the block's bsums as well (mk_xd_off) - register k holds element 64 k + lane, so sum
-// 4 k + (lane >> 4) is register k's quant added up over one 16-lane DPP row (integers: exact in any order; an all-zero block has zero quants and zero sums)
-template <bool SUMS = false>
-__device__ __forceinline__ void mk_quant_block(const float (&v)[4], int lane, unsigned char * op, int nbk, int blk) {
-    float amax = fabsf(v[0]); int at = lane;
-#pragma unroll
-    for (int k = 1; k < 4; ++k) if (fabsf(v[k]) > amax) { amax = fabsf(v[k]); at = 64 * k + lane; }
-    const float wmax = wave_max(amax);
-    int first = amax == wmax ? at : 256;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) first = min(first, __shfl_xor(first, o, WAVE));
-    const int fk = first >> 6;
-    const float max = __shfl(fk == 0 ? v[0] : fk == 1 ? v[1] : fk == 2 ? v[2] : v[3], first & 63, WAVE);
-    const float iscale = wmax != 0.0f ? -127.f / max : 0.0f;
-    const float dq = wmax != 0.0f ? 1.0f / iscale : 0.0f;
-    unsigned char * run = op + (size_t) ((lane & 31) >> 2) * mk_ls(nbk) + (size_t) blk * 32 + (lane >> 5) * 4;      // element 64 k + i: group 2 k + (i >> 5), lane (i & 31) >> 2, byte i & 3
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const int qi = wmax != 0.0f ? min(127, (int) rintf(iscale * v[k])) : 0;
-        const unsigned q = (unsigned) qi & 0xffu;
-        const unsigned w = q | (dpp_u32<0x101>(q) << 8) | (dpp_u32<0x102>(q) << 16) | (dpp_u32<0x103>(q) << 24);      // row_shl:1..3
-        if ((lane & 3) == 0) *(unsigned *) (run + 8 * k) = w;
-        if constexpr (SUMS) {
-            int s = qi;
-            s += __builtin_amdgcn_update_dpp(0, s, 0x128, 0xf, 0xf, true);      // row_ror:8, 4, 2, 1: the row's sum in every lane of it
-            s += __builtin_amdgcn_update_dpp(0, s, 0x124, 0xf, 0xf, true);
-            s += __builtin_amdgcn_update_dpp(0, s, 0x122, 0xf, 0xf, true);
-            s += __builtin_amdgcn_update_dpp(0, s, 0x121, 0xf, 0xf, true);
-            if ((lane & 15) == 0) ((short *) (op + (size_t) 8 * mk_ls(nbk)))[16 * blk + 4 * k + (lane >> 4)] = (short) s;
-        }
-    }
-    if (lane == 0) ((float *) (op + mk_xd_off(nbk, SUMS)))[blk] = dq;
-}
 
 // The block's 16 scale bytes in every lane of an output's eight, from the halves they hold (lanes 0..3 the first eight bytes, lanes 4..7 the second, as
 // the Q6_K form reads them): one DPP exchange of the two registers.  Q5_K: lo = the eight scales, hi = the eight minimums.  Q2_K: the lane's own half
@@ -469,15 +427,27 @@ __device__ __forceinline__ float mk_min2(int ma, int mb, int bs2) { return (floa
 //         per block, one DPP move hands the total to lane 0 at the end); the result is hsum_float_8(acc) + summs
 //   Q2_K: lane u adds its two sub-blocks' minimums into acc by an fma of their own, per block before the product term
 // the running sum of the minimum chain a lane keeps beside its lane chains: Q5_K only (an empty member elsewhere, so that the other formats' code is what it was)
-template <int F> struct mk_min_chain {};
-template <> struct mk_min_chain<WK_Q5> { float summs = 0.0f; };
+// M4 (Q4_K's plain product, ggml_vec_dot_q4_K_q8_K - the logits): FOUR minimum chains, one per pair of sub-blocks, each an fma, joined as (a0 + a2) + (a1 + a3)
+template <int F, bool M4 = false> struct mk_min_chain {};
+template <> struct mk_min_chain<WK_Q5, false> { float summs = 0.0f; };
+template <> struct mk_min_chain<WK_Q5, true> { float am[4] = { 0.0f, 0.0f, 0.0f, 0.0f }; };
+// Q4_K: one block's step of the four minimum chains of ONE token row (wa_q4_K_dot_plain: acc_m[k] = fma(-d_x dmin_w, (float) (m[2 k] s[2 k] + m[2 k + 1] s[2 k + 1]), acc_m[k]))
+__device__ __forceinline__ void mk_min4(wk_i2 mm, const unsigned char * xs, float dx, float dwm, float (&am)[4]) {
+    const wk_i4 g0 = *(const wk_i4 *) xs, g1 = *(const wk_i4 *) (xs + 16);
+    const float dm = -dx * dwm;
+    am[0] = fmaf(dm, (float) (wk_byte<WK_Q5>(mm, 0) * mk_pair_sum(g0.x) + wk_byte<WK_Q5>(mm, 1) * mk_pair_sum(g0.y)), am[0]);
+    am[1] = fmaf(dm, (float) (wk_byte<WK_Q5>(mm, 2) * mk_pair_sum(g0.z) + wk_byte<WK_Q5>(mm, 3) * mk_pair_sum(g0.w)), am[1]);
+    am[2] = fmaf(dm, (float) (wk_byte<WK_Q5>(mm, 4) * mk_pair_sum(g1.x) + wk_byte<WK_Q5>(mm, 5) * mk_pair_sum(g1.y)), am[2]);
+    am[3] = fmaf(dm, (float) (wk_byte<WK_Q5>(mm, 6) * mk_pair_sum(g1.z) + wk_byte<WK_Q5>(mm, 7) * mk_pair_sum(g1.w)), am[3]);
+}
 // Q5_K, Q2_K: one weight block (quants w0 | w1, its 16 scale bytes lo | hi, d, dmin) against block b of BC token rows, the step of both chains
-template <int BC, int F>
+template <int BC, int F, bool M4 = false>
 __device__ __forceinline__ void mk_block_step(wk_i4 w0, wk_i4 w1, wk_i2 lo, wk_i2 hi, float dw, float dwm, int u, int nbk, int b, const unsigned char * const (&xq)[BC], const float * const (&xd)[BC],
-                                              const unsigned char * xown /* Q5_K: the token row whose minimum chain this lane runs */, float (&acc)[BC], mk_min_chain<F> & mc) {
+                                              const unsigned char * xown /* Q5_K: the token row whose minimum chain this lane runs */, float (&acc)[BC], mk_min_chain<F, M4> & mc) {
     wk_i2 s = lo;
     int ma = 0, mb = 0;
-    if constexpr (F == WK_Q5) mc.summs = mk_min5(hi, xown + (size_t) 8 * mk_ls(nbk) + 32 * b, ((const float *) (xown + mk_xd_off(nbk, true)))[b], dwm, mc.summs);
+    if constexpr (F == WK_Q5 && M4) mk_min4(hi, xown + (size_t) 8 * mk_ls(nbk) + 32 * b, ((const float *) (xown + mk_xd_off(nbk, true)))[b], dwm, mc.am);
+    else if constexpr (F == WK_Q5) mc.summs = mk_min5(hi, xown + (size_t) 8 * mk_ls(nbk) + 32 * b, ((const float *) (xown + mk_xd_off(nbk, true)))[b], dwm, mc.summs);
     if constexpr (F == WK_Q2) {
         const int sh = 8 * (u & 3) + 4;
         s = u < 4 ? lo : hi;
@@ -550,6 +520,109 @@ __device__ __forceinline__ void mb_products_k(const unsigned char * slot, int so
 }
 
 // -------------------------------------------------------------------------------------------------
+// Q4_K models (k_decode_rows_q4k_np*; contract: wa_quant4.h - wa_q4_K_dot8, the reference's interleaved 8-row product).  Every output carries TWO chains
+// over the 256-value blocks, in block order - acc and accmin, out = acc - accmin - and HOW a chain steps depends on the token row's place in the pass the
+// reference would have run: a row below `rows4` (wa_q4_K_rows4 of the pass's M) is a gemm row - a chain step per PAIR of sub-blocks, four a block, and
+// its operand rows quantised by the four-row rule (mk_quant_block<., true>) -, every other row a gemv row: one step per block, the row rule.  The rows of
+// one launch may be of both kinds (M = 5, 6, 7), the rows of a lock-step pass are all gemv rows whatever their number.
+//
+// A weight row in the slot is the arena's: nibble words u32 [l = 0..7][block][j = 0..3] (K / 2 bytes; byte e of word (l, b, j): low nibble element 4 l + e of
+// sub-block 2 j, high nibble the same element of sub-block 2 j + 1, both unsigned), 16 scale bytes per block (sc[0..7], then m[0..7]), d and dmin F32 per
+// block.  No int8 copy is made.  Lane l of an output's eight IS activation lane l (the operand rows are the K formats', mk_ls): per block ONE 16-byte read
+// of the nibble words, unpacked once for all token rows of the task; per token row two 16-byte reads of its quants, eight dot4 - the lane's share of the
+// eight sub-block sums -, times sc[s] in int32 into the four PAIR sums s = 2 j, 2 j + 1, and those summed over the eight lanes by DPP so that every lane
+// holds them (a mirror and two quad permutations; integers: exact in any order).  Lane r < BC of the eight then runs token row b0 + r's two chains: the four
+// minimum terms m[s] (bsums[2 s] + bsums[2 s + 1]) by pairs from its row's block sums, d_w d_x and dmin_w d_x rounded once per block, and - the rule of ITS
+// row - four fma steps from the pair sums, or one from their int32 total (converted to nearest even: it can pass 2^24).  ONE body for both rules; the
+// rule is per chain lane, not per task.  No float chain is re-associated; no exchange through LDS, no barrier.
+// The slot's image of rc weight rows of length K: nibble rows (stride K / 2 + MB_PAD) | scale bytes (stride K / 16 + MB_PAD) | d | dmin (rc K / 256
+// consecutive floats each, by dwords as the K forms'), each region in whole KB, then the KB of bias and column scale.  The kernel and wa_rows_lds_bytes
+// share this rule exactly (as mkm_slot_need).
+// -------------------------------------------------------------------------------------------------
+__host__ __device__ __forceinline__ int mq4k_soff(int rc, int K) { return (rc * ((K >> 1) + MB_PAD) + 1023) & ~1023; }
+__host__ __device__ __forceinline__ int mq4k_doff(int rc, int K) { return mq4k_soff(rc, K) + ((rc * ((K >> 4) + MB_PAD) + 1023) & ~1023); }
+__host__ __device__ __forceinline__ int mq4k_moff(int rc, int K) { return mq4k_doff(rc, K) + ((rc * (K >> 8) * 4 + 1023) & ~1023); }
+__host__ __device__ __forceinline__ int mq4k_slot_need(int rc, int K) { return mq4k_moff(rc, K) + ((rc * (K >> 8) * 4 + 1023) & ~1023) + 1024; }
+// an integer's sum over the eight lanes of an output, in every one of them
+__device__ __forceinline__ int mq4k_sum8(int v) {
+    v += __builtin_amdgcn_update_dpp(0, v, 0x141, 0xf, 0xf, true);      // row_half_mirror: v[u] + v[7 - u] - lanes 0..3 (and 4..7) hold the four disjoint pairs
+    v += __builtin_amdgcn_update_dpp(0, v, 0xb1, 0xf, 0xf, true);       // quad_perm [1,0,3,2]
+    v += __builtin_amdgcn_update_dpp(0, v, 0x4e, 0xf, 0xf, true);       // quad_perm [2,3,0,1]
+    return v;
+}
+template <int BC>
+__device__ __forceinline__ void mb_dotq4k(const unsigned char * wrow, const unsigned char * ws, const float * wd, const float * wm, const unsigned char * xop, size_t op_bytes,
+                                          int lane_, int nbk, int b0, int B, int rows4, float (&res)[BC]) {
+    int lane = lane_;
+    asm volatile("" : "+v"(lane));      // (as mb_ln_row: hoisted out of the layer loop, the per-lane addresses of every inlined copy of this body cost registers all kernel long)
+    const int u = lane & 7;
+    const unsigned char * wq = wrow + (size_t) u * nbk * 16;
+    const unsigned char * xq[BC];
+#pragma unroll
+    for (int j = 0; j < BC; ++j) xq[j] = xop + (size_t) (b0 + j < B ? b0 + j : B - 1) * op_bytes + (size_t) u * mk_ls(nbk);
+    // the chains this lane runs: token row b0 + u of the task (lanes u >= BC repeat token row b0's; nobody reads them)
+    const int own = b0 + (u < BC ? u : 0);
+    const bool gemm = own < rows4;
+    const unsigned char * xown = xop + (size_t) (own < B ? own : B - 1) * op_bytes;
+    const unsigned char * xs_own = xown + (size_t) 8 * mk_ls(nbk);
+    const float * xd_own = (const float *) (xown + mk_xd_off(nbk, true));
+    float acc = 0.0f, accmin = 0.0f;
+    for (int b = 0; b < nbk; ++b) {
+        const wk_i4 w = *(const wk_i4 *) (wq + 16 * b);
+        const wk_i2 sc = *(const wk_i2 *) (ws + 16 * b), mn = *(const wk_i2 *) (ws + 16 * b + 8);
+        const wk_i4 lo = w & 0x0f0f0f0f, hi = (w >> 4) & 0x0f0f0f0f;      // sub-blocks 0, 2, 4, 6 | 1, 3, 5, 7: values 0..15, signed bytes as they are
+        int mine[4] = { 0, 0, 0, 0 };
+#pragma unroll
+        for (int j = 0; j < BC; ++j) {
+            const wk_i4 x0 = *(const wk_i4 *) (xq[j] + 32 * b), x1 = *(const wk_i4 *) (xq[j] + 32 * b + 16);      // the lane's quads of sub-blocks 0..3 | 4..7
+            int p[4];
+            p[0] = wk_byte<WK_Q5>(sc, 0) * __builtin_amdgcn_sdot4(lo.x, x0.x, 0, false) + wk_byte<WK_Q5>(sc, 1) * __builtin_amdgcn_sdot4(hi.x, x0.y, 0, false);
+            p[1] = wk_byte<WK_Q5>(sc, 2) * __builtin_amdgcn_sdot4(lo.y, x0.z, 0, false) + wk_byte<WK_Q5>(sc, 3) * __builtin_amdgcn_sdot4(hi.y, x0.w, 0, false);
+            p[2] = wk_byte<WK_Q5>(sc, 4) * __builtin_amdgcn_sdot4(lo.z, x1.x, 0, false) + wk_byte<WK_Q5>(sc, 5) * __builtin_amdgcn_sdot4(hi.z, x1.y, 0, false);
+            p[3] = wk_byte<WK_Q5>(sc, 6) * __builtin_amdgcn_sdot4(lo.w, x1.z, 0, false) + wk_byte<WK_Q5>(sc, 7) * __builtin_amdgcn_sdot4(hi.w, x1.w, 0, false);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) { const int t = mq4k_sum8(p[k]); mine[k] = (j == 0 || u == j) ? t : mine[k]; }
+        }
+        const wk_i4 g0 = *(const wk_i4 *) (xs_own + 32 * b), g1 = *(const wk_i4 *) (xs_own + 32 * b + 16);      // the row's 16 sums of this block, a pair to a dword
+        int im[4];
+        im[0] = wk_byte<WK_Q5>(mn, 0) * mk_pair_sum(g0.x) + wk_byte<WK_Q5>(mn, 1) * mk_pair_sum(g0.y);
+        im[1] = wk_byte<WK_Q5>(mn, 2) * mk_pair_sum(g0.z) + wk_byte<WK_Q5>(mn, 3) * mk_pair_sum(g0.w);
+        im[2] = wk_byte<WK_Q5>(mn, 4) * mk_pair_sum(g1.x) + wk_byte<WK_Q5>(mn, 5) * mk_pair_sum(g1.y);
+        im[3] = wk_byte<WK_Q5>(mn, 6) * mk_pair_sum(g1.z) + wk_byte<WK_Q5>(mn, 7) * mk_pair_sum(g1.w);
+        const float dx = xd_own[b];
+        const float pd = wd[b] * dx, pm = wm[b] * dx;
+        if (gemm) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) { acc = fmaf((float) mine[k], pd, acc); accmin = fmaf((float) im[k], pm, accmin); }
+        } else {
+            acc = fmaf((float) (mine[0] + mine[1] + mine[2] + mine[3]), pd, acc);
+            accmin = fmaf((float) (im[0] + im[1] + im[2] + im[3]), pm, accmin);
+        }
+    }
+    const float out = acc - accmin;
+#pragma unroll
+    for (int j = 0; j < BC; ++j) res[j] = wk_from_lane(out, j);      // lane 0 of the group takes token row b0 + j's result from lane j
+}
+// product tasks of a Q4_K chunk (as mb_products_k); doff, moff: where the rows' d and dmin start
+template <int BC, typename EPI>
+__device__ __forceinline__ void mb_products_q4k(const unsigned char * slot, int soff, int doff, int moff, int Rc, int row_base, int N, const float * bias_l, const float * scale_l,
+                                                const unsigned char * xop, size_t op_bytes, int K, int B, int rows4, int wave, int lane, EPI epi) {
+    const int nbk = K >> 8, stride_q = (K >> 1) + MB_PAD, stride_s = 16 * nbk + MB_PAD;
+    const int groups = (Rc + 7) >> 3, nsub = (B + BC - 1) / BC, per = (B + nsub - 1) / nsub, ntasks = groups * nsub;
+    const int u = lane & 7;
+    for (int t = wave; t < ntasks; t += MB_NCW) {
+        const int g = t / nsub, sb = t - g * nsub, b0 = sb * per, b1 = min(B, b0 + per);
+        const int ri = g * 8 + (lane >> 3), rr = ri < Rc ? ri : Rc - 1;
+        const bool has = ri < Rc && row_base + ri < N && u == 0;
+        const float bv = bias_l[ri < 64 ? ri : 63], sv = scale_l ? scale_l[ri < 64 ? ri : 63] : 1.0f;
+        float res[BC];
+        mb_dotq4k<BC>(slot + (size_t) rr * stride_q, slot + soff + (size_t) rr * stride_s, (const float *) (slot + doff) + (size_t) rr * nbk, (const float *) (slot + moff) + (size_t) rr * nbk,
+                      xop, op_bytes, lane, nbk, b0, B, rows4, res);
+        epi(res, b0, b1, row_base + ri, has, bv, sv);
+    }
+}
+
+// -------------------------------------------------------------------------------------------------
 // LayerNorm of ONE token row by ONE wave (ops.cpp:3225-3242 semantics as wa_exact.hip: wa_ln_stats - F64 sums in any order, accepted
 // when certified order-independent, else redone in index order): the row comes from granules (or the embeddings), stays in registers,
 // and leaves as F16 in `dst`.  The in-order fallback walks the registers lane by lane (no LDS copy of the row).
@@ -576,7 +649,7 @@ __device__ __forceinline__ double mb_seq_sum(const float (&xv)[NP], int d, bool 
 }
 template <int NP, bool Q = false, bool Q1 = false, int QK = MK_NO>       // Q: the normalised row leaves as Q8_0 (the next product's operand), not as F16; Q1: as Q8_1; QK: as Q8_K
 __device__ __forceinline__ void mb_ln_row(mb_kargs A, mo_ctl & c, gu64 * edge_row /* null: embeddings */, const float * lnp /* LDS: gamma | beta, each d floats in whole KB */, const float * gw_g, const float * gb_g /* global, when non-null */,
-                                          int b, int lane_, wa_f16 * dst, float * xres_b, int row_d, int r_d, unsigned code, int token = 0, bool tw = false, int tslot = 0) {
+                                          int b, int lane_, wa_f16 * dst, float * xres_b, int row_d, int r_d, unsigned code, int token = 0, bool tw = false, int tslot = 0, bool row4 = false /* MK_Q4K: the four-row rule of the quantiser */) {
     // (nothing derived from the lane index may live across calls: hoisted out of the layer loop the per-element LDS addresses went to scratch, and every
     //  reload waits for the vector-memory queue)
     int lane = lane_;
@@ -610,7 +683,7 @@ __device__ __forceinline__ void mb_ln_row(mb_kargs A, mo_ctl & c, gu64 * edge_ro
                 } else {        // dequantize_row_q5_K / q2_K: (d * sc) * q, then - (dmin * m), no fma
                     const gcf tm = (gcf) A->te_m + (size_t) token * nbk;
                     int sc, mn;
-                    if constexpr (QK == MK_Q5) { sc = (int) (unsigned char) tsc[bb * 16 + (el >> 5)]; mn = (int) (unsigned char) tsc[bb * 16 + 8 + (el >> 5)]; }
+                    if constexpr (QK == MK_Q5 || QK == MK_Q4K) { sc = (int) (unsigned char) tsc[bb * 16 + (el >> 5)]; mn = (int) (unsigned char) tsc[bb * 16 + 8 + (el >> 5)]; }
                     else { const int sb = (int) (unsigned char) tsc[bb * 16 + 8 * ((el >> 4) & 1) + (el >> 5)]; sc = sb & 15; mn = sb >> 4; }
                     const float d1 = td[bb] * (float) sc;
                     const float m1 = tm[bb] * (float) mn;
@@ -704,7 +777,7 @@ __device__ __forceinline__ void mb_ln_row(mb_kargs A, mo_ctl & c, gu64 * edge_ro
     if constexpr (QK != MK_NO) {         // d % 256 == 0: every block below d / 256 is whole
 #pragma unroll
         for (int bk = 0; bk < NP / 4; ++bk)
-            if (256 * bk < d) { const float v4[4] = { xv[4 * bk], xv[4 * bk + 1], xv[4 * bk + 2], xv[4 * bk + 3] }; mk_quant_block<(QK >= MK_Q5)>(v4, lane, (unsigned char *) dst, d >> 8, bk); }
+            if (256 * bk < d) { const float v4[4] = { xv[4 * bk], xv[4 * bk + 1], xv[4 * bk + 2], xv[4 * bk + 3] }; mk_quant_block<(QK >= MK_Q5), QK == MK_Q4K>(v4, lane, (unsigned char *) dst, d >> 8, bk, row4); }
     }
 }
 
@@ -1501,7 +1574,7 @@ __device__ __forceinline__ void mb_logits_q1(mb_kargs A, const unsigned char * x
 
 // the same for a K-format token embedding: a piece is 4 blocks of 256 (mk_te_piece: 11 registers a block, 12 with dmin), the token rows are Q8_K
 // (mb_dotk's chains, which go on across the pieces of a row; Q5_K: lane u runs the minimum chain of token row u)
-template <int BT, int F = WK_Q6>
+template <int BT, int F = WK_Q6, bool M4 = false>
 __device__ __forceinline__ void mb_logits_k(mb_kargs A, const unsigned char * xop, size_t op_bytes, int B, int lane, int wave, unsigned (&pfa)[48], float * lg) {
     constexpr bool KM = F != WK_Q6;
     const int d = A->d, nbk = d >> 8, nbat = (nbk + 3) / 4, n_vocab = A->n_vocab;
@@ -1517,7 +1590,7 @@ __device__ __forceinline__ void mb_logits_k(mb_kargs A, const unsigned char * xo
         mk_te_piece<KM>(A, row < n_vocab ? row : 0, u, bt, buf);
     };
     float acc[BT];
-    mk_min_chain<F> mc;
+    mk_min_chain<F, M4> mc;
     const unsigned char * xq[BT]; const float * xd[BT];
 #pragma unroll
     for (int m = 0; m < BT; ++m) { const unsigned char * r = xop + (size_t) (m < B ? m : B - 1) * op_bytes; xq[m] = r + (size_t) u * mk_ls(nbk); xd[m] = (const float *) (r + mk_xd_off(nbk, KM)); }
@@ -1526,7 +1599,8 @@ __device__ __forceinline__ void mb_logits_k(mb_kargs A, const unsigned char * xo
         if (bt == 0) {
 #pragma unroll
             for (int m = 0; m < BT; ++m) acc[m] = 0.0f;
-            if constexpr (F == WK_Q5) mc.summs = 0.0f;
+            if constexpr (F == WK_Q5 && M4) mc.am[0] = mc.am[1] = mc.am[2] = mc.am[3] = 0.0f;
+            else if constexpr (F == WK_Q5) mc.summs = 0.0f;
         }
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
@@ -1540,7 +1614,7 @@ __device__ __forceinline__ void mb_logits_k(mb_kargs A, const unsigned char * xo
                 if constexpr (KM) {
                     wk_i2 lo, hi;
                     mk_sc16(s, u, lo, hi);
-                    mk_block_step<BT, F>(w0, w1, lo, hi, dw, __uint_as_float(buf[44 + k]), u, nbk, bb, xq, xd, xop + (size_t) (u < B ? u : B - 1) * op_bytes, acc, mc);
+                    mk_block_step<BT, F, M4>(w0, w1, lo, hi, dw, __uint_as_float(buf[44 + k]), u, nbk, bb, xq, xd, xop + (size_t) (u < B ? u : B - 1) * op_bytes, acc, mc);
                 } else {
 #pragma unroll
                     for (int m = 0; m < BT; ++m) {
@@ -1556,7 +1630,8 @@ __device__ __forceinline__ void mb_logits_k(mb_kargs A, const unsigned char * xo
 #pragma unroll
             for (int m = 0; m < BT; ++m) {
                 float v = wk_hsum8(acc[m]);
-                if constexpr (F == WK_Q5) v = v + wk_from_lane(mc.summs, m);
+                if constexpr (F == WK_Q5 && M4) { const float t = (mc.am[0] + mc.am[2]) + (mc.am[1] + mc.am[3]); v = v + wk_from_lane(t, m); }
+                else if constexpr (F == WK_Q5) v = v + wk_from_lane(mc.summs, m);
                 if (u == 0 && j < 4) lg[m * 256 + (8 * j + wave) * 8 + (lane >> 3)] = v;
                 else if (u == 0 && row < n_vocab && m < B) logits[(size_t) m * n_vocab + row] = v;
             }
@@ -1623,7 +1698,8 @@ __host__ __device__ __forceinline__ int mq1_slot_need(int rc, int K) { return mq
 template <int NP, bool Q, bool Q1 = false, int QK = MK_NO, bool Q4 = false>
 __device__ __forceinline__ void mb_body(mb_kargs A_) {
     constexpr bool KM = QK >= MK_Q5;
-    constexpr int WF = QK != MK_NO ? QK - 1 : WK_Q6;       // wa_quantk_dev.h's name of the format
+    constexpr bool Q4K = QK == MK_Q4K;                     // Q4_K: the seven layer products are mb_dotq4k's, on nibble rows; a token row's rule from A->rows4
+    constexpr int WF = Q4K ? WK_Q5 : QK != MK_NO ? QK - 1 : WK_Q6;       // wa_quantk_dev.h's name of the format (Q4_K: of its token embedding, which lies in Q5_K's arrays)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const mb_kargs A = mo_uniform(A_);
     const int tid = threadIdx.x, lane = tid & 63;
@@ -1677,9 +1753,9 @@ __device__ __forceinline__ void mb_body(mb_kargs A_) {
             ph.S = p == 0 ? Y.qkv_sc : p == 1 ? Y.out_sc : p == 2 ? Y.cq_sc : p == 3 ? Y.co_sc : p == 4 ? Y.fc1_sc : Y.fc2_sc;
             if constexpr (KM) ph.M = p == 0 ? Y.qkv_m : p == 1 ? Y.out_m : p == 2 ? Y.cq_m : p == 3 ? Y.co_m : p == 4 ? Y.fc1_m : Y.fc2_m;      // (the rows' dmin, behind their d: mkm_moff)
             int rc = rmax;
-            while (rc > 8 && (KM ? mkm_slot_need(rc, ph.K) : mk_slot_need(rc, ph.K)) > slot_bytes) rc -= 8;
+            while (rc > 8 && (Q4K ? mq4k_slot_need(rc, ph.K) : KM ? mkm_slot_need(rc, ph.K) : mk_slot_need(rc, ph.K)) > slot_bytes) rc -= 8;
             ph.rc = rc;
-            ph.moff = mk_doff(rc, ph.K);
+            ph.moff = Q4K ? mq4k_doff(rc, ph.K) : mk_doff(rc, ph.K);
         } else if constexpr (Q1) {     // the most octets of rows whose three regions fit the slot (wa_rows_lds_bytes admits a slot that holds one)
             ph.M = p == 0 ? Y.qkv_m : p == 1 ? Y.out_m : p == 2 ? Y.cq_m : p == 3 ? Y.co_m : p == 4 ? Y.fc1_m : Y.fc2_m;
             int rc = ((slot_bytes - 1024) / (ph.K + MB_PAD + 2 * ((ph.K >> 3) + MB_PAD))) / 8 * 8;
@@ -1697,7 +1773,7 @@ __device__ __forceinline__ void mb_body(mb_kargs A_) {
             ph.rc = rc > rmax ? rmax : rc;
         }
         ph.nck = (ph.r + ph.rc - 1) / ph.rc;
-        ph.soff = Q4 ? mq4_soff(ph.rc, ph.K) : (ph.rc * (ph.K + MB_PAD) + 1023) & ~1023;          // (quantised) where the scales' image starts
+        ph.soff = Q4 ? mq4_soff(ph.rc, ph.K) : Q4K ? mq4k_soff(ph.rc, ph.K) : (ph.rc * (ph.K + MB_PAD) + 1023) & ~1023;          // (quantised) where the scales' image starts
         return ph;
     };
     // wave 7: request chunk ck of phase (l, p) into the slot of parity `par`
@@ -1709,12 +1785,12 @@ __device__ __forceinline__ void mb_body(mb_kargs A_) {
         unsigned char * slot = slot0 + (size_t) par * slot_bytes;
         if constexpr (QK != MK_NO) {
             const int nbk = ph.K >> 8, nd = R * nbk, last = ph.N * nbk - 1;
-            mb_dma_rows((const GAS unsigned char *) ph.W, ph.K, row0, R, ph.N, slot, lane);
+            mb_dma_rows((const GAS unsigned char *) ph.W, Q4K ? ph.K >> 1 : ph.K, row0, R, ph.N, slot, lane);      // (Q4_K: the nibble rows as the arena holds them)
             mb_dma_rows((const GAS unsigned char *) ph.S, ph.K >> 4, row0, R, ph.N, slot + ph.soff, lane);
             for (int p64 = 0; p64 * 64 < nd; ++p64) {       // the rows' d: consecutive floats, a dword per lane (clamped to the matrix)
                 const int i = row0 * nbk + p64 * 64 + lane;
                 __builtin_amdgcn_global_load_lds((const GAS void *) ((gcf) ph.D + (i < last ? i : last)), (LAS void *) (slot + ph.moff + p64 * 256), 4, 0, 0);
-                if constexpr (KM) __builtin_amdgcn_global_load_lds((const GAS void *) ((gcf) ph.M + (i < last ? i : last)), (LAS void *) (slot + mkm_moff(ph.rc, ph.K) + p64 * 256), 4, 0, 0);
+                if constexpr (KM) __builtin_amdgcn_global_load_lds((const GAS void *) ((gcf) ph.M + (i < last ? i : last)), (LAS void *) (slot + (Q4K ? mq4k_moff(ph.rc, ph.K) : mkm_moff(ph.rc, ph.K)) + p64 * 256), 4, 0, 0);
             }
         } else if constexpr (Q) {
             mb_dma_rows((const GAS unsigned char *) ph.W, Q4 ? ph.K >> 1 : ph.K, row0, R, ph.N, slot, lane);      // (Q4: the nibble rows as the arena holds them)
@@ -1763,7 +1839,12 @@ __device__ __forceinline__ void mb_body(mb_kargs A_) {
         const float * bias_l = (const float *) (slot + slot_bytes - 512);
         const int groups = (Rc + 7) >> 3;
         const int bc = groups * B <= MB_NCW ? 1 : groups * ((B + 1) >> 1) <= MB_NCW ? 2 : 3;
-        if constexpr (QK != MK_NO) {
+        if constexpr (Q4K) {
+            const int r4 = A->rows4;
+            if (bc == 1)      mb_products_q4k<1>(slot, ph.soff, ph.moff, mq4k_moff(ph.rc, ph.K), Rc, row_base, ph.N, bias_l, scale_l, xop, opb, ph.K, B, r4, wave, lane, epi);
+            else if (bc == 2) mb_products_q4k<2>(slot, ph.soff, ph.moff, mq4k_moff(ph.rc, ph.K), Rc, row_base, ph.N, bias_l, scale_l, xop, opb, ph.K, B, r4, wave, lane, epi);
+            else              mb_products_q4k<3>(slot, ph.soff, ph.moff, mq4k_moff(ph.rc, ph.K), Rc, row_base, ph.N, bias_l, scale_l, xop, opb, ph.K, B, r4, wave, lane, epi);
+        } else if constexpr (QK != MK_NO) {
             if (bc == 1)      mb_products_k<1, WF>(slot, ph.soff, ph.moff, Rc, row_base, ph.N, bias_l, scale_l, xop, opb, ph.K, B, wave, lane, epi, KM ? mkm_moff(ph.rc, ph.K) : 0);
             else if (bc == 2) mb_products_k<2, WF>(slot, ph.soff, ph.moff, Rc, row_base, ph.N, bias_l, scale_l, xop, opb, ph.K, B, wave, lane, epi, KM ? mkm_moff(ph.rc, ph.K) : 0);
             else              mb_products_k<3, WF>(slot, ph.soff, ph.moff, Rc, row_base, ph.N, bias_l, scale_l, xop, opb, ph.K, B, wave, lane, epi, KM ? mkm_moff(ph.rc, ph.K) : 0);
@@ -1797,7 +1878,7 @@ __device__ __forceinline__ void mb_body(mb_kargs A_) {
                     if (f < total) {        // (wave-uniform)
                         const int b = f / nbk;
                         const float v4[4] = { __uint_as_float(v[4 * j]), __uint_as_float(v[4 * j + 1]), __uint_as_float(v[4 * j + 2]), __uint_as_float(v[4 * j + 3]) };
-                        mk_quant_block<KM>(v4, lane, xin + (size_t) b * opb, nbk, f - b * nbk);
+                        mk_quant_block<KM, QK == MK_Q4K>(v4, lane, xin + (size_t) b * opb, nbk, f - b * nbk, QK == MK_Q4K && b < A->rows4);      // (Q4_K: a gemm row's operand rows by the four-row rule)
                     }
                 }
             }
@@ -1830,7 +1911,7 @@ __device__ __forceinline__ void mb_body(mb_kargs A_) {
         if (wave < B) {
             if constexpr (Q) {
                 mb_ln_row<NP, Q, Q1, QK>(A, c, l == 0 ? nullptr : mb_edge(A, l - 1, E_X3) + (size_t) wave * RG, lnp, l == 0 ? Y.ln1_w : nullptr, l == 0 ? Y.ln1_b : nullptr,
-                                 wave, lane, (wa_f16 *) (xinB + (size_t) wave * opB), xres + wave * 8, row_d, r_d, 100u + l, pk[8 * wave], tw, l * 32 + 29);
+                                 wave, lane, (wa_f16 *) (xinB + (size_t) wave * opB), xres + wave * 8, row_d, r_d, 100u + l, pk[8 * wave], tw, l * 32 + 29, Q4K && wave < A->rows4);
             } else {
                 if (l == 0) mb_ln_row<NP, Q, Q1, QK>(A, c, nullptr, lnp, Y.ln1_w, Y.ln1_b, wave, lane, (wa_f16 *) (xinB + (size_t) wave * opB), xres + wave * 8, row_d, r_d, 100u, pk[8 * wave]);
                 else        mb_ln_row<NP, Q, Q1, QK>(A, c, mb_edge(A, l - 1, E_X3) + (size_t) wave * RG, lnp, nullptr, nullptr, wave, lane, (wa_f16 *) (xinB + (size_t) wave * opB), nullptr, 0, 0, 100u + l, 0, tw, l * 32 + 29);
@@ -1883,7 +1964,7 @@ __device__ __forceinline__ void mb_body(mb_kargs A_) {
         run_phase(l, 1, [&](const mb_phase & ph, const unsigned char * slot, int row_base, int Rc, int) { prod8(ph, slot, row_base, Rc, nullptr, xin, opD, resid_epi(mb_edge(A, l, E_X1))); });
         MB_T(5);
         // ---------------- P4: LayerNorm + cross query ----------------
-        if (wave < B) mb_ln_row<NP, Q, Q1, QK>(A, c, mb_edge(A, l, E_X1) + (size_t) wave * RG, lnp, nullptr, nullptr, wave, lane, (wa_f16 *) (xinB + (size_t) wave * opB), nullptr, 0, 0, 300u + l);
+        if (wave < B) mb_ln_row<NP, Q, Q1, QK>(A, c, mb_edge(A, l, E_X1) + (size_t) wave * RG, lnp, nullptr, nullptr, wave, lane, (wa_f16 *) (xinB + (size_t) wave * opB), nullptr, 0, 0, 300u + l, 0, false, 0, Q4K && wave < A->rows4);
         MB_T(6);
         run_phase(l, 2, [&](const mb_phase & ph, const unsigned char * slot, int row_base, int Rc, int) {
             gu64 * eq = mb_edge(A, l, E_QC);
@@ -1918,7 +1999,7 @@ __device__ __forceinline__ void mb_body(mb_kargs A_) {
         run_phase(l, 3, [&](const mb_phase & ph, const unsigned char * slot, int row_base, int Rc, int) { prod8(ph, slot, row_base, Rc, nullptr, xin, opD, resid_epi(mb_edge(A, l, E_X2))); });
         MB_T(10);
         // ---------------- P7: LayerNorm + FC1 + GELU ----------------
-        if (wave < B) mb_ln_row<NP, Q, Q1, QK>(A, c, mb_edge(A, l, E_X2) + (size_t) wave * RG, lnp, nullptr, nullptr, wave, lane, (wa_f16 *) (xinB + (size_t) wave * opB), nullptr, 0, 0, 500u + l);
+        if (wave < B) mb_ln_row<NP, Q, Q1, QK>(A, c, mb_edge(A, l, E_X2) + (size_t) wave * RG, lnp, nullptr, nullptr, wave, lane, (wa_f16 *) (xinB + (size_t) wave * opB), nullptr, 0, 0, 500u + l, 0, false, 0, Q4K && wave < A->rows4);
         MB_T(11);
         run_phase(l, 4, [&](const mb_phase & ph, const unsigned char * slot, int row_base, int Rc, int ck_row) {
             gu64 * eh = mb_edge(A, l, E_HF);
@@ -1963,7 +2044,10 @@ __device__ __forceinline__ void mb_body(mb_kargs A_) {
         run_phase(l, 5, [&](const mb_phase & ph, const unsigned char * slot, int row_base, int Rc, int) {
             const float * bias_l = (const float *) (slot + slot_bytes - 512);
             const int groups = (Rc + (Q ? 7 : 3)) / (Q ? 8 : 4);
-            if constexpr (QK != MK_NO) {
+            if constexpr (Q4K) {
+                if (groups * B <= MB_NCW) mb_products_q4k<1>(slot, ph.soff, ph.moff, mq4k_moff(ph.rc, ph.K), Rc, row_base, ph.N, bias_l, nullptr, xin, op4, ph.K, B, A->rows4, wave, lane, resid_epi(mb_edge(A, l, E_X3)));
+                else                      mb_products_q4k<2>(slot, ph.soff, ph.moff, mq4k_moff(ph.rc, ph.K), Rc, row_base, ph.N, bias_l, nullptr, xin, op4, ph.K, B, A->rows4, wave, lane, resid_epi(mb_edge(A, l, E_X3)));
+            } else if constexpr (QK != MK_NO) {
                 if (groups * B <= MB_NCW) mb_products_k<1, WF>(slot, ph.soff, ph.moff, Rc, row_base, ph.N, bias_l, nullptr, xin, op4, ph.K, B, wave, lane, resid_epi(mb_edge(A, l, E_X3)), KM ? mkm_moff(ph.rc, ph.K) : 0);
                 else                      mb_products_k<2, WF>(slot, ph.soff, ph.moff, Rc, row_base, ph.N, bias_l, nullptr, xin, op4, ph.K, B, wave, lane, resid_epi(mb_edge(A, l, E_X3)), KM ? mkm_moff(ph.rc, ph.K) : 0);
             } else if constexpr (Q4) {
@@ -1998,8 +2082,8 @@ __device__ __forceinline__ void mb_body(mb_kargs A_) {
     float * lg = (float *) area;            // (the gathered-inputs area holds nothing any more) the workgroup's logits, staged for whole-line stores and the records
     wa_barrier_lds();
     if constexpr (QK != MK_NO) {
-        if (n_out <= 2) mb_logits_k<2, WF>(A, xinB, opB, n_out, lane, wave, pf0, lg); else if (n_out <= 4) mb_logits_k<4, WF>(A, xinB, opB, n_out, lane, wave, pf0, lg);
-        else if (n_out <= 5) mb_logits_k<5, WF>(A, xinB, opB, n_out, lane, wave, pf0, lg); else mb_logits_k<8, WF>(A, xinB, opB, n_out, lane, wave, pf0, lg);
+        if (n_out <= 2) mb_logits_k<2, WF, Q4K>(A, xinB, opB, n_out, lane, wave, pf0, lg); else if (n_out <= 4) mb_logits_k<4, WF, Q4K>(A, xinB, opB, n_out, lane, wave, pf0, lg);
+        else if (n_out <= 5) mb_logits_k<5, WF, Q4K>(A, xinB, opB, n_out, lane, wave, pf0, lg); else mb_logits_k<8, WF, Q4K>(A, xinB, opB, n_out, lane, wave, pf0, lg);
     } else if constexpr (Q1) {
         if (n_out <= 2) mb_logits_q1<2>(A, xinB, opB, n_out, lane, wave, pf0, lg); else if (n_out <= 4) mb_logits_q1<4>(A, xinB, opB, n_out, lane, wave, pf0, lg);
         else if (n_out <= 5) mb_logits_q1<5>(A, xinB, opB, n_out, lane, wave, pf0, lg); else mb_logits_q1<8>(A, xinB, opB, n_out, lane, wave, pf0, lg);
@@ -2083,6 +2167,24 @@ bool MB_CAT(wa_rows_launch_q4_np, WA_ROWS_NP)(hipStream_t s, const wa_rows_args 
     hipLaunchKernelGGL(MB_CAT(k_decode_rows_q4_np, WA_ROWS_NP), dim3(n_wg), dim3(MB_THREADS), lds, s, a);
     return hipGetLastError() == hipSuccess;
 }
+#elif defined(WA_ROWS_Q4K_TU)
+// The step for a Q4_K model (Q8_K operand rows with block sums, both quantiser rules; the interleaved product's two chains per output, stepped by the
+// token row's rule - wa_rows_args::rows4): again a kernel of its own per width in a code object of its own (-DWA_ROWS_Q4K_TU)
+__global__ __launch_bounds__(MB_THREADS) void MB_CAT(k_decode_rows_q4k_np, WA_ROWS_NP)(const wa_rows_args A) {
+    mb_body<WA_ROWS_NP, true, false, MK_Q4K>((mb_kargs) __builtin_amdgcn_kernarg_segment_ptr());
+}
+bool MB_CAT(wa_rows_launch_q4k_np, WA_ROWS_NP)(hipStream_t s, const wa_rows_args & a, int n_wg, size_t lds) {
+    int dev = 0;
+    (void) hipGetDevice(&dev);
+    static bool attr_set[64] = {};
+    if (!attr_set[dev & 63]) {
+        if (hipFuncSetAttribute((const void *) MB_CAT(k_decode_rows_q4k_np, WA_ROWS_NP), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return false;
+        attr_set[dev & 63] = true;
+    }
+    if (!a.te_d || !a.te_sc || !a.te_m || a.row_gr < 4 * a.d || a.rows4 < 0 || a.rows4 > a.B) return false;
+    hipLaunchKernelGGL(MB_CAT(k_decode_rows_q4k_np, WA_ROWS_NP), dim3(n_wg), dim3(MB_THREADS), lds, s, a);
+    return hipGetLastError() == hipSuccess;
+}
 #elif defined(WA_ROWS_KM_TU)
 // The step for a Q5_K or a Q2_K model, the K formats whose product has a minimum term: a kernel per format and width, the pair of a width in a code
 // object of its own (-DWA_ROWS_KM_TU)
@@ -2118,11 +2220,13 @@ bool MB_CAT(wa_rows_launch_q1_np, WA_ROWS_NP)(hipStream_t s, const wa_rows_args 
 bool MB_CAT(wa_rows_launch_k_np, WA_ROWS_NP)(hipStream_t s, const wa_rows_args & a, int n_wg, size_t lds);
 bool MB_CAT(wa_rows_launch_km_np, WA_ROWS_NP)(hipStream_t s, const wa_rows_args & a, int n_wg, size_t lds);
 bool MB_CAT(wa_rows_launch_q4_np, WA_ROWS_NP)(hipStream_t s, const wa_rows_args & a, int n_wg, size_t lds);
+bool MB_CAT(wa_rows_launch_q4k_np, WA_ROWS_NP)(hipStream_t s, const wa_rows_args & a, int n_wg, size_t lds);
 bool MB_CAT(wa_rows_launch_np, WA_ROWS_NP)(hipStream_t s, const wa_rows_args & a, int n_wg, size_t lds) {
     if (a.quant == 2) return MB_CAT(wa_rows_launch_q1_np, WA_ROWS_NP)(s, a, n_wg, lds);
     if (a.quant == 3) return MB_CAT(wa_rows_launch_k_np, WA_ROWS_NP)(s, a, n_wg, lds);
     if (a.quant == 4) return MB_CAT(wa_rows_launch_km_np, WA_ROWS_NP)(s, a, n_wg, lds);
     if (a.quant == 5) return MB_CAT(wa_rows_launch_q4_np, WA_ROWS_NP)(s, a, n_wg, lds);
+    if (a.quant == 6) return MB_CAT(wa_rows_launch_q4k_np, WA_ROWS_NP)(s, a, n_wg, lds);
     int dev = 0;
     (void) hipGetDevice(&dev);
     static bool attr_set[64] = {};
@@ -2142,8 +2246,9 @@ bool wa_rows_launch_np20(hipStream_t s, const wa_rows_args & a, int n_wg, size_t
 
 size_t wa_rows_lds_bytes(int d, int B, int n_wg, int quant, int * slot_bytes) {
     if (B < 1 || B > WA_ROWS_MAX || d < 64 || d > WA_MEGA_MAX_D || (d & 127) != 0 || n_wg < 1) return 0;
-    if (quant < 0 || quant > 5) return 0;
-    const bool qk = quant == 3 || quant == 4, km = quant == 4, q4 = quant == 5;    // K formats; Q5_K / Q2_K: operand rows with their block sums, weight slots with a dmin region; Q4_0: nibble rows, an exchange area
+    if (quant < 0 || quant > 6) return 0;
+    const bool q4k = quant == 6;                    // Q4_K: the operand rows of Q5_K / Q2_K, weight slots of nibble rows | scale bytes | d | dmin
+    const bool qk = quant == 3 || quant == 4 || q4k, km = quant == 4 || q4k, q4 = quant == 5;    // K formats; Q5_K / Q2_K: operand rows with their block sums, weight slots with a dmin region; Q4_0: nibble rows, an exchange area
     if (qk && (d & 255) != 0) return 0;             // (K formats: blocks of 256)
     const size_t opB = qk ? mk_row_bytes(d >> 8, km) : quant ? mq_row_bytes(d >> 5) : (size_t) d * 2;
     const size_t op4 = qk ? mk_row_bytes((4 * d) >> 8, km) : quant ? mq_row_bytes((4 * d) >> 5) : (size_t) 4 * d * 2;
@@ -2163,7 +2268,7 @@ size_t wa_rows_lds_bytes(int d, int B, int n_wg, int quant, int * slot_bytes) {
         want = std::max(want, (size_t) mq1_slot_need(32, d));
         want = std::max(want, (size_t) mq1_slot_need((rpw(d) + 7) / 8 * 8, 4 * d));
     } else if (qk) {            // K formats: quants | scale bytes | d (| dmin), the kernel's own rule (mk_slot_need, mkm_slot_need); the first MLP product's rows are dealt evenly
-        auto slot_need = [&](int rc, int K) { return (size_t) (km ? mkm_slot_need(rc, K) : mk_slot_need(rc, K)); };
+        auto slot_need = [&](int rc, int K) { return (size_t) (q4k ? mq4k_slot_need(rc, K) : km ? mkm_slot_need(rc, K) : mk_slot_need(rc, K)); };
         need_min = slot_need(8, 4 * d);
         want = std::max(want, slot_need((rpw(3 * d) + 7) / 8 * 8, d));
         want = std::max(want, slot_need((rpw(4 * d) + 7) / 8 * 8, d));
@@ -2206,4 +2311,4 @@ bool wa_launch_decode_rows(hipStream_t s, const wa_rows_args & a, int n_wg) {
     return wa_rows_launch_np20(s, a, n_wg, lds);
 }
 #endif
-#endif      // WA_ROWS_Q1_TU, WA_ROWS_K_TU, WA_ROWS_Q4_TU, WA_ROWS_KM_TU
+#endif      // WA_ROWS_Q1_TU, WA_ROWS_K_TU, WA_ROWS_Q4_TU, WA_ROWS_Q4K_TU, WA_ROWS_KM_TU
